@@ -1,10 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the sampling hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
 
 A "step" = one pass of the hot path over one batch of synthetic channels with the
 output left resident in HBM (that is where the API leaves it: BatchSampler.launch).
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step = wall
+milliseconds per timed step, and the roofline of the timed kernel from the same HIP events).
+--full adds everything else the line used to carry: the `also` legs of the default workload
+(C4 chain, IIR stages, fp32, C2 / C3 / far / AWG shapes, tiers beside the BASELINE configs) and the
+CPU baselines with the parity check against the NumPy reference path.
+--dump-outputs DIR writes what the last timed step computed (the array a caller of the timed path
+receives) as DIR/output.npy (DIR/output_rank<r>.npy for ranks r > 0 of an N > 1 job), in the
+output's own dtype: the whole array if it fits DUMP_BYTES, else the values at a fixed, seeded
+sample of flat indices (sorted np.unique of default_rng(0).integers over rows x points).  The
+workloads are seeded, so the same arguments give the same inputs on every run and every build.
 Workloads (SURVEY.md §8(d) / BASELINE.json configs):
   sampler256 (default)  256 channels x 1e7 points, 100 gaussian+DRAG pulses per
                         channel (the C4/C5 channel spec), fp64, grid mode
@@ -51,6 +62,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md); ~6300 achievable
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes written in all (over every rank)
 
 
 def parse_args(argv=None):
@@ -63,7 +75,13 @@ def parse_args(argv=None):
     ap.add_argument('--points', type=float, default=None)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-also', action='store_true',
-                    help='skip the secondary workloads (c2, c3, c4) of the default line')
+                    help='skip the secondary workloads (c2, c3, c4) of the default --full line')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the secondary workloads (`also`) and the CPU baselines with the parity check; '
+                         'a plain run only times the --steps steps of the workload')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the output of the last step to DIR/output.npy '
+                         '(a fixed, seeded sample when it exceeds DUMP_BYTES)')
     ap.add_argument('--gather-rows', type=int, default=0,
                     help='N > 1 only: after the timed steps, also time an RCCL all_gather of this '
                          'many rows per rank (result placement, SURVEY 8(e); reported under '
@@ -396,6 +414,21 @@ def valu_roofline(key, kernel_ms, samples):
     return out
 
 
+def dump_outputs(dirname, name, arr, budget):
+    """--dump-outputs: the device array `arr` (rows x points, float64 or float32) -> dirname/<name>.npy in its
+    own dtype; whole when it fits `budget` bytes, else the values at a fixed, seeded sample of flat indices."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    k = max(1, budget // arr.element_size())
+    if arr.numel() <= k:
+        host = arr.cpu().numpy()
+    else:
+        idx = np.unique(np.random.default_rng(0).integers(0, arr.numel(), size=k))
+        host = arr.reshape(-1)[torch.from_numpy(idx).to(arr.device)].cpu().numpy()
+    np.save(os.path.join(dirname, name + '.npy'), host)
+
+
 # ---------------------------------------------------------------------------------------
 # plan-only rehearsal (CPU): sharding, rendezvous, reductions -- no kernels
 # ---------------------------------------------------------------------------------------
@@ -517,7 +550,6 @@ def run_rank(args):
     else:
         sh = ShardedSampler(channels * world, make_channel, grid, rank, world, tile=tile)
     bs = sh.local
-    chans = [make_channel(c) for c in range(min(channels // tile, 32))] if rank == 0 else []
     tdt = torch.float64 if dtype == np.float64 else torch.float32
     out = torch.empty((bs.n_channels, bs.n), dtype=tdt, device='cuda')
     fir = chain = None
@@ -595,6 +627,10 @@ def run_rank(args):
     fence()
     elapsed = allreduce_max(time.perf_counter() - t0)
     kern_ms = float(np.mean([a.elapsed_time(b) for a, b in ev]))
+    if args.dump_outputs:
+        # what the caller of the timed path receives: the FIR stage's output when it ran as a second kernel
+        dump_outputs(args.dump_outputs, 'output' if rank == 0 else f'output_rank{rank}',
+                     out2 if fir is not None else out, DUMP_BYTES // world)
 
     samples_per_step = bs.n_channels * bs.n * world
     if time_sharded:          # the ranks' slices differ by at most one sample: the job is channels x points
@@ -682,7 +718,7 @@ def run_rank(args):
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / steps
 
-    if name == 'sampler256' and world == 1 and not args.no_also:
+    if args.full and name == 'sampler256' and world == 1 and not args.no_also:
         also = {}
         # C4 = this workload followed by the 1024-tap FIR stage: time the FIR kernel on the
         # buffer just sampled so that the one default line carries both stages
@@ -943,8 +979,9 @@ def run_rank(args):
         b2.close()
         del o2
         line['also'] = also
-    if rank == 0 and not args.no_cpu_baseline and name in (
+    if args.full and rank == 0 and not args.no_cpu_baseline and name in (
             'sampler256', 'c4', 'c5', 'c2', 'far', 'far_sparse', 'awg', 'awg_duty30'):
+        chans = [make_channel(c) for c in range(min(channels // tile, 32))]
         base, outs = cpu_baseline(chans, grid)
         line['cpu_baseline'] = base        # (timed after the last barrier of the timed region: rank 0's host only)
         line['speedup_vs_cpu_baseline'] = line['value'] / base['value']
@@ -1026,6 +1063,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be >= 1 and --warmup >= 0')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         return launch_ranks(args, argv)
     return run_rank(args)

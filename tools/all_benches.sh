@@ -1,6 +1,7 @@
 #!/bin/bash
-# every bench line DESIGN.md quotes, in one GPU call:  bash tools/all_benches.sh > gpurun_out/all_benches.log
-python bench.py > gpurun_out/bench_default.json && cut -c1-400 gpurun_out/bench_default.json
+# every bench line DESIGN.md quotes, in one run:  bash tools/all_benches.sh
+# (the first line is the whole default line with its `also` legs and CPU baselines)
+python bench.py --full
 for w in "c4" "c3" "c2" "c2_duty30" "c2_drag" "sampler256 --dtype f32"; do
   python bench.py --workload $w --no-cpu-baseline | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$w', d['dtype'], 'value %.0f Msamples/s' % d['value'], 'ms/step %.4f' % d['ms_per_step'], r['kernel'], 'kernel_ms %.4f' % r['kernel_ms'], 'frac %.3f' % r['frac'], 'sampler_ms', r.get('sampler_kernel_ms'))"
 done

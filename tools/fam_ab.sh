@@ -3,7 +3,7 @@
 # 10 tones, flat-top readout, chirps -- default library against _ab/libwfk_head.so (the commit before)
 for lib in "" _ab/libwfk_head.so ""; do
   echo "== ${lib:-default}"
-  WFK_LIB=$lib python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+  WFK_LIB=$lib python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('headline', round(d['roofline']['kernel_ms'],4), d['roofline']['kernel'])

@@ -2,7 +2,7 @@
 # same-box A/B of a libwfk build on the default bench line (headline + also):  tools/lean_ab.sh <lib>
 for lib in "" "$@" ""; do
   echo "== ${lib:-default}"
-  WFK_LIB=$lib python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+  WFK_LIB=$lib python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('headline', round(d['roofline']['kernel_ms'],4), round(d['roofline']['frac'],4))
