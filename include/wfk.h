@@ -303,6 +303,25 @@ int wfk_spectral_apply(wfk_spectral_plan* plan, const void* in_dev, void* out_de
                        const void* H_dev, void* hip_stream);
 int wfk_spectral_plan_destroy(wfk_spectral_plan* plan);
 
+/* -- readout demodulation (reference utils.py:35-84: traces @ getFTMatrix(...)) ---------------- */
+/* out[s, j] = sum_k x[s, k] * e[k, j] for real traces x (n_shots rows of >= n_points samples, row stride
+ * trace_stride elements) and a complex matrix e (n_points x n_freq, complex128 interleaved, point-major: the
+ * memory of NumPy's (N, nf) complex128 array).  fp64 arithmetic throughout; int16 codes are exact in fp64.
+ * The plan uploads e once (zero-padded column blocks); out is complex128, row stride out_stride complex
+ * elements, 16-byte aligned.  Small n_shots split n_points across workgroups into a workspace the plan owns,
+ * reduced in a fixed order (bitwise reproducible for a given shape).  wfk_demod_apply() allocates nothing and
+ * does not synchronise; use one plan per concurrent stream.                                               */
+enum { WFK_IN_F64 = 0, WFK_IN_F32 = 1, WFK_IN_I16 = 4 };
+typedef struct wfk_demod_plan wfk_demod_plan;
+int wfk_demod_plan_create(const double* e_host, int64_t n_points, int32_t n_freq, int in_kind,
+                          wfk_demod_plan** out);
+int wfk_demod_apply(wfk_demod_plan* p, const void* traces_dev, int64_t n_shots, int64_t trace_stride,
+                    void* out_dev, int64_t out_stride, void* hip_stream);
+/* "demod_tile<T,NB>", with " + demod_reduce" when a launch of n_shots splits n_points; the string lives
+ * until the next call on this plan                                                                      */
+const char* wfk_demod_kernel_name(const wfk_demod_plan* p, int64_t n_shots);
+int wfk_demod_plan_destroy(wfk_demod_plan* p);
+
 /* -- pinned host blocks for results ------------------------------------------------------- */
 /* Page-locked host memory from a per-process cache (power-of-two blocks, parked on free).  A result
  * buffer taken from here costs no page faults, takes the D2H DMA directly and lets wfk_plan_run_host

@@ -21,6 +21,7 @@ case "$WL" in
   iir) ARGS="tools/iir_bench.py" ;;
   readout) ARGS="tools/readout_bench.py" ;;
   multitone) ARGS="tools/multitone_bench.py 10" ;;
+  demod) ARGS="tools/demod_bench.py --no-baseline --reps 5" ;;
   awg_f32) ARGS="bench.py --workload awg --dtype f32 --steps 5 --warmup 1 --no-cpu-baseline --no-also" ;;
 esac
 echo "== stats pass ($WL)"

@@ -110,6 +110,11 @@ def lib():
         l.wfk_spectral_plan_create.argtypes = [I64, I32, C.c_int, P(VP)]
         l.wfk_spectral_apply.argtypes = [VP, VP, VP, VP, VP]
         l.wfk_spectral_plan_destroy.argtypes = [VP]
+        l.wfk_demod_plan_create.argtypes = [VP, I64, I32, C.c_int, P(VP)]
+        l.wfk_demod_apply.argtypes = [VP, VP, I64, I64, VP, I64, VP]
+        l.wfk_demod_kernel_name.argtypes = [VP, I64]
+        l.wfk_demod_kernel_name.restype = C.c_char_p
+        l.wfk_demod_plan_destroy.argtypes = [VP]
         l.wfk_host_alloc.argtypes = [P(VP), C.c_size_t]
         l.wfk_host_free.argtypes = [VP]
         l.wfk_host_all_finite.argtypes = [VP, I64]
@@ -471,6 +476,40 @@ class SpectralPlan:
     def close(self):
         if self._h and _lib is not None:
             _lib.wfk_spectral_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+
+IN_F64, IN_F32, IN_I16 = 0, 1, 4
+DEMOD_IN_KIND = {np.dtype(np.float64): IN_F64, np.dtype(np.float32): IN_F32, np.dtype(np.int16): IN_I16}
+
+
+class DemodPlan:
+    """out[s, j] = sum_k x[s, k] * e[k, j]: real traces (shots, >= N) of float64 / float32 / int16 times a complex
+    (N, nf) matrix, fp64 on the device; `e` is uploaded once."""
+
+    def __init__(self, e, dtype=np.float64):
+        e = np.ascontiguousarray(e, dtype=np.complex128)
+        if e.ndim != 2 or e.shape[0] < 1 or e.shape[1] < 1:
+            raise ValueError('e must be a non-empty (N, nf) complex matrix')
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in DEMOD_IN_KIND:
+            raise ValueError('trace dtype must be float64, float32 or int16')
+        self.n, self.nf = int(e.shape[0]), int(e.shape[1])
+        self._h = C.c_void_p()
+        check(lib().wfk_demod_plan_create(e.ctypes.data, self.n, self.nf, DEMOD_IN_KIND[self.dtype],
+                                          C.byref(self._h)))
+
+    def apply(self, x_ptr, n_shots, x_stride, out_ptr, out_stride, stream=0):
+        check(lib().wfk_demod_apply(self._h, x_ptr, n_shots, x_stride, out_ptr, out_stride, stream))
+
+    def kernel_name(self, n_shots: int) -> str:
+        return lib().wfk_demod_kernel_name(self._h, n_shots).decode()
+
+    def close(self):
+        if self._h and _lib is not None:
+            _lib.wfk_demod_plan_destroy(self._h)
             self._h = C.c_void_p()
 
     __del__ = close
