@@ -265,6 +265,34 @@ int wfk_iir_apply(wfk_iir_plan* plan, const void* in_dev, int64_t in_stride, voi
 int wfk_iir_status(wfk_iir_plan* plan, void* hip_stream);
 int wfk_iir_plan_destroy(wfk_iir_plan* plan);
 
+/* -- IIR stage with one cascade PER ROW ------------------------------------------------------- */
+/* Row r runs through its OWN cascade: out[r] = F_r(in[r] - initial[r]) + initial[r] -- every flux line has its
+ * own exp-decay correction (exp_decay_filter / predistort / distort, waveforms/distortion.py:100-185, 298-346).
+ * The SHAPE (n_sections, orders) is shared by all rows; the coefficients are not: b_rows / a_rows hold, row after
+ * row, the sections back to back with orders[s]+1 coefficients each, as wfk_iir_plan_create takes them for one row
+ * (a[0] of a section need not be 1; a row with a lower order is padded with zero coefficients, which is exact for
+ * this form).  zi_dev / zf_dev: optional [batch][state_dim] device arrays in scipy's layout per row; initial_dev:
+ * optional [batch] device array (NULL = zeros).
+ * Shapes: sections of EQUAL order >= 1 with a total state dimension <= 4 -- one section of order 1..4, 1..4
+ * first-order sections, one or two biquads; anything else: WFK_EUNSUP, wfk_last_error() names the limit.
+ * One kernel (iir_rows_tile): a workgroup owns a row and walks it tile by tile through LDS, x read once and y
+ * written once; no workgroup waits for another, so there is no status call and no timeout, and results are
+ * bitwise reproducible and independent of a row's position in the batch.  The plan holds one table of block
+ * transition matrices per row (built in quad precision at creation, ~18 KB per row at state dimension 4) and no
+ * scratch: a plan may serve several streams at once.  wfk_iir_rows_apply() allocates nothing and does not
+ * synchronise; in place (out_dev == in_dev) is allowed; strides are in elements.                              */
+typedef struct wfk_iir_rows_plan wfk_iir_rows_plan;
+int wfk_iir_rows_plan_create(int32_t n_sections, const int32_t* orders, const double* b_rows,
+                             const double* a_rows, int64_t n, int32_t batch,
+                             int kind /* WFK_OUT_F64|F32 */, wfk_iir_rows_plan** out);
+int wfk_iir_rows_state_dim(const wfk_iir_rows_plan* plan);
+int wfk_iir_rows_apply(wfk_iir_rows_plan* plan, const void* in_dev, int64_t in_stride, void* out_dev,
+                       int64_t out_stride, const double* zi_dev, double* zf_dev,
+                       const double* initial_dev, void* hip_stream);
+/* "iir_rows_tile<T,NSEC,ORD>"; the string lives as long as the plan */
+const char* wfk_iir_rows_kernel_name(const wfk_iir_rows_plan* plan);
+int wfk_iir_rows_plan_destroy(wfk_iir_rows_plan* plan);
+
 /* -- sampler -> IIR (-> FIR) chain ------------------------------------------------------------ */
 /* out = F(wav(t) - initial) + initial for every channel of `prog` on `grid`, F the cascade of wfk_iir_plan_create
  * (same section layout, same zi / zf state layout, [n_channels][state_dim]) -- Waveform.sample(filters=(sos, initial))

@@ -107,6 +107,12 @@ def lib():
         l.wfk_iir_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP, C.c_double, VP]
         l.wfk_iir_plan_destroy.argtypes = [VP]
         l.wfk_iir_status.argtypes = [VP, VP]
+        l.wfk_iir_rows_plan_create.argtypes = [I32, VP, VP, VP, I64, I32, C.c_int, P(VP)]
+        l.wfk_iir_rows_state_dim.argtypes = [VP]
+        l.wfk_iir_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP, VP, VP]
+        l.wfk_iir_rows_kernel_name.argtypes = [VP]
+        l.wfk_iir_rows_kernel_name.restype = C.c_char_p
+        l.wfk_iir_rows_plan_destroy.argtypes = [VP]
         l.wfk_spectral_plan_create.argtypes = [I64, I32, C.c_int, P(VP)]
         l.wfk_spectral_apply.argtypes = [VP, VP, VP, VP, VP]
         l.wfk_spectral_plan_destroy.argtypes = [VP]
@@ -456,6 +462,77 @@ class IirPlan:
     def close(self):
         if self._h and _lib is not None:
             _lib.wfk_iir_plan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+
+def pack_sections_rows(sections_per_row):
+    """list (one entry per row) of cascades [(b, a), ...] -> (orders int32, b (batch, NC), a (batch, NC), own):
+    every section padded with zero coefficients to the widest order of ANY section of any row, and every row to the
+    largest section count with pass-through sections (b = [1, 0, ...], a = [1, 0, ...]) -- both exact for the
+    direct form II transposed.  `own[r]` lists the orders row r came with (what its zi / zf hold).
+    ValueError: no rows, an empty cascade; NotImplementedError: complex coefficients."""
+    rows = []
+    for secs in sections_per_row:
+        row = []
+        for b, a in secs:
+            b, a = np.atleast_1d(np.asarray(b)), np.atleast_1d(np.asarray(a))
+            if np.iscomplexobj(b) or np.iscomplexobj(a):
+                raise NotImplementedError('IIR sections with complex coefficients')
+            if b.ndim != 1 or a.ndim != 1 or len(a) < 1 or len(b) < 1:
+                raise ValueError('a section is a pair of 1-D coefficient sequences (b, a)')
+            row.append((b.astype(np.float64), a.astype(np.float64)))
+        if not row:
+            raise ValueError('a row without sections')
+        rows.append(row)
+    if not rows:
+        raise ValueError('no rows')
+    nsec = max(len(r) for r in rows)
+    order = max(1, max(max(len(b), len(a)) - 1 for r in rows for b, a in r))
+    bm = np.zeros((len(rows), nsec, order + 1))
+    am = np.zeros((len(rows), nsec, order + 1))
+    bm[:, :, 0] = 1.0
+    am[:, :, 0] = 1.0
+    own = []
+    for r, row in enumerate(rows):
+        for s, (b, a) in enumerate(row):
+            bm[r, s, :] = 0.0
+            am[r, s, :] = 0.0
+            bm[r, s, :len(b)] = b
+            am[r, s, :len(a)] = a
+        own.append([max(len(b), len(a)) - 1 for b, a in row])
+    orders = np.full(nsec, order, dtype=np.int32)
+    return orders, bm.reshape(len(rows), -1), am.reshape(len(rows), -1), own
+
+
+class IirRowsPlan:
+    """One cascade PER ROW (wfk_iir_rows_plan_create): `sections_per_row[r]` is the list of (b, a) sections of
+    row r, in IirPlan's conventions.  Rows are padded to a common shape (`pack_sections_rows`); the library takes
+    sections of equal order with a total state dimension <= 4 and raises EngineError beyond that.
+    `state_dim` is the padded state dimension: zi / zf are (batch, state_dim) device arrays."""
+
+    def __init__(self, sections_per_row, n: int, dtype=np.float64):
+        orders, bm, am, self.own_orders = pack_sections_rows(sections_per_row)
+        self.n, self.batch, self.dtype = int(n), int(bm.shape[0]), np.dtype(dtype)
+        self.orders = orders
+        self._h = C.c_void_p()
+        bm, am = np.ascontiguousarray(bm), np.ascontiguousarray(am)
+        check(lib().wfk_iir_rows_plan_create(len(orders), orders.ctypes.data, bm.ctypes.data, am.ctypes.data,
+                                             self.n, self.batch, _KIND_OF[self.dtype], C.byref(self._h)))
+        self.state_dim = int(orders.sum())
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, zi_ptr=None, zf_ptr=None, initial_ptr=None, stream=0):
+        """initial_ptr: device array of `batch` doubles (one level per row) or None"""
+        check(lib().wfk_iir_rows_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, zi_ptr, zf_ptr,
+                                       initial_ptr, stream))
+
+    def kernel_name(self) -> str:
+        return lib().wfk_iir_rows_kernel_name(self._h).decode()
+
+    def close(self):
+        if self._h and _lib is not None:
+            _lib.wfk_iir_rows_plan_destroy(self._h)
             self._h = C.c_void_p()
 
     __del__ = close

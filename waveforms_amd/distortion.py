@@ -49,6 +49,126 @@ class FirStage:
         self.plan.close()
 
 
+class IirStage:
+    """Device-resident IIR stage for `batch` rows of `n` samples (build once, apply many times), the
+    counterpart of `FirStage`:  y[r] = F_r(x[r] - initial[r]) + initial[r].
+
+    `sections` is either ONE cascade for all rows -- a list of (b, a) pairs or an SOS matrix (n_sections, 6);
+    it runs on `_engine.IirPlan`, results as ever -- or a list of `batch` cascades, one list of (b, a) pairs
+    per row (`per_row`; `_engine.IirRowsPlan`, one launch for the whole batch).  Per-row cascades are padded
+    with zero coefficients to a common shape, which must be sections of equal order with a total state
+    dimension <= 4 (NotImplementedError otherwise, the message names the limit).
+
+        st = IirStage([[exp_decay_filter(A, tau, 2e9)] for A, tau in lines], n, len(lines))
+        st.apply_torch(x)                      # in place, on torch's current stream
+        st.apply_torch(x, out=y, initial=levels, zi=zi, zf=zf)
+
+    zi / zf: (batch, state_dim) float64 device tensors in scipy's layout per row.  With per-row cascades
+    `state_dim` is that of the common shape; `row_state(zf, r)` cuts row r's own state out of it (the padding
+    entries are zero)."""
+
+    def __init__(self, sections, n: int, batch: int, dtype=np.float64):
+        self.n, self.batch, self.dtype = int(n), int(batch), np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError('IirStage: dtype must be float64 or float32')
+        if self.batch < 1 or self.n < 0:
+            raise ValueError('IirStage: batch >= 1 and n >= 0')
+        depth = _nesting(sections)
+        if depth == 2:                                             # an SOS matrix (scipy.signal.sosfilt)
+            sec = np.asarray(sections, dtype=np.float64)
+            if sec.ndim != 2 or sec.shape[1] != 6:
+                raise ValueError('IirStage: an SOS matrix has shape (n_sections, 6)')
+            sections, depth = [(r[:3], r[3:]) for r in sec], 3
+        if depth not in (3, 4):
+            raise ValueError('IirStage: sections is [(b, a), ...], an SOS matrix, or one [(b, a), ...] per row')
+        self.per_row = depth == 4
+        self._initial_cache = None
+        if self.per_row:
+            if len(sections) != self.batch:
+                raise ValueError(f'IirStage: {len(sections)} cascades for {self.batch} rows')
+            self.plan = _engine.IirRowsPlan(sections, self.n, self.dtype)
+            self.own_orders = self.plan.own_orders
+            self.section_order = int(self.plan.orders[0])
+        else:
+            if any(np.iscomplexobj(np.asarray(c)) for sec in sections for c in sec):
+                raise NotImplementedError('IIR sections with complex coefficients')
+            self.plan = _engine.IirPlan(sections, self.n, self.batch, self.dtype)
+        self.state_dim = self.plan.state_dim
+
+    def kernel_name(self) -> str:
+        """'iir_rows_tile<T,NSEC,ORD>' for per-row cascades; the shared-cascade plan picks its kernels per launch"""
+        return self.plan.kernel_name() if self.per_row else 'iir_plan'
+
+    def row_state(self, z, r: int):
+        """row r's own state (scipy layout, its sections back to back) out of a (batch, state_dim) host array"""
+        z = np.asarray(z)
+        if not self.per_row:
+            return z[r]
+        m = self.section_order
+        return np.concatenate([z[r, s * m:s * m + o] for s, o in enumerate(self.own_orders[r])] or [z[r, :0]])
+
+    def _initial_tensor(self, initial, device):
+        """None (all zero), or a (batch,) float64 device tensor; a tensor of the last values is kept"""
+        import torch
+        if isinstance(initial, torch.Tensor):
+            if (not initial.is_cuda or initial.dtype != torch.float64 or tuple(initial.shape) != (self.batch, )
+                    or not initial.is_contiguous()):
+                raise ValueError('initial: a (batch,) contiguous float64 device tensor')
+            return initial
+        arr = np.asarray(initial, dtype=np.float64)
+        if arr.ndim == 0:
+            arr = np.full(self.batch, float(arr))
+        if arr.shape != (self.batch, ):
+            raise ValueError('initial: a scalar or one value per row')
+        if not arr.any():
+            return None
+        c = self._initial_cache
+        if c is None or c[1] != device or not np.array_equal(c[0], arr):
+            self._initial_cache = c = (arr.copy(), device, torch.from_numpy(arr.copy()).to(device))
+        return c[2]
+
+    def apply_torch(self, x, out=None, initial=0.0, zi=None, zf=None):
+        """x, out: (batch, >= n) row-contiguous device tensors of the stage's dtype (rows may be windows of a wider
+        tensor); out=None or out is x: in place.  `initial`: a scalar, one value per row, or a (batch,) float64 device
+        tensor (per-row values need per-row cascades).  Asynchronous on torch's current stream.  -> out"""
+        import torch
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        out = x if out is None else out
+        for t in (x, out):
+            if (not t.is_cuda or t.dtype != want or t.dim() != 2 or t.shape[0] != self.batch or
+                    t.shape[1] < self.n or t.stride(1) != 1 or (self.batch > 1 and t.stride(0) < self.n)):
+                raise ValueError('expected (batch, >=n) row-contiguous device tensors of the stage dtype')
+        for z in (zi, zf):
+            if z is not None and (not z.is_cuda or z.dtype != torch.float64 or not z.is_contiguous()
+                                  or tuple(z.shape) != (self.batch, self.state_dim)):
+                raise ValueError('zi / zf must be contiguous (batch, state_dim) float64 device tensors')
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        zip_, zfp = None if zi is None else zi.data_ptr(), None if zf is None else zf.data_ptr()
+        if self.per_row:
+            ini = self._initial_tensor(initial, x.device)
+            self.plan.apply(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), zip_, zfp,
+                            None if ini is None else ini.data_ptr(), stream)
+            return out
+        if isinstance(initial, torch.Tensor) or np.ndim(initial) != 0:
+            raise ValueError('a shared cascade takes a scalar `initial`; per-row levels need per-row cascades')
+        for attempt in range(2):     # (a look-back timeout of the shared-cascade plan: it has switched form)
+            if self.plan.apply(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), zip_, zfp,
+                               float(initial), stream):
+                return out
+        raise _engine.EngineError('IIR stage refused twice')
+
+    def close(self):
+        self.plan.close()
+
+
+def _nesting(x) -> int:
+    """levels of list / tuple / array around the first scalar"""
+    d = 0
+    while isinstance(x, (list, tuple, np.ndarray)) and len(x) > 0:
+        x, d = x[0], d + 1
+    return d
+
+
 class SampledFir:
     """`predistort(wav(t), ker=ker)` for many channels on one uniform grid, device-resident:
     the sampler runs INSIDE the FIR transform when the channels are fully fused (`fused`; on fine grids
@@ -431,6 +551,137 @@ def distort(points, params, sample_rate, initial=0.0):
     for amp, tau in np.asarray(params).reshape(-1, 2):
         filters.append(exp_decay_filter(amp, abs(tau), sample_rate))
     return predistort(points, filters, initial=initial)
+
+
+ROWS_MAX_ORDER = 4     # combined order per row that the per-row plan takes (state dimension <= 4)
+
+
+def _rows_arguments(sig, filters_rows, initial, zi):
+    """host-side checks and filter design of predistort_rows: -> (sig, [(b, a)] per row, initial (batch,), zi or None)"""
+    sig = np.asarray(sig)
+    if sig.ndim != 2:
+        raise ValueError('predistort_rows: sig must be 2-D (rows, samples)')
+    batch = sig.shape[0]
+    filters_rows = list(filters_rows)
+    if len(filters_rows) != batch:
+        raise ValueError(f'predistort_rows: {len(filters_rows)} filter lists for {batch} rows')
+    ini = np.asarray(initial)
+    if ini.ndim == 0:
+        ini = np.full(batch, ini[()])
+    if ini.shape != (batch, ):
+        raise ValueError('predistort_rows: initial is a scalar or one value per row')
+    ba = []
+    for filters in filters_rows:
+        filters = list(filters)
+        if any(np.iscomplexobj(np.asarray(c)) for sec in filters for c in sec):
+            raise NotImplementedError('IIR sections with complex coefficients')
+        b, a = combine_filters(filters)
+        ba.append((np.atleast_1d(np.asarray(b, dtype=np.float64)), np.atleast_1d(np.asarray(a, dtype=np.float64))))
+    if zi is not None:
+        zi = [np.atleast_1d(np.asarray(z)) for z in zi]
+        if len(zi) != batch:
+            raise ValueError(f'predistort_rows: {len(zi)} states for {batch} rows')
+        for r, ((b, a), z) in enumerate(zip(ba, zi)):
+            if z.shape != (max(len(b), len(a)) - 1, ):
+                raise ValueError(f'predistort_rows: zi[{r}] must hold the {max(len(b), len(a)) - 1} lfilter state '
+                                 f'values of row {r}')
+    return sig, ba, ini, zi
+
+
+def _iir_rows_real(sig2, ba, zi):
+    """real rows through one IirRowsPlan launch: -> (out, [zf per row]); ba: one combined (b, a) per row"""
+    batch, n = sig2.shape
+    sig2 = np.ascontiguousarray(sig2, dtype=np.float64)
+    plan = _engine.IirRowsPlan([[s] for s in ba], n, np.float64)
+    D = plan.state_dim
+    bufs = []
+
+    def dev(nbytes):
+        b = _engine.DeviceBuffer(max(nbytes, 8))
+        bufs.append(b)
+        return b
+
+    try:
+        x = dev(sig2.nbytes)
+        x.upload(sig2)
+        z = np.zeros((batch, D))
+        for r, zr in enumerate(zi):
+            z[r, :len(zr)] = zr
+        dzi, dzf = dev(z.nbytes), dev(z.nbytes)
+        dzi.upload(z)
+        plan.apply(x.ptr, n, x.ptr, n, dzi.ptr, dzf.ptr)
+        _engine.sync()
+        out = x.download(sig2.shape, np.float64)
+        zf = dzf.download((batch, D), np.float64)
+    finally:
+        for b in bufs:
+            b.close()
+        plan.close()
+    return out, [zf[r, :plan.own_orders[r][0]] for r in range(batch)]
+
+
+def predistort_rows(sig, filters_rows, initial=0.0, zi=None, return_zf=False):
+    """`predistort(sig[r], filters_rows[r], initial=initial[r])` for every row r of a 2-D `sig` (reference
+    distortion.py:298-321 per row: one lfilter over the row's combined (b, a), started from lfiltic for the level
+    `initial[r]`), all rows in ONE launch with one filter per row.
+
+    filters_rows: one list of (b, a) sections per row.  initial: a scalar or one value per row.  zi: optional, one
+    lfilter state per row (row r: combined order of that row), used instead of lfiltic.  return_zf: also return the
+    list of final states, one array per row (rows differ in length when their orders do).
+    Complex rows / levels / states run as two real passes.  A row whose poles are not all inside the unit circle
+    warns 'filter is unstable' as predistort does.
+    Rows whose combined order exceeds 4 do not fit the per-row plan: they go through `predistort` one by one
+    (correct, one launch per row -- slow).
+    Raises ValueError (sig not 2-D, wrong number of rows, initial neither scalar nor one value per row, a zi of
+    the wrong length) and NotImplementedError (complex coefficients) before any device work."""
+    from scipy.signal import lfiltic, tf2zpk
+    sig, ba, ini, zi = _rows_arguments(sig, filters_rows, initial, zi)
+    batch, n = sig.shape
+    unstable = False
+    for b, a in ba:
+        _, p, _ = tf2zpk(b, a)
+        unstable = unstable or not np.all(np.abs(p) < 1)
+    if unstable:
+        warnings.warn('Warning: filter is unstable')
+    if zi is None:
+        zi = [lfiltic(b, a, np.full(len(a) - 1, c), np.full(len(b) - 1, c)) for (b, a), c in zip(ba, ini)]
+    cplx = np.iscomplexobj(sig) or any(np.iscomplexobj(z) for z in zi)
+    out = np.empty(sig.shape, dtype=np.complex128 if cplx else np.float64)
+    zf = [None] * batch
+    small = [r for r, (b, a) in enumerate(ba) if max(len(b), len(a)) - 1 <= ROWS_MAX_ORDER]
+    big = [r for r in range(batch) if max(len(ba[r][0]), len(ba[r][1])) - 1 > ROWS_MAX_ORDER]
+    if n == 0:
+        out[...] = sig
+        zf = [np.array(z) for z in zi]
+    else:
+        if small:
+            sub = [ba[r] for r in small]
+            o, z = _iir_rows_real(np.real(sig[small]), sub, [np.real(zi[r]) for r in small])
+            if cplx:
+                oi, zim = _iir_rows_real(np.imag(sig[small]), sub, [np.imag(zi[r]) for r in small])
+                o, z = o + 1j * oi, [p + 1j * q for p, q in zip(z, zim)]
+            out[small] = o
+            for r, zr in zip(small, z):
+                zf[r] = zr
+        for r in big:
+            with warnings.catch_warnings():
+                warnings.simplefilter('ignore')            # (warned once above)
+                o, z = predistort(sig[r], [ba[r]], zi=zi[r], return_zf=True)
+            out[r], zf[r] = o, (z + 0j if cplx else z)
+    return (out, zf) if return_zf else out
+
+
+def distort_rows(points, params_rows, sample_rate, initial=0.0):
+    """`distort(points[r], params_rows[r], sample_rate, initial[r])` for every row of a 2-D `points` (reference
+    distortion.py:340-346 per row): params_rows[r] = [amp0, tau0, amp1, tau1, ...] of line r; rows may have
+    different numbers of time constants.  One launch (see predistort_rows, whose errors it shares)."""
+    points = np.asarray(points)
+    params_rows = list(params_rows)
+    if points.ndim != 2 or len(params_rows) != points.shape[0]:
+        raise ValueError('distort_rows: points must be 2-D with one parameter list per row')
+    filters_rows = [[exp_decay_filter(amp, abs(tau), sample_rate) for amp, tau in np.asarray(p).reshape(-1, 2)]
+                    for p in params_rows]
+    return predistort_rows(points, filters_rows, initial=initial)
 
 
 # --------------------------------------------------------------------------
