@@ -219,15 +219,15 @@ class TimeShardedIir:
         """This rank's pass alone: x -> y ((rows, >= n) device tensors, y may be x) from `state` (rows, D) -> the
         final state (rows, D), both float64 device tensors."""
         import torch
+        from . import _engine
         zf = torch.empty_like(state)
         stream = torch.cuda.current_stream(x.device).cuda_stream if x.is_cuda else 0
-        for attempt in range(2):
-            ok = self.plan.apply(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), state.data_ptr(), zf.data_ptr(),
-                                 initial, stream)
-            if self.plan.status(stream) and ok:
-                return zf
-            if x.data_ptr() == y.data_ptr():
-                break                          # (the input is gone: the caller samples again)
+        if _engine.iir_run_checked(
+                lambda: self.plan.apply(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), state.data_ptr(),
+                                        zf.data_ptr(), initial, stream),
+                lambda: self.plan.status(stream),
+                retry=x.data_ptr() != y.data_ptr()):   # (in place the input is gone: the caller samples again)
+            return zf
         raise RuntimeError('IIR stage timed out (a look-back that never completed); sample again and re-apply')
 
     def apply_torch(self, x, y, initial=0.0, zi=None, group=None):

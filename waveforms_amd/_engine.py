@@ -348,6 +348,31 @@ class ChainPlan:
     __del__ = close
 
 
+def _accepted(rc) -> bool:
+    """An IIR launch / status code: False for WFK_ETIMEOUT (a look-back timed out; the plan has switched to the
+    three-launch form), True for success; any other error raises"""
+    if rc == E_TIMEOUT:
+        return False
+    check(rc)
+    return True
+
+
+def iir_run_checked(launch, status, retry=True) -> bool:
+    """The synchronous form of the look-back protocol, spelt once: `launch()` (-> False: refused after an earlier
+    timeout), then `status()` (synchronises; -> False: a look-back of this launch timed out, the outputs hold NaN);
+    after a failure the plan runs in the three-launch form, so launch and check once more -- unless `retry` is
+    False (an in-place pass: the input is gone).  -> whether the outputs are good; the caller raises its own error."""
+    def attempt():
+        ok = launch()
+        return status() and ok
+    return attempt() or (retry and attempt())
+
+
+def sos_sections(sos):
+    """an SOS matrix (scipy.signal.sosfilt) -> [(b, a), ...]"""
+    return [(row[:3], row[3:]) for row in np.asarray(sos, dtype=np.float64).reshape(-1, 6)]
+
+
 def _pack_sections(sections):
     """list of (b, a) -> (orders int32, b flat, a flat), every section padded to max(len(b), len(a))"""
     orders, bs, as_ = [], [], []
@@ -394,19 +419,12 @@ class ChainIirPlan:
     def launch(self, out_ptr: int, out_stride: int, zi_ptr=None, zf_ptr=None, initial=0.0, stream: int = 0) -> bool:
         """-> False when the library refused the launch with WFK_ETIMEOUT (an earlier launch of this plan ran into a
         look-back timeout; the plan has switched to the unfused three-launch form: launch again)"""
-        rc = lib().wfk_chain_iir_launch(self._h, out_ptr, out_stride, zi_ptr, zf_ptr, float(initial), stream)
-        if rc == E_TIMEOUT:
-            return False
-        check(rc)
-        return True
+        return _accepted(lib().wfk_chain_iir_launch(self._h, out_ptr, out_stride, zi_ptr, zf_ptr, float(initial),
+                                                    stream))
 
     def status(self, stream=0) -> bool:
         """Synchronise `stream`; False if a launch since the last check timed out in a look-back (outputs hold NaN)"""
-        rc = lib().wfk_chain_iir_status(self._h, stream)
-        if rc == E_TIMEOUT:
-            return False
-        check(rc)
-        return True
+        return _accepted(lib().wfk_chain_iir_status(self._h, stream))
 
     def kernel_name(self) -> str:
         return lib().wfk_chain_iir_kernel_name(self._h).decode()
@@ -443,21 +461,13 @@ class IirPlan:
         """-> False when the library refused the launch with WFK_ETIMEOUT: an EARLIER launch of this plan
         (for instance the other row of a complex waveform) ran into a look-back timeout; nothing was
         launched, the plan has switched to the three-launch form -- treat it like `status() == False`."""
-        rc = lib().wfk_iir_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, zi_ptr,
-                                 zf_ptr, float(initial), stream)
-        if rc == E_TIMEOUT:
-            return False
-        check(rc)
-        return True
+        return _accepted(lib().wfk_iir_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, zi_ptr,
+                                             zf_ptr, float(initial), stream))
 
     def status(self, stream=0) -> bool:
         """Synchronise `stream`; False if a single-pass launch since the last check ran into a look-back
         timeout (its outputs hold NaN; the plan has switched to the three-launch form: apply again)."""
-        rc = lib().wfk_iir_status(self._h, stream)
-        if rc == E_TIMEOUT:
-            return False
-        check(rc)
-        return True
+        return _accepted(lib().wfk_iir_status(self._h, stream))
 
     def close(self):
         if self._h and _lib is not None:

@@ -226,11 +226,6 @@ def call_vstack(w, x, function_lib=None):
             plan.close()
 
 
-def _sos_sections(sos):
-    sos = np.asarray(sos, dtype=np.float64).reshape(-1, 6)
-    return [(row[:3], row[3:]) for row in sos]
-
-
 def _rotated(prog):
     """The program with every amplitude multiplied by -1j: its real part is the imaginary part of `prog`."""
     arrays = dict(prog.arrays)
@@ -256,7 +251,7 @@ def _sample_filtered(w, plan, sos, initial, zi):
     # one sampler -> IIR chain per real row (wfk_chain_iir_*): the wave that owns a chunk of the IIR scan evaluates its
     # input itself when the tree is fully fused (the unfiltered samples never exist in memory), otherwise sampler and
     # filter run back to back on the device buffer
-    sections = _sos_sections(sos)
+    sections = _engine.sos_sections(sos)
     chains = [_engine.ChainIirPlan(plan.prog, plan.grid, sections)]
     D = chains[0].state_dim
     buf = _engine.DeviceBuffer(max(n, 1) * 8 * rows)
@@ -268,19 +263,14 @@ def _sample_filtered(w, plan, sos, initial, zi):
         if cplx:
             chains.append(_engine.ChainIirPlan(_rotated(plan.prog), plan.grid, sections))
         dzi.upload(np.ascontiguousarray(np.concatenate([z0.real, z0.imag])[:D * rows]))
-        for attempt in range(2):
-            ok = True
-            for r, chain in enumerate(chains):
-                off, zoff = r * max(n, 1) * 8, r * max(D, 1) * 8
-                ok = chain.launch(buf.ptr + off, max(n, 1), dzi.ptr + zoff, dzf.ptr + zoff,
-                                  init.imag if r else init.real) and ok
-            ok = all([chain.status() for chain in chains]) and ok
-            if ok:
-                break
-            # a single-pass look-back timed out (its outputs hold NaN): the chains have switched to the
-            # three-launch form behind the plain sampler; launch again
-            if attempt == 1:
-                raise _engine.EngineError('IIR stage failed twice')
+        def launch():
+            return all([chain.launch(buf.ptr + r * max(n, 1) * 8, max(n, 1), dzi.ptr + r * max(D, 1) * 8,
+                                     dzf.ptr + r * max(D, 1) * 8, init.imag if r else init.real)
+                        for r, chain in enumerate(chains)])
+
+        # (after a look-back timeout the chains run in the three-launch form behind the plain sampler)
+        if not _engine.iir_run_checked(launch, lambda: all([chain.status() for chain in chains])):
+            raise _engine.EngineError('IIR stage failed twice')
         _engine.sync()
         if n:
             sig = buf.download((rows, max(n, 1)), np.float64)

@@ -26,19 +26,19 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "wfk.h"
 #include "wfk_chain_dev.h"
+#include "wfk_iir_common.h"
 #include "wfk_internal.h"
 
 #define IIR_MAXD 16
 #define IIR_MAXSEC 8
 #define IIR_LB 2048   // block length (samples)
 #define IIR_SEG 16    // samples per block per LDS tile (64 blocks x 16 samples = 8.7 KB)
-
-extern "C" void wfk_internal_set_error(const char* msg);
 
 namespace {
 
@@ -71,27 +71,9 @@ __device__ __forceinline__ double iir_step_t(const IirCoef& c, double x, double 
   if constexpr (NSEC == 0) {
     return iir_step(c, x, z);
   } else {
-#pragma unroll
-    for (int s = 0; s < NSEC; ++s) {
-      const double y = c.b[s][0] * x + z[s * ORD];
-#pragma unroll
-      for (int i = 0; i + 1 < ORD; ++i)
-        z[s * ORD + i] = c.b[s][i + 1] * x - c.a[s][i + 1] * y + z[s * ORD + i + 1];
-      z[s * ORD + ORD - 1] = c.b[s][ORD] * x - c.a[s][ORD] * y;
-      x = y;
-    }
-    return x;
+    return iir_cascade_step<NSEC, ORD>([&](int s, int i) { return c.b[s][i]; },
+                                       [&](int s, int i) { return c.a[s][i]; }, x, z);
   }
-}
-
-// (sh + sl) += (th + tl) * x in double-double (TwoProd via fma, TwoSum)
-__device__ __forceinline__ void dd_acc(double& sh, double& sl, double th, double tl, double x) {
-  const double p = th * x;
-  const double e = fma(th, x, -p) + tl * x;
-  const double s = sh + p;
-  const double bb = s - sh;
-  sl += ((sh - (s - bb)) + (p - bb)) + e;
-  sh = s;
 }
 
 // Inclusive scan over the 64 lanes of a wave: v_l <- sum_{j<=l} M^(l-j) v_j, with
@@ -127,27 +109,6 @@ __device__ __forceinline__ void wave_scan(double (&v)[IIR_MAXD], const double* _
         if (i < D) v[i] = nv[i];
     }
   }
-}
-
-// v += M * c in double-double; M = D x D (hi, lo) pairs
-template <int DD>
-__device__ __forceinline__ void dd_matvec_add(double (&v)[IIR_MAXD], const double* __restrict__ M,
-                                              const double (&c)[IIR_MAXD], int D_rt) {
-  const int D = DD > 0 ? DD : D_rt;
-  double nv[IIR_MAXD];
-#pragma unroll
-  for (int i = 0; i < (DD > 0 ? DD : IIR_MAXD); ++i) {
-    if (i < D) {
-      double sh = v[i], sl = 0.0;
-#pragma unroll
-      for (int j = 0; j < (DD > 0 ? DD : IIR_MAXD); ++j)
-        if (j < D) dd_acc(sh, sl, M[(i * D + j) * 2], M[(i * D + j) * 2 + 1], c[j]);
-      nv[i] = sh + sl;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < (DD > 0 ? DD : IIR_MAXD); ++i)
-    if (i < D) v[i] = nv[i];
 }
 
 // One wave per 64 consecutive blocks of one row.  WRITE=false: zero initial state, emit the
@@ -188,7 +149,7 @@ __global__ void __launch_bounds__(64) iir_pass(const IirCoef c, const T* __restr
 #pragma unroll
       for (int i = 0; i < IIR_MAXD; ++i)
         if (i < D) z[i] = s[i];
-      dd_matvec_add<DD>(z, lanep + (int64_t)(lane - 1) * D * D * 2, carry, D);
+      dd_matvec_add<DD>(z, z, lanep + (int64_t)(lane - 1) * D * D * 2, carry, D);
     }
   }
   const int nact = (int)(nblk - blk0 < 64 ? nblk - blk0 : 64);   // active blocks in this wave
@@ -528,7 +489,7 @@ __global__ void __launch_bounds__(64, OP_WAVES) iir_onepass(const IirCoef c, con
 #pragma unroll
           for (int i = 0; i < DD; ++i) contrib[i] = v[i];   // U^0
         } else {
-          dd_matvec_add<DD>(contrib, lanepU + (int64_t)(lane - 1) * DD * DD * 2, v, DD);   // U^lane
+          dd_matvec_add<DD>(contrib, contrib, lanepU + (int64_t)(lane - 1) * DD * DD * 2, v, DD);   // U^lane
         }
       }
       double wsum[IIR_MAXD];
@@ -545,7 +506,7 @@ __global__ void __launch_bounds__(64, OP_WAVES) iir_onepass(const IirCoef c, con
         double nx[IIR_MAXD];
 #pragma unroll
         for (int i = 0; i < IIR_MAXD; ++i) nx[i] = 0.0;
-        dd_matvec_add<DD>(nx, lanepU + (int64_t)63 * DD * DD * 2, wsum, DD);
+        dd_matvec_add<DD>(nx, nx, lanepU + (int64_t)63 * DD * DD * 2, wsum, DD);
 #pragma unroll
         for (int i = 0; i < IIR_MAXD; ++i) wsum[i] = nx[i];
       }
@@ -567,7 +528,7 @@ __global__ void __launch_bounds__(64, OP_WAVES) iir_onepass(const IirCoef c, con
     double so[IIR_MAXD];
 #pragma unroll
     for (int i = 0; i < IIR_MAXD; ++i) so[i] = i < DD ? agg[i < DD ? i : 0] : 0.0;
-    dd_matvec_add<DD>(so, lanepU, sin_, DD);                 // U^1 (plain double where PLAIN allows it: 9.82 -> 9.65 ms at 256 x 1e7, inside the noise; not kept)
+    dd_matvec_add<DD>(so, so, lanepU, sin_, DD);                 // U^1 (plain double where PLAIN allows it: 9.82 -> 9.65 ms at 256 x 1e7, inside the noise; not kept)
     if (chunk + 1 < nchunks) {
 #pragma unroll
       for (int i = 0; i < DD; ++i) op_store(prefbuf + slot * DD + i, so[i]);
@@ -585,7 +546,7 @@ __global__ void __launch_bounds__(64, OP_WAVES) iir_onepass(const IirCoef c, con
   } else if (PLAIN) {
     matvec_add_plain<DD>(z, lanep1 + (int64_t)(lane - 1) * DD * DD * 2, sin_);
   } else {
-    dd_matvec_add<DD>(z, lanep1 + (int64_t)(lane - 1) * DD * DD * 2, sin_, DD);
+    dd_matvec_add<DD>(z, z, lanep1 + (int64_t)(lane - 1) * DD * DD * 2, sin_, DD);
   }
   const double bad = poisoned ? __builtin_nan("") : 0.0;
   if (whole) {
@@ -951,7 +912,7 @@ __global__ void __launch_bounds__(64, OPS_WAVES) iir_sampled(const IirCoef c, co
 #pragma unroll
           for (int i = 0; i < DD; ++i) contrib[i] = v[i];     // U^0
         } else {
-          dd_matvec_add<DD>(contrib, lanepU + (int64_t)(lane - 1) * DD * DD * 2, v, DD);   // U^lane
+          dd_matvec_add<DD>(contrib, contrib, lanepU + (int64_t)(lane - 1) * DD * DD * 2, v, DD);   // U^lane
         }
       }
       double wsum[IIR_MAXD];
@@ -968,7 +929,7 @@ __global__ void __launch_bounds__(64, OPS_WAVES) iir_sampled(const IirCoef c, co
         double nx[IIR_MAXD];
 #pragma unroll
         for (int i = 0; i < IIR_MAXD; ++i) nx[i] = 0.0;
-        dd_matvec_add<DD>(nx, lanepU + (int64_t)63 * DD * DD * 2, wsum, DD);
+        dd_matvec_add<DD>(nx, nx, lanepU + (int64_t)63 * DD * DD * 2, wsum, DD);
 #pragma unroll
         for (int i = 0; i < IIR_MAXD; ++i) wsum[i] = nx[i];
       }
@@ -987,7 +948,7 @@ __global__ void __launch_bounds__(64, OPS_WAVES) iir_sampled(const IirCoef c, co
     double so[IIR_MAXD];
 #pragma unroll
     for (int i = 0; i < IIR_MAXD; ++i) so[i] = i < DD ? agg[i < DD ? i : 0] : 0.0;
-    dd_matvec_add<DD>(so, lanepU, sin_, DD);
+    dd_matvec_add<DD>(so, so, lanepU, sin_, DD);
     if (chunk + 1 < nchunks) {
 #pragma unroll
       for (int i = 0; i < DD; ++i) op_store(prefbuf + slot * DD + i, so[i]);
@@ -1005,7 +966,7 @@ __global__ void __launch_bounds__(64, OPS_WAVES) iir_sampled(const IirCoef c, co
   } else if (PLAIN) {
     matvec_add_plain<DD>(z, lanepL + (int64_t)(lane - 1) * DD * DD * 2, sin_);
   } else {
-    dd_matvec_add<DD>(z, lanepL + (int64_t)(lane - 1) * DD * DD * 2, sin_, DD);
+    dd_matvec_add<DD>(z, z, lanepL + (int64_t)(lane - 1) * DD * DD * 2, sin_, DD);
   }
   const double bad = poisoned ? __builtin_nan("") : 0.0;
 #pragma unroll 1
@@ -1064,37 +1025,6 @@ __global__ void __launch_bounds__(256) iir_scale(const T* __restrict__ in, int64
     out[row * out_stride + j] = (T)(g * ((double)in[row * in_stride + j] - pre) + post);
 }
 
-int iir_fail(int code, const std::string& m) {
-  wfk_internal_set_error(m.c_str());
-  return code;
-}
-
-// Host-side transition matrices in quad precision.  In direct-form coordinates T is wildly
-// non-normal for clustered poles (entries ~1e5 while every eigenvalue is < 1): a T computed
-// by a double-precision recurrence is off by ~1e-9 relative, which the scan would amplify
-// into 1e-6 output errors.  Computed in __float128 and rounded once, T*S is as accurate as
-// the sequential filter itself.
-typedef __float128 quad;
-
-void quad_step(const IirCoef& c, quad x, quad* z) {
-  for (int s = 0; s < c.nsec; ++s) {
-    quad* zs = z + c.off[s];
-    const int ord = c.ord[s];
-    const quad y = (quad)c.b[s][0] * x + (ord > 0 ? zs[0] : (quad)0);
-    for (int i = 0; i + 1 < ord; ++i)
-      zs[i] = (quad)c.b[s][i + 1] * x - (quad)c.a[s][i + 1] * y + zs[i + 1];
-    if (ord > 0) zs[ord - 1] = (quad)c.b[s][ord] * x - (quad)c.a[s][ord] * y;
-    x = y;
-  }
-}
-
-void qmatmul(const std::vector<quad>& A, const std::vector<quad>& B, std::vector<quad>& C, int D) {
-  C.assign((size_t)D * D, (quad)0);
-  for (int i = 0; i < D; ++i)
-    for (int k = 0; k < D; ++k)
-      for (int j = 0; j < D; ++j) C[(size_t)i * D + j] += A[(size_t)i * D + k] * B[(size_t)k * D + j];
-}
-
 }  // namespace
 
 struct wfk_iir_plan {
@@ -1102,19 +1032,19 @@ struct wfk_iir_plan {
   int64_t n = 0, nblk = 0;
   int32_t batch = 0, kind = 0;
   int64_t ngrp = 0;          // groups of 64 blocks per row
-  double* state = nullptr;   // [batch][nblk][D]  group-local prefixes
-  double* grp = nullptr;     // [batch][ngrp][D]  group totals -> group start states
-  double* pw = nullptr;      // [7][D][D][2]   T^(2^k)
-  double* lanep = nullptr;   // [64][D][D][2]  T^(l+1)
-  double* pw2 = nullptr;     // the same for U = T^64
-  double* lanep2 = nullptr;
+  DevBuf<double> state;      // [batch][nblk][D]  group-local prefixes
+  DevBuf<double> grp;        // [batch][ngrp][D]  group totals -> group start states
+  DevBuf<double> pw;         // [7][D][D][2]   T^(2^k)
+  DevBuf<double> lanep;      // [64][D][D][2]  T^(l+1)
+  DevBuf<double> pw2;        // the same for U = T^64
+  DevBuf<double> lanep2;
   // A cascade of more than 4 biquads has no register-resident kernel (its 10+ state values
   // would go to scratch: 34 ms instead of 3.3 on 64 x 1e7).  It runs as consecutive passes of
   // <= 4 biquads each, in place on `out`, every pass with its own slice of zi / zf.
-  std::vector<wfk_iir_plan*> parts;
+  std::vector<std::unique_ptr<wfk_iir_plan>> parts;
   std::vector<int> part_off;     // state offset of each part
-  double* zi_tmp = nullptr;      // [batch][D_part] repacked state slices
-  double* zf_tmp = nullptr;
+  DevBuf<double> zi_tmp;         // [batch][D_part] repacked state slices
+  DevBuf<double> zf_tmp;
   double gain = 1.0;             // D == 0: y = gain * (x - pre) + post
   // single-pass form (biquad cascades with <= 4 states): chunk flags / aggregates / prefixes, ticket,
   // and the tables of the 32-step block transition T1 and of U = T1^64
@@ -1122,49 +1052,26 @@ struct wfk_iir_plan {
   bool op_plain = false;         // in-wave scan in plain double (entries of T1^1..T1^64 of order 1)
   int64_t op_chunks = 0;
   unsigned epoch = 0;
-  unsigned* op_status = nullptr;
-  unsigned* op_ticket = nullptr;
-  double* op_agg = nullptr;
-  double* op_pref = nullptr;
-  double* op_pw1 = nullptr;
-  double* op_lanep1 = nullptr;
-  double* op_lanepU = nullptr;
+  DevBuf<unsigned> op_status;
+  DevBuf<unsigned> op_ticket;
+  DevBuf<double> op_agg;
+  DevBuf<double> op_pref;
+  DevBuf<double> op_pw1;
+  DevBuf<double> op_lanep1;
+  DevBuf<double> op_lanepU;
   // iir_sampled: a lane owns a run of op_run samples: TL = T1^(op_run / OP_LB), UL = TL^64
-  double* op_pwL = nullptr;          // TL^(2^k)
-  double* op_lanepL = nullptr;       // TL^(l+1)
-  double* op_lanepUL = nullptr;      // UL^(l+1)
-  double* op_wdot = nullptr;         // [op_run][4]: end state of a run from zero state per unit sample at position k (dot-product form)
+  DevBuf<double> op_pwL;             // TL^(2^k)
+  DevBuf<double> op_lanepL;          // TL^(l+1)
+  DevBuf<double> op_lanepUL;         // UL^(l+1)
+  DevBuf<double> op_wdot;            // [op_run][4]: end state of a run from zero state per unit sample at position k (dot-product form)
   int op_run = 0;                    // samples per lane run of iir_sampled: OPS_RUN (dot-product form) | OPS_RUN_SWEEP
   bool op_plainL = false;
-  unsigned* op_fault = nullptr;      // host memory, mapped: raised by a chunk whose look-back timed out
-  unsigned* op_fault_dev = nullptr;  // ... its device address
+  MappedWord op_fault;               // host memory, mapped: raised by a chunk whose look-back timed out
 };
 
 extern "C" {
 
 int wfk_iir_plan_destroy(wfk_iir_plan* p) {
-  if (!p) return WFK_OK;
-  for (wfk_iir_plan* q : p->parts) wfk_iir_plan_destroy(q);
-  (void)hipFree(p->zi_tmp);
-  (void)hipFree(p->zf_tmp);
-  (void)hipFree(p->op_status);
-  (void)hipFree(p->op_ticket);
-  (void)hipFree(p->op_agg);
-  (void)hipFree(p->op_pref);
-  (void)hipFree(p->op_pw1);
-  (void)hipFree(p->op_lanep1);
-  (void)hipFree(p->op_lanepU);
-  (void)hipFree(p->op_pwL);
-  (void)hipFree(p->op_lanepL);
-  (void)hipFree(p->op_lanepUL);
-  (void)hipFree(p->op_wdot);
-  if (p->op_fault) (void)hipHostFree(p->op_fault);
-  (void)hipFree(p->state);
-  (void)hipFree(p->grp);
-  (void)hipFree(p->pw);
-  (void)hipFree(p->lanep);
-  (void)hipFree(p->pw2);
-  (void)hipFree(p->lanep2);
   delete p;
   return WFK_OK;
 }
@@ -1177,7 +1084,7 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
       batch > 65535)
     return iir_fail(WFK_EINVAL, "bad IIR arguments");
   if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return iir_fail(WFK_EINVAL, "IIR kind must be F64 or F32");
-  wfk_iir_plan* p = new wfk_iir_plan();
+  std::unique_ptr<wfk_iir_plan> p(new wfk_iir_plan());
   IirCoef& c = p->c;
   std::memset(&c, 0, sizeof c);
   {
@@ -1189,14 +1096,11 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
     int Dtot = 0;
     bool single_too_big = false;
     for (int s = 0; s < n_sections; ++s) {
-      if (orders[s] < 0) { delete p; return iir_fail(WFK_EINVAL, "negative section order"); }
+      if (orders[s] < 0) return iir_fail(WFK_EINVAL, "negative section order");
       single_too_big = single_too_big || orders[s] > IIR_MAXD;
       Dtot += orders[s];
     }
-    if (single_too_big) {
-      delete p;
-      return iir_fail(WFK_EUNSUP, "a single IIR section of order > 16 (factor it into a cascade)");
-    }
+    if (single_too_big) return iir_fail(WFK_EUNSUP, "a single IIR section of order > 16 (factor it into a cascade)");
     // Register-resident kernels exist for runs of EQUAL order: up to four first-order sections or
     // four biquads, single sections of order 3..8; anything else (mixed orders in one pass, two
     // sections of order 3, ...) would take the runtime-shaped kernel with its state in scratch
@@ -1214,15 +1118,10 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
     }
     const bool split = n_sections > IIR_MAXSEC || Dtot > IIR_MAXD || !one_run;
     if (split) {
-      int ndev = 0;
-      if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        (void)hipGetLastError();
-        delete p;
-        return iir_fail(WFK_EHIP, "no HIP device visible");
-      }
+      if (!iir_have_device()) return iir_fail(WFK_EHIP, "no HIP device visible");
       c.nsec = 0; c.D = Dtot;
       p->n = n; p->batch = batch; p->kind = kind;
-      if (n == 0) { *out = p; return WFK_OK; }
+      if (n == 0) { *out = p.release(); return WFK_OK; }
       int s0 = 0, pos0 = 0, doff = 0;
       while (s0 < n_sections) {
         // greedy run of equal orders, as long as a register-resident kernel takes it
@@ -1235,38 +1134,33 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
         }
         wfk_iir_plan* q = nullptr;
         int rc = wfk_iir_plan_create(cnt, orders + s0, b + pos0, a + pos0, n, batch, kind, &q);
-        if (rc) { wfk_iir_plan_destroy(p); return rc; }
-        p->parts.push_back(q);
+        if (rc) return rc;
+        p->parts.emplace_back(q);
         p->part_off.push_back(doff);
         s0 += cnt; pos0 += pp; doff += dd;
       }
-      if (hipMalloc(&p->zi_tmp, (size_t)batch * IIR_MAXD * 8) != hipSuccess ||
-          hipMalloc(&p->zf_tmp, (size_t)batch * IIR_MAXD * 8) != hipSuccess) {
-        wfk_iir_plan_destroy(p);
+      if (!p->zi_tmp.alloc((size_t)batch * IIR_MAXD * 8) || !p->zf_tmp.alloc((size_t)batch * IIR_MAXD * 8))
         return iir_fail(WFK_ENOMEM, "IIR buffer allocation failed");
-      }
-      *out = p;
+      *out = p.release();
       return WFK_OK;
     }
   }
   c.nsec = n_sections;
   int D = 0, pos = 0;
+  std::vector<double> bn, an;   // the normalised coefficients, sections back to back (the table builders' layout)
   for (int s = 0; s < n_sections; ++s) {
     const int ord = orders[s];
-    if (ord < 0 || ord > IIR_MAXD || D + ord > IIR_MAXD) {
-      delete p;
+    if (ord < 0 || ord > IIR_MAXD || D + ord > IIR_MAXD)
       return iir_fail(WFK_EINVAL, "IIR order too large (total state dimension <= 16)");
-    }
     const double a0 = a[pos];
-    if (!(a0 != 0.0) || !std::isfinite(a0)) {
-      delete p;
-      return iir_fail(WFK_EINVAL, "a[0] must be finite and non-zero");
-    }
+    if (!(a0 != 0.0) || !std::isfinite(a0)) return iir_fail(WFK_EINVAL, "a[0] must be finite and non-zero");
     c.ord[s] = ord;
     c.off[s] = D;
     for (int i = 0; i <= ord; ++i) {   // scipy normalises by a[0]
       c.b[s][i] = b[pos + i] / a0;
       c.a[s][i] = a[pos + i] / a0;
+      bn.push_back(c.b[s][i]);
+      an.push_back(c.a[s][i]);
     }
     pos += ord + 1;
     D += ord;
@@ -1275,67 +1169,27 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
   p->n = n; p->batch = batch; p->kind = kind;
   p->nblk = n > 0 ? (n + IIR_LB - 1) / IIR_LB : 0;
   p->ngrp = (p->nblk + 63) / 64;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    (void)hipGetLastError();
-    delete p;
-    return iir_fail(WFK_EHIP, "no HIP device visible");
-  }
+  if (!iir_have_device()) return iir_fail(WFK_EHIP, "no HIP device visible");
   if (n == 0 || D == 0) {
     // order-0 sections only: a pure gain (lfilter with len(a) == len(b) == 1 per section)
     p->gain = 1.0;
     for (int s = 0; s < n_sections; ++s) p->gain *= c.b[s][0];
-    *out = p;
+    *out = p.release();
     return WFK_OK;
   }
-  // LB-step transition matrix T: column i = homogeneous response to unit state e_i
-  std::vector<quad> T((size_t)D * D);
-  for (int i = 0; i < D; ++i) {
-    quad z[IIR_MAXD];
-    for (int r = 0; r < IIR_MAXD; ++r) z[r] = 0;
-    z[i] = 1;
-    for (int k = 0; k < IIR_LB; ++k) quad_step(c, (quad)0, z);
-    for (int r = 0; r < D; ++r) T[(size_t)r * D + i] = z[r];
-  }
-  auto put = [](std::vector<double>& dst, size_t at, quad q) {   // quad -> (hi, lo)
-    const double hi = (double)q;
-    dst[at] = hi;
-    dst[at + 1] = (double)(q - (quad)hi);
-  };
   // tables of a base matrix B: pw[k] = B^(2^k) (k < 7), lanep[l] = B^(l+1) (l < 64); returns B^64
   auto tables = [&](const std::vector<quad>& B, std::vector<double>& pw, std::vector<double>& lanep) {
     pw.assign((size_t)7 * D * D * 2, 0.0);
     lanep.assign((size_t)64 * D * D * 2, 0.0);
-    std::vector<quad> cur = B, nxt;
-    for (int k = 0; k < 7; ++k) {
-      for (size_t e = 0; e < cur.size(); ++e) put(pw, ((size_t)k * D * D + e) * 2, cur[e]);
-      qmatmul(cur, cur, nxt, D);
-      cur = nxt;
-    }
-    cur = B;
-    std::vector<quad> last;
-    for (int l = 0; l < 64; ++l) {
-      for (size_t e = 0; e < cur.size(); ++e) put(lanep, ((size_t)l * D * D + e) * 2, cur[e]);
-      last = cur;
-      qmatmul(cur, B, nxt, D);
-      cur = nxt;
-    }
-    return last;
+    return iir_power_tables(B, D, 1, pw.data(), lanep.data());
   };
+  auto transition = [&](int steps) { return iir_transition(n_sections, orders, bn.data(), an.data(), D, steps); };
   std::vector<double> pw, lanep, pw2, lanep2;
-  const std::vector<quad> U = tables(T, pw, lanep);   // U = T^64: one group
+  const std::vector<quad> U = tables(transition(IIR_LB), pw, lanep);   // T = LB-step transition; U = T^64: one group
   tables(U, pw2, lanep2);
-  auto upload = [](double** dst, const std::vector<double>& src) {
-    return hipMalloc(dst, src.size() * 8) == hipSuccess &&
-           hipMemcpy(*dst, src.data(), src.size() * 8, hipMemcpyHostToDevice) == hipSuccess;
-  };
-  bool ok = hipMalloc(&p->state, (size_t)batch * p->nblk * D * 8) == hipSuccess;
-  ok = ok && hipMalloc(&p->grp, (size_t)batch * p->ngrp * D * 8) == hipSuccess;
-  ok = ok && upload(&p->pw, pw) && upload(&p->lanep, lanep) && upload(&p->pw2, pw2) && upload(&p->lanep2, lanep2);
-  if (!ok) {
-    wfk_iir_plan_destroy(p);
+  if (!p->state.alloc((size_t)batch * p->nblk * D * 8) || !p->grp.alloc((size_t)batch * p->ngrp * D * 8) ||
+      !p->pw.upload(pw) || !p->lanep.upload(lanep) || !p->pw2.upload(pw2) || !p->lanep2.upload(lanep2))
     return iir_fail(WFK_ENOMEM, "IIR buffer allocation failed");
-  }
   // single-pass form: one or two biquads (state dimension <= 4), rows long enough to chain
   {
     // shapes: one or two biquads, or up to four FIRST-order sections -- the cascade of exponential
@@ -1357,14 +1211,7 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
     const bool band = batch >= 8 && batch < 64 && (double)batch * (double)n >= 6e7;
     const bool want = on ? on[0] != '0' : !band;
     if (biq && n >= 4 * OP_CHUNK && want) {
-      std::vector<quad> T1((size_t)D * D);
-      for (int i = 0; i < D; ++i) {
-        quad z[IIR_MAXD];
-        for (int r = 0; r < IIR_MAXD; ++r) z[r] = 0;
-        z[i] = 1;
-        for (int k = 0; k < OP_LB; ++k) quad_step(c, (quad)0, z);
-        for (int r = 0; r < D; ++r) T1[(size_t)r * D + i] = z[r];
-      }
+      const std::vector<quad> T1 = transition(OP_LB);
       std::vector<double> pw1, lanep1, pwU, lanepU;
       const std::vector<quad> U1 = tables(T1, pw1, lanep1);    // U1 = T1^64: one chunk
       tables(U1, pwU, lanepU);                                  // U1^(l+1), l < 64: the look-back window
@@ -1374,7 +1221,7 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
       for (int attempt = 0; attempt < 2; ++attempt) {
         pwL.clear(); lanepL.clear(); pwUL.clear(); lanepUL.clear();
         std::vector<quad> TL = T1, nxt;
-        for (int k = 1; k < p->op_run / OP_LB; ++k) { qmatmul(TL, T1, nxt, D); TL = nxt; }
+        for (int k = 1; k < p->op_run / OP_LB; ++k) { iir_qmatmul(TL, T1, nxt, D); TL.swap(nxt); }
         const std::vector<quad> UL = tables(TL, pwL, lanepL);
         tables(UL, pwUL, lanepUL);
         double tm = 0.0;
@@ -1388,7 +1235,8 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
       for (int k = 0; k < p->op_run && p->op_plainL; ++k) {
         quad z[IIR_MAXD];
         for (int r = 0; r < IIR_MAXD; ++r) z[r] = 0;
-        for (int t = k; t < p->op_run; ++t) quad_step(c, t == k ? (quad)1 : (quad)0, z);
+        for (int t = k; t < p->op_run; ++t)
+          iir_quad_step(n_sections, orders, bn.data(), an.data(), t == k ? (quad)1 : (quad)0, z);
         for (int r = 0; r < D && r < 4; ++r) wdot[(size_t)k * 4 + r] = (double)z[r];
       }
       double tmax = 0.0;                                        // largest entry of T1^1 .. T1^64 (hi words)
@@ -1397,20 +1245,12 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
       p->op_plain = tmax < 16.0 && !(ddenv && ddenv[0] == '1');
       p->op_chunks = (n + OP_CHUNK - 1) / OP_CHUNK;
       const size_t slots = (size_t)batch * (size_t)p->op_chunks;
-      bool ok1 = hipMalloc(&p->op_status, slots * 4) == hipSuccess &&
-                 hipMemset(p->op_status, 0, slots * 4) == hipSuccess &&
-                 hipMalloc(&p->op_ticket, (size_t)batch * 64) == hipSuccess &&
-                 hipMalloc(&p->op_agg, slots * D * 8) == hipSuccess &&
-                 hipMalloc(&p->op_pref, slots * D * 8) == hipSuccess && upload(&p->op_pw1, pw1) &&
-                 upload(&p->op_lanep1, lanep1) && upload(&p->op_lanepU, lanepU) && upload(&p->op_pwL, pwL) &&
-                 upload(&p->op_lanepL, lanepL) && upload(&p->op_lanepUL, lanepUL) && upload(&p->op_wdot, wdot);
-      ok1 = ok1 && hipHostMalloc((void**)&p->op_fault, 64, hipHostMallocMapped) == hipSuccess &&
-            hipHostGetDevicePointer((void**)&p->op_fault_dev, p->op_fault, 0) == hipSuccess;
-      if (!ok1) {
-        wfk_iir_plan_destroy(p);
+      if (!p->op_status.alloc(slots * 4) || hipMemset(p->op_status.get(), 0, slots * 4) != hipSuccess ||
+          !p->op_ticket.alloc((size_t)batch * 64) || !p->op_agg.alloc(slots * D * 8) ||
+          !p->op_pref.alloc(slots * D * 8) || !p->op_pw1.upload(pw1) || !p->op_lanep1.upload(lanep1) ||
+          !p->op_lanepU.upload(lanepU) || !p->op_pwL.upload(pwL) || !p->op_lanepL.upload(lanepL) ||
+          !p->op_lanepUL.upload(lanepUL) || !p->op_wdot.upload(wdot) || !p->op_fault.alloc())
         return iir_fail(WFK_ENOMEM, "IIR single-pass buffer allocation failed");
-      }
-      *p->op_fault = 0;
       // ONE section of order 3 / 4 whose transition powers grow past 1e3 (clustered poles: butter(4, 0.022) as a single
       // (b, a), 3.2e3): the block start states this form re-injects every 32 samples as doubles cost it a digit against
       // the three-launch form (iirchain_soak seed 12713, against a long-double recursion: 1.1e-10 vs 2.4e-11 of peak;
@@ -1418,7 +1258,7 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
       p->onepass = (on && on[0] == '1') || !(orders[0] >= 3 && tmax > 1e3);
     }
   }
-  *out = p;
+  *out = p.release();
   return WFK_OK;
 }
 
@@ -1431,12 +1271,12 @@ static void iir_launch_t(wfk_iir_plan* p, const void* in, int64_t is, void* out,
                          const double* zi, double* zf, double initial, double post, hipStream_t s) {
   const dim3 g((unsigned)p->ngrp, (unsigned)p->batch);
   hipLaunchKernelGGL((iir_pass<T, false, NSEC, ORD>), g, dim3(64), 0, s, p->c, (const T*)in, is,
-                     (T*)nullptr, (int64_t)0, p->state, p->grp, p->pw, p->lanep, (double*)nullptr,
+                     (T*)nullptr, (int64_t)0, p->state.get(), p->grp.get(), p->pw.get(), p->lanep.get(), (double*)nullptr,
                      p->n, p->nblk, initial, 0.0);
-  hipLaunchKernelGGL(iir_scan, dim3((unsigned)p->batch), dim3(64), 0, s, p->grp, p->pw2, p->lanep2,
+  hipLaunchKernelGGL(iir_scan, dim3((unsigned)p->batch), dim3(64), 0, s, p->grp.get(), p->pw2.get(), p->lanep2.get(),
                      zi, p->ngrp, p->c.D);
   hipLaunchKernelGGL((iir_pass<T, true, NSEC, ORD>), g, dim3(64), 0, s, p->c, (const T*)in, is,
-                     (T*)out, os, p->state, p->grp, p->pw, p->lanep, zf, p->n, p->nblk, initial,
+                     (T*)out, os, p->state.get(), p->grp.get(), p->pw.get(), p->lanep.get(), zf, p->n, p->nblk, initial,
                      post);
 }
 
@@ -1483,10 +1323,10 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
   if (!p->parts.empty()) {
     const size_t D = (size_t)p->c.D;
     for (size_t i = 0; i < p->parts.size(); ++i) {
-      wfk_iir_plan* q = p->parts[i];
+      wfk_iir_plan* q = p->parts[i].get();
       const size_t Di = (size_t)q->c.D, off = (size_t)p->part_off[i];
       if (zi_dev && Di > 0 &&
-          hipMemcpy2DAsync(p->zi_tmp, Di * 8, zi_dev + off, D * 8, Di * 8, (size_t)p->batch,
+          hipMemcpy2DAsync(p->zi_tmp.get(), Di * 8, zi_dev + off, D * 8, Di * 8, (size_t)p->batch,
                            hipMemcpyDeviceToDevice, s) != hipSuccess)
         return iir_fail(WFK_EHIP, "IIR state repack failed");
       // the DC offset comes off before the first pass and goes back on after the last one only:
@@ -1494,22 +1334,22 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
       // first four sections), which an fp32 buffer holding signal + offset would wipe out
       const bool first = i == 0, last = i + 1 == p->parts.size();
       int rc = iir_apply_impl(q, first ? in_dev : out_dev, first ? in_stride : out_stride, out_dev,
-                              out_stride, zi_dev ? p->zi_tmp : nullptr, zf_dev ? p->zf_tmp : nullptr,
+                              out_stride, zi_dev ? p->zi_tmp.get() : nullptr, zf_dev ? p->zf_tmp.get() : nullptr,
                               first ? initial : 0.0, last ? post : 0.0, hip_stream, first ? src : nullptr);
       if (rc == WFK_ETIMEOUT)   // a part reported an earlier stall: no part of this plan may wait on a chain again
-        for (wfk_iir_plan* r : p->parts) r->onepass = false;
+        for (auto& r : p->parts) r->onepass = false;
       if (rc) return rc;
       if (zf_dev && Di > 0 &&
-          hipMemcpy2DAsync(zf_dev + off, D * 8, p->zf_tmp, Di * 8, Di * 8, (size_t)p->batch,
+          hipMemcpy2DAsync(zf_dev + off, D * 8, p->zf_tmp.get(), Di * 8, Di * 8, (size_t)p->batch,
                            hipMemcpyDeviceToDevice, s) != hipSuccess)
         return iir_fail(WFK_EHIP, "IIR state repack failed");
     }
     return WFK_OK;
   }
-  if (p->onepass && *(volatile unsigned*)p->op_fault != 0) {
+  if (p->onepass && *p->op_fault.host() != 0) {
     // an earlier launch of this plan timed out in a look-back (its outputs hold NaN): say so now, and
     // serve this plan in the three-launch form from here on (no chained waits, cannot time out)
-    *(volatile unsigned*)p->op_fault = 0;
+    *p->op_fault.host() = 0;
     p->onepass = false;
     return iir_fail(WFK_ETIMEOUT, "IIR single pass: a look-back timed out in an EARLIER launch of this plan (a stalled or "
                                   "preempted predecessor chunk); its outputs hold NaN. The plan now runs in the three-launch form: launch again");
@@ -1519,7 +1359,7 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
     int spin_limit = OP_SPIN;
     if (const char* e = getenv("WFK_IIR_SPIN")) spin_limit = atoi(e);   // (tests: force the timeout)
     // tickets restart at 0; the flags of earlier launches are told apart by the epoch
-    if (hipMemsetAsync(p->op_ticket, 0, (size_t)p->batch * 64, s) != hipSuccess)
+    if (hipMemsetAsync(p->op_ticket.get(), 0, (size_t)p->batch * 64, s) != hipSuccess)
       return iir_fail(WFK_EHIP, "IIR ticket reset failed");
     const unsigned epoch = ++p->epoch;
     // Few long rows: with one chunk per workgroup 2304 / rows chunks of a row are in flight, and a
@@ -1548,18 +1388,18 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
 #define OP_LAUNCH_K(KERNEL, PL, FIRST, TABS, NCH, TT, NS, OR)                                                     \
     if (PL)                                                                                                   \
     hipLaunchKernelGGL((KERNEL<TT, NS, OR, true>), dim3(total), dim3(64), 0, s, p->c, FIRST,                   \
-                       (TT*)out_dev, out_stride, p->op_status, p->op_agg, p->op_pref, p->op_ticket,              \
+                       (TT*)out_dev, out_stride, p->op_status.get(), p->op_agg.get(), p->op_pref.get(), p->op_ticket.get(),             \
                        TABS, zi_dev, zf_dev, p->n, NCH, (int)p->batch, epoch,                                     \
-                       initial, post, persist, p->op_fault_dev, spin_limit);                                            \
+                       initial, post, persist, p->op_fault.dev(), spin_limit);                                            \
     else                                                                                                       \
     hipLaunchKernelGGL((KERNEL<TT, NS, OR, false>), dim3(total), dim3(64), 0, s, p->c, FIRST,                  \
-                       (TT*)out_dev, out_stride, p->op_status, p->op_agg, p->op_pref, p->op_ticket,              \
+                       (TT*)out_dev, out_stride, p->op_status.get(), p->op_agg.get(), p->op_pref.get(), p->op_ticket.get(),             \
                        TABS, zi_dev, zf_dev, p->n, NCH, (int)p->batch, epoch,                                     \
-                       initial, post, persist, p->op_fault_dev, spin_limit)
+                       initial, post, persist, p->op_fault.dev(), spin_limit)
 #define OP_COMMA ,
 #define OP_LAUNCH(TT, NS, OR)                                                                                     \
-    if (src) { OP_LAUNCH_K(iir_sampled, p->op_plainL, *src, p->op_pwL OP_COMMA p->op_lanepL OP_COMMA p->op_lanepUL OP_COMMA p->op_wdot, nchunks, TT, NS, OR); } \
-    else { OP_LAUNCH_K(iir_onepass, p->op_plain, (const TT*)in_dev OP_COMMA in_stride, p->op_pw1 OP_COMMA p->op_lanep1 OP_COMMA p->op_lanepU, p->op_chunks, TT, NS, OR); }
+    if (src) { OP_LAUNCH_K(iir_sampled, p->op_plainL, *src, p->op_pwL.get() OP_COMMA p->op_lanepL.get() OP_COMMA p->op_lanepUL.get() OP_COMMA p->op_wdot.get(), nchunks, TT, NS, OR); } \
+    else { OP_LAUNCH_K(iir_onepass, p->op_plain, (const TT*)in_dev OP_COMMA in_stride, p->op_pw1.get() OP_COMMA p->op_lanep1.get() OP_COMMA p->op_lanepU.get(), p->op_chunks, TT, NS, OR); }
 #ifdef OPS_ONLY_22     /* A/B builds (tools/iirchain_ablate.sh): one shape, a third of the compile time */
 #define OP_SHAPES(TT)  do { OP_LAUNCH(TT, 2, 2); } while (0)
 #else
@@ -1602,18 +1442,18 @@ extern "C" int wfk_iir_status(wfk_iir_plan* p, void* hip_stream) {
 
   bool fault = false;
   auto look = [&](wfk_iir_plan* q) {
-    if (q->op_fault && *(volatile unsigned*)q->op_fault != 0) {
-      *(volatile unsigned*)q->op_fault = 0;
+    if (q->op_fault.host() && *q->op_fault.host() != 0) {
+      *q->op_fault.host() = 0;
       q->onepass = false;
       fault = true;
     }
   };
   look(p);
-  for (wfk_iir_plan* q : p->parts) look(q);
+  for (auto& q : p->parts) look(q.get());
   if (fault) {
     // one chunk chain stalled: the retry must not be able to time out in ANOTHER part either
     p->onepass = false;
-    for (wfk_iir_plan* q : p->parts) q->onepass = false;
+    for (auto& q : p->parts) q->onepass = false;
   }
   if (fault)
     return iir_fail(WFK_ETIMEOUT, "IIR single pass: a look-back timed out (a stalled or preempted predecessor chunk); the outputs "
@@ -1643,26 +1483,25 @@ struct wfk_chain_iir_plan {
   std::string why;                 // why the sampler does not run inside the IIR pass
   int32_t kind = 0, n_channels = 0;
   int64_t n = 0;
-  void* d_tables = nullptr;        // fused path: the plan compiled for the chunk geometry (a lane owns 32 consecutive samples)
+  DevBuf<char> d_tables;           // fused path: the plan compiled for the chunk geometry (a lane owns 32 consecutive samples)
   IirSampArgs sa{};
   int64_t table_bytes = 0;
-  void* workspace = nullptr;       // FIR stage: the filtered rows between the IIR pass and the FIR
+  DevBuf<char> workspace;          // FIR stage: the filtered rows between the IIR pass and the FIR
+  ~wfk_chain_iir_plan() {          // (the buffers go after this body: nothing on the device reads them any more)
+    if (d_tables || workspace) (void)hipDeviceSynchronize();
+    wfk_plan_destroy(sampler);
+    wfk_iir_plan_destroy(iir);
+    wfk_fir_plan_destroy(fir);
+  }
 };
 
 static wfk_iir_plan* chain_first_stage(wfk_chain_iir_plan* p) {
-  return p->iir->parts.empty() ? p->iir : p->iir->parts[0];
+  return p->iir->parts.empty() ? p->iir : p->iir->parts[0].get();
 }
 
 extern "C" {
 
 int wfk_chain_iir_plan_destroy(wfk_chain_iir_plan* p) {
-  if (!p) return WFK_OK;
-  if (p->d_tables || p->workspace) (void)hipDeviceSynchronize();
-  (void)hipFree(p->d_tables);
-  (void)hipFree(p->workspace);
-  wfk_plan_destroy(p->sampler);
-  wfk_iir_plan_destroy(p->iir);
-  wfk_fir_plan_destroy(p->fir);
   delete p;
   return WFK_OK;
 }
@@ -1675,9 +1514,8 @@ int wfk_chain_iir_plan_create(const wfk_program* prog, const wfk_grid* grid, int
   if (!prog || !grid) return iir_fail(WFK_EINVAL, "null argument");
   if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return iir_fail(WFK_EINVAL, "chain kind must be F64 or F32");
   if (ker_host && K < 1) return iir_fail(WFK_EINVAL, "empty FIR kernel");
-  wfk_chain_iir_plan* p = nullptr;
   try {
-    p = new wfk_chain_iir_plan();
+    std::unique_ptr<wfk_chain_iir_plan> p(new wfk_chain_iir_plan());
     p->kind = kind;
     p->n = grid->n;
     p->n_channels = prog->n_channels;
@@ -1686,15 +1524,13 @@ int wfk_chain_iir_plan_create(const wfk_program* prog, const wfk_grid* grid, int
     if (!rc && ker_host)
       rc = ker_per_row ? wfk_fir_plan_create_rows(ker_host, K, grid->n, std::max(1, prog->n_channels), kind, &p->fir)
                        : wfk_fir_plan_create(ker_host, K, grid->n, std::max(1, prog->n_channels), kind, &p->fir);
-    if (rc) { wfk_chain_iir_plan_destroy(p); return rc; }
-    if (p->n == 0 || p->n_channels == 0) { *out = p; return WFK_OK; }
+    if (rc) return rc;
+    if (p->n == 0 || p->n_channels == 0) { *out = p.release(); return WFK_OK; }
     const size_t es = kind == WFK_OUT_F32 ? 4 : 8;
-    if (p->fir && hipMalloc(&p->workspace, (size_t)p->n_channels * (size_t)p->n * es) != hipSuccess) {
-      wfk_chain_iir_plan_destroy(p);
+    if (p->fir && !p->workspace.alloc((size_t)p->n_channels * (size_t)p->n * es))
       return iir_fail(WFK_ENOMEM, "chain workspace allocation failed");
-    }
     // ---- can the sampler run inside the first IIR pass? ----------------------------------------------
-    wfk_iir_plan* first = chain_first_stage(p);
+    wfk_iir_plan* first = chain_first_stage(p.get());
     const char* off = getenv("WFK_CHAIN_UNFUSED");
     HostPlan H;
     std::string err;
@@ -1766,12 +1602,8 @@ int wfk_chain_iir_plan_create(const wfk_program* prog, const wfk_grid* grid, int
       std::memcpy(stage.data() + o_pc, H.pieces.data(), b_pc);
       std::memcpy(stage.data() + o_pa, H.params.data(), b_pa);
       std::memcpy(stage.data() + o_cf, chunk_first.data(), b_cf);
-      if (hipMalloc(&p->d_tables, total) != hipSuccess ||
-          hipMemcpy(p->d_tables, stage.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
-        wfk_chain_iir_plan_destroy(p);
-        return iir_fail(WFK_ENOMEM, "chain table allocation failed");
-      }
-      char* base = static_cast<char*>(p->d_tables);
+      if (!p->d_tables.upload(stage)) return iir_fail(WFK_ENOMEM, "chain table allocation failed");
+      char* base = p->d_tables.get();
       IirSampArgs& sa = p->sa;
       sa.channels = reinterpret_cast<const DevChannel*>(base);
       sa.pieces = reinterpret_cast<const DevPiece*>(base + o_pc);
@@ -1783,10 +1615,9 @@ int wfk_chain_iir_plan_create(const wfk_program* prog, const wfk_grid* grid, int
       p->table_bytes = (int64_t)total;
       p->fused = true;
     }
-    *out = p;
+    *out = p.release();
     return WFK_OK;
   } catch (const std::bad_alloc&) {
-    if (p) wfk_chain_iir_plan_destroy(p);
     return iir_fail(WFK_ENOMEM, "out of host memory while building the chain plan");
   }
 }
@@ -1833,7 +1664,7 @@ int wfk_chain_iir_launch(wfk_chain_iir_plan* p, void* out_dev, int64_t out_strid
   if (p->n == 0 || p->n_channels == 0) return WFK_OK;
   if (!out_dev) return iir_fail(WFK_EINVAL, "null output");
   if (out_stride < p->n) return iir_fail(WFK_EINVAL, "out_stride smaller than n");
-  void* mid = p->fir ? p->workspace : out_dev;
+  void* mid = p->fir ? p->workspace.get() : out_dev;
   const int64_t mid_stride = p->fir ? p->n : out_stride;
   int rc;
   if (wfk_chain_iir_is_fused(p)) {
@@ -1843,7 +1674,7 @@ int wfk_chain_iir_launch(wfk_chain_iir_plan* p, void* out_dev, int64_t out_strid
     if (!rc) rc = iir_apply_impl(p->iir, mid, mid_stride, mid, mid_stride, zi_dev, zf_dev, initial, initial, hip_stream);
   }
   if (rc) return rc;
-  if (p->fir) return wfk_fir_apply(p->fir, p->workspace, p->n, out_dev, out_stride, hip_stream);
+  if (p->fir) return wfk_fir_apply(p->fir, p->workspace.get(), p->n, out_dev, out_stride, hip_stream);
   return WFK_OK;
 }
 

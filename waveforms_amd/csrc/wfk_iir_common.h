@@ -1,0 +1,194 @@
+// wfk_iir_common.h -- what every IIR form shares (wfk_iir.hip: three-launch scan, iir_onepass, iir_sampled;
+// wfk_iir_rows.hip: one cascade per row): the cascade step, the double-double mat-vec that applies the
+// transition tables, the quad-precision builder of those tables, and the owner of a plan's device memory.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <utility>
+#include <vector>
+
+extern "C" void wfk_internal_set_error(const char* msg);
+
+namespace {
+
+// ---- device ---------------------------------------------------------------------------------------------------
+
+// One sample through a cascade of NSEC direct-form-II-transposed sections of order ORD each:
+//     y = b0*x + z[0];   z[i] = b[i+1]*x - a[i+1]*y + z[i+1];   z[ord-1] = b[ord]*x - a[ord]*y
+// b(s, i), a(s, i): coefficient i of section s, wherever the caller keeps them (a kernel argument, registers);
+// section s has its state at z + s * ORD.  Every index is a constant, so the state stays in registers.
+// (Accessors and the array reference, not pointers: this form compiles to the code of the kernels' own loops.)
+template <int NSEC, int ORD, int N, class CB, class CA>
+__device__ __forceinline__ double iir_cascade_step(CB b, CA a, double x, double (&z)[N]) {
+#pragma unroll
+  for (int s = 0; s < NSEC; ++s) {
+    const double y = b(s, 0) * x + z[s * ORD];
+#pragma unroll
+    for (int i = 0; i + 1 < ORD; ++i) z[s * ORD + i] = b(s, i + 1) * x - a(s, i + 1) * y + z[s * ORD + i + 1];
+    z[s * ORD + ORD - 1] = b(s, ORD) * x - a(s, ORD) * y;
+    x = y;
+  }
+  return x;
+}
+
+// (sh + sl) += (th + tl) * x in double-double (TwoProd via fma, TwoSum)
+__device__ __forceinline__ void dd_acc(double& sh, double& sl, double th, double tl, double x) {
+  const double p = th * x;
+  const double e = fma(th, x, -p) + tl * x;
+  const double s = sh + p;
+  const double bb = s - sh;
+  sl += ((sh - (s - bb)) + (p - bb)) + e;
+  sh = s;
+}
+
+// r = v + M c in double-double; M = D x D (hi, lo) pairs.  DD > 0: compile-time dimension, the first DD entries
+// of the arrays (extent N >= DD) are used; DD == 0: D_rt at run time.  r may be v; c is neither.
+template <int DD, int N>
+__device__ __forceinline__ void dd_matvec_add(double (&r)[N], const double (&v)[N], const double* M,
+                                              const double (&c)[N], int D_rt = DD) {
+  const int D = DD > 0 ? DD : D_rt;
+  double nv[N];
+#pragma unroll
+  for (int i = 0; i < (DD > 0 ? DD : N); ++i) {
+    if (i < D) {
+      double sh = v[i], sl = 0.0;
+#pragma unroll
+      for (int j = 0; j < (DD > 0 ? DD : N); ++j)
+        if (j < D) dd_acc(sh, sl, M[(i * D + j) * 2], M[(i * D + j) * 2 + 1], c[j]);
+      nv[i] = sh + sl;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < (DD > 0 ? DD : N); ++i)
+    if (i < D) r[i] = nv[i];
+}
+
+// ---- host: transition tables in quad precision ------------------------------------------------------------------
+// In direct-form coordinates the k-step transition matrix T is wildly non-normal for clustered poles (entries
+// ~1e5 while every eigenvalue is < 1): a T computed by a double-precision recurrence is off by ~1e-9 relative,
+// which a scan would amplify into 1e-6 output errors.  Computed in __float128 and stored as (hi, lo) pairs that
+// the kernels apply in double-double, T*S is as accurate as the sequential filter itself.
+// (Host functions only: no kernel touches a quad.)
+typedef __float128 quad;
+
+// one sample through the cascade; b, a: normalised coefficients, sections back to back (orders[s] + 1 each);
+// z: the states, back to back
+inline void iir_quad_step(int nsec, const int32_t* orders, const double* b, const double* a, quad x, quad* z) {
+  for (int s = 0; s < nsec; ++s) {
+    const int ord = orders[s];
+    const quad y = (quad)b[0] * x + (ord > 0 ? z[0] : (quad)0);
+    for (int i = 0; i + 1 < ord; ++i) z[i] = (quad)b[i + 1] * x - (quad)a[i + 1] * y + z[i + 1];
+    if (ord > 0) z[ord - 1] = (quad)b[ord] * x - (quad)a[ord] * y;
+    x = y;
+    b += ord + 1; a += ord + 1; z += ord;
+  }
+}
+
+// the D x D transition matrix over `steps` samples: column i = homogeneous response to the unit state e_i
+inline std::vector<quad> iir_transition(int nsec, const int32_t* orders, const double* b, const double* a, int D,
+                                        int steps) {
+  std::vector<quad> T((size_t)D * D), z((size_t)D);
+  for (int i = 0; i < D; ++i) {
+    for (int r = 0; r < D; ++r) z[r] = r == i ? 1 : 0;
+    for (int k = 0; k < steps; ++k) iir_quad_step(nsec, orders, b, a, (quad)0, z.data());
+    for (int r = 0; r < D; ++r) T[(size_t)r * D + i] = z[r];
+  }
+  return T;
+}
+
+// C = A B (C is neither); every element is summed with k ascending from zero
+inline void iir_qmatmul(const std::vector<quad>& A, const std::vector<quad>& B, std::vector<quad>& C, int D) {
+  C.resize((size_t)D * D);
+  for (int i = 0; i < D; ++i)
+    for (int j = 0; j < D; ++j) {
+      quad acc = 0;
+      for (int k = 0; k < D; ++k) acc += A[(size_t)i * D + k] * B[(size_t)k * D + j];
+      C[(size_t)i * D + j] = acc;
+    }
+}
+
+// Tables of a base matrix B as (hi, lo) pairs: pw[k] = B^(2^k), k < 7; lanep[l] = B^(first_power + l), l < 64
+// (pw: 7 * D * D * 2 doubles, lanep: 64 * D * D * 2).  Returns B^64, the product B^63 B of the lanep chain.
+inline std::vector<quad> iir_power_tables(const std::vector<quad>& B, int D, int first_power, double* pw,
+                                          double* lanep) {
+  const size_t MM = (size_t)D * D * 2;
+  auto put = [&](double* at, const std::vector<quad>& M) {   // quad -> (hi, lo)
+    for (size_t e = 0; e < M.size(); ++e) {
+      const double hi = (double)M[e];
+      at[2 * e] = hi;
+      at[2 * e + 1] = (double)(M[e] - (quad)hi);
+    }
+  };
+  std::vector<quad> cur = B, nxt;
+  for (int k = 0; k < 7; ++k) {
+    put(pw + k * MM, cur);
+    iir_qmatmul(cur, cur, nxt, D);
+    cur.swap(nxt);
+  }
+  cur = B;
+  if (first_power == 0)
+    for (int e = 0; e < D * D; ++e) cur[e] = (e / D == e % D) ? 1 : 0;
+  for (int l = 0; l < 64; ++l) {
+    put(lanep + l * MM, cur);
+    if (first_power + l == 64) break;
+    iir_qmatmul(cur, B, nxt, D);
+    cur.swap(nxt);
+  }
+  return cur;
+}
+
+// ---- host: errors, device probe, memory ownership ---------------------------------------------------------------
+inline int iir_fail(int code, const std::string& m) {
+  wfk_internal_set_error(m.c_str());
+  return code;
+}
+
+inline bool iir_have_device() {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) return true;
+  (void)hipGetLastError();
+  return false;
+}
+
+// owner of one device allocation
+template <typename T>
+class DevBuf {
+  T* p_ = nullptr;
+
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); return *this; }
+  ~DevBuf() { if (p_) (void)hipFree(p_); }
+  bool alloc(size_t bytes) { return hipMalloc((void**)&p_, bytes) == hipSuccess; }
+  bool upload(const void* src, size_t bytes) {
+    return alloc(bytes) && hipMemcpy(p_, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+  }
+  bool upload(const std::vector<T>& src) { return upload(src.data(), src.size() * sizeof(T)); }
+  T* get() const { return p_; }
+  explicit operator bool() const { return p_ != nullptr; }
+};
+
+// owner of one word of mapped host memory that kernels raise and the host polls (a plan's fault word)
+class MappedWord {
+  unsigned* host_ = nullptr;
+  unsigned* dev_ = nullptr;
+
+ public:
+  MappedWord() = default;
+  MappedWord(const MappedWord&) = delete;
+  MappedWord& operator=(const MappedWord&) = delete;
+  ~MappedWord() { if (host_) (void)hipHostFree(host_); }
+  bool alloc() {
+    if (hipHostMalloc((void**)&host_, 64, hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&dev_, host_, 0) != hipSuccess)
+      return false;
+    *host_ = 0;
+    return true;
+  }
+  volatile unsigned* host() const { return host_; }
+  unsigned* dev() const { return dev_; }
+};
+
+}  // namespace

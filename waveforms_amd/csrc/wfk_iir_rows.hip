@@ -30,11 +30,13 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "wfk.h"
+#include "wfk_iir_common.h"
 
 #define IRW_RUN 16                        // samples per lane and tile
 #define IRW_THREADS 256
@@ -44,58 +46,11 @@
 #define IRW_MAXD 4                        // state dimension limit
 #define IRW_NPW 7                         // T^(2^k), k = 0 .. 6 (k = 6: one wave)
 
-extern "C" void wfk_internal_set_error(const char* msg);
-
 namespace {
-
-int rfail(int code, const std::string& m) {
-  wfk_internal_set_error(m.c_str());
-  return code;
-}
 
 // per-row table (doubles): b[NC] a[NC] | pw[IRW_NPW][D][D][2] | lanep[64][D][D][2] (T^l, l = 0 .. 63)
 __host__ __device__ constexpr int irw_row_doubles(int nsec, int ord) {
   return 2 * nsec * (ord + 1) + (IRW_NPW + 64) * (nsec * ord) * (nsec * ord) * 2;
-}
-
-// one sample through the row's cascade: NSEC sections of order ORD, every index a constant
-template <int NSEC, int ORD>
-__device__ __forceinline__ double irw_step(const double (&cb)[NSEC * (ORD + 1)], const double (&ca)[NSEC * (ORD + 1)],
-                                           double x, double (&z)[NSEC * ORD]) {
-#pragma unroll
-  for (int s = 0; s < NSEC; ++s) {
-    const double* b = cb + s * (ORD + 1);
-    const double* a = ca + s * (ORD + 1);
-    const double y = b[0] * x + z[s * ORD];
-#pragma unroll
-    for (int i = 0; i + 1 < ORD; ++i) z[s * ORD + i] = b[i + 1] * x - a[i + 1] * y + z[s * ORD + i + 1];
-    z[s * ORD + ORD - 1] = b[ORD] * x - a[ORD] * y;
-    x = y;
-  }
-  return x;
-}
-
-// (sh + sl) += (th + tl) * x in double-double (TwoProd via fma, TwoSum)
-__device__ __forceinline__ void irw_dd_acc(double& sh, double& sl, double th, double tl, double x) {
-  const double p = th * x;
-  const double e = fma(th, x, -p) + tl * x;
-  const double s = sh + p;
-  const double bb = s - sh;
-  sl += ((sh - (s - bb)) + (p - bb)) + e;
-  sh = s;
-}
-
-// r = v + M c in double-double; M = D x D (hi, lo) pairs
-template <int D>
-__device__ __forceinline__ void irw_matvec_add(double (&r)[D], const double (&v)[D], const double* M,
-                                               const double (&c)[D]) {
-#pragma unroll
-  for (int i = 0; i < D; ++i) {
-    double sh = v[i], sl = 0.0;
-#pragma unroll
-    for (int j = 0; j < D; ++j) irw_dd_acc(sh, sl, M[(i * D + j) * 2], M[(i * D + j) * 2 + 1], c[j]);
-    r[i] = sh + sl;
-  }
 }
 
 template <typename T, int NSEC, int ORD>
@@ -114,6 +69,8 @@ __global__ void __launch_bounds__(IRW_THREADS) iir_rows_tile(const T* in, int64_
   double cb[NC], ca[NC];
 #pragma unroll
   for (int i = 0; i < NC; ++i) { cb[i] = rt[i]; ca[i] = rt[NC + i]; }
+  const auto B = [&](int s, int i) { return cb[s * (ORD + 1) + i]; };
+  const auto A = [&](int s, int i) { return ca[s * (ORD + 1) + i]; };
   const double* pw = rt + 2 * NC;
   const double* W = pw + (IRW_NPW - 1) * MM;                            // T^64
   double L[MM];                                                         // T^lane, kept for the whole row
@@ -159,9 +116,9 @@ __global__ void __launch_bounds__(IRW_THREADS) iir_rows_tile(const T* in, int64_
     for (int i = 0; i < D; ++i) z[i] = 0.0;
     if (cnt == IRW_RUN) {
 #pragma unroll
-      for (int i = 0; i < IRW_RUN; ++i) (void)irw_step<NSEC, ORD>(cb, ca, (double)my[i] - pre, z);
+      for (int i = 0; i < IRW_RUN; ++i) (void)iir_cascade_step<NSEC, ORD>(B, A, (double)my[i] - pre, z);
     } else {
-      for (int i = 0; i < cnt; ++i) (void)irw_step<NSEC, ORD>(cb, ca, (double)my[i] - pre, z);
+      for (int i = 0; i < cnt; ++i) (void)iir_cascade_step<NSEC, ORD>(B, A, (double)my[i] - pre, z);
     }
     // (a lane past the end of the row keeps a zero state; the scan still multiplies by T per lane, which only
     //  matters AFTER the last sample -- nothing there is used)
@@ -171,7 +128,7 @@ __global__ void __launch_bounds__(IRW_THREADS) iir_rows_tile(const T* in, int64_
       double u[D], r[D];
 #pragma unroll
       for (int i = 0; i < D; ++i) u[i] = __shfl_up(z[i], d);
-      irw_matvec_add<D>(r, z, pw + k * MM, u);
+      dd_matvec_add<D>(r, z, pw + k * MM, u);
 #pragma unroll
       for (int i = 0; i < D; ++i) z[i] = lane >= d ? r[i] : z[i];
     }
@@ -195,13 +152,13 @@ __global__ void __launch_bounds__(IRW_THREADS) iir_rows_tile(const T* in, int64_
       double tot[D], r[D];
 #pragma unroll
       for (int i = 0; i < D; ++i) tot[i] = s_tot[w][i];
-      irw_matvec_add<D>(r, tot, W, S);
+      dd_matvec_add<D>(r, tot, W, S);
 #pragma unroll
       for (int i = 0; i < D; ++i) S[i] = r[i];
     }
     if (wv == IRW_WAVES - 1) {     // the next tile's carry (double-buffered: the other waves still read this tile's)
       double r[D];
-      irw_matvec_add<D>(r, z, W, S);                                    // lane 63: z = this wave's total
+      dd_matvec_add<D>(r, z, W, S);                                    // lane 63: z = this wave's total
       if (lane == 63) {
 #pragma unroll
         for (int i = 0; i < D; ++i) s_carry[(t + 1) & 1][i] = r[i];
@@ -209,12 +166,12 @@ __global__ void __launch_bounds__(IRW_THREADS) iir_rows_tile(const T* in, int64_
     }
 
     // ---- sweep 2 from the true start state v_(l-1) + T^l S_w, y over x in LDS
-    irw_matvec_add<D>(z, vprev, L, S);
+    dd_matvec_add<D>(z, vprev, L, S);
     if (cnt == IRW_RUN) {
 #pragma unroll
-      for (int i = 0; i < IRW_RUN; ++i) my[i] = (T)(irw_step<NSEC, ORD>(cb, ca, (double)my[i] - pre, z) + pre);
+      for (int i = 0; i < IRW_RUN; ++i) my[i] = (T)(iir_cascade_step<NSEC, ORD>(B, A, (double)my[i] - pre, z) + pre);
     } else {
-      for (int i = 0; i < cnt; ++i) my[i] = (T)(irw_step<NSEC, ORD>(cb, ca, (double)my[i] - pre, z) + pre);
+      for (int i = 0; i < cnt; ++i) my[i] = (T)(iir_cascade_step<NSEC, ORD>(B, A, (double)my[i] - pre, z) + pre);
     }
     if (zf && cnt > 0 && mine <= IRW_RUN) {                             // the lane that holds the row's last sample
 #pragma unroll
@@ -238,63 +195,14 @@ __global__ void __launch_bounds__(IRW_THREADS) iir_rows_tile(const T* in, int64_
   }
 }
 
-// ---- host: the per-row tables in quad precision (see wfk_iir.hip: a T computed by a double-precision
-// recurrence is off by ~1e-9 relative for clustered poles, which the scan would amplify)
-typedef __float128 quad;
-
-void irw_qmatmul(const quad* A, const quad* B, quad* C, int D) {
-  for (int i = 0; i < D; ++i)
-    for (int j = 0; j < D; ++j) {
-      quad acc = 0;
-      for (int k = 0; k < D; ++k) acc += A[i * D + k] * B[k * D + j];
-      C[i * D + j] = acc;
-    }
-}
-
+// ---- host: one row's table (wfk_iir_common.h: quad precision, (hi, lo) pairs)
 // b, a: the row's normalised coefficients, sections back to back
-void irw_build_row(int nsec, int ord, const double* b, const double* a, double* dst) {
-  const int D = nsec * ord, NC = nsec * (ord + 1), MM = D * D * 2;
+void irw_build_row(int nsec, const int32_t* orders, const double* b, const double* a, double* dst) {
+  const int ord = orders[0], D = nsec * ord, NC = nsec * (ord + 1);
   std::memcpy(dst, b, (size_t)NC * 8);
   std::memcpy(dst + NC, a, (size_t)NC * 8);
-  quad T[IRW_MAXD * IRW_MAXD], cur[IRW_MAXD * IRW_MAXD], tmp[IRW_MAXD * IRW_MAXD];
-  for (int col = 0; col < D; ++col) {   // column col = homogeneous response to the unit state e_col
-    quad z[IRW_MAXD] = {0, 0, 0, 0};
-    z[col] = 1;
-    for (int k = 0; k < IRW_RUN; ++k) {
-      quad x = 0;
-      for (int s = 0; s < nsec; ++s) {
-        quad* zs = z + s * ord;
-        const double* bs = b + s * (ord + 1);
-        const double* as = a + s * (ord + 1);
-        const quad y = (quad)bs[0] * x + zs[0];
-        for (int i = 0; i + 1 < ord; ++i) zs[i] = (quad)bs[i + 1] * x - (quad)as[i + 1] * y + zs[i + 1];
-        zs[ord - 1] = (quad)bs[ord] * x - (quad)as[ord] * y;
-        x = y;
-      }
-    }
-    for (int r = 0; r < D; ++r) T[r * D + col] = z[r];
-  }
-  auto put = [&](double* at, const quad* M) {   // quad -> (hi, lo)
-    for (int e = 0; e < D * D; ++e) {
-      const double hi = (double)M[e];
-      at[2 * e] = hi;
-      at[2 * e + 1] = (double)(M[e] - (quad)hi);
-    }
-  };
   double* pw = dst + 2 * NC;
-  std::memcpy(cur, T, sizeof(quad) * D * D);
-  for (int k = 0; k < IRW_NPW; ++k) {
-    put(pw + (size_t)k * MM, cur);
-    irw_qmatmul(cur, cur, tmp, D);
-    std::memcpy(cur, tmp, sizeof(quad) * D * D);
-  }
-  double* lp = pw + (size_t)IRW_NPW * MM;
-  for (int e = 0; e < D * D; ++e) cur[e] = (e / D == e % D) ? 1 : 0;
-  for (int l = 0; l < 64; ++l) {
-    put(lp + (size_t)l * MM, cur);
-    irw_qmatmul(cur, T, tmp, D);
-    std::memcpy(cur, tmp, sizeof(quad) * D * D);
-  }
+  iir_power_tables(iir_transition(nsec, orders, b, a, D, IRW_RUN), D, 0, pw, pw + (size_t)IRW_NPW * D * D * 2);
 }
 
 }  // namespace
@@ -303,7 +211,7 @@ struct wfk_iir_rows_plan {
   int nsec = 0, ord = 0, D = 0;
   int64_t n = 0;
   int32_t batch = 0, kind = 0;
-  double* tab = nullptr;     // [batch][irw_row_doubles]
+  DevBuf<double> tab;        // [batch][irw_row_doubles]
   std::string name;
 };
 
@@ -311,7 +219,7 @@ template <typename T, int NSEC, int ORD>
 static void irw_launch_t(const wfk_iir_rows_plan* p, const void* in, int64_t is, void* out, int64_t os,
                          const double* zi, double* zf, const double* initial, hipStream_t s) {
   hipLaunchKernelGGL((iir_rows_tile<T, NSEC, ORD>), dim3((unsigned)p->batch), dim3(IRW_THREADS), 0, s,
-                     (const T*)in, is, (T*)out, os, p->tab, zi, zf, initial, p->n);
+                     (const T*)in, is, (T*)out, os, p->tab.get(), zi, zf, initial, p->n);
 }
 
 template <typename T>
@@ -323,35 +231,33 @@ static int irw_launch(const wfk_iir_rows_plan* p, const void* in, int64_t is, vo
   IRW_CASE(2, 1) IRW_CASE(3, 1) IRW_CASE(4, 1)                          // cascades of first-order corrections
   IRW_CASE(2, 2)                                                        // two biquads
 #undef IRW_CASE
-  return rfail(WFK_EINVAL, "per-row IIR: no kernel for this shape");
+  return iir_fail(WFK_EINVAL, "per-row IIR: no kernel for this shape");
 }
 
 extern "C" {
 
 int wfk_iir_rows_plan_destroy(wfk_iir_rows_plan* p) {
-  if (!p) return WFK_OK;
-  (void)hipFree(p->tab);
   delete p;
   return WFK_OK;
 }
 
 int wfk_iir_rows_plan_create(int32_t n_sections, const int32_t* orders, const double* b_rows, const double* a_rows,
                              int64_t n, int32_t batch, int kind, wfk_iir_rows_plan** out) {
-  if (!out) return rfail(WFK_EINVAL, "null out");
+  if (!out) return iir_fail(WFK_EINVAL, "null out");
   *out = nullptr;
   if (n_sections < 1 || !orders || !b_rows || !a_rows || n < 0 || batch < 1)
-    return rfail(WFK_EINVAL, "bad per-row IIR arguments");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return rfail(WFK_EINVAL, "IIR kind must be F64 or F32");
+    return iir_fail(WFK_EINVAL, "bad per-row IIR arguments");
+  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return iir_fail(WFK_EINVAL, "IIR kind must be F64 or F32");
   bool equal = true;
   int64_t Dtot = 0;
   for (int s = 0; s < n_sections; ++s) {
-    if (orders[s] < 0) return rfail(WFK_EINVAL, "negative section order");
+    if (orders[s] < 0) return iir_fail(WFK_EINVAL, "negative section order");
     equal = equal && orders[s] == orders[0];
     Dtot += orders[s];
   }
   const int ord = orders[0];
   if (!equal || ord < 1 || Dtot > IRW_MAXD || (ord == 2 && n_sections > 2))
-    return rfail(WFK_EUNSUP,
+    return iir_fail(WFK_EUNSUP,
                  "per-row IIR cascades take sections of EQUAL order >= 1 with a total state dimension <= " +
                      std::to_string(IRW_MAXD) + " (one section of order 1..4, 1..4 first-order sections, one or two "
                      "biquads); got " + std::to_string(n_sections) + " section(s), state dimension " +
@@ -364,18 +270,14 @@ int wfk_iir_rows_plan_create(int32_t n_sections, const int32_t* orders, const do
       const size_t at = (size_t)r * NC + (size_t)s * (ord + 1);
       const double a0 = a_rows[at];
       if (!(a0 != 0.0) || !std::isfinite(a0))
-        return rfail(WFK_EINVAL, "a[0] must be finite and non-zero (row " + std::to_string((long long)r) + ")");
+        return iir_fail(WFK_EINVAL, "a[0] must be finite and non-zero (row " + std::to_string((long long)r) + ")");
       for (int i = 0; i <= ord; ++i) {
         bn[at + i] = b_rows[at + i] / a0;
         an[at + i] = a_rows[at + i] / a0;
       }
     }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    (void)hipGetLastError();
-    return rfail(WFK_EHIP, "no HIP device visible");
-  }
-  wfk_iir_rows_plan* p = new wfk_iir_rows_plan();
+  if (!iir_have_device()) return iir_fail(WFK_EHIP, "no HIP device visible");
+  std::unique_ptr<wfk_iir_rows_plan> p(new wfk_iir_rows_plan());
   p->nsec = n_sections; p->ord = ord; p->D = (int)Dtot;
   p->n = n; p->batch = batch; p->kind = kind;
   p->name = std::string("iir_rows_tile<") + (kind == WFK_OUT_F64 ? "f64" : "f32") + "," + std::to_string(n_sections) +
@@ -393,7 +295,7 @@ int wfk_iir_rows_plan_create(int32_t n_sections, const int32_t* orders, const do
         const int64_t r0 = next.fetch_add(16);
         if (r0 >= batch) return;
         for (int64_t r = r0; r < std::min<int64_t>(r0 + 16, batch); ++r)
-          irw_build_row(n_sections, ord, bn.data() + (size_t)r * NC, an.data() + (size_t)r * NC,
+          irw_build_row(n_sections, orders, bn.data() + (size_t)r * NC, an.data() + (size_t)r * NC,
                         tab.data() + (size_t)r * rd);
       }
     };
@@ -402,13 +304,11 @@ int wfk_iir_rows_plan_create(int32_t n_sections, const int32_t* orders, const do
     work();
     for (std::thread& th : pool) th.join();
   }
-  if (hipMalloc(&p->tab, tab.size() * 8) != hipSuccess ||
-      hipMemcpy(p->tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+  if (!p->tab.upload(tab)) {
     (void)hipGetLastError();
-    wfk_iir_rows_plan_destroy(p);
-    return rfail(WFK_ENOMEM, "per-row IIR plan: device allocation / upload failed");
+    return iir_fail(WFK_ENOMEM, "per-row IIR plan: device allocation / upload failed");
   }
-  *out = p;
+  *out = p.release();
   return WFK_OK;
 }
 
@@ -419,16 +319,16 @@ const char* wfk_iir_rows_kernel_name(const wfk_iir_rows_plan* p) { return p ? p-
 int wfk_iir_rows_apply(wfk_iir_rows_plan* p, const void* in_dev, int64_t in_stride, void* out_dev,
                        int64_t out_stride, const double* zi_dev, double* zf_dev, const double* initial_dev,
                        void* hip_stream) {
-  if (!p) return rfail(WFK_EINVAL, "null plan");
+  if (!p) return iir_fail(WFK_EINVAL, "null plan");
   if (p->n == 0) return WFK_OK;
-  if (!in_dev || !out_dev) return rfail(WFK_EINVAL, "null argument");
-  if (in_stride < p->n || out_stride < p->n) return rfail(WFK_EINVAL, "row stride < n");
+  if (!in_dev || !out_dev) return iir_fail(WFK_EINVAL, "null argument");
+  if (in_stride < p->n || out_stride < p->n) return iir_fail(WFK_EINVAL, "row stride < n");
   hipStream_t s = (hipStream_t)hip_stream;
   const int rc = p->kind == WFK_OUT_F64
                      ? irw_launch<double>(p, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial_dev, s)
                      : irw_launch<float>(p, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial_dev, s);
   if (rc != WFK_OK) return rc;
-  if (hipGetLastError() != hipSuccess) return rfail(WFK_EHIP, "per-row IIR launch failed");
+  if (hipGetLastError() != hipSuccess) return iir_fail(WFK_EHIP, "per-row IIR launch failed");
   return WFK_OK;
 }
 

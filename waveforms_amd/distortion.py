@@ -78,7 +78,7 @@ class IirStage:
             sec = np.asarray(sections, dtype=np.float64)
             if sec.ndim != 2 or sec.shape[1] != 6:
                 raise ValueError('IirStage: an SOS matrix has shape (n_sections, 6)')
-            sections, depth = [(r[:3], r[3:]) for r in sec], 3
+            sections, depth = _engine.sos_sections(sec), 3
         if depth not in (3, 4):
             raise ValueError('IirStage: sections is [(b, a), ...], an SOS matrix, or one [(b, a), ...] per row')
         self.per_row = depth == 4
@@ -236,7 +236,7 @@ class SampledIir:
         except (ValueError, TypeError):
             sec = None
         if sec is not None and sec.ndim == 2 and sec.shape[1] == 6:
-            sections = [(r[:3], r[3:]) for r in sec]              # an SOS matrix (scipy.signal.sosfilt)
+            sections = _engine.sos_sections(sec)
         self.prog = _flatten.tile_program(_flatten.flatten(list(channels), grid, function_lib), tile)
         self.plan = _engine.ChainIirPlan(self.prog, grid, sections, ker, dtype)
         self.n, self.n_channels, self.dtype = self.plan.n, self.plan.n_channels, np.dtype(dtype)
@@ -282,12 +282,10 @@ class SampledIir:
                                     if np.ndim(zi) > 1 else np.asarray(zi, dtype=np.float64),
                                     (self.n_channels, self.state_dim))
                 dzi.upload(np.ascontiguousarray(z))
-            for attempt in range(2):
-                ok = self.launch(buf.ptr, None, None if dzi is None else dzi.ptr, None if dzf is None else dzf.ptr, initial)
-                if self.plan.status() and ok:
-                    break
-                if attempt == 1:
-                    raise _engine.EngineError('IIR chain failed twice')
+            if not _engine.iir_run_checked(
+                    lambda: self.launch(buf.ptr, None, None if dzi is None else dzi.ptr,
+                                        None if dzf is None else dzf.ptr, initial), self.plan.status):
+                raise _engine.EngineError('IIR chain failed twice')
             out = buf.download((self.n_channels, self.n), self.dtype)
             if return_zf:
                 return out, dzf.download((self.n_channels, D), np.float64)[:, :self.state_dim]
@@ -432,11 +430,9 @@ def iir_host(sig, sections, zi=None, initial=0.0, ker=None):
             dzi = dev(z.nbytes)
             dzi.upload(z)
         dzf = dev(batch * D * 8)
-        ok = plan.apply(x.ptr, n, y.ptr, n, dzi.ptr if dzi else None, dzf.ptr, initial)
-        if not (plan.status() and ok):   # a single-pass look-back timed out (stalled predecessor chunk): every part
-            ok = plan.apply(x.ptr, n, y.ptr, n, dzi.ptr if dzi else None, dzf.ptr, initial)  # of the plan has switched
-            if not (plan.status() and ok):                                                   # form; x is intact
-                raise _engine.EngineError('IIR stage failed twice')
+        if not _engine.iir_run_checked(      # (x stays intact: a launch whose look-back timed out can be repeated)
+                lambda: plan.apply(x.ptr, n, y.ptr, n, dzi.ptr if dzi else None, dzf.ptr, initial), plan.status):
+            raise _engine.EngineError('IIR stage failed twice')
         res = y
         if ker is not None and n > 0:
             fir = FirStage(ker, n, batch, np.float64)
