@@ -3,8 +3,8 @@
 
     tools/kernel_cmp.py A B [object ...]
 
-A, B: two object files, or two trees (then waveforms_amd/csrc/_obj/<object> of each, default wfk_iir.o and
-wfk_iir_rows.o).  The code object is taken out of each object file as tools/kernel_regs.sh does, disassembled
+A, B: two object files, or two trees (then waveforms_amd/csrc/_obj/<object> of each, default every object that is
+built with an offload arch: all but wfk_compile.o).  The code object is taken out of each object file as tools/kernel_regs.sh does, disassembled
 with llvm-objdump -d, and compared per kernel symbol: the encoded instruction words (branches are PC-relative, so
 a kernel that merely moved compares equal) and the metadata kernel_regs.sh prints (VGPR / AGPR / SGPR, spills,
 LDS, scratch).  Exit status 0: same set of kernels, every one identical.
@@ -28,6 +28,8 @@ def kernels(obj):
     """{kernel symbol: (metadata tuple, [encoded instruction words])}"""
     with tempfile.TemporaryDirectory() as tmp:
         fat, co = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "k.co")
+        if ".hip_fatbin" not in run(f"{B}/llvm-readelf", "-S", obj):
+            return {}                                        # host code only (wfk_api.o today): no kernels
         run(f"{B}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj)
         run(f"{B}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={fat}",
             "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}")
@@ -64,7 +66,8 @@ def main():
         sys.exit(__doc__)
     a, b = sys.argv[1:3]
     if os.path.isdir(a):
-        names = sys.argv[3:] or ["wfk_iir.o", "wfk_iir_rows.o"]
+        names = sys.argv[3:] or [f"wfk_{x}.o" for x in ("api", "kernels", "short", "fir", "fir_fused", "fir_sampled", "iir",
+                                                        "iir_rows", "spectral", "demod")]
         pairs = [(n, *(os.path.join(t, "waveforms_amd/csrc/_obj", n) for t in (a, b))) for n in names]
     else:
         pairs = [(os.path.basename(a), a, b)]

@@ -184,12 +184,30 @@ def detect_grid_runs(t: np.ndarray, min_len: int = 4096, max_runs: int = 256):
     return out
 
 
-class Plan:
+class _Handle:
+    """Owner of one library handle: `_h` is there from the first moment of the object's life (so `close` and `__del__`
+    are safe on an object whose constructor raised), `_destroy` names the library function that releases it."""
+    _destroy = None
+
+    def __new__(cls, *args, **kwargs):
+        self = super().__new__(cls)
+        self._h = C.c_void_p()
+        return self
+
+    def close(self):
+        if self._h and _lib is not None:      # (_lib is None once the interpreter takes the module down)
+            getattr(_lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+
+class Plan(_Handle):
     """A compiled program bound to a time axis (grid or explicit t)."""
+    _destroy = 'wfk_plan_destroy'
 
     def __init__(self, prog: Program, grid: wfk_grid | None = None, t=None):
         self.prog = prog
-        self._h = C.c_void_p()
         if grid is not None:
             self.grid = grid
             check(lib().wfk_plan_create_grid(C.byref(prog.struct), C.byref(grid),
@@ -203,13 +221,6 @@ class Plan:
         self.info = info
         self.n = int(info.n)
         self.n_channels = int(info.n_channels)
-
-    def close(self):
-        if self._h and _lib is not None:
-            _lib.wfk_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
     def member_index(self, member: int) -> np.ndarray:
         """np.searchsorted(x - shift, bounds) of one member, computed by the library."""
@@ -279,46 +290,39 @@ def pinned_empty(shape, dtype) -> np.ndarray:
     return np.frombuffer(buf, dtype=dtype).reshape(shape)
 
 
-class FirPlan:
+class FirPlan(_Handle):
     """out[i] = sum_k ker[k] * sig[i + K//2 - k] (zero padded) for `batch` rows.  A 2-D `ker` of shape
     (batch, K) gives every row its own kernel (one predistortion kernel per AWG line)."""
+    _destroy = 'wfk_fir_plan_destroy'
 
     def __init__(self, ker, n: int, batch: int = 1, dtype=np.float64):
         ker = np.ascontiguousarray(ker, dtype=np.float64)
         self.n, self.batch, self.dtype = int(n), int(batch), np.dtype(dtype)
-        self._h = C.c_void_p()
         if ker.ndim == 2:
             if ker.shape[0] != self.batch:
                 raise ValueError('per-row kernels: ker must have shape (batch, K)')
             check(lib().wfk_fir_plan_create_rows(ker.ctypes.data, ker.shape[1], self.n, self.batch,
                                                  _KIND_OF[self.dtype], C.byref(self._h)))
-            return
-        check(lib().wfk_fir_plan_create(ker.ctypes.data, len(ker), self.n, self.batch,
-                                        _KIND_OF[self.dtype], C.byref(self._h)))
+        else:
+            check(lib().wfk_fir_plan_create(ker.ctypes.data, len(ker), self.n, self.batch,
+                                            _KIND_OF[self.dtype], C.byref(self._h)))
 
     def apply(self, in_ptr: int, in_stride: int, out_ptr: int, out_stride: int,
               stream: int = 0):
         check(lib().wfk_fir_apply(self._h, in_ptr, in_stride, out_ptr, out_stride,
                                   stream))
 
-    def close(self):
-        if self._h and _lib is not None:
-            _lib.wfk_fir_plan_destroy(self._h)
-            self._h = C.c_void_p()
 
-    __del__ = close
-
-
-class ChainPlan:
+class ChainPlan(_Handle):
     """sampler -> FIR for every channel of `prog` on `grid` (predistort(wav(t), ker=ker)); fused
     into ONE kernel when the program is fully fused (lean plan on a fine grid, or a pure short-tier
     plan at AWG sample rates) and K <= 1537 (`fused`, `why_not`, `kernel_name()`)."""
+    _destroy = 'wfk_chain_plan_destroy'
 
     def __init__(self, prog: Program, grid: wfk_grid, ker, dtype=np.float64):
         ker = np.ascontiguousarray(ker, dtype=np.float64)
         self.prog, self.grid, self.dtype = prog, grid, np.dtype(dtype)
         self.n, self.n_channels = int(grid.n), prog.n_channels
-        self._h = C.c_void_p()
         if ker.ndim == 2:          # one kernel per channel
             if ker.shape[0] != prog.n_channels:
                 raise ValueError('per-channel kernels: ker must have shape (n_channels, K)')
@@ -339,13 +343,6 @@ class ChainPlan:
 
     def table_bytes(self) -> int:
         return int(lib().wfk_chain_table_bytes(self._h))
-
-    def close(self):
-        if self._h and _lib is not None:
-            _lib.wfk_chain_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
 
 def _accepted(rc) -> bool:
@@ -387,19 +384,19 @@ def _pack_sections(sections):
             np.ascontiguousarray(np.concatenate(as_)))
 
 
-class ChainIirPlan:
+class ChainIirPlan(_Handle):
     """sampler -> IIR cascade (-> FIR) for every channel of `prog` on `grid`, device-resident:
     `sosfilt(sos, wav(t) - initial, zi) + initial` of Waveform.sample(filters=) (reference waveform.py:190-203,
     244-251) and `predistort(wav(t), filters, ker)` (distortion.py:298-337).  When the program is fully fused and the
     (first pass of the) cascade has a state dimension <= 4, the wave that owns a chunk of the IIR scan EVALUATES its
     input (`iir_sampled<...>`): the unfiltered samples never touch HBM (`fused`, `why_not`, `kernel_name()`).
     `ker` (K,) or (n_channels, K): an FIR stage behind the cascade."""
+    _destroy = 'wfk_chain_iir_plan_destroy'
 
     def __init__(self, prog: Program, grid: wfk_grid, sections, ker=None, dtype=np.float64):
         orders, bflat, aflat = _pack_sections(sections)
         self.prog, self.grid, self.dtype = prog, grid, np.dtype(dtype)
         self.n, self.n_channels = int(grid.n), prog.n_channels
-        self._h = C.c_void_p()
         kp, K, rows = None, 0, 0
         if ker is not None:
             ker = np.ascontiguousarray(ker, dtype=np.float64)
@@ -432,25 +429,18 @@ class ChainIirPlan:
     def table_bytes(self) -> int:
         return int(lib().wfk_chain_iir_table_bytes(self._h))
 
-    def close(self):
-        if self._h and _lib is not None:
-            _lib.wfk_chain_iir_plan_destroy(self._h)
-            self._h = C.c_void_p()
 
-    __del__ = close
-
-
-class IirPlan:
+class IirPlan(_Handle):
     """Cascade of direct-form-II-transposed sections along each of `batch` rows.
 
     sections: list of (b, a) coefficient sequences; a section's order is
     max(len(b), len(a)) - 1 (scipy.signal.lfilter convention).  An SOS matrix is the
     list [(row[:3], row[3:]) for row in sos] (scipy.signal.sosfilt)."""
+    _destroy = 'wfk_iir_plan_destroy'
 
     def __init__(self, sections, n: int, batch: int = 1, dtype=np.float64):
         orders, bflat, aflat = _pack_sections(sections)
         self.n, self.batch, self.dtype = int(n), int(batch), np.dtype(dtype)
-        self._h = C.c_void_p()
         check(lib().wfk_iir_plan_create(len(orders), orders.ctypes.data, bflat.ctypes.data,
                                         aflat.ctypes.data, self.n, self.batch,
                                         _KIND_OF[self.dtype], C.byref(self._h)))
@@ -468,13 +458,6 @@ class IirPlan:
         """Synchronise `stream`; False if a single-pass launch since the last check ran into a look-back
         timeout (its outputs hold NaN; the plan has switched to the three-launch form: apply again)."""
         return _accepted(lib().wfk_iir_status(self._h, stream))
-
-    def close(self):
-        if self._h and _lib is not None:
-            _lib.wfk_iir_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
 
 def pack_sections_rows(sections_per_row):
@@ -516,17 +499,17 @@ def pack_sections_rows(sections_per_row):
     return orders, bm.reshape(len(rows), -1), am.reshape(len(rows), -1), own
 
 
-class IirRowsPlan:
+class IirRowsPlan(_Handle):
     """One cascade PER ROW (wfk_iir_rows_plan_create): `sections_per_row[r]` is the list of (b, a) sections of
     row r, in IirPlan's conventions.  Rows are padded to a common shape (`pack_sections_rows`); the library takes
     sections of equal order with a total state dimension <= 4 and raises EngineError beyond that.
     `state_dim` is the padded state dimension: zi / zf are (batch, state_dim) device arrays."""
+    _destroy = 'wfk_iir_rows_plan_destroy'
 
     def __init__(self, sections_per_row, n: int, dtype=np.float64):
         orders, bm, am, self.own_orders = pack_sections_rows(sections_per_row)
         self.n, self.batch, self.dtype = int(n), int(bm.shape[0]), np.dtype(dtype)
         self.orders = orders
-        self._h = C.c_void_p()
         bm, am = np.ascontiguousarray(bm), np.ascontiguousarray(am)
         check(lib().wfk_iir_rows_plan_create(len(orders), orders.ctypes.data, bm.ctypes.data, am.ctypes.data,
                                              self.n, self.batch, _KIND_OF[self.dtype], C.byref(self._h)))
@@ -540,41 +523,28 @@ class IirRowsPlan:
     def kernel_name(self) -> str:
         return lib().wfk_iir_rows_kernel_name(self._h).decode()
 
-    def close(self):
-        if self._h and _lib is not None:
-            _lib.wfk_iir_rows_plan_destroy(self._h)
-            self._h = C.c_void_p()
 
-    __del__ = close
-
-
-class SpectralPlan:
+class SpectralPlan(_Handle):
     """out = irfft(rfft(x) * H) along each of `batch` contiguous rows of n samples."""
+    _destroy = 'wfk_spectral_plan_destroy'
 
     def __init__(self, n: int, batch: int = 1, dtype=np.float64):
         self.n, self.batch, self.dtype = int(n), int(batch), np.dtype(dtype)
-        self._h = C.c_void_p()
         check(lib().wfk_spectral_plan_create(self.n, self.batch, _KIND_OF[self.dtype],
                                              C.byref(self._h)))
 
     def apply(self, in_ptr, out_ptr, H_ptr, stream=0):
         check(lib().wfk_spectral_apply(self._h, in_ptr, out_ptr, H_ptr, stream))
 
-    def close(self):
-        if self._h and _lib is not None:
-            _lib.wfk_spectral_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
-
 
 IN_F64, IN_F32, IN_I16 = 0, 1, 4
 DEMOD_IN_KIND = {np.dtype(np.float64): IN_F64, np.dtype(np.float32): IN_F32, np.dtype(np.int16): IN_I16}
 
 
-class DemodPlan:
+class DemodPlan(_Handle):
     """out[s, j] = sum_k x[s, k] * e[k, j]: real traces (shots, >= N) of float64 / float32 / int16 times a complex
     (N, nf) matrix, fp64 on the device; `e` is uploaded once."""
+    _destroy = 'wfk_demod_plan_destroy'
 
     def __init__(self, e, dtype=np.float64):
         e = np.ascontiguousarray(e, dtype=np.complex128)
@@ -584,7 +554,6 @@ class DemodPlan:
         if self.dtype not in DEMOD_IN_KIND:
             raise ValueError('trace dtype must be float64, float32 or int16')
         self.n, self.nf = int(e.shape[0]), int(e.shape[1])
-        self._h = C.c_void_p()
         check(lib().wfk_demod_plan_create(e.ctypes.data, self.n, self.nf, DEMOD_IN_KIND[self.dtype],
                                           C.byref(self._h)))
 
@@ -593,13 +562,6 @@ class DemodPlan:
 
     def kernel_name(self, n_shots: int) -> str:
         return lib().wfk_demod_kernel_name(self._h, n_shots).decode()
-
-    def close(self):
-        if self._h and _lib is not None:
-            _lib.wfk_demod_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    __del__ = close
 
 
 class DeviceBuffer:

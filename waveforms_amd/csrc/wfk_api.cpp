@@ -14,20 +14,16 @@
 #include <vector>
 
 #include "wfk.h"
+#include "wfk_host.h"
 #include "wfk_internal.h"
 
 static thread_local std::string g_err;
 
-static int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess)                                                          \
-      return fail(WFK_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
+#define HIP_TRY(expr)                                                                 \
+  do {                                                                                \
+    hipError_t e_ = (expr);                                                           \
+    if (e_ != hipSuccess)                                                             \
+      return wfk_fail(WFK_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
   } while (0)
 
 // ---- device block cache ------------------------------------------------------------------
@@ -143,53 +139,34 @@ struct wfk_plan {
   bool async_launch = false;   // launched on a caller stream since the last host-side sync
 };
 
-static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
 static int plan_upload(wfk_plan* p, const double* tlist) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    (void)hipGetLastError();
+  if (!wfk_have_device()) {
     p->on_device = false;  // host-only plan: index/info queries work, launch fails loudly
     return WFK_OK;
   }
   const HostPlan& h = p->h;
-  const size_t b_ch = h.channels.size() * sizeof(DevChannel);
-  const size_t b_pc = h.shortp && !h.mixed ? 0 : h.pieces.size() * sizeof(DevPiece);   // (the short kernel walks units, not pieces)
-  const size_t b_pa = h.params.size() * sizeof(double);
-  const size_t b_po = h.pool.size() * sizeof(double);
-  const size_t b_cf = h.chunk_first.size() * sizeof(int32_t);
-  const size_t b_lf = h.lean_chunk_first.size() * sizeof(int32_t);
-  const size_t b_ff = h.f32_chunk_first.size() * sizeof(int32_t);
-  const size_t b_un = h.s_units.size() * sizeof(ShortUnit), b_sl = h.s_slots.size() * sizeof(uint32_t);
-  const size_t o_ch = 0, o_pc = align256(o_ch + b_ch), o_pa = align256(o_pc + b_pc),
-               o_po = align256(o_pa + b_pa), o_cf = align256(o_po + b_po),
-               o_lf = align256(o_cf + b_cf), o_ff = align256(o_lf + b_lf), o_un = align256(o_ff + b_ff),
-               o_sl = align256(o_un + b_un), o_tl = align256(o_sl + b_sl);
+  // the small tables travel in ONE copy; the time axis (as large as the output) on its own
+  DevTables t;
+  const size_t o_ch = t.add(h.channels);
+  const size_t o_pc = t.add(h.pieces.data(), h.shortp && !h.mixed ? 0 : h.pieces.size() * sizeof(DevPiece));   // (the short kernel walks units, not pieces)
+  const size_t o_pa = t.add(h.params), o_po = t.add(h.pool), o_cf = t.add(h.chunk_first);
+  const size_t o_lf = t.add(h.lean_chunk_first), o_ff = t.add(h.f32_chunk_first);
+  const size_t o_un = t.add(h.s_units), o_sl = t.add(h.s_slots);
   const size_t b_tl = tlist ? (size_t)h.n * sizeof(double) : 0;
-  const size_t total = align256(o_tl + b_tl) + 256;
+  const size_t o_tl = t.reserve(b_tl), total = t.total();
   HIP_TRY(dev_cache().get(total, &p->d_tables, &p->tables_cap, &p->dev));
   char* base = static_cast<char*>(p->d_tables);
-  p->d_channels = reinterpret_cast<DevChannel*>(base + o_ch);
-  p->d_pieces = reinterpret_cast<DevPiece*>(base + o_pc);
-  p->d_params = reinterpret_cast<double*>(base + o_pa);
-  p->d_pool = reinterpret_cast<double*>(base + o_po);
-  p->d_chunk_first = reinterpret_cast<int32_t*>(base + o_cf);
-  p->d_lean_chunk_first = reinterpret_cast<int32_t*>(base + o_lf);
-  p->d_f32_chunk_first = reinterpret_cast<int32_t*>(base + o_ff);
-  p->d_units = reinterpret_cast<ShortUnit*>(base + o_un);
-  p->d_slots = reinterpret_cast<uint32_t*>(base + o_sl);
-  p->d_tlist = tlist ? reinterpret_cast<double*>(base + o_tl) : nullptr;
-  // the small tables travel in ONE copy; the time axis (as large as the output) on its own
-  std::vector<char> stage(o_tl);
-  if (b_ch) std::memcpy(stage.data() + o_ch, h.channels.data(), b_ch);
-  if (b_pc) std::memcpy(stage.data() + o_pc, h.pieces.data(), b_pc);
-  if (b_pa) std::memcpy(stage.data() + o_pa, h.params.data(), b_pa);
-  if (b_po) std::memcpy(stage.data() + o_po, h.pool.data(), b_po);
-  if (b_cf) std::memcpy(stage.data() + o_cf, h.chunk_first.data(), b_cf);
-  if (b_lf) std::memcpy(stage.data() + o_lf, h.lean_chunk_first.data(), b_lf);
-  if (b_ff) std::memcpy(stage.data() + o_ff, h.f32_chunk_first.data(), b_ff);
-  if (b_un) std::memcpy(stage.data() + o_un, h.s_units.data(), b_un);
-  if (b_sl) std::memcpy(stage.data() + o_sl, h.s_slots.data(), b_sl);
+  p->d_channels = t.at<DevChannel>(base, o_ch);
+  p->d_pieces = t.at<DevPiece>(base, o_pc);
+  p->d_params = t.at<double>(base, o_pa);
+  p->d_pool = t.at<double>(base, o_po);
+  p->d_chunk_first = t.at<int32_t>(base, o_cf);
+  p->d_lean_chunk_first = t.at<int32_t>(base, o_lf);
+  p->d_f32_chunk_first = t.at<int32_t>(base, o_ff);
+  p->d_units = t.at<ShortUnit>(base, o_un);
+  p->d_slots = t.at<uint32_t>(base, o_sl);
+  p->d_tlist = tlist ? t.at<double>(base, o_tl) : nullptr;
+  const std::vector<char>& stage = t.image();
   if (o_tl) HIP_TRY(hipMemcpy(base, stage.data(), o_tl, hipMemcpyHostToDevice));
   if (b_tl) HIP_TRY(hipMemcpy(base + o_tl, tlist, b_tl, hipMemcpyHostToDevice));
   p->on_device = true;
@@ -198,7 +175,7 @@ static int plan_upload(wfk_plan* p, const double* tlist) {
 
 extern "C" {
 
-// shared with wfk_fir.hip (not part of the public header)
+// shared with the other stages (wfk_internal.h; not part of the public header)
 void wfk_internal_set_error(const char* msg) { g_err = msg ? msg : ""; }
 
 int wfk_abi_version(void) { return WFK_ABI_VERSION; }
@@ -206,12 +183,12 @@ int wfk_abi_version(void) { return WFK_ABI_VERSION; }
 const char* wfk_last_error(void) { return g_err.c_str(); }
 
 int wfk_device_count(int* count) {
-  if (!count) return fail(WFK_EINVAL, "null count");
+  if (!count) return wfk_fail(WFK_EINVAL, "null count");
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess) {
     *count = 0;
-    return fail(WFK_EHIP, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
+    return wfk_fail(WFK_EHIP, std::string("hipGetDeviceCount: ") + hipGetErrorString(e));
   }
   *count = n;
   return WFK_OK;
@@ -233,7 +210,7 @@ struct TlistNsGuard {
 static int plan_create_impl(const wfk_program* prog, const wfk_grid* grid, const double* tlist,
                             int64_t n, wfk_plan** out) {
   wfk_plan* p = new (std::nothrow) wfk_plan();
-  if (!p) return fail(WFK_ENOMEM, "out of host memory");
+  if (!p) return wfk_fail(WFK_ENOMEM, "out of host memory");
   std::string err;
   int rc = WFK_RETRY_STD;
   try {
@@ -251,7 +228,7 @@ static int plan_create_impl(const wfk_program* prog, const wfk_grid* grid, const
   }
   if (rc) {
     delete p;
-    return fail(rc, err);
+    return wfk_fail(rc, err);
   }
   // A grid whose pieces are tens to hundreds of samples long (AWG rates) with shapes the short tier does not take
   // (libm shapes, chirps, sinc, derivatives of mollifiers ...): the standard tiers would evaluate EVERY piece over whole
@@ -298,25 +275,25 @@ static int plan_create_impl(const wfk_program* prog, const wfk_grid* grid, const
 // No exception crosses the C boundary: the compiler and the upload allocate host vectors.
 static int plan_create(const wfk_program* prog, const wfk_grid* grid, const double* tlist,
                        int64_t n, wfk_plan** out) {
-  if (!out) return fail(WFK_EINVAL, "null out");
+  if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
   try {
     return plan_create_impl(prog, grid, tlist, n, out);
   } catch (const std::bad_alloc&) {
-    return fail(WFK_ENOMEM, "out of host memory while compiling the plan");
+    return wfk_fail(WFK_ENOMEM, "out of host memory while compiling the plan");
   } catch (const std::exception& e) {
-    return fail(WFK_EINVAL, std::string("plan creation failed: ") + e.what());
+    return wfk_fail(WFK_EINVAL, std::string("plan creation failed: ") + e.what());
   }
 }
 
 int wfk_plan_create_grid(const wfk_program* prog, const wfk_grid* grid, wfk_plan** out) {
-  if (!grid) return fail(WFK_EINVAL, "null grid");
+  if (!grid) return wfk_fail(WFK_EINVAL, "null grid");
   return plan_create(prog, grid, nullptr, 0, out);
 }
 
 int wfk_plan_create_tlist(const wfk_program* prog, const double* t_host, int64_t n,
                           wfk_plan** out) {
-  if (!t_host && n > 0) return fail(WFK_EINVAL, "null t_host");
+  if (!t_host && n > 0) return wfk_fail(WFK_EINVAL, "null t_host");
   static const double dummy = 0.0;
   return plan_create(prog, nullptr, t_host ? t_host : &dummy, n, out);
 }
@@ -336,7 +313,7 @@ int wfk_plan_destroy(wfk_plan* p) {
 }
 
 int wfk_plan_get_info(const wfk_plan* p, wfk_plan_info* info) {
-  if (!p || !info) return fail(WFK_EINVAL, "null argument");
+  if (!p || !info) return wfk_fail(WFK_EINVAL, "null argument");
   info->n_channels = p->h.n_channels;
   info->n = p->h.n;
   info->tile = p->h.tile;
@@ -352,14 +329,14 @@ int wfk_plan_get_info(const wfk_plan* p, wfk_plan_info* info) {
 
 int wfk_plan_member_index(const wfk_plan* p, int32_t member, int64_t* idx, int32_t cap) {
   if (!p || member < 0 || member >= (int32_t)p->h.member_idx.size())
-    return fail(WFK_EINVAL, "bad member");
+    return wfk_fail(WFK_EINVAL, "bad member");
   const auto& v = p->h.member_idx[member];
   for (int32_t i = 0; i < cap && i < (int32_t)v.size(); ++i) idx[i] = v[i];
   return (int)v.size();
 }
 
 int wfk_plan_channel_is_complex(const wfk_plan* p, int32_t channel) {
-  if (!p || channel < 0 || channel >= p->h.n_channels) return fail(WFK_EINVAL, "bad channel");
+  if (!p || channel < 0 || channel >= p->h.n_channels) return wfk_fail(WFK_EINVAL, "bad channel");
   return p->h.channel_complex[channel];
 }
 
@@ -371,7 +348,7 @@ void wfk_internal_plan_tables(const wfk_plan* p, const HostPlan** h, const doubl
 }
 
 int64_t wfk_plan_table_bytes(const wfk_plan* p) {
-  if (!p) return fail(WFK_EINVAL, "null plan");
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   const HostPlan& h = p->h;
   size_t b = h.channels.size() * sizeof(DevChannel) + h.params.size() * sizeof(double) + h.pool.size() * sizeof(double);
   if (h.shortp) b += h.s_units.size() * sizeof(ShortUnit) + h.s_slots.size() * sizeof(uint32_t);
@@ -422,13 +399,13 @@ const char* wfk_plan_kernel_name(const wfk_plan* p, int out_kind) {
 // a contiguous sample range, returned in *s_lo / *s_hi).  nparts == 1: everything.
 static int plan_launch_part(wfk_plan* p, void* out_dev, int64_t ch_stride, int out_kind, uint32_t flags,
                             void* hip_stream, int part, int nparts, int64_t* s_lo, int64_t* s_hi) {
-  if (!p || (!out_dev && p->h.n > 0)) return fail(WFK_EINVAL, "null plan or output");
+  if (!p || (!out_dev && p->h.n > 0)) return wfk_fail(WFK_EINVAL, "null plan or output");
   if (!p->on_device)
-    return fail(WFK_EHIP, "plan has no device tables (no HIP device was visible at plan creation)");
-  if (ch_stride < p->h.n) return fail(WFK_EINVAL, "ch_stride smaller than samples per channel");
+    return wfk_fail(WFK_EHIP, "plan has no device tables (no HIP device was visible at plan creation)");
+  if (ch_stride < p->h.n) return wfk_fail(WFK_EINVAL, "ch_stride smaller than samples per channel");
   if (s_lo) { *s_lo = 0; *s_hi = p->h.n; }
   if (p->h.n == 0 || p->h.n_channels == 0) return WFK_OK;
-  if (nparts > 1 && (p->h.n_channels != 1 || p->h.mixed)) return fail(WFK_EINVAL, "partial launch of a multi-channel or mixed plan");
+  if (nparts > 1 && (p->h.n_channels != 1 || p->h.mixed)) return wfk_fail(WFK_EINVAL, "partial launch of a multi-channel or mixed plan");
   auto sub = [&](int64_t total, int64_t& base, int64_t& count) {
     base = total * part / nparts;
     count = total * (part + 1) / nparts - base;
@@ -463,7 +440,7 @@ static int plan_launch_part(wfk_plan* p, void* out_dev, int64_t ch_stride, int o
     std::string serr;
     const bool foreign_only = (flags & WFK_PLAN_FOREIGN_ONLY) && p->h.mixed;   // (the chain at AWG rates samples the short pieces itself)
     const int src = sa.n_chunks > 0 && !foreign_only ? wfk_launch_short(sa, out_kind, hip_stream, serr) : WFK_OK;
-    if (src) return fail(src, serr);
+    if (src) return wfk_fail(src, serr);
     if (!p->h.mixed) return WFK_OK;
   }
   KArgs a{};
@@ -512,7 +489,7 @@ static int plan_launch_part(wfk_plan* p, void* out_dev, int64_t ch_stride, int o
     KArgs l = a;
     l.mixed = 1;
     rc = wfk_launch_sampler(l, p->h.n_channels, out_kind, true, p->h.ns, false, false, false, hip_stream, err);
-    if (rc) return fail(rc, err);
+    if (rc) return wfk_fail(rc, err);
     a.mixed = 1;   // ... then the pieces with generic terms on the build with the direct tier
   } else if (p->h.mixed) {
     // lean and zero pieces first (own chunking: one wave per workgroup) ...
@@ -524,7 +501,7 @@ static int plan_launch_part(wfk_plan* p, void* out_dev, int64_t ch_stride, int o
     l.tiles_per_chunk = p->h.lean_tiles_per_chunk;
     if (f32_lean) use_f32_chunks(l);
     rc = wfk_launch_sampler(l, p->h.n_channels, out_kind, false, p->h.ns, true, false, false, hip_stream, err);
-    if (rc) return fail(rc, err);
+    if (rc) return wfk_fail(rc, err);
     a.mixed = 1;   // ... then the pieces with generic terms
   }
   if (nparts > 1) {
@@ -541,7 +518,7 @@ static int plan_launch_part(wfk_plan* p, void* out_dev, int64_t ch_stride, int o
                           p->h.n_generic > 0 || (p->h.tlist && p->h.n_direct > 0),   // (time lists: either generic + direct or neither)
                           p->h.n_direct > 0 || (p->h.tlist && p->h.n_generic > 0),
                           hip_stream, err);
-  return rc ? fail(rc, err) : WFK_OK;
+  return rc ? wfk_fail(rc, err) : WFK_OK;
 }
 
 int wfk_plan_launch(wfk_plan* p, void* out_dev, int64_t ch_stride, int out_kind, uint32_t flags,
@@ -590,7 +567,7 @@ HostBlockCache& host_cache() {
 }  // extern "C++"
 
 int wfk_host_alloc(void** host_ptr, size_t bytes) {
-  if (!host_ptr) return fail(WFK_EINVAL, "null host_ptr");
+  if (!host_ptr) return wfk_fail(WFK_EINVAL, "null host_ptr");
   HostBlockCache& hc = host_cache();
   size_t b = HostBlockCache::kMinBlock;
   while (b < bytes) b <<= 1;
@@ -605,12 +582,12 @@ int wfk_host_alloc(void** host_ptr, size_t bytes) {
       hc.handed_[*host_ptr] = b;
       return WFK_OK;
     }
-    if (hc.live + b > HostBlockCache::kMaxLive) return fail(WFK_ENOMEM, "pinned host memory budget exhausted");
+    if (hc.live + b > HostBlockCache::kMaxLive) return wfk_fail(WFK_ENOMEM, "pinned host memory budget exhausted");
   }
   void* ptr = nullptr;
   if (hipHostMalloc(&ptr, b, hipHostMallocDefault) != hipSuccess) {
     (void)hipGetLastError();
-    return fail(WFK_ENOMEM, "hipHostMalloc failed");
+    return wfk_fail(WFK_ENOMEM, "hipHostMalloc failed");
   }
   std::lock_guard<std::mutex> g(hc.mu);
   hc.live += b;
@@ -626,7 +603,7 @@ int wfk_host_free(void* host_ptr) {
   {
     std::lock_guard<std::mutex> g(hc.mu);
     auto it = hc.handed_.find(host_ptr);
-    if (it == hc.handed_.end()) return fail(WFK_EINVAL, "wfk_host_free: not a wfk_host_alloc block");
+    if (it == hc.handed_.end()) return wfk_fail(WFK_EINVAL, "wfk_host_free: not a wfk_host_alloc block");
     b = it->second;
     hc.handed_.erase(it);
     if (hc.cached + b <= HostBlockCache::kMaxCachedTotal) {
@@ -661,12 +638,12 @@ HostPipe& host_pipe(int dev) {
 }  // extern "C++"
 
 int wfk_plan_run_host(wfk_plan* p, void* out_host, int64_t ch_stride, int out_kind) {
-  if (!p) return fail(WFK_EINVAL, "null plan");
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   size_t es = elem_size(out_kind);
-  if (!es) return fail(WFK_EINVAL, "bad out_kind");
+  if (!es) return wfk_fail(WFK_EINVAL, "bad out_kind");
   if (p->h.n == 0 || p->h.n_channels == 0) return WFK_OK;
   if (!p->on_device)
-    return fail(WFK_EHIP, "plan has no device tables (no HIP device was visible at plan creation)");
+    return wfk_fail(WFK_EHIP, "plan has no device tables (no HIP device was visible at plan creation)");
   size_t bytes = (size_t)p->h.n_channels * (size_t)p->h.n * es;
   DeviceGuard guard(p->dev);   // scratch, launch and copy all happen on the plan's own device
   if (bytes > p->scratch_bytes) {
@@ -755,7 +732,7 @@ int wfk_host_all_finite(const double* host, int64_t n) {
 }
 
 int wfk_malloc(void** dev_ptr, size_t bytes) {
-  if (!dev_ptr) return fail(WFK_EINVAL, "null dev_ptr");
+  if (!dev_ptr) return wfk_fail(WFK_EINVAL, "null dev_ptr");
   size_t cap = 0;
   int dev = 0;
   HIP_TRY(dev_cache().get(bytes ? bytes : 1, dev_ptr, &cap, &dev));
@@ -771,7 +748,7 @@ int wfk_free(void* dev_ptr) {
   {
     std::lock_guard<std::mutex> g(dev_cache().mu);
     auto it = dev_cache().handed_.find(dev_ptr);
-    if (it == dev_cache().handed_.end()) return fail(WFK_EINVAL, "wfk_free: not a wfk_malloc block");
+    if (it == dev_cache().handed_.end()) return wfk_fail(WFK_EINVAL, "wfk_free: not a wfk_malloc block");
     cap = it->second.first;
     dev = it->second.second;
     dev_cache().handed_.erase(it);

@@ -21,11 +21,12 @@
 // atomics, the result is bitwise reproducible for a given shape.
 #include <hip/hip_runtime.h>
 
+#include <memory>
+#include <new>
 #include <string>
 
 #include "wfk.h"
-
-extern "C" void wfk_internal_set_error(const char* msg);
+#include "wfk_host.h"
 
 namespace {
 
@@ -36,11 +37,6 @@ constexpr int kSeg = kRowBytes / 16;    // 16-B segments per row and chunk
 constexpr int kPitch = kRowBytes + 16;  // LDS row pitch
 constexpr int kLoads = kRows * kSeg / 64;  // 16-B loads per lane and chunk
 constexpr int kTarget = 1024;           // workgroups a split launch aims at (4 per CU)
-
-int dfail(int code, const std::string& m) {
-  wfk_internal_set_error(m.c_str());
-  return code;
-}
 
 // First sample of a 16-B segment as fp64, and the segment shifted down by one sample.  Taking the
 // samples one at a time keeps the sample loop rollable, so the compiler fetches B's rows a few at a
@@ -227,7 +223,7 @@ int launch_t(int nb, dim3 grid, hipStream_t st, const T* X, int64_t S, int64_t N
     WFK_DEMOD_CASE(32)
 #undef WFK_DEMOD_CASE
     default:
-      return dfail(WFK_EINVAL, "bad column bucket");
+      return wfk_fail(WFK_EINVAL, "bad column bucket");
   }
   return WFK_OK;
 }
@@ -238,8 +234,8 @@ struct wfk_demod_plan {
   int64_t n = 0, npad = 0, nch = 0;
   int32_t nf = 0, nb = 0, ncb = 0;
   int kind = 0;
-  double* B = nullptr;     // [ncb][npad][nb] complex
-  double* ws = nullptr;    // split partials: kTarget * 64 * nb complex
+  DevBuf<double> B;        // [ncb][npad][nb] complex
+  DevBuf<double> ws;       // split partials: kTarget * 64 * nb complex
   std::string name;
 };
 
@@ -259,28 +255,21 @@ int64_t splits_for(const wfk_demod_plan* p, int64_t S) {
 extern "C" {
 
 int wfk_demod_plan_destroy(wfk_demod_plan* p) {
-  if (!p) return WFK_OK;
-  (void)hipFree(p->B);
-  (void)hipFree(p->ws);
   delete p;
   return WFK_OK;
 }
 
 int wfk_demod_plan_create(const double* e_host, int64_t n_points, int32_t n_freq, int in_kind,
-                          wfk_demod_plan** out) {
-  if (!out) return dfail(WFK_EINVAL, "null out");
+                          wfk_demod_plan** out) try {
+  if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
-  if (!e_host) return dfail(WFK_EINVAL, "null matrix");
+  if (!e_host) return wfk_fail(WFK_EINVAL, "null matrix");
   if (n_points < 1 || n_freq < 1 || n_freq > 65535 * 32)
-    return dfail(WFK_EINVAL, "bad demodulator shape (n_points >= 1, 1 <= n_freq <= 2097120)");
+    return wfk_fail(WFK_EINVAL, "bad demodulator shape (n_points >= 1, 1 <= n_freq <= 2097120)");
   if (in_kind != WFK_IN_F64 && in_kind != WFK_IN_F32 && in_kind != WFK_IN_I16)
-    return dfail(WFK_EINVAL, "in_kind must be WFK_IN_F64, WFK_IN_F32 or WFK_IN_I16");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    (void)hipGetLastError();
-    return dfail(WFK_EHIP, "no HIP device visible");
-  }
-  wfk_demod_plan* p = new wfk_demod_plan();
+    return wfk_fail(WFK_EINVAL, "in_kind must be WFK_IN_F64, WFK_IN_F32 or WFK_IN_I16");
+  if (!wfk_have_device()) return wfk_fail(WFK_EHIP, "no HIP device visible");
+  std::unique_ptr<wfk_demod_plan> p(new wfk_demod_plan());
   p->n = n_points;
   p->nf = n_freq;
   p->kind = in_kind;
@@ -290,62 +279,63 @@ int wfk_demod_plan_create(const double* e_host, int64_t n_points, int32_t n_freq
   p->nch = (n_points + kc - 1) / kc;
   p->npad = p->nch * kc;
   const size_t bbytes = (size_t)p->ncb * p->npad * p->nb * 16;
-  bool ok = hipMalloc(&p->B, bbytes) == hipSuccess && hipMemset(p->B, 0, bbytes) == hipSuccess;
+  bool ok = p->B.alloc(bbytes) && hipMemset(p->B.get(), 0, bbytes) == hipSuccess;
   // column block cb of e (point-major rows of nf complex) -> rows of nb complex
   for (int32_t cb = 0; ok && cb < p->ncb; ++cb) {
     const int32_t w = n_freq - cb * p->nb < p->nb ? n_freq - cb * p->nb : p->nb;
-    ok = hipMemcpy2D((char*)p->B + (size_t)cb * p->npad * p->nb * 16, (size_t)p->nb * 16,
+    ok = hipMemcpy2D((char*)p->B.get() + (size_t)cb * p->npad * p->nb * 16, (size_t)p->nb * 16,
                      e_host + (size_t)cb * p->nb * 2, (size_t)n_freq * 16, (size_t)w * 16,
                      (size_t)n_points, hipMemcpyHostToDevice) == hipSuccess;
   }
   if (ok && p->nch >= 4 * kWaves)
-    ok = hipMalloc(&p->ws, (size_t)kTarget * kRows * p->nb * 16) == hipSuccess;
+    ok = p->ws.alloc((size_t)kTarget * kRows * p->nb * 16);
   if (!ok) {
     (void)hipGetLastError();
-    wfk_demod_plan_destroy(p);
-    return dfail(WFK_ENOMEM, "demodulator plan: device allocation / upload failed");
+    return wfk_fail(WFK_ENOMEM, "demodulator plan: device allocation / upload failed");
   }
-  *out = p;
+  *out = p.release();
   return WFK_OK;
+} catch (const std::bad_alloc&) {
+  return wfk_fail(WFK_ENOMEM, "out of host memory while building the demodulator plan");
 }
 
 int wfk_demod_apply(wfk_demod_plan* p, const void* traces_dev, int64_t n_shots, int64_t trace_stride,
                     void* out_dev, int64_t out_stride, void* hip_stream) {
-  if (!p) return dfail(WFK_EINVAL, "null plan");
-  if (n_shots < 0) return dfail(WFK_EINVAL, "n_shots < 0");
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
+  if (n_shots < 0) return wfk_fail(WFK_EINVAL, "n_shots < 0");
   if (n_shots == 0) return WFK_OK;
-  if (!traces_dev || !out_dev) return dfail(WFK_EINVAL, "null argument");
-  if (trace_stride < p->n) return dfail(WFK_EINVAL, "trace_stride < n_points");
-  if (out_stride < p->nf) return dfail(WFK_EINVAL, "out_stride < n_freq");
-  if (((uintptr_t)out_dev & 15) != 0) return dfail(WFK_EINVAL, "out must be 16-byte aligned");
+  if (!traces_dev || !out_dev) return wfk_fail(WFK_EINVAL, "null argument");
+  if (trace_stride < p->n) return wfk_fail(WFK_EINVAL, "trace_stride < n_points");
+  if (out_stride < p->nf) return wfk_fail(WFK_EINVAL, "out_stride < n_freq");
+  if (((uintptr_t)out_dev & 15) != 0) return wfk_fail(WFK_EINVAL, "out must be 16-byte aligned");
   if (((uintptr_t)traces_dev % elem_bytes(p->kind)) != 0)
-    return dfail(WFK_EINVAL, "traces not aligned to their element size");
+    return wfk_fail(WFK_EINVAL, "traces not aligned to their element size");
   hipStream_t st = (hipStream_t)hip_stream;
   const int64_t ks = splits_for(p, n_shots);
   const int64_t nsb = (n_shots + kRows - 1) / kRows;
   const int64_t cps = (p->nch + ks - 1) / ks;
   const int64_t spad = nsb * kRows;
-  if (nsb > 0x7fffffff) return dfail(WFK_EINVAL, "too many shots");
+  if (nsb > 0x7fffffff) return wfk_fail(WFK_EINVAL, "too many shots");
   const dim3 grid((unsigned)nsb, (unsigned)ks, (unsigned)p->ncb);
-  double* part = ks > 1 ? p->ws : nullptr;
+  double* part = ks > 1 ? p->ws.get() : nullptr;
   int rc;
   if (p->kind == WFK_IN_F64)
-    rc = launch_t<double>(p->nb, grid, st, (const double*)traces_dev, n_shots, p->n, trace_stride, p->B,
+    rc = launch_t<double>(p->nb, grid, st, (const double*)traces_dev, n_shots, p->n, trace_stride, p->B.get(),
                           p->npad, cps, (double*)out_dev, out_stride, p->nf, part, spad);
   else if (p->kind == WFK_IN_F32)
-    rc = launch_t<float>(p->nb, grid, st, (const float*)traces_dev, n_shots, p->n, trace_stride, p->B,
+    rc = launch_t<float>(p->nb, grid, st, (const float*)traces_dev, n_shots, p->n, trace_stride, p->B.get(),
                          p->npad, cps, (double*)out_dev, out_stride, p->nf, part, spad);
   else
-    rc = launch_t<int16_t>(p->nb, grid, st, (const int16_t*)traces_dev, n_shots, p->n, trace_stride, p->B,
+    rc = launch_t<int16_t>(p->nb, grid, st, (const int16_t*)traces_dev, n_shots, p->n, trace_stride, p->B.get(),
                            p->npad, cps, (double*)out_dev, out_stride, p->nf, part, spad);
   if (rc != WFK_OK) return rc;
   if (ks > 1) {
     const int64_t nout = n_shots * p->nf;
     hipLaunchKernelGGL(demod_reduce, dim3((unsigned)((nout + 3) / 4)), dim3(256), 0, st,
-                       (const double2*)p->ws, ks, n_shots, spad, (int64_t)p->ncb * p->nb, p->nf,
+                       (const double2*)p->ws.get(), ks, n_shots, spad, (int64_t)p->ncb * p->nb, p->nf,
                        (double2*)out_dev, out_stride);
   }
-  if (hipGetLastError() != hipSuccess) return dfail(WFK_EHIP, "demodulator launch failed");
+  if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "demodulator launch failed");
   return WFK_OK;
 }
 

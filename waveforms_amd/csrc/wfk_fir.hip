@@ -14,16 +14,18 @@
 // All buffers and rocFFT plans are created in wfk_fir_plan_create; wfk_fir_apply only
 // enqueues work on the caller's stream.
 #include <hip/hip_runtime.h>
-#include <rocfft/rocfft.h>
 
 #include <algorithm>
 #include <cmath>
 #include <complex>
-#include <mutex>
+#include <memory>
+#include <new>
 #include <string>
 #include <vector>
 
 #include "wfk.h"
+#include "wfk_host.h"
+#include "wfk_rocfft.h"
 
 namespace {
 
@@ -67,41 +69,34 @@ __global__ void __launch_bounds__(256) fir_scatter(const T* __restrict__ win, T*
   out[ch * out_stride + dst] = win[(ch * nblk + b) * L + (K - 1) + r];
 }
 
-std::once_flag g_rocfft_once;
+// long double -> the plan's element kind: complex element `at` of `dst`
+void put_cx(std::vector<char>& dst, bool f32, size_t at, const std::complex<long double>& v) {
+  if (f32) {
+    float* d = reinterpret_cast<float*>(dst.data()) + 2 * at;
+    d[0] = (float)v.real(); d[1] = (float)v.imag();
+  } else {
+    double* d = reinterpret_cast<double*>(dst.data()) + 2 * at;
+    d[0] = (double)v.real(); d[1] = (double)v.imag();
+  }
+}
 
 }  // namespace
-
-// fused single-kernel path for short kernels (wfk_fir_fused.hip)
-extern "C" int wfk_internal_fir_fused_launch(int kind, const void* in, int64_t in_stride, void* out,
-                                             int64_t out_stride, const void* hspec, const void* tw,
-                                             int64_t n, int M, int K, int lead, int64_t nblk,
-                                             int32_t batch, int accumulate, void* stream, int64_t hspec_row_stride);
-extern "C" int wfk_internal_fir_fused_len(void);
 
 struct wfk_fir_plan {
   bool fused = false;
   int32_t nseg = 1, Kseg = 0;  // fused: the kernel is cut into nseg segments of Kseg taps, one
                                // pass of the fused kernel each (passes after the first accumulate)
-  void* tw = nullptr;          // fused: exp(-2 pi i j / L), j < 256
   int32_t K = 0, batch = 0, kind = 0, L = 0, M = 0, lead = 0, chunk = 0;
   int64_t n = 0, nblk = 0;
-  rocfft_plan fwd = nullptr, inv = nullptr, fwd_tail = nullptr, inv_tail = nullptr;
   int32_t tail = 0;  // channels in the last, smaller chunk (0: none)
-  rocfft_execution_info info = nullptr;
-  void* work = nullptr;
-  void* win = nullptr;
-  void* spec = nullptr;
-  void* kspec = nullptr;
   int64_t krow = 0;            // per-row kernels (wfk_fir_plan_create_rows): complex elements between the
                                // spectra of consecutive rows; 0: one kernel for every row
+  // (members go in reverse order: the rocFFT plans and the execution info before the work buffer they were given)
+  DevBuf<char> tw;             // fused: exp(-2 pi i j / L), j < 256
+  DevBuf<char> kspec, spec, win, work;
+  RocfftInfo info;
+  RocfftPlan fwd, inv, fwd_tail, inv_tail;
 };
-
-extern "C" void wfk_internal_set_error(const char* msg);  // wfk_api.cpp (thread-local)
-
-static int fir_fail(int code, const std::string& msg) {
-  wfk_internal_set_error(msg.c_str());
-  return code;
-}
 
 static int make_plans(wfk_fir_plan* p, int32_t channels, rocfft_plan* fwd, rocfft_plan* inv,
                       size_t* work_bytes) {
@@ -110,27 +105,25 @@ static int make_plans(wfk_fir_plan* p, int32_t channels, rocfft_plan* fwd, rocff
   const size_t len[1] = {(size_t)p->L};
   const size_t nb = (size_t)channels * (size_t)p->nblk;
   const size_t nf = (size_t)p->L / 2 + 1;
-  rocfft_plan_description df = nullptr, di = nullptr;
+  RocfftDesc df, di;
   const size_t one[1] = {1};
-  if (rocfft_plan_description_create(&df) != rocfft_status_success) return -1;
-  if (rocfft_plan_description_set_data_layout(df, rocfft_array_type_real,
+  if (rocfft_plan_description_create(df.out()) != rocfft_status_success) return -1;
+  if (rocfft_plan_description_set_data_layout(df.get(), rocfft_array_type_real,
                                               rocfft_array_type_hermitian_interleaved, nullptr,
                                               nullptr, 1, one, (size_t)p->L, 1, one, nf) !=
       rocfft_status_success)
     return -1;
   if (rocfft_plan_create(fwd, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec,
-                         1, len, nb, df) != rocfft_status_success)
+                         1, len, nb, df.get()) != rocfft_status_success)
     return -1;
-  rocfft_plan_description_destroy(df);
-  if (rocfft_plan_description_create(&di) != rocfft_status_success) return -1;
-  if (rocfft_plan_description_set_data_layout(di, rocfft_array_type_hermitian_interleaved,
+  if (rocfft_plan_description_create(di.out()) != rocfft_status_success) return -1;
+  if (rocfft_plan_description_set_data_layout(di.get(), rocfft_array_type_hermitian_interleaved,
                                               rocfft_array_type_real, nullptr, nullptr, 1, one, nf,
                                               1, one, (size_t)p->L) != rocfft_status_success)
     return -1;
   if (rocfft_plan_create(inv, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec,
-                         1, len, nb, di) != rocfft_status_success)
+                         1, len, nb, di.get()) != rocfft_status_success)
     return -1;
-  rocfft_plan_description_destroy(di);
   size_t a = 0, b = 0;
   rocfft_plan_get_work_buffer_size(*fwd, &a);
   rocfft_plan_get_work_buffer_size(*inv, &b);
@@ -143,34 +136,34 @@ static int fir_run(wfk_fir_plan* p, const void* in_dev, int64_t in_stride, void*
                    int64_t out_stride, hipStream_t s) {
   const int L = p->L, M = p->M;
   const int64_t nf = L / 2 + 1;
-  if (rocfft_execution_info_set_stream(p->info, s) != rocfft_status_success)
-    return fir_fail(WFK_EHIP, "rocfft set_stream failed");
+  if (rocfft_execution_info_set_stream(p->info.get(), s) != rocfft_status_success)
+    return wfk_fail(WFK_EHIP, "rocfft set_stream failed");
   for (int32_t c0 = 0; c0 < p->batch; c0 += p->chunk) {
     const int32_t nc = std::min(p->chunk, p->batch - c0);
     const bool tail = nc != p->chunk;
     const T* in = static_cast<const T*>(in_dev) + (int64_t)c0 * in_stride;
     T* out = static_cast<T*>(out_dev) + (int64_t)c0 * out_stride;
-    T* win = static_cast<T*>(p->win);
-    C* spec = static_cast<C*>(p->spec);
+    T* win = reinterpret_cast<T*>(p->win.get());
+    C* spec = reinterpret_cast<C*>(p->spec.get());
     dim3 gg((L + 255) / 256, (unsigned)p->nblk, (unsigned)nc);
     hipLaunchKernelGGL(fir_gather<T>, gg, dim3(256), 0, s, in, in_stride, win, p->n, L, M, p->lead,
                        p->nblk);
     void* ib[1] = {win};
     void* ob[1] = {spec};
-    if (rocfft_execute(tail ? p->fwd_tail : p->fwd, ib, ob, p->info) != rocfft_status_success)
-      return fir_fail(WFK_EHIP, "rocfft forward execute failed");
+    if (rocfft_execute((tail ? p->fwd_tail : p->fwd).get(), ib, ob, p->info.get()) != rocfft_status_success)
+      return wfk_fail(WFK_EHIP, "rocfft forward execute failed");
     const int64_t total = (int64_t)nc * p->nblk * nf;
     hipLaunchKernelGGL(fir_multiply<C>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, spec,
-                       static_cast<const C*>(p->kspec), (int)nf, total);
+                       reinterpret_cast<const C*>(p->kspec.get()), (int)nf, total);
     void* ib2[1] = {spec};
     void* ob2[1] = {win};
-    if (rocfft_execute(tail ? p->inv_tail : p->inv, ib2, ob2, p->info) != rocfft_status_success)
-      return fir_fail(WFK_EHIP, "rocfft inverse execute failed");
+    if (rocfft_execute((tail ? p->inv_tail : p->inv).get(), ib2, ob2, p->info.get()) != rocfft_status_success)
+      return wfk_fail(WFK_EHIP, "rocfft inverse execute failed");
     dim3 gs((M + 255) / 256, (unsigned)p->nblk, (unsigned)nc);
     hipLaunchKernelGGL(fir_scatter<T>, gs, dim3(256), 0, s, win, out, out_stride, p->n, L, M, p->K,
                        p->nblk);
   }
-  if (hipGetLastError() != hipSuccess) return fir_fail(WFK_EHIP, "FIR kernel launch failed");
+  if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "FIR kernel launch failed");
   return WFK_OK;
 }
 
@@ -178,7 +171,7 @@ static int fir_run(wfk_fir_plan* p, const void* in_dev, int64_t in_stride, void*
 // plan that runs as ONE pass of the on-chip transform
 extern "C" void wfk_internal_fir_tables(const wfk_fir_plan* p, const void** kspec, const void** tw,
                                         int* fused, int* nseg, int* K, int* lead) {
-  *kspec = p->kspec; *tw = p->tw; *fused = p->fused ? 1 : 0; *nseg = p->nseg; *K = p->K;
+  *kspec = p->kspec.get(); *tw = p->tw.get(); *fused = p->fused ? 1 : 0; *nseg = p->nseg; *K = p->K;
   *lead = (p->K - 1) - p->K / 2;
 }
 
@@ -187,17 +180,6 @@ extern "C" int64_t wfk_internal_fir_krow(const wfk_fir_plan* p) { return p->krow
 extern "C" {
 
 int wfk_fir_plan_destroy(wfk_fir_plan* p) {
-  if (!p) return WFK_OK;
-  if (p->fwd) rocfft_plan_destroy(p->fwd);
-  if (p->inv) rocfft_plan_destroy(p->inv);
-  if (p->fwd_tail) rocfft_plan_destroy(p->fwd_tail);
-  if (p->inv_tail) rocfft_plan_destroy(p->inv_tail);
-  if (p->info) rocfft_execution_info_destroy(p->info);
-  (void)hipFree(p->work);
-  (void)hipFree(p->win);
-  (void)hipFree(p->spec);
-  (void)hipFree(p->kspec);
-  (void)hipFree(p->tw);
   delete p;
   return WFK_OK;
 }
@@ -216,18 +198,14 @@ int wfk_fir_plan_create_rows(const double* kers_host, int32_t K, int64_t n, int3
 }
 
 static int fir_plan_create(const double* ker_host, int32_t K, int64_t n, int32_t batch, int kind,
-                           wfk_fir_plan** out, bool per_row) {
-  if (!out) return fir_fail(WFK_EINVAL, "null out");
+                           wfk_fir_plan** out, bool per_row) try {
+  if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
-  if (!ker_host || K < 1 || n < 0 || batch < 1) return fir_fail(WFK_EINVAL, "bad FIR arguments");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return fir_fail(WFK_EINVAL, "FIR kind must be F64 or F32");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-    (void)hipGetLastError();
-    return fir_fail(WFK_EHIP, "no HIP device visible");
-  }
-  std::call_once(g_rocfft_once, [] { rocfft_setup(); });
-  wfk_fir_plan* p = new wfk_fir_plan();
+  if (!ker_host || K < 1 || n < 0 || batch < 1) return wfk_fail(WFK_EINVAL, "bad FIR arguments");
+  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return wfk_fail(WFK_EINVAL, "FIR kind must be F64 or F32");
+  if (!wfk_have_device()) return wfk_fail(WFK_EHIP, "no HIP device visible");
+  wfk_rocfft_setup_once();
+  std::unique_ptr<wfk_fir_plan> p(new wfk_fir_plan());
   p->K = K; p->n = n; p->batch = batch; p->kind = kind;
   const int FL = wfk_internal_fir_fused_len();
   const char* force = getenv("WFK_FIR_ROCFFT");
@@ -241,10 +219,8 @@ static int fir_plan_create(const double* ker_host, int32_t K, int64_t n, int32_t
   p->Kseg = (K + p->nseg - 1) / p->nseg;
   p->fused = p->nseg <= WFK_FIR_MAXSEG && batch <= 65535 && !(force && force[0] == '1');
   if (!p->fused) { p->nseg = 1; p->Kseg = K; }
-  if (per_row && !p->fused) {
-    wfk_fir_plan_destroy(p);
-    return fir_fail(WFK_EUNSUP, "per-row FIR kernels need the on-chip transform (K <= 6148, batch <= 65535, WFK_FIR_ROCFFT unset)");
-  }
+  if (per_row && !p->fused)
+    return wfk_fail(WFK_EUNSUP, "per-row FIR kernels need the on-chip transform (K <= 6148, batch <= 65535, WFK_FIR_ROCFFT unset)");
   int L = 1024;
   while (L < 8 * K) L *= 2;               // hop M = L - K + 1 >= 7/8 L
   if (const char* e = getenv("WFK_FIR_L")) { int v = atoi(e); if (v >= 2 * K && (v & (v - 1)) == 0) L = v; }
@@ -252,61 +228,51 @@ static int fir_plan_create(const double* ker_host, int32_t K, int64_t n, int32_t
   const int Kt = p->fused ? p->Kseg : K;             // taps per transform
   p->L = L; p->M = L - Kt + 1; p->lead = (Kt - 1) - K / 2;   // fused: + j*Kseg for segment j
   p->nblk = n > 0 ? (n + p->M - 1) / p->M : 0;
-  if (n == 0) { *out = p; return WFK_OK; }
-  const size_t es = kind == WFK_OUT_F32 ? 4 : 8;
+  if (n == 0) { *out = p.release(); return WFK_OK; }
+  const bool f32 = kind == WFK_OUT_F32;
+  const size_t es = f32 ? 4 : 8;
   const size_t nf = p->fused ? (size_t)L : (size_t)L / 2 + 1;   // fused: full complex spectrum
   if (!p->fused) {
-  const double per_ch = (double)p->nblk * ((double)L * es + (double)nf * 2 * es);
-  int64_t chunk = (int64_t)(3.0e9 / per_ch);
-  chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, batch));
-  p->chunk = (int32_t)chunk;
-  p->tail = batch % p->chunk;
-  size_t work_bytes = 0;
-  if (make_plans(p, p->chunk, &p->fwd, &p->inv, &work_bytes) ||
-      (p->tail && make_plans(p, p->tail, &p->fwd_tail, &p->inv_tail, &work_bytes))) {
-    wfk_fir_plan_destroy(p);
-    return fir_fail(WFK_EHIP, "rocFFT plan creation failed");
-  }
-  bool ok = rocfft_execution_info_create(&p->info) == rocfft_status_success;
-  ok = ok && hipMalloc(&p->win, (size_t)p->chunk * p->nblk * L * es) == hipSuccess;
-  ok = ok && hipMalloc(&p->spec, (size_t)p->chunk * p->nblk * nf * 2 * es) == hipSuccess;
-  if (ok && work_bytes) {
-    ok = hipMalloc(&p->work, work_bytes) == hipSuccess &&
-         rocfft_execution_info_set_work_buffer(p->info, p->work, work_bytes) == rocfft_status_success;
-  }
-  if (!ok) {
-    wfk_fir_plan_destroy(p);
-    return fir_fail(WFK_ENOMEM, "FIR buffer allocation failed");
-  }
+    const double per_ch = (double)p->nblk * ((double)L * es + (double)nf * 2 * es);
+    int64_t chunk = (int64_t)(3.0e9 / per_ch);
+    chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, batch));
+    p->chunk = (int32_t)chunk;
+    p->tail = batch % p->chunk;
+    size_t work_bytes = 0;
+    if (make_plans(p.get(), p->chunk, p->fwd.out(), p->inv.out(), &work_bytes) ||
+        (p->tail && make_plans(p.get(), p->tail, p->fwd_tail.out(), p->inv_tail.out(), &work_bytes)))
+      return wfk_fail(WFK_EHIP, "rocFFT plan creation failed");
+    bool ok = rocfft_execution_info_create(p->info.out()) == rocfft_status_success;
+    ok = ok && p->win.alloc((size_t)p->chunk * p->nblk * L * es);
+    ok = ok && p->spec.alloc((size_t)p->chunk * p->nblk * nf * 2 * es);
+    if (ok && work_bytes)
+      ok = p->work.alloc(work_bytes) &&
+           rocfft_execution_info_set_work_buffer(p->info.get(), p->work.get(), work_bytes) == rocfft_status_success;
+    if (!ok) return wfk_fail(WFK_ENOMEM, "FIR buffer allocation failed");
   }
   const size_t nrow = per_row ? (size_t)batch : 1;
   p->krow = per_row ? (int64_t)((size_t)p->nseg * nf) : 0;
-  if (hipMalloc(&p->kspec, nrow * (size_t)p->nseg * nf * 2 * es) != hipSuccess ||
-      (p->fused && hipMalloc(&p->tw, 256 * 2 * es) != hipSuccess)) {
-    wfk_fir_plan_destroy(p);
-    return fir_fail(WFK_ENOMEM, "FIR buffer allocation failed");
-  }
-  // kernel spectrum on the host (K*L/2 flops, once): DFT of ker zero-padded to L, times 1/L
+  std::vector<char> ks(nrow * (size_t)p->nseg * nf * 2 * es);
+  if (!p->kspec.alloc(ks.size()) || (p->fused && !p->tw.alloc(256 * 2 * es)))
+    return wfk_fail(WFK_ENOMEM, "FIR buffer allocation failed");
+  // kernel spectrum on the host (K*L/2 flops, once): DFT of ker zero-padded to L, times 1/L, in long double and
+  // narrowed once to the plan's kind
   std::vector<std::complex<long double>> tw(L);
   for (int i = 0; i < L; ++i) {
     long double th = -2.0L * 3.141592653589793238462643383279502884L * i / L;
     tw[i] = {cosl(th), sinl(th)};
   }
-  std::vector<double> ks64(2 * nf * p->nseg * nrow);
-  std::vector<float> ks32(2 * nf * p->nseg * nrow);
   if (!per_row) {
-  for (int sg = 0; sg < p->nseg; ++sg) {
-    const int k0 = sg * p->Kseg, k1 = std::min(K, k0 + (p->fused ? p->Kseg : K));
-    for (size_t f = 0; f < nf; ++f) {
-      std::complex<long double> acc = 0;
-      for (int k = k0; k < k1; ++k)
-        acc += (long double)ker_host[k] * tw[(size_t)((f * (size_t)(k - k0)) % L)];
-      acc /= (long double)L;
-      const size_t at = 2 * (sg * nf + f);
-      ks64[at] = (double)acc.real(); ks64[at + 1] = (double)acc.imag();
-      ks32[at] = (float)acc.real(); ks32[at + 1] = (float)acc.imag();
+    for (int sg = 0; sg < p->nseg; ++sg) {
+      const int k0 = sg * p->Kseg, k1 = std::min(K, k0 + (p->fused ? p->Kseg : K));
+      for (size_t f = 0; f < nf; ++f) {
+        std::complex<long double> acc = 0;
+        for (int k = k0; k < k1; ++k)
+          acc += (long double)ker_host[k] * tw[(size_t)((f * (size_t)(k - k0)) % L)];
+        acc /= (long double)L;
+        put_cx(ks, f32, sg * nf + f, acc);
+      }
     }
-  }
   } else {
     // one spectrum per row: a radix-2 transform in long double (K L / 2 products per kernel, as above, would
     // be seconds for a few thousand rows); bit-reversed input, L = 4096 here (fused path only)
@@ -330,52 +296,39 @@ static int fir_plan_create(const double* ker_host, int32_t K, int64_t n, int32_t
               z[(size_t)(i0 + j)] += t;
             }
         }
-        for (size_t f = 0; f < nf; ++f) {
-          const std::complex<long double> acc = z[f] / (long double)L;
-          const size_t at = 2 * ((r * p->nseg + sg) * nf + f);
-          ks64[at] = (double)acc.real(); ks64[at + 1] = (double)acc.imag();
-          ks32[at] = (float)acc.real(); ks32[at + 1] = (float)acc.imag();
-        }
+        for (size_t f = 0; f < nf; ++f) put_cx(ks, f32, (r * p->nseg + sg) * nf + f, z[f] / (long double)L);
       }
   }
-  hipError_t e = kind == WFK_OUT_F32
-                     ? hipMemcpy(p->kspec, ks32.data(), ks32.size() * 4, hipMemcpyHostToDevice)
-                     : hipMemcpy(p->kspec, ks64.data(), ks64.size() * 8, hipMemcpyHostToDevice);
+  hipError_t e = hipMemcpy(p->kspec.get(), ks.data(), ks.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess && p->fused) {
-    std::vector<double> t64(512);
-    std::vector<float> t32(512);
-    for (int j = 0; j < 256; ++j) {
-      t64[2 * j] = (double)tw[j].real(); t64[2 * j + 1] = (double)tw[j].imag();
-      t32[2 * j] = (float)tw[j].real(); t32[2 * j + 1] = (float)tw[j].imag();
-    }
-    e = kind == WFK_OUT_F32 ? hipMemcpy(p->tw, t32.data(), 256 * 8, hipMemcpyHostToDevice)
-                            : hipMemcpy(p->tw, t64.data(), 256 * 16, hipMemcpyHostToDevice);
+    std::vector<char> t(256 * 2 * es);
+    for (int j = 0; j < 256; ++j) put_cx(t, f32, j, tw[j]);
+    e = hipMemcpy(p->tw.get(), t.data(), t.size(), hipMemcpyHostToDevice);
   }
-  if (e != hipSuccess) {
-    wfk_fir_plan_destroy(p);
-    return fir_fail(WFK_EHIP, "kernel spectrum upload failed");
-  }
-  *out = p;
+  if (e != hipSuccess) return wfk_fail(WFK_EHIP, "kernel spectrum upload failed");
+  *out = p.release();
   return WFK_OK;
+} catch (const std::bad_alloc&) {
+  return wfk_fail(WFK_ENOMEM, "out of host memory while building the FIR plan");
 }
 
 int wfk_fir_apply(wfk_fir_plan* p, const void* in_dev, int64_t in_stride, void* out_dev,
                   int64_t out_stride, void* hip_stream) {
-  if (!p) return fir_fail(WFK_EINVAL, "null plan");
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0) return WFK_OK;
-  if (!in_dev || !out_dev) return fir_fail(WFK_EINVAL, "null buffer");
-  if (in_stride < p->n || out_stride < p->n) return fir_fail(WFK_EINVAL, "stride smaller than n");
+  if (!in_dev || !out_dev) return wfk_fail(WFK_EINVAL, "null buffer");
+  if (in_stride < p->n || out_stride < p->n) return wfk_fail(WFK_EINVAL, "stride smaller than n");
   hipStream_t s = (hipStream_t)hip_stream;
   if (p->fused) {
     const size_t seg_bytes = (size_t)p->L * 2 * (p->kind == WFK_OUT_F32 ? 4 : 8);
     for (int sg = 0; sg < p->nseg; ++sg)
       if (wfk_internal_fir_fused_launch(p->kind, in_dev, in_stride, out_dev, out_stride,
-                                        (const char*)p->kspec + sg * seg_bytes, p->tw, p->n, p->M,
+                                        p->kspec.get() + sg * seg_bytes, p->tw.get(), p->n, p->M,
                                         p->Kseg, p->lead + sg * p->Kseg, p->nblk, p->batch, sg > 0, s, p->krow))
-        return fir_fail(WFK_EHIP, "fused FIR kernel launch failed");
+        return wfk_fail(WFK_EHIP, "fused FIR kernel launch failed");
     return WFK_OK;
   }
-  if (p->nblk > 65535) return fir_fail(WFK_EINVAL, "signal too long for one rocFFT FIR plan (blocks > 65535)");
+  if (p->nblk > 65535) return wfk_fail(WFK_EINVAL, "signal too long for one rocFFT FIR plan (blocks > 65535)");
   if (p->kind == WFK_OUT_F32) return fir_run<float, float2>(p, in_dev, in_stride, out_dev, out_stride, s);
   return fir_run<double, double2>(p, in_dev, in_stride, out_dev, out_stride, s);
 }

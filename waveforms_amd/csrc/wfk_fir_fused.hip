@@ -17,6 +17,7 @@
 
 #include "wfk.h"
 #include "wfk_fft4096.h"
+#include "wfk_internal.h"
 
 namespace {
 

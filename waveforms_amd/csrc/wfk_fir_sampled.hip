@@ -24,6 +24,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
+#include <new>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -31,16 +33,10 @@
 
 #include "wfk.h"
 #include "wfk_fft4096.h"
+#include "wfk_host.h"
 #include "wfk_internal.h"
 #include "wfk_short_dev.h"
 #include "wfk_chain_dev.h"
-
-extern "C" void wfk_internal_set_error(const char* msg);
-extern "C" void wfk_internal_fir_tables(const wfk_fir_plan* p, const void** kspec, const void** tw,
-                                        int* fused, int* nseg, int* K, int* lead);
-extern "C" void wfk_internal_plan_tables(const wfk_plan* p, const HostPlan** h, const double** d_params);
-extern "C" int64_t wfk_internal_fir_krow(const wfk_fir_plan* p);
-extern "C" int wfk_internal_plan_launch_foreign(wfk_plan* p, void* out_dev, int64_t ch_stride, int out_kind, void* hip_stream);
 
 namespace {
 
@@ -459,11 +455,6 @@ __global__ void __launch_bounds__(256, WFK_FIRS_WAVES) fir_short(const ChainShor
   }
 }
 
-int chain_fail(int code, const std::string& m) {
-  wfk_internal_set_error(m.c_str());
-  return code;
-}
-
 }  // namespace
 
 struct wfk_chain_plan {
@@ -473,8 +464,9 @@ struct wfk_chain_plan {
   int32_t kind = 0, n_channels = 0, hopb = 0;
   int64_t n = 0, npairs = 0;
   std::string why;                // why the chain is not fused (diagnostics)
-  // fused path: device tables of the plan compiled for the window geometry
-  void* d_tables = nullptr;
+  // fused path: device tables of the plan compiled for the window geometry.  The typed pointers below look INTO
+  // d_tables (d_recs: into the sampler's own tables) and own nothing.
+  DevBuf<char> d_tables;
   DevChannel* d_channels = nullptr;
   DevPiece* d_pieces = nullptr;
   double* d_params = nullptr;
@@ -489,18 +481,17 @@ struct wfk_chain_plan {
   int32_t has_last = 0;
   int64_t i0 = 0;
   // unfused path: the sampler's output
-  void* workspace = nullptr;
+  DevBuf<char> workspace;
+  ~wfk_chain_plan() {             // (the buffers go after this body: nothing on the device reads them any more)
+    if (d_tables || workspace) (void)hipDeviceSynchronize();
+    wfk_plan_destroy(sampler);
+    wfk_fir_plan_destroy(fir);
+  }
 };
 
 extern "C" {
 
 int wfk_chain_plan_destroy(wfk_chain_plan* p) {
-  if (!p) return WFK_OK;
-  if (p->d_tables || p->workspace) (void)hipDeviceSynchronize();
-  (void)hipFree(p->d_tables);
-  (void)hipFree(p->workspace);
-  wfk_plan_destroy(p->sampler);
-  wfk_fir_plan_destroy(p->fir);
   delete p;
   return WFK_OK;
 }
@@ -519,17 +510,17 @@ int wfk_chain_plan_create_rows(const wfk_program* prog, const wfk_grid* grid, co
 }
 
 static int chain_plan_create(const wfk_program* prog, const wfk_grid* grid, const double* ker_host, int32_t K,
-                             int kind, wfk_chain_plan** out, bool per_row) {
-  if (!out) return chain_fail(WFK_EINVAL, "null out");
+                             int kind, wfk_chain_plan** out, bool per_row) try {
+  if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
-  if (!prog || !grid || !ker_host) return chain_fail(WFK_EINVAL, "null argument");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return chain_fail(WFK_EINVAL, "chain kind must be F64 or F32");
-  wfk_chain_plan* p = new wfk_chain_plan();
+  if (!prog || !grid || !ker_host) return wfk_fail(WFK_EINVAL, "null argument");
+  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return wfk_fail(WFK_EINVAL, "chain kind must be F64 or F32");
+  std::unique_ptr<wfk_chain_plan> p(new wfk_chain_plan());
   p->kind = kind;
   wfk_internal_keep_mixed_short(true);       // (fir_short samples the short pieces itself: a mixed short plan stays one)
   int rc = wfk_plan_create_grid(prog, grid, &p->sampler);
   wfk_internal_keep_mixed_short(false);
-  if (rc) { wfk_chain_plan_destroy(p); return rc; }
+  if (rc) return rc;
   {
     // pieces that close with a table / mollifier multiplier: fir_short does not evaluate those, the general kernel
     // writes them to the chain's workspace like the other pieces the short tier hands on
@@ -544,16 +535,16 @@ static int chain_plan_create(const wfk_program* prog, const wfk_grid* grid, cons
       rc = wfk_plan_create_grid(prog, grid, &p->sampler);
       wfk_internal_keep_mixed_short(false);
       wfk_internal_no_short_fmul(false);
-      if (rc) { wfk_chain_plan_destroy(p); return rc; }
+      if (rc) return rc;
     }
   }
   p->n = grid->n;
   p->n_channels = prog->n_channels;
   rc = per_row ? wfk_fir_plan_create_rows(ker_host, K, grid->n, std::max(1, prog->n_channels), kind, &p->fir)
                : wfk_fir_plan_create(ker_host, K, grid->n, std::max(1, prog->n_channels), kind, &p->fir);
-  if (rc) { wfk_chain_plan_destroy(p); return rc; }
+  if (rc) return rc;
   p->t0 = grid->t0; p->step = grid->step; p->last = grid->last; p->has_last = grid->has_last; p->i0 = grid->i0;
-  if (p->n == 0 || p->n_channels == 0) { *out = p; return WFK_OK; }
+  if (p->n == 0 || p->n_channels == 0) { *out = p.release(); return WFK_OK; }
 
   // ---- can the sampler run inside the transform? ---------------------------------------
   const void *kspec = nullptr, *tw = nullptr;
@@ -592,37 +583,28 @@ static int chain_plan_create(const wfk_program* prog, const wfk_grid* grid, cons
       (void)wfk_chain_windows(*hs, p->n, hop, lead, HALF, p->npairs, wins, ents, bad);
       if (bad.empty()) {
         if (ents.empty()) ents.push_back(0);
-        auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-        const size_t b_ch = hs->channels.size() * sizeof(DevChannel), b_w = wins.size() * sizeof(ShortWin),
-                     b_e = ents.size() * sizeof(uint32_t);
-        const size_t o_w = al(b_ch), o_e = al(o_w + b_w), total = al(o_e + b_e) + 256;
-        if (hipMalloc(&p->d_tables, total) != hipSuccess ||
-            hipMemcpy(p->d_tables, hs->channels.data(), b_ch, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(static_cast<char*>(p->d_tables) + o_w, wins.data(), b_w, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(static_cast<char*>(p->d_tables) + o_e, ents.data(), b_e, hipMemcpyHostToDevice) != hipSuccess) {
-          wfk_chain_plan_destroy(p);
-          return chain_fail(WFK_ENOMEM, "chain table allocation failed");
-        }
-        char* base = static_cast<char*>(p->d_tables);
-        p->d_channels = reinterpret_cast<DevChannel*>(base);
-        p->d_wins = reinterpret_cast<ShortWin*>(base + o_w);
-        p->d_entries = reinterpret_cast<uint32_t*>(base + o_e);
+        DevTables t;
+        const size_t o_ch = t.add(hs->channels), o_w = t.add(wins), o_e = t.add(ents);
+        if (!p->d_tables.alloc(t.total()) || !t.upload(p->d_tables.get()))
+          return wfk_fail(WFK_ENOMEM, "chain table allocation failed");
+        p->d_channels = t.at<DevChannel>(p->d_tables.get(), o_ch);
+        p->d_wins = t.at<ShortWin>(p->d_tables.get(), o_w);
+        p->d_entries = t.at<uint32_t>(p->d_tables.get(), o_e);
         p->d_recs = d_recs;
-        p->table_bytes = (int64_t)(b_ch + b_w + b_e + hs->params.size() * sizeof(double));
+        p->table_bytes = (int64_t)(hs->channels.size() * sizeof(DevChannel) + wins.size() * sizeof(ShortWin) +
+                                   ents.size() * sizeof(uint32_t) + hs->params.size() * sizeof(double));
         if (hs->mixed) {
           // the general kernel's pieces (few, by construction: a plan dominated by them is not short) travel
           // through rows of a workspace, written sparsely in a launch of their own
           const size_t es = kind == WFK_OUT_F32 ? 4 : 8;
-          if (hipMalloc(&p->workspace, (size_t)p->n_channels * (size_t)p->n * es) != hipSuccess) {
-            wfk_chain_plan_destroy(p);
-            return chain_fail(WFK_ENOMEM, "chain workspace allocation failed");
-          }
+          if (!p->workspace.alloc((size_t)p->n_channels * (size_t)p->n * es))
+            return wfk_fail(WFK_ENOMEM, "chain workspace allocation failed");
           p->hybrid = true;
         }
         p->shortw = true;
         p->fused = true;
         p->why.clear();
-        *out = p;
+        *out = p.release();
         return WFK_OK;
       }
       p->why += "; short geometry: " + bad;
@@ -641,37 +623,26 @@ static int chain_plan_create(const wfk_program* prog, const wfk_grid* grid, cons
         pair_first[(size_t)c * p->npairs + pr] = q;
       }
     }
-    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    const size_t b_ch = H.channels.size() * sizeof(DevChannel), b_pc = H.pieces.size() * sizeof(DevPiece),
-                 b_pa = H.params.size() * sizeof(double), b_pf = pair_first.size() * sizeof(int32_t);
-    const size_t o_pc = al(b_ch), o_pa = al(o_pc + b_pc), o_pf = al(o_pa + b_pa), total = al(o_pf + b_pf) + 256;
-    std::vector<char> stage(total, 0);
-    std::memcpy(stage.data(), H.channels.data(), b_ch);
-    std::memcpy(stage.data() + o_pc, H.pieces.data(), b_pc);
-    std::memcpy(stage.data() + o_pa, H.params.data(), b_pa);
-    std::memcpy(stage.data() + o_pf, pair_first.data(), b_pf);
-    if (hipMalloc(&p->d_tables, total) != hipSuccess ||
-        hipMemcpy(p->d_tables, stage.data(), total, hipMemcpyHostToDevice) != hipSuccess) {
-      wfk_chain_plan_destroy(p);
-      return chain_fail(WFK_ENOMEM, "chain table allocation failed");
-    }
-    char* base = static_cast<char*>(p->d_tables);
-    p->d_channels = reinterpret_cast<DevChannel*>(base);
-    p->d_pieces = reinterpret_cast<DevPiece*>(base + o_pc);
-    p->d_params = reinterpret_cast<double*>(base + o_pa);
-    p->d_pair_first = reinterpret_cast<int32_t*>(base + o_pf);
-    p->table_bytes = (int64_t)total;
+    DevTables t;
+    const size_t o_ch = t.add(H.channels), o_pc = t.add(H.pieces), o_pa = t.add(H.params), o_pf = t.add(pair_first);
+    if (!p->d_tables.alloc(t.total()) || !t.upload(p->d_tables.get()))
+      return wfk_fail(WFK_ENOMEM, "chain table allocation failed");
+    p->d_channels = t.at<DevChannel>(p->d_tables.get(), o_ch);
+    p->d_pieces = t.at<DevPiece>(p->d_tables.get(), o_pc);
+    p->d_params = t.at<double>(p->d_tables.get(), o_pa);
+    p->d_pair_first = t.at<int32_t>(p->d_tables.get(), o_pf);
+    p->table_bytes = (int64_t)t.total();
     p->fused = true;
   } else {
     // unfused: the samples go through a workspace owned by the plan (no allocation at launch)
     const size_t es = kind == WFK_OUT_F32 ? 4 : 8;
-    if (hipMalloc(&p->workspace, (size_t)p->n_channels * (size_t)p->n * es) != hipSuccess) {
-      wfk_chain_plan_destroy(p);
-      return chain_fail(WFK_ENOMEM, "chain workspace allocation failed");
-    }
+    if (!p->workspace.alloc((size_t)p->n_channels * (size_t)p->n * es))
+      return wfk_fail(WFK_ENOMEM, "chain workspace allocation failed");
   }
-  *out = p;
+  *out = p.release();
   return WFK_OK;
+} catch (const std::bad_alloc&) {
+  return wfk_fail(WFK_ENOMEM, "out of host memory while building the chain plan");
 }
 
 int wfk_chain_is_fused(const wfk_chain_plan* p) { return p && p->fused ? 1 : 0; }
@@ -679,7 +650,7 @@ int wfk_chain_is_fused(const wfk_chain_plan* p) { return p && p->fused ? 1 : 0; 
 const char* wfk_chain_unfused_reason(const wfk_chain_plan* p) { return p ? p->why.c_str() : ""; }
 
 int64_t wfk_chain_table_bytes(const wfk_chain_plan* p) {
-  if (!p) return chain_fail(WFK_EINVAL, "null plan");
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   return p->fused ? p->table_bytes : wfk_plan_table_bytes(p->sampler);
 }
 
@@ -696,26 +667,26 @@ const char* wfk_chain_kernel_name(const wfk_chain_plan* p) {
 }
 
 int wfk_chain_launch(wfk_chain_plan* p, void* out_dev, int64_t out_stride, void* hip_stream) {
-  if (!p) return chain_fail(WFK_EINVAL, "null plan");
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0 || p->n_channels == 0) return WFK_OK;
-  if (!out_dev) return chain_fail(WFK_EINVAL, "null output");
-  if (out_stride < p->n) return chain_fail(WFK_EINVAL, "out_stride smaller than n");
+  if (!out_dev) return wfk_fail(WFK_EINVAL, "null output");
+  if (out_stride < p->n) return wfk_fail(WFK_EINVAL, "out_stride smaller than n");
   hipStream_t s = (hipStream_t)hip_stream;
   if (!p->fused) {
-    int rc = wfk_plan_launch(p->sampler, p->workspace, p->n, p->kind, 0, hip_stream);
+    int rc = wfk_plan_launch(p->sampler, p->workspace.get(), p->n, p->kind, 0, hip_stream);
     if (rc) return rc;
-    return wfk_fir_apply(p->fir, p->workspace, p->n, out_dev, out_stride, hip_stream);
+    return wfk_fir_apply(p->fir, p->workspace.get(), p->n, out_dev, out_stride, hip_stream);
   }
   const void *kspec = nullptr, *tw = nullptr;
   int fir_fused = 0, nseg = 0, K = 0, lead = 0;
   wfk_internal_fir_tables(p->fir, &kspec, &tw, &fir_fused, &nseg, &K, &lead);
   if (p->shortw) {
     if (p->hybrid) {
-      const int rc = wfk_internal_plan_launch_foreign(p->sampler, p->workspace, p->n, p->kind, hip_stream);
+      const int rc = wfk_internal_plan_launch_foreign(p->sampler, p->workspace.get(), p->n, p->kind, hip_stream);
       if (rc) return rc;
     }
     ChainShortArgs a{};
-    a.ws = p->workspace; a.ws_stride = p->n;
+    a.ws = p->workspace.get(); a.ws_stride = p->n;
     a.channels = p->d_channels; a.wins = p->d_wins; a.entries = p->d_entries; a.recs = p->d_recs;
     a.out = out_dev; a.out_stride = out_stride; a.n = p->n; a.npairs = p->npairs;
     a.hspec = kspec; a.tw = tw; a.step = p->step; a.hrow = wfk_internal_fir_krow(p->fir);
@@ -728,7 +699,7 @@ int wfk_chain_launch(wfk_chain_plan* p, void* out_dev, int64_t out_stride, void*
       if (p->hopb == 12) hipLaunchKernelGGL((fir_short<double, 12>), grid, dim3(256), 0, s, a);
       else hipLaunchKernelGGL((fir_short<double, 10>), grid, dim3(256), 0, s, a);
     }
-    if (hipGetLastError() != hipSuccess) return chain_fail(WFK_EHIP, "fused sampler->FIR kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "fused sampler->FIR kernel launch failed");
     return WFK_OK;
   }
   ChainArgs a{};
@@ -745,7 +716,7 @@ int wfk_chain_launch(wfk_chain_plan* p, void* out_dev, int64_t out_stride, void*
     if (p->hopb == 12) hipLaunchKernelGGL((fir_sampled<double, 12>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((fir_sampled<double, 10>), grid, dim3(256), 0, s, a);
   }
-  if (hipGetLastError() != hipSuccess) return chain_fail(WFK_EHIP, "fused sampler->FIR kernel launch failed");
+  if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "fused sampler->FIR kernel launch failed");
   return WFK_OK;
 }
 

@@ -1,0 +1,102 @@
+// wfk_host.h -- what the host side of every stage shares: the error helper, the device probe, the owners of a
+// plan's device memory (DevBuf, MappedWord), the packer of several host tables into one device block (DevTables),
+// next to the prototypes of the functions one stage's file calls in another's (wfk_internal.h).  Host code only.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "wfk_internal.h"
+
+namespace {
+
+inline int wfk_fail(int code, const std::string& m) {
+  wfk_internal_set_error(m.c_str());
+  return code;
+}
+
+inline bool wfk_have_device() {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) return true;
+  (void)hipGetLastError();
+  return false;
+}
+
+// owner of one device allocation
+template <typename T>
+class DevBuf {
+  T* p_ = nullptr;
+
+ public:
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); return *this; }
+  ~DevBuf() { if (p_) (void)hipFree(p_); }
+  bool alloc(size_t bytes) { return hipMalloc((void**)&p_, bytes) == hipSuccess; }
+  bool upload(const void* src, size_t bytes) {
+    return alloc(bytes) && hipMemcpy(p_, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+  }
+  bool upload(const std::vector<T>& src) { return upload(src.data(), src.size() * sizeof(T)); }
+  T* get() const { return p_; }
+  explicit operator bool() const { return p_ != nullptr; }
+};
+
+// owner of one word of mapped host memory that kernels raise and the host polls (a plan's fault word)
+class MappedWord {
+  unsigned* host_ = nullptr;
+  unsigned* dev_ = nullptr;
+
+ public:
+  MappedWord() = default;
+  MappedWord(const MappedWord&) = delete;
+  MappedWord& operator=(const MappedWord&) = delete;
+  ~MappedWord() { if (host_) (void)hipHostFree(host_); }
+  bool alloc() {
+    if (hipHostMalloc((void**)&host_, 64, hipHostMallocMapped) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&dev_, host_, 0) != hipSuccess)
+      return false;
+    *host_ = 0;
+    return true;
+  }
+  volatile unsigned* host() const { return host_; }
+  unsigned* dev() const { return dev_; }
+};
+
+// Several host tables packed into ONE device block, each at a 256-byte boundary: add() copies a table into the
+// host image and returns its offset, reserve() leaves room for a region the caller uploads on its own (a time axis
+// as large as the output), total() is the size of the block to take (a spare 256 bytes behind the last table),
+// upload() sends the image in one copy, at<T>() is the typed address of an offset in the block.  reserve() comes
+// after the last add(): the image ends where the first reserved region starts.
+class DevTables {
+  std::vector<char> image_;   // [0, offset of the first reserved region)
+  size_t end_ = 0;
+
+  static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+ public:
+  size_t add(const void* src, size_t bytes) {
+    const size_t o = reserve(bytes);
+    image_.resize(end_, 0);
+    if (bytes) std::memcpy(image_.data() + o, src, bytes);
+    return o;
+  }
+  template <typename T>
+  size_t add(const std::vector<T>& v) { return add(v.data(), v.size() * sizeof(T)); }
+  size_t reserve(size_t bytes) {
+    const size_t o = end_;
+    end_ = align256(o + bytes);
+    return o;
+  }
+  size_t total() const { return end_ + 256; }
+  const std::vector<char>& image() const { return image_; }
+  bool upload(void* block) const {
+    return image_.empty() || hipMemcpy(block, image_.data(), image_.size(), hipMemcpyHostToDevice) == hipSuccess;
+  }
+  template <typename T>
+  static T* at(void* block, size_t offset) { return reinterpret_cast<T*>(static_cast<char*>(block) + offset); }
+};
+
+}  // namespace

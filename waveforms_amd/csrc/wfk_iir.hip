@@ -1078,12 +1078,12 @@ int wfk_iir_plan_destroy(wfk_iir_plan* p) {
 
 int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double* b, const double* a,
                         int64_t n, int32_t batch, int kind, wfk_iir_plan** out) {
-  if (!out) return iir_fail(WFK_EINVAL, "null out");
+  if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
   if (n_sections < 1 || n_sections > 4096 || !orders || !b || !a || n < 0 || batch < 1 ||
       batch > 65535)
-    return iir_fail(WFK_EINVAL, "bad IIR arguments");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return iir_fail(WFK_EINVAL, "IIR kind must be F64 or F32");
+    return wfk_fail(WFK_EINVAL, "bad IIR arguments");
+  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return wfk_fail(WFK_EINVAL, "IIR kind must be F64 or F32");
   std::unique_ptr<wfk_iir_plan> p(new wfk_iir_plan());
   IirCoef& c = p->c;
   std::memset(&c, 0, sizeof c);
@@ -1096,11 +1096,11 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
     int Dtot = 0;
     bool single_too_big = false;
     for (int s = 0; s < n_sections; ++s) {
-      if (orders[s] < 0) return iir_fail(WFK_EINVAL, "negative section order");
+      if (orders[s] < 0) return wfk_fail(WFK_EINVAL, "negative section order");
       single_too_big = single_too_big || orders[s] > IIR_MAXD;
       Dtot += orders[s];
     }
-    if (single_too_big) return iir_fail(WFK_EUNSUP, "a single IIR section of order > 16 (factor it into a cascade)");
+    if (single_too_big) return wfk_fail(WFK_EUNSUP, "a single IIR section of order > 16 (factor it into a cascade)");
     // Register-resident kernels exist for runs of EQUAL order: up to four first-order sections or
     // four biquads, single sections of order 3..8; anything else (mixed orders in one pass, two
     // sections of order 3, ...) would take the runtime-shaped kernel with its state in scratch
@@ -1118,7 +1118,7 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
     }
     const bool split = n_sections > IIR_MAXSEC || Dtot > IIR_MAXD || !one_run;
     if (split) {
-      if (!iir_have_device()) return iir_fail(WFK_EHIP, "no HIP device visible");
+      if (!wfk_have_device()) return wfk_fail(WFK_EHIP, "no HIP device visible");
       c.nsec = 0; c.D = Dtot;
       p->n = n; p->batch = batch; p->kind = kind;
       if (n == 0) { *out = p.release(); return WFK_OK; }
@@ -1140,7 +1140,7 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
         s0 += cnt; pos0 += pp; doff += dd;
       }
       if (!p->zi_tmp.alloc((size_t)batch * IIR_MAXD * 8) || !p->zf_tmp.alloc((size_t)batch * IIR_MAXD * 8))
-        return iir_fail(WFK_ENOMEM, "IIR buffer allocation failed");
+        return wfk_fail(WFK_ENOMEM, "IIR buffer allocation failed");
       *out = p.release();
       return WFK_OK;
     }
@@ -1151,9 +1151,9 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
   for (int s = 0; s < n_sections; ++s) {
     const int ord = orders[s];
     if (ord < 0 || ord > IIR_MAXD || D + ord > IIR_MAXD)
-      return iir_fail(WFK_EINVAL, "IIR order too large (total state dimension <= 16)");
+      return wfk_fail(WFK_EINVAL, "IIR order too large (total state dimension <= 16)");
     const double a0 = a[pos];
-    if (!(a0 != 0.0) || !std::isfinite(a0)) return iir_fail(WFK_EINVAL, "a[0] must be finite and non-zero");
+    if (!(a0 != 0.0) || !std::isfinite(a0)) return wfk_fail(WFK_EINVAL, "a[0] must be finite and non-zero");
     c.ord[s] = ord;
     c.off[s] = D;
     for (int i = 0; i <= ord; ++i) {   // scipy normalises by a[0]
@@ -1169,7 +1169,7 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
   p->n = n; p->batch = batch; p->kind = kind;
   p->nblk = n > 0 ? (n + IIR_LB - 1) / IIR_LB : 0;
   p->ngrp = (p->nblk + 63) / 64;
-  if (!iir_have_device()) return iir_fail(WFK_EHIP, "no HIP device visible");
+  if (!wfk_have_device()) return wfk_fail(WFK_EHIP, "no HIP device visible");
   if (n == 0 || D == 0) {
     // order-0 sections only: a pure gain (lfilter with len(a) == len(b) == 1 per section)
     p->gain = 1.0;
@@ -1189,7 +1189,7 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
   tables(U, pw2, lanep2);
   if (!p->state.alloc((size_t)batch * p->nblk * D * 8) || !p->grp.alloc((size_t)batch * p->ngrp * D * 8) ||
       !p->pw.upload(pw) || !p->lanep.upload(lanep) || !p->pw2.upload(pw2) || !p->lanep2.upload(lanep2))
-    return iir_fail(WFK_ENOMEM, "IIR buffer allocation failed");
+    return wfk_fail(WFK_ENOMEM, "IIR buffer allocation failed");
   // single-pass form: one or two biquads (state dimension <= 4), rows long enough to chain
   {
     // shapes: one or two biquads, or up to four FIRST-order sections -- the cascade of exponential
@@ -1250,7 +1250,7 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
           !p->op_pref.alloc(slots * D * 8) || !p->op_pw1.upload(pw1) || !p->op_lanep1.upload(lanep1) ||
           !p->op_lanepU.upload(lanepU) || !p->op_pwL.upload(pwL) || !p->op_lanepL.upload(lanepL) ||
           !p->op_lanepUL.upload(lanepUL) || !p->op_wdot.upload(wdot) || !p->op_fault.alloc())
-        return iir_fail(WFK_ENOMEM, "IIR single-pass buffer allocation failed");
+        return wfk_fail(WFK_ENOMEM, "IIR single-pass buffer allocation failed");
       // ONE section of order 3 / 4 whose transition powers grow past 1e3 (clustered poles: butter(4, 0.022) as a single
       // (b, a), 3.2e3): the block start states this form re-injects every 32 samples as doubles cost it a digit against
       // the three-launch form (iirchain_soak seed 12713, against a long-double recursion: 1.1e-10 vs 2.4e-11 of peak;
@@ -1303,11 +1303,11 @@ extern "C" {
 static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride, void* out_dev,
                           int64_t out_stride, const double* zi_dev, double* zf_dev, double initial,
                           double post, void* hip_stream, const IirSampArgs* src = nullptr) {
-  if (!p) return iir_fail(WFK_EINVAL, "null plan");
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0) return WFK_OK;
   if (src) { in_dev = out_dev; in_stride = out_stride; }     // (never read)
-  if (!in_dev || !out_dev) return iir_fail(WFK_EINVAL, "null buffer");
-  if (in_stride < p->n || out_stride < p->n) return iir_fail(WFK_EINVAL, "stride smaller than n");
+  if (!in_dev || !out_dev) return wfk_fail(WFK_EINVAL, "null buffer");
+  if (in_stride < p->n || out_stride < p->n) return wfk_fail(WFK_EINVAL, "stride smaller than n");
   hipStream_t s = (hipStream_t)hip_stream;
   if (p->c.D == 0) {
     const dim3 g((unsigned)std::min<int64_t>((p->n + 255) / 256, 4096), (unsigned)p->batch);
@@ -1317,7 +1317,7 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
     else
       hipLaunchKernelGGL(iir_scale<double>, g, dim3(256), 0, s, (const double*)in_dev, in_stride,
                          (double*)out_dev, out_stride, p->n, p->gain, initial, post);
-    if (hipGetLastError() != hipSuccess) return iir_fail(WFK_EHIP, "IIR kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "IIR kernel launch failed");
     return WFK_OK;
   }
   if (!p->parts.empty()) {
@@ -1328,7 +1328,7 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
       if (zi_dev && Di > 0 &&
           hipMemcpy2DAsync(p->zi_tmp.get(), Di * 8, zi_dev + off, D * 8, Di * 8, (size_t)p->batch,
                            hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return iir_fail(WFK_EHIP, "IIR state repack failed");
+        return wfk_fail(WFK_EHIP, "IIR state repack failed");
       // the DC offset comes off before the first pass and goes back on after the last one only:
       // between passes the signal can be 1e-7 of the offset (a 16th-order Butterworth after its
       // first four sections), which an fp32 buffer holding signal + offset would wipe out
@@ -1342,7 +1342,7 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
       if (zf_dev && Di > 0 &&
           hipMemcpy2DAsync(zf_dev + off, D * 8, p->zf_tmp.get(), Di * 8, Di * 8, (size_t)p->batch,
                            hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return iir_fail(WFK_EHIP, "IIR state repack failed");
+        return wfk_fail(WFK_EHIP, "IIR state repack failed");
     }
     return WFK_OK;
   }
@@ -1351,16 +1351,16 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
     // serve this plan in the three-launch form from here on (no chained waits, cannot time out)
     *p->op_fault.host() = 0;
     p->onepass = false;
-    return iir_fail(WFK_ETIMEOUT, "IIR single pass: a look-back timed out in an EARLIER launch of this plan (a stalled or "
+    return wfk_fail(WFK_ETIMEOUT, "IIR single pass: a look-back timed out in an EARLIER launch of this plan (a stalled or "
                                   "preempted predecessor chunk); its outputs hold NaN. The plan now runs in the three-launch form: launch again");
   }
-  if (src && !p->onepass) return iir_fail(WFK_EINVAL, "sampled source on a stage that is not in the single-pass form");
+  if (src && !p->onepass) return wfk_fail(WFK_EINVAL, "sampled source on a stage that is not in the single-pass form");
   if (p->onepass) {
     int spin_limit = OP_SPIN;
     if (const char* e = getenv("WFK_IIR_SPIN")) spin_limit = atoi(e);   // (tests: force the timeout)
     // tickets restart at 0; the flags of earlier launches are told apart by the epoch
     if (hipMemsetAsync(p->op_ticket.get(), 0, (size_t)p->batch * 64, s) != hipSuccess)
-      return iir_fail(WFK_EHIP, "IIR ticket reset failed");
+      return wfk_fail(WFK_EHIP, "IIR ticket reset failed");
     const unsigned epoch = ++p->epoch;
     // Few long rows: with one chunk per workgroup 2304 / rows chunks of a row are in flight, and a
     // look-back reads every one of them.  Below OP_DEPTH_ROWS rows the grid is op_depth persistent waves
@@ -1424,12 +1424,12 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
 #undef OP_LAUNCH
 #undef OP_LAUNCH_K
 #undef OP_COMMA
-    if (hipGetLastError() != hipSuccess) return iir_fail(WFK_EHIP, "IIR kernel launch failed");
+    if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "IIR kernel launch failed");
     return WFK_OK;
   }
   if (p->kind == WFK_OUT_F32) iir_launch<float>(p, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial, post, s);
   else iir_launch<double>(p, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial, post, s);
-  if (hipGetLastError() != hipSuccess) return iir_fail(WFK_EHIP, "IIR kernel launch failed");
+  if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "IIR kernel launch failed");
   return WFK_OK;
 }
 
@@ -1437,8 +1437,8 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
 // passes) ran into a look-back timeout since the last check.  On a fault the plan switches to the
 // three-launch form, so the caller can simply launch again (not in place: the input is gone then).
 extern "C" int wfk_iir_status(wfk_iir_plan* p, void* hip_stream) {
-  if (!p) return iir_fail(WFK_EINVAL, "null plan");
-  if (hipStreamSynchronize((hipStream_t)hip_stream) != hipSuccess) return iir_fail(WFK_EHIP, "stream synchronisation failed");
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
+  if (hipStreamSynchronize((hipStream_t)hip_stream) != hipSuccess) return wfk_fail(WFK_EHIP, "stream synchronisation failed");
 
   bool fault = false;
   auto look = [&](wfk_iir_plan* q) {
@@ -1456,7 +1456,7 @@ extern "C" int wfk_iir_status(wfk_iir_plan* p, void* hip_stream) {
     for (auto& q : p->parts) q->onepass = false;
   }
   if (fault)
-    return iir_fail(WFK_ETIMEOUT, "IIR single pass: a look-back timed out (a stalled or preempted predecessor chunk); the outputs "
+    return wfk_fail(WFK_ETIMEOUT, "IIR single pass: a look-back timed out (a stalled or preempted predecessor chunk); the outputs "
                                   "of that launch hold NaN. The plan now runs in the three-launch form: launch again");
   return WFK_OK;
 }
@@ -1473,8 +1473,6 @@ extern "C" int wfk_iir_apply(wfk_iir_plan* p, const void* in_dev, int64_t in_str
 // ---- sampler -> IIR (-> FIR) chain --------------------------------------------------------------------------
 // Reference: Waveform.sample(filters=(sos, initial)) (waveforms/waveform.py:190-203,244-251) and
 // predistort(wav(t), filters, ker) (waveforms/distortion.py:298-337): sampler -> sosfilt / lfilter -> FIR.
-extern "C" void wfk_internal_plan_tables(const wfk_plan* p, const HostPlan** h, const double** d_params);
-
 struct wfk_chain_iir_plan {
   wfk_plan* sampler = nullptr;     // the plain sampler plan: the unfused path, queries
   wfk_iir_plan* iir = nullptr;
@@ -1509,11 +1507,11 @@ int wfk_chain_iir_plan_destroy(wfk_chain_iir_plan* p) {
 int wfk_chain_iir_plan_create(const wfk_program* prog, const wfk_grid* grid, int32_t n_sections,
                               const int32_t* orders, const double* b, const double* a, const double* ker_host,
                               int32_t K, int32_t ker_per_row, int kind, wfk_chain_iir_plan** out) {
-  if (!out) return iir_fail(WFK_EINVAL, "null out");
+  if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
-  if (!prog || !grid) return iir_fail(WFK_EINVAL, "null argument");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return iir_fail(WFK_EINVAL, "chain kind must be F64 or F32");
-  if (ker_host && K < 1) return iir_fail(WFK_EINVAL, "empty FIR kernel");
+  if (!prog || !grid) return wfk_fail(WFK_EINVAL, "null argument");
+  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return wfk_fail(WFK_EINVAL, "chain kind must be F64 or F32");
+  if (ker_host && K < 1) return wfk_fail(WFK_EINVAL, "empty FIR kernel");
   try {
     std::unique_ptr<wfk_chain_iir_plan> p(new wfk_chain_iir_plan());
     p->kind = kind;
@@ -1528,7 +1526,7 @@ int wfk_chain_iir_plan_create(const wfk_program* prog, const wfk_grid* grid, int
     if (p->n == 0 || p->n_channels == 0) { *out = p.release(); return WFK_OK; }
     const size_t es = kind == WFK_OUT_F32 ? 4 : 8;
     if (p->fir && !p->workspace.alloc((size_t)p->n_channels * (size_t)p->n * es))
-      return iir_fail(WFK_ENOMEM, "chain workspace allocation failed");
+      return wfk_fail(WFK_ENOMEM, "chain workspace allocation failed");
     // ---- can the sampler run inside the first IIR pass? ----------------------------------------------
     wfk_iir_plan* first = chain_first_stage(p.get());
     const char* off = getenv("WFK_CHAIN_UNFUSED");
@@ -1593,32 +1591,25 @@ int wfk_chain_iir_plan_create(const wfk_program* prog, const wfk_grid* grid, int
       }
     }
     if (p->why.empty()) {
-      auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-      const size_t b_ch = H.channels.size() * sizeof(DevChannel), b_pc = H.pieces.size() * sizeof(DevPiece),
-                   b_pa = H.params.size() * sizeof(double), b_cf = chunk_first.size() * sizeof(int32_t);
-      const size_t o_pc = al(b_ch), o_pa = al(o_pc + b_pc), o_cf = al(o_pa + b_pa), total = al(o_cf + b_cf) + 256;
-      std::vector<char> stage(total, 0);
-      std::memcpy(stage.data(), H.channels.data(), b_ch);
-      std::memcpy(stage.data() + o_pc, H.pieces.data(), b_pc);
-      std::memcpy(stage.data() + o_pa, H.params.data(), b_pa);
-      std::memcpy(stage.data() + o_cf, chunk_first.data(), b_cf);
-      if (!p->d_tables.upload(stage)) return iir_fail(WFK_ENOMEM, "chain table allocation failed");
-      char* base = p->d_tables.get();
+      DevTables t;
+      const size_t o_ch = t.add(H.channels), o_pc = t.add(H.pieces), o_pa = t.add(H.params), o_cf = t.add(chunk_first);
+      if (!p->d_tables.alloc(t.total()) || !t.upload(p->d_tables.get()))
+        return wfk_fail(WFK_ENOMEM, "chain table allocation failed");
       IirSampArgs& sa = p->sa;
-      sa.channels = reinterpret_cast<const DevChannel*>(base);
-      sa.pieces = reinterpret_cast<const DevPiece*>(base + o_pc);
-      sa.params = reinterpret_cast<const double*>(base + o_pa);
-      sa.chunk_first = reinterpret_cast<const int32_t*>(base + o_cf);
+      sa.channels = t.at<const DevChannel>(p->d_tables.get(), o_ch);
+      sa.pieces = t.at<const DevPiece>(p->d_tables.get(), o_pc);
+      sa.params = t.at<const double>(p->d_tables.get(), o_pa);
+      sa.chunk_first = t.at<const int32_t>(p->d_tables.get(), o_cf);
       sa.nchunks = nch;
       sa.t0 = grid->t0; sa.step = grid->step; sa.last = grid->last; sa.has_last = grid->has_last;
       sa.n = grid->n; sa.i0 = grid->i0;
-      p->table_bytes = (int64_t)total;
+      p->table_bytes = (int64_t)t.total();
       p->fused = true;
     }
     *out = p.release();
     return WFK_OK;
   } catch (const std::bad_alloc&) {
-    return iir_fail(WFK_ENOMEM, "out of host memory while building the chain plan");
+    return wfk_fail(WFK_ENOMEM, "out of host memory while building the chain plan");
   }
 }
 
@@ -1638,7 +1629,7 @@ const char* wfk_chain_iir_unfused_reason(const wfk_chain_iir_plan* p) {
 int wfk_chain_iir_state_dim(const wfk_chain_iir_plan* p) { return p ? wfk_iir_state_dim(p->iir) : WFK_EINVAL; }
 
 int64_t wfk_chain_iir_table_bytes(const wfk_chain_iir_plan* p) {
-  if (!p) return iir_fail(WFK_EINVAL, "null plan");
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   return p->fused ? p->table_bytes : wfk_plan_table_bytes(p->sampler);
 }
 
@@ -1660,10 +1651,10 @@ const char* wfk_chain_iir_kernel_name(const wfk_chain_iir_plan* p) {
 
 int wfk_chain_iir_launch(wfk_chain_iir_plan* p, void* out_dev, int64_t out_stride, const double* zi_dev,
                          double* zf_dev, double initial, void* hip_stream) {
-  if (!p) return iir_fail(WFK_EINVAL, "null plan");
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0 || p->n_channels == 0) return WFK_OK;
-  if (!out_dev) return iir_fail(WFK_EINVAL, "null output");
-  if (out_stride < p->n) return iir_fail(WFK_EINVAL, "out_stride smaller than n");
+  if (!out_dev) return wfk_fail(WFK_EINVAL, "null output");
+  if (out_stride < p->n) return wfk_fail(WFK_EINVAL, "out_stride smaller than n");
   void* mid = p->fir ? p->workspace.get() : out_dev;
   const int64_t mid_stride = p->fir ? p->n : out_stride;
   int rc;
@@ -1681,7 +1672,7 @@ int wfk_chain_iir_launch(wfk_chain_iir_plan* p, void* out_dev, int64_t out_strid
 /* as wfk_iir_status: synchronises, WFK_ETIMEOUT if a look-back of a launch since the last check timed out (outputs
  * hold NaN); launching again then takes the three-launch form behind the plain sampler */
 int wfk_chain_iir_status(wfk_chain_iir_plan* p, void* hip_stream) {
-  if (!p) return iir_fail(WFK_EINVAL, "null plan");
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   return wfk_iir_status(p->iir, hip_stream);
 }
 

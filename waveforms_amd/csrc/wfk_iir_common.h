@@ -1,14 +1,12 @@
 // wfk_iir_common.h -- what every IIR form shares (wfk_iir.hip: three-launch scan, iir_onepass, iir_sampled;
 // wfk_iir_rows.hip: one cascade per row): the cascade step, the double-double mat-vec that applies the
-// transition tables, the quad-precision builder of those tables, and the owner of a plan's device memory.
+// transition tables, and the quad-precision builder of those tables.  (Errors, device memory: wfk_host.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <string>
-#include <utility>
 #include <vector>
 
-extern "C" void wfk_internal_set_error(const char* msg);
+#include "wfk_host.h"
 
 namespace {
 
@@ -137,58 +135,5 @@ inline std::vector<quad> iir_power_tables(const std::vector<quad>& B, int D, int
   }
   return cur;
 }
-
-// ---- host: errors, device probe, memory ownership ---------------------------------------------------------------
-inline int iir_fail(int code, const std::string& m) {
-  wfk_internal_set_error(m.c_str());
-  return code;
-}
-
-inline bool iir_have_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) return true;
-  (void)hipGetLastError();
-  return false;
-}
-
-// owner of one device allocation
-template <typename T>
-class DevBuf {
-  T* p_ = nullptr;
-
- public:
-  DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)) {}
-  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); return *this; }
-  ~DevBuf() { if (p_) (void)hipFree(p_); }
-  bool alloc(size_t bytes) { return hipMalloc((void**)&p_, bytes) == hipSuccess; }
-  bool upload(const void* src, size_t bytes) {
-    return alloc(bytes) && hipMemcpy(p_, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  }
-  bool upload(const std::vector<T>& src) { return upload(src.data(), src.size() * sizeof(T)); }
-  T* get() const { return p_; }
-  explicit operator bool() const { return p_ != nullptr; }
-};
-
-// owner of one word of mapped host memory that kernels raise and the host polls (a plan's fault word)
-class MappedWord {
-  unsigned* host_ = nullptr;
-  unsigned* dev_ = nullptr;
-
- public:
-  MappedWord() = default;
-  MappedWord(const MappedWord&) = delete;
-  MappedWord& operator=(const MappedWord&) = delete;
-  ~MappedWord() { if (host_) (void)hipHostFree(host_); }
-  bool alloc() {
-    if (hipHostMalloc((void**)&host_, 64, hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&dev_, host_, 0) != hipSuccess)
-      return false;
-    *host_ = 0;
-    return true;
-  }
-  volatile unsigned* host() const { return host_; }
-  unsigned* dev() const { return dev_; }
-};
 
 }  // namespace

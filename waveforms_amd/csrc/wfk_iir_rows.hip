@@ -231,7 +231,7 @@ static int irw_launch(const wfk_iir_rows_plan* p, const void* in, int64_t is, vo
   IRW_CASE(2, 1) IRW_CASE(3, 1) IRW_CASE(4, 1)                          // cascades of first-order corrections
   IRW_CASE(2, 2)                                                        // two biquads
 #undef IRW_CASE
-  return iir_fail(WFK_EINVAL, "per-row IIR: no kernel for this shape");
+  return wfk_fail(WFK_EINVAL, "per-row IIR: no kernel for this shape");
 }
 
 extern "C" {
@@ -243,21 +243,21 @@ int wfk_iir_rows_plan_destroy(wfk_iir_rows_plan* p) {
 
 int wfk_iir_rows_plan_create(int32_t n_sections, const int32_t* orders, const double* b_rows, const double* a_rows,
                              int64_t n, int32_t batch, int kind, wfk_iir_rows_plan** out) {
-  if (!out) return iir_fail(WFK_EINVAL, "null out");
+  if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
   if (n_sections < 1 || !orders || !b_rows || !a_rows || n < 0 || batch < 1)
-    return iir_fail(WFK_EINVAL, "bad per-row IIR arguments");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return iir_fail(WFK_EINVAL, "IIR kind must be F64 or F32");
+    return wfk_fail(WFK_EINVAL, "bad per-row IIR arguments");
+  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return wfk_fail(WFK_EINVAL, "IIR kind must be F64 or F32");
   bool equal = true;
   int64_t Dtot = 0;
   for (int s = 0; s < n_sections; ++s) {
-    if (orders[s] < 0) return iir_fail(WFK_EINVAL, "negative section order");
+    if (orders[s] < 0) return wfk_fail(WFK_EINVAL, "negative section order");
     equal = equal && orders[s] == orders[0];
     Dtot += orders[s];
   }
   const int ord = orders[0];
   if (!equal || ord < 1 || Dtot > IRW_MAXD || (ord == 2 && n_sections > 2))
-    return iir_fail(WFK_EUNSUP,
+    return wfk_fail(WFK_EUNSUP,
                  "per-row IIR cascades take sections of EQUAL order >= 1 with a total state dimension <= " +
                      std::to_string(IRW_MAXD) + " (one section of order 1..4, 1..4 first-order sections, one or two "
                      "biquads); got " + std::to_string(n_sections) + " section(s), state dimension " +
@@ -270,13 +270,13 @@ int wfk_iir_rows_plan_create(int32_t n_sections, const int32_t* orders, const do
       const size_t at = (size_t)r * NC + (size_t)s * (ord + 1);
       const double a0 = a_rows[at];
       if (!(a0 != 0.0) || !std::isfinite(a0))
-        return iir_fail(WFK_EINVAL, "a[0] must be finite and non-zero (row " + std::to_string((long long)r) + ")");
+        return wfk_fail(WFK_EINVAL, "a[0] must be finite and non-zero (row " + std::to_string((long long)r) + ")");
       for (int i = 0; i <= ord; ++i) {
         bn[at + i] = b_rows[at + i] / a0;
         an[at + i] = a_rows[at + i] / a0;
       }
     }
-  if (!iir_have_device()) return iir_fail(WFK_EHIP, "no HIP device visible");
+  if (!wfk_have_device()) return wfk_fail(WFK_EHIP, "no HIP device visible");
   std::unique_ptr<wfk_iir_rows_plan> p(new wfk_iir_rows_plan());
   p->nsec = n_sections; p->ord = ord; p->D = (int)Dtot;
   p->n = n; p->batch = batch; p->kind = kind;
@@ -306,7 +306,7 @@ int wfk_iir_rows_plan_create(int32_t n_sections, const int32_t* orders, const do
   }
   if (!p->tab.upload(tab)) {
     (void)hipGetLastError();
-    return iir_fail(WFK_ENOMEM, "per-row IIR plan: device allocation / upload failed");
+    return wfk_fail(WFK_ENOMEM, "per-row IIR plan: device allocation / upload failed");
   }
   *out = p.release();
   return WFK_OK;
@@ -319,16 +319,16 @@ const char* wfk_iir_rows_kernel_name(const wfk_iir_rows_plan* p) { return p ? p-
 int wfk_iir_rows_apply(wfk_iir_rows_plan* p, const void* in_dev, int64_t in_stride, void* out_dev,
                        int64_t out_stride, const double* zi_dev, double* zf_dev, const double* initial_dev,
                        void* hip_stream) {
-  if (!p) return iir_fail(WFK_EINVAL, "null plan");
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0) return WFK_OK;
-  if (!in_dev || !out_dev) return iir_fail(WFK_EINVAL, "null argument");
-  if (in_stride < p->n || out_stride < p->n) return iir_fail(WFK_EINVAL, "row stride < n");
+  if (!in_dev || !out_dev) return wfk_fail(WFK_EINVAL, "null argument");
+  if (in_stride < p->n || out_stride < p->n) return wfk_fail(WFK_EINVAL, "row stride < n");
   hipStream_t s = (hipStream_t)hip_stream;
   const int rc = p->kind == WFK_OUT_F64
                      ? irw_launch<double>(p, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial_dev, s)
                      : irw_launch<float>(p, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial_dev, s);
   if (rc != WFK_OK) return rc;
-  if (hipGetLastError() != hipSuccess) return iir_fail(WFK_EHIP, "per-row IIR launch failed");
+  if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "per-row IIR launch failed");
   return WFK_OK;
 }
 

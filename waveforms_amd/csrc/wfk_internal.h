@@ -256,6 +256,8 @@ struct KArgs {
 #include <vector>
 struct wfk_program;
 struct wfk_grid;
+struct wfk_plan;
+struct wfk_fir_plan;
 
 struct HostPlan {
   bool tlist = false;
@@ -348,4 +350,21 @@ int wfk_launch_sampler(const KArgs& a, int32_t n_channels, int out_kind, bool tl
                        bool lean, bool generic, bool direct, void* stream, std::string& err);
 // (a.corr selects the lean kernel variant with the per-sample grid-rounding correction)
 int wfk_launch_short(const SArgs& a, int out_kind, void* stream, std::string& err);
+
+// functions one stage's file calls in another's, exported but not part of include/wfk.h
+extern "C" {
+void wfk_internal_set_error(const char* msg);   // wfk_api.cpp: this thread's text behind wfk_last_error
+// wfk_api.cpp: the compiled plan and its parameter table on the device; launch of a mixed short plan's general-kernel part
+void wfk_internal_plan_tables(const wfk_plan* p, const HostPlan** h, const double** d_params);
+int wfk_internal_plan_launch_foreign(wfk_plan* p, void* out_dev, int64_t ch_stride, int out_kind, void* hip_stream);
+// wfk_fir.hip: kernel spectrum and twiddles of a plan that runs as ONE pass of the on-chip transform; its row stride
+void wfk_internal_fir_tables(const wfk_fir_plan* p, const void** kspec, const void** tw, int* fused, int* nseg,
+                             int* K, int* lead);
+int64_t wfk_internal_fir_krow(const wfk_fir_plan* p);
+// wfk_fir_fused.hip: the single-kernel FIR for short kernels
+int wfk_internal_fir_fused_launch(int kind, const void* in, int64_t in_stride, void* out, int64_t out_stride,
+                                  const void* hspec, const void* tw, int64_t n, int M, int K, int lead, int64_t nblk,
+                                  int32_t batch, int accumulate, void* stream, int64_t hspec_row_stride);
+int wfk_internal_fir_fused_len(void);
+}
 #endif
