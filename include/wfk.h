@@ -289,6 +289,13 @@ int wfk_iir_rows_state_dim(const wfk_iir_rows_plan* plan);
 int wfk_iir_rows_apply(wfk_iir_rows_plan* plan, const void* in_dev, int64_t in_stride, void* out_dev,
                        int64_t out_stride, const double* zi_dev, double* zf_dev,
                        const double* initial_dev, void* hip_stream);
+/* The same launch with ONE input row for all rows: every row r reads in_dev[0..n) (row stride 0 inside) and
+ * writes out[r] = F_r(in - initial[r]) + initial[r] -- one signal through `batch` candidate corrections, the
+ * shape of a fit (phase_curve below).  `out` must not overlap `in` (WFK_EINVAL): rows are written while others
+ * still read.  Otherwise as wfk_iir_rows_apply, whose own checks (in_stride >= n) are unchanged.              */
+int wfk_iir_rows_apply_shared_in(wfk_iir_rows_plan* plan, const void* in_dev, void* out_dev, int64_t out_stride,
+                                 const double* zi_dev, double* zf_dev, const double* initial_dev,
+                                 void* hip_stream);
 /* "iir_rows_tile<T,NSEC,ORD>"; the string lives as long as the plan */
 const char* wfk_iir_rows_kernel_name(const wfk_iir_rows_plan* plan);
 int wfk_iir_rows_plan_destroy(wfk_iir_rows_plan* plan);
@@ -349,6 +356,30 @@ int wfk_demod_apply(wfk_demod_plan* p, const void* traces_dev, int64_t n_shots, 
  * until the next call on this plan                                                                      */
 const char* wfk_demod_kernel_name(const wfk_demod_plan* p, int64_t n_shots);
 int wfk_demod_plan_destroy(wfk_demod_plan* p);
+
+/* -- boxcar integral read off at probe times (reference distortion.py:349-366: the tail of phase_curve) ----- */
+/* out[r, q] = np.interp(t_q, tlist, conv[r]) with conv[r, i] = gain * sum_{m < pp} y[r, i + c - m] (y zero outside
+ * [0, n)) -- np.convolve(s, [ones(pp), zeros(sp)], 'same') for c = (pp + sp - 1) / 2 -- for every row of y
+ * (n_rows rows of >= n doubles, row stride y_stride elements) and every one of the n_query probe times, without
+ * forming conv: a probe needs it at its two bracketing grid points only.  The plan is built on the host from the
+ * caller's own tlist[0..n) (ascending, no NaN) and t[0..n_query): per query the bracket index j, dx = t - tlist[j]
+ * and w = tlist[j + 1] - tlist[j] by np.interp's rules (t outside the grid takes the first / last grid value, a NaN
+ * t gives NaN, t in any order), uploaded once.  out[r, q] = f0 + (f1 - f0) / w * dx with f_i = gain * (the pp samples
+ * ending at j + i + c).  fp64 throughout; out is (n_rows, n_query) doubles, row stride out_stride elements.
+ * One kernel (boxprobe_wave): a wave per (row, query), lanes stride the pp + 1 samples both windows share, partial
+ * sums added in a fixed order, no atomics: bitwise reproducible, equal rows give equal results wherever they sit.
+ * wfk_boxprobe_apply() allocates nothing and does not synchronise; a plan holds no scratch and may serve several
+ * streams.  wfk_boxprobe_brackets() is the host-only table builder the plan uses (no device needed).              */
+typedef struct wfk_boxprobe_plan wfk_boxprobe_plan;
+int wfk_boxprobe_brackets(const double* tlist, int64_t n, const double* t, int64_t n_query, int64_t* j_out,
+                          double* dx_out, double* w_out);
+int wfk_boxprobe_plan_create(const double* tlist_host, int64_t n, const double* t_host, int32_t n_query,
+                             int64_t pp, int64_t c, double gain, wfk_boxprobe_plan** out);
+int wfk_boxprobe_apply(wfk_boxprobe_plan* p, const double* y_dev, int64_t n_rows, int64_t y_stride,
+                       double* out_dev, int64_t out_stride, void* hip_stream);
+/* "boxprobe_wave" */
+const char* wfk_boxprobe_kernel_name(const wfk_boxprobe_plan* p);
+int wfk_boxprobe_plan_destroy(wfk_boxprobe_plan* p);
 
 /* -- pinned host blocks for results ------------------------------------------------------- */
 /* Page-locked host memory from a per-process cache (power-of-two blocks, parked on free).  A result

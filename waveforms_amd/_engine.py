@@ -110,6 +110,7 @@ def lib():
         l.wfk_iir_rows_plan_create.argtypes = [I32, VP, VP, VP, I64, I32, C.c_int, P(VP)]
         l.wfk_iir_rows_state_dim.argtypes = [VP]
         l.wfk_iir_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP, VP, VP]
+        l.wfk_iir_rows_apply_shared_in.argtypes = [VP, VP, VP, I64, VP, VP, VP, VP]
         l.wfk_iir_rows_kernel_name.argtypes = [VP]
         l.wfk_iir_rows_kernel_name.restype = C.c_char_p
         l.wfk_iir_rows_plan_destroy.argtypes = [VP]
@@ -121,6 +122,12 @@ def lib():
         l.wfk_demod_kernel_name.argtypes = [VP, I64]
         l.wfk_demod_kernel_name.restype = C.c_char_p
         l.wfk_demod_plan_destroy.argtypes = [VP]
+        l.wfk_boxprobe_brackets.argtypes = [VP, I64, VP, I64, VP, VP, VP]
+        l.wfk_boxprobe_plan_create.argtypes = [VP, I64, VP, I32, I64, I64, C.c_double, P(VP)]
+        l.wfk_boxprobe_apply.argtypes = [VP, VP, I64, I64, VP, I64, VP]
+        l.wfk_boxprobe_kernel_name.argtypes = [VP]
+        l.wfk_boxprobe_kernel_name.restype = C.c_char_p
+        l.wfk_boxprobe_plan_destroy.argtypes = [VP]
         l.wfk_host_alloc.argtypes = [P(VP), C.c_size_t]
         l.wfk_host_free.argtypes = [VP]
         l.wfk_host_all_finite.argtypes = [VP, I64]
@@ -520,6 +527,11 @@ class IirRowsPlan(_Handle):
         check(lib().wfk_iir_rows_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, zi_ptr, zf_ptr,
                                        initial_ptr, stream))
 
+    def apply_shared_in(self, in_ptr, out_ptr, out_stride, zi_ptr=None, zf_ptr=None, initial_ptr=None, stream=0):
+        """every row reads the SAME n input samples at `in_ptr`; `out` must not overlap them (EngineError)"""
+        check(lib().wfk_iir_rows_apply_shared_in(self._h, in_ptr, out_ptr, out_stride, zi_ptr, zf_ptr,
+                                                 initial_ptr, stream))
+
     def kernel_name(self) -> str:
         return lib().wfk_iir_rows_kernel_name(self._h).decode()
 
@@ -562,6 +574,38 @@ class DemodPlan(_Handle):
 
     def kernel_name(self, n_shots: int) -> str:
         return lib().wfk_demod_kernel_name(self._h, n_shots).decode()
+
+
+def probe_brackets(tlist, t):
+    """np.interp's bracket of every probe time `t` in the ascending grid `tlist`, as the probe plan uploads it (host
+    only, no device): -> (j int64, dx, w) with dx = t - tlist[j], w = tlist[j + 1] - tlist[j]; t outside the grid:
+    the first / last index with dx = 0, w = 1; NaN: j = 0, dx = NaN."""
+    tlist = np.ascontiguousarray(tlist, dtype=np.float64).reshape(-1)
+    t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
+    j, dx, w = np.empty(len(t), dtype=np.int64), np.empty(len(t)), np.empty(len(t))
+    check(lib().wfk_boxprobe_brackets(tlist.ctypes.data, len(tlist), t.ctypes.data, len(t), j.ctypes.data,
+                                      dx.ctypes.data, w.ctypes.data))
+    return j, dx, w
+
+
+class BoxProbePlan(_Handle):
+    """out[r, q] = np.interp(t[q], tlist, conv[r]), conv[r, i] = gain * sum_{m < pp} y[r, i + c - m] (zero padded):
+    the boxcar integral of every row of a (rows, >= n) float64 device array read off at the probe times `t`;
+    tlist and t are bracketed on the host and uploaded once."""
+    _destroy = 'wfk_boxprobe_plan_destroy'
+
+    def __init__(self, tlist, t, pp: int, c: int, gain: float):
+        tlist = np.ascontiguousarray(tlist, dtype=np.float64).reshape(-1)
+        t = np.ascontiguousarray(t, dtype=np.float64).reshape(-1)
+        self.n, self.nq, self.pp, self.c, self.gain = len(tlist), len(t), int(pp), int(c), float(gain)
+        check(lib().wfk_boxprobe_plan_create(tlist.ctypes.data, self.n, t.ctypes.data, self.nq, self.pp, self.c,
+                                             self.gain, C.byref(self._h)))
+
+    def apply(self, y_ptr, n_rows, y_stride, out_ptr, out_stride, stream=0):
+        check(lib().wfk_boxprobe_apply(self._h, y_ptr, n_rows, y_stride, out_ptr, out_stride, stream))
+
+    def kernel_name(self) -> str:
+        return lib().wfk_boxprobe_kernel_name(self._h).decode()
 
 
 class DeviceBuffer:

@@ -681,6 +681,174 @@ def distort_rows(points, params_rows, sample_rate, initial=0.0):
 
 
 # --------------------------------------------------------------------------
+# the Z-distortion fit model (reference distortion.py:349-366)
+# --------------------------------------------------------------------------
+def _phase_geometry(t, pulse_width, start, sample_rate):
+    """host side of phase_curve, before any device work: -> (t as float64 array, lim, num, pp, sp).
+    ValueError wherever the reference raises: an empty t (np.max of nothing), a NaN t (round(nan)), a negative
+    sp (np.zeros of a negative length), an empty kernel (np.convolve: v cannot be empty) and a kernel longer
+    than the signal (np.convolve then returns pp + sp values, which np.interp refuses next to num grid values)."""
+    tq = np.asarray(t, dtype=np.float64)
+    if tq.size == 0:
+        raise ValueError('phase_curve: t is empty')
+    lim = max(np.max(np.abs(tq)), 20e-6)
+    num = round(2 * lim * sample_rate)                     # (ValueError for a NaN)
+    pp = round(pulse_width * sample_rate)
+    sp = round((start + pulse_width) * sample_rate) - 1
+    if pp < 0 or sp < 0:
+        raise ValueError(f'phase_curve: negative kernel dimensions (pulse points {pp}, start points {sp})')
+    if pp + sp == 0:
+        raise ValueError('phase_curve: the kernel is empty (pulse points + start points == 0)')
+    if pp + sp > num:
+        raise ValueError(f'phase_curve: the kernel ({pp + sp} points) is longer than the signal ({num} points)')
+    return tq, lim, num, pp, sp
+
+
+def _param_rows(params_rows):
+    rows = [np.asarray(p, dtype=np.float64).reshape(-1, 2) for p in params_rows]
+    if not rows:
+        raise ValueError('no parameter rows')
+    return rows
+
+
+class PhaseCurve:
+    """`phase_curve(t, params, df_dphi, pulse_width, start, wav, sample_rate)` (reference distortion.py:349-366)
+    for MANY parameter sets, built once per fit: the wave is sampled once (`wav(tlist)`, the drop-in call) and its
+    row stays on the device, the probe plan (csrc/wfk_probe.hip) is built once; an evaluation of P parameter sets is
+    ONE per-row IIR launch that reads that row P times (`IirRowsPlan.apply_shared_in`) plus ONE probe launch, both
+    asynchronous on torch's current stream.
+
+        pc = PhaseCurve(x, df_dphi, 10e-9, 25e-9, wav, 2e9)
+        popt, pcov = curve_fit(pc.model, x, y, p0=[-0.03, 0.1e-6, 0.02, 0.3e-6], jac=pc.jac_model)
+
+    pc(params) -> (nq,); pc.rows(params_rows) -> (P, nq) NumPy; pc.rows_torch(params_rows, out=None) -> device
+    tensor; pc.jac(params) -> (nq, len(params)), forward differences, p and every p + h e_k rows of one evaluation.
+    Row r's params are [amp0, tau0, amp1, tau1, ...] with any number of time constants (rows may differ); its filter is
+    the CASCADE of the first-order sections exp_decay_filter(amp, |tau|, sample_rate), from rest -- in exact arithmetic
+    the reference's combined (b, a), numerically better conditioned.  A launch takes four
+    sections per row: rows with more than 4 constants cost one more in-place IIR launch over the workspace per further
+    four constants -- correct, but slower than the one-launch shape of a usual fit.  The (P, num) workspace is kept and
+    grown as needed."""
+
+    def __init__(self, t, df_dphi, pulse_width, start, wav, sample_rate):
+        self.t, lim, self.num, self.pp, self.sp = _phase_geometry(t, pulse_width, start, sample_rate)
+        self.shape = self.t.shape
+        self.sample_rate = sample_rate
+        self.nq = self.t.size
+        self.tlist = np.arange(self.num) / sample_rate - lim
+        self._x_host = np.ascontiguousarray(wav(self.tlist), dtype=np.float64)
+        if self._x_host.shape != (self.num, ):
+            raise ValueError('phase_curve: wav(tlist) must give one real sample per time')
+        import torch
+        self._dev = torch.device('cuda', torch.cuda.current_device())
+        self._x = torch.from_numpy(self._x_host).to(self._dev)
+        self.gain = 2 * np.pi * df_dphi / sample_rate
+        self.probe = _engine.BoxProbePlan(self.tlist, self.t.reshape(-1), self.pp, (self.pp + self.sp - 1) // 2,
+                                          self.gain)
+        self._ws = None
+        self._iir = []            # the plans of the last evaluation: their tables live until the next one replaces them
+
+    def sections(self, params):
+        """[[(b, a)] * 4, ...]: the first-order sections exp_decay_filter(amp, |tau|, sample_rate) of one parameter set
+        in groups of four (one group per IIR launch), the last group filled up with pass-through sections; no time
+        constant at all: one group of pass-through sections.  EVERY row runs in the four-section shape, whatever
+        else is in its batch: a row's result is then bitwise the same in any batch and on its own."""
+        secs = [exp_decay_filter(amp, abs(tau), self.sample_rate)
+                for amp, tau in np.asarray(params, dtype=np.float64).reshape(-1, 2)]
+        secs += [([1.0, 0.0], [1.0, 0.0])] * (-len(secs) % ROWS_MAX_ORDER or (0 if secs else ROWS_MAX_ORDER))
+        return [secs[i:i + ROWS_MAX_ORDER] for i in range(0, len(secs), ROWS_MAX_ORDER)]
+
+    def rows_torch(self, params_rows, out=None):
+        """-> (P, nq) float64 device tensor (`out`, row-contiguous, when given); asynchronous on the current stream"""
+        import torch
+        rows = _param_rows(params_rows)
+        P = len(rows)
+        if out is None:
+            out = torch.empty((P, self.nq), dtype=torch.float64, device=self._dev)
+        elif (not out.is_cuda or out.dtype != torch.float64 or tuple(out.shape) != (P, self.nq)
+              or (self.nq > 1 and out.stride(1) != 1) or (P > 1 and out.stride(0) < self.nq)):
+            raise ValueError(f'out must be a ({P}, {self.nq}) row-contiguous float64 device tensor')
+        if self._ws is None or self._ws.shape[0] < P:
+            self._ws = None
+            self._ws = torch.empty((P, self.num), dtype=torch.float64, device=self._dev)
+        ws = self._ws
+        stream = torch.cuda.current_stream(self._dev).cuda_stream
+        groups = [self.sections(p) for p in rows]
+        for plan in self._iir:                # (the tables of the last evaluation lived until here)
+            plan.close()
+        self._iir = []
+        passthrough = [([1.0, 0.0], [1.0, 0.0])] * ROWS_MAX_ORDER
+        for k in range(max(len(g) for g in groups)):
+            # pass k: the k-th group of four sections of every row that has one.  Pass 0 reads the one sampled row;
+            # later passes (rows with more than 4 constants) filter the workspace in place, over the span of rows
+            # that need them -- rows in between without a k-th group take pass-through sections, which are exact.
+            need = [r for r in range(P) if len(groups[r]) > k]
+            lo, hi = (0, P) if k == 0 else (need[0], need[-1] + 1)
+            plan = _engine.IirRowsPlan([groups[r][k] if len(groups[r]) > k else passthrough for r in range(lo, hi)],
+                                       self.num, np.float64)
+            self._iir.append(plan)
+            if k == 0:
+                plan.apply_shared_in(self._x.data_ptr(), ws.data_ptr(), ws.stride(0), stream=stream)
+            else:
+                at = ws[lo].data_ptr()
+                plan.apply(at, ws.stride(0), at, ws.stride(0), stream=stream)
+        self.probe.apply(ws.data_ptr(), P, ws.stride(0), out.data_ptr(), max(out.stride(0), self.nq), stream)
+        return out
+
+    def rows(self, params_rows):
+        """-> (P, nq) NumPy array"""
+        return self.rows_torch(params_rows).cpu().numpy()
+
+    def __call__(self, params):
+        """-> what the reference's phase_curve returns for `params`: np.interp's shape and dtype for `t`"""
+        return self.rows([params])[0].reshape(self.shape)[()]
+
+    @staticmethod
+    def step(params, rel_step=None):
+        """the forward-difference steps of scipy.optimize.curve_fit's default method ('lm': MINPACK's fdjac2):
+        h_k = rel_step * |p_k|, rel_step = sqrt(machine epsilon) when None, and h_k = rel_step where p_k == 0"""
+        p = np.asarray(params, dtype=np.float64).reshape(-1)
+        rel = np.sqrt(np.finfo(np.float64).eps) if rel_step is None else float(rel_step)
+        h = rel * np.abs(p)
+        return np.where(h == 0, rel, h)
+
+    def jac(self, params, rel_step=None):
+        """-> (nq, len(params)): column k is (f(p + h_k e_k) - f(p)) / h_k with `step`'s h; ONE evaluation of
+        1 + len(params) rows"""
+        p = np.asarray(params, dtype=np.float64).reshape(-1)
+        h = self.step(p, rel_step)
+        f = self.rows([p] + [np.where(np.arange(len(p)) == k, p + h, p) for k in range(len(p))])
+        return ((f[1:] - f[0]) / h[:, None]).T
+
+    def model(self, t_ignored, *params):
+        """f of `curve_fit(f, x, y, p0)`: the probe times are those of the constructor"""
+        return np.asarray(self(params)).reshape(-1)
+
+    def jac_model(self, t_ignored, *params):
+        """jac of `curve_fit(f, x, y, p0, jac=)`"""
+        return self.jac(params)
+
+    def close(self):
+        self.probe.close()
+        for plan in self._iir:
+            plan.close()
+        self._iir = []
+        self._ws = self._x = None
+
+
+def phase_curve(t, params, df_dphi, pulse_width, start, wav, sample_rate):
+    """reference: waveforms/distortion.py:349-366 -- the phase a qubit picks up from a Z pulse `wav` distorted by the
+    exp-decay `params`, integrated over `pulse_width` and read off at the delays `t`.  Same signature, same return
+    (np.interp's shape and dtype, a scalar t included), ValueError wherever the reference raises.  One `PhaseCurve`
+    evaluation; a fit should build a `PhaseCurve` once instead."""
+    pc = PhaseCurve(t, df_dphi, pulse_width, start, wav, sample_rate)
+    try:
+        return pc(params)
+    finally:
+        pc.close()
+
+
+# --------------------------------------------------------------------------
 # FFT-domain operations (SURVEY.md §8(f) N3)
 # --------------------------------------------------------------------------
 def reflection_filter(f, A, tau):
