@@ -338,6 +338,40 @@ int wfk_spectral_apply(wfk_spectral_plan* plan, const void* in_dev, void* out_de
                        const void* H_dev, void* hip_stream);
 int wfk_spectral_plan_destroy(wfk_spectral_plan* plan);
 
+/* -- per-row reflection / inverse reflection / delay, transfer function built on the device --- */
+/* out[r] = irfft(rfft(in[r]) * H_r) for `batch` rows of n samples, H_r(k) the product of row r's terms at
+ * f_k = k * sample_rate / n; with e = exp(-2 pi i f_k tau):
+ *   WFK_SPEC_REFLECT  (1 - A) / (1 - A e)   reflection(sig, A, tau, fs)          (waveforms/distortion.py:188-210)
+ *   WFK_SPEC_CORRECT  (1 - A e) / (1 - A)   correct_reflection(sig, A, tau, fs)  (waveforms/distortion.py:213-223)
+ *   WFK_SPEC_DELAY    e                     band-limited circular delay by tau (A ignored, tau of either sign)
+ * terms_host: the rows' terms back to back in row order, n_terms_per_row_host[r] of them for row r (0 ..
+ * WFK_SPEC_ROWS_MAX_TERMS; 0: the row passes unchanged).  More terms, an unknown kind, a tau that is not finite,
+ * or |A| >= 1 on a REFLECT / CORRECT term (the reference divides by zero at A = 1): WFK_EINVAL.
+ * H is not stored: one kernel (spec_rows_mul) makes one pass over the R2C output and forms H per (row, bin) from
+ * the row's terms; the phase k * (tau fs / n) is reduced to [-1/2, 1/2] cycles BEFORE it is rounded (the plan
+ * keeps tau fs / n as a quad-precision (hi, lo) pair), so delays of thousands of cycles cost no accuracy.
+ * The plan owns the batched rocFFT pair, its work / spectrum / staging buffers and the term table.
+ * wfk_spectral_rows_apply() allocates nothing and does not synchronise; strides are in elements, >= n, otherwise
+ * arbitrary; in place (out_dev == in_dev) and any other overlap are allowed (the input is staged before anything
+ * is written).  A row's result does not depend on its position in the batch.  One plan per concurrent stream. */
+#define WFK_SPEC_ROWS_MAX_TERMS 8
+enum { WFK_SPEC_REFLECT = 0, WFK_SPEC_CORRECT = 1, WFK_SPEC_DELAY = 2 };
+typedef struct wfk_spec_term {
+  int32_t kind;      /* WFK_SPEC_* */
+  int32_t reserved;  /* 0 */
+  double A;
+  double tau;        /* seconds */
+} wfk_spec_term;
+typedef struct wfk_spectral_rows_plan wfk_spectral_rows_plan;
+int wfk_spectral_rows_plan_create(int64_t n, int32_t batch, int kind /* WFK_OUT_F64|F32 */, double sample_rate,
+                                  const wfk_spec_term* terms_host, const int32_t* n_terms_per_row_host,
+                                  wfk_spectral_rows_plan** out);
+int wfk_spectral_rows_apply(wfk_spectral_rows_plan* plan, const void* in_dev, int64_t in_stride, void* out_dev,
+                            int64_t out_stride, void* hip_stream);
+int wfk_spectral_rows_plan_destroy(wfk_spectral_rows_plan* plan);
+/* host only, no device: tau * sample_rate / n in quad precision as the (hi, lo) pair of doubles the plan stores */
+int wfk_spectral_rows_phase_step(double tau, double sample_rate, int64_t n, double* hi_out, double* lo_out);
+
 /* -- readout demodulation (reference utils.py:35-84: traces @ getFTMatrix(...)) ---------------- */
 /* out[s, j] = sum_k x[s, k] * e[k, j] for real traces x (n_shots rows of >= n_points samples, row stride
  * trace_stride elements) and a complex matrix e (n_points x n_freq, complex128 interleaved, point-major: the

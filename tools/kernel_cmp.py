@@ -67,7 +67,7 @@ def main():
     a, b = sys.argv[1:3]
     if os.path.isdir(a):
         names = sys.argv[3:] or [f"wfk_{x}.o" for x in ("api", "kernels", "short", "fir", "fir_fused", "fir_sampled", "iir",
-                                                        "iir_rows", "spectral", "demod")]
+                                                        "iir_rows", "spectral", "spectral_rows", "demod")]
         pairs = [(n, *(os.path.join(t, "waveforms_amd/csrc/_obj", n) for t in (a, b))) for n in names]
     else:
         pairs = [(os.path.basename(a), a, b)]

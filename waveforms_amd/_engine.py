@@ -117,6 +117,10 @@ def lib():
         l.wfk_spectral_plan_create.argtypes = [I64, I32, C.c_int, P(VP)]
         l.wfk_spectral_apply.argtypes = [VP, VP, VP, VP, VP]
         l.wfk_spectral_plan_destroy.argtypes = [VP]
+        l.wfk_spectral_rows_plan_create.argtypes = [I64, I32, C.c_int, C.c_double, VP, VP, P(VP)]
+        l.wfk_spectral_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP]
+        l.wfk_spectral_rows_plan_destroy.argtypes = [VP]
+        l.wfk_spectral_rows_phase_step.argtypes = [C.c_double, C.c_double, I64, P(C.c_double), P(C.c_double)]
         l.wfk_demod_plan_create.argtypes = [VP, I64, I32, C.c_int, P(VP)]
         l.wfk_demod_apply.argtypes = [VP, VP, I64, I64, VP, I64, VP]
         l.wfk_demod_kernel_name.argtypes = [VP, I64]
@@ -547,6 +551,68 @@ class SpectralPlan(_Handle):
 
     def apply(self, in_ptr, out_ptr, H_ptr, stream=0):
         check(lib().wfk_spectral_apply(self._h, in_ptr, out_ptr, H_ptr, stream))
+
+
+SPEC_ROWS_MAX_TERMS = 8                                    # WFK_SPEC_ROWS_MAX_TERMS of include/wfk.h
+SPEC_KINDS = {'reflect': 0, 'correct': 1, 'delay': 2}      # WFK_SPEC_REFLECT / CORRECT / DELAY
+SPEC_TERM = np.dtype([('kind', np.int32), ('reserved', np.int32), ('A', np.float64), ('tau', np.float64)])
+
+
+def pack_spec_terms(terms_rows):
+    """list (one entry per row) of term lists -> (terms, counts): the wfk_spec_term records of all rows back to back
+    and the int32 number of terms per row.  A term is ('reflect', A, tau), ('correct', A, tau) or ('delay', tau).
+    ValueError: no rows, an unknown kind, a term of the wrong length, more than SPEC_ROWS_MAX_TERMS terms in a row,
+    a tau that is not finite, |A| >= 1 (A = 1 divides by zero in the reference's filter)."""
+    rows = [list(r) for r in terms_rows]
+    if not rows:
+        raise ValueError('no rows')
+    recs = []
+    for r, row in enumerate(rows):
+        if len(row) > SPEC_ROWS_MAX_TERMS:
+            raise ValueError(f'row {r}: {len(row)} terms, a row takes at most {SPEC_ROWS_MAX_TERMS}')
+        for term in row:
+            term = tuple(term)
+            kind = term[0] if term else None
+            if not isinstance(kind, str) or kind not in SPEC_KINDS:
+                raise ValueError(f"row {r}: a term is ('reflect' | 'correct', A, tau) or ('delay', tau), got {term!r}")
+            if len(term) != (2 if kind == 'delay' else 3):
+                raise ValueError(f"row {r}: a term is ('reflect' | 'correct', A, tau) or ('delay', tau), got {term!r}")
+            A, tau = (0.0, float(term[1])) if kind == 'delay' else (float(term[1]), float(term[2]))
+            if not np.isfinite(tau):
+                raise ValueError(f'row {r}: tau is not finite')
+            if not abs(A) < 1.0:
+                raise ValueError(f'row {r}: a reflection needs |A| < 1, got {A!r}')
+            recs.append((SPEC_KINDS[kind], 0, A, tau))
+    return (np.array(recs, dtype=SPEC_TERM).reshape(-1),
+            np.array([len(row) for row in rows], dtype=np.int32))
+
+
+def spec_phase_step(tau: float, sample_rate: float, n: int):
+    """(hi, lo): tau * sample_rate / n as the pair of doubles a SpectralRowsPlan stores (host only, no device)"""
+    hi, lo = C.c_double(), C.c_double()
+    check(lib().wfk_spectral_rows_phase_step(float(tau), float(sample_rate), int(n), C.byref(hi), C.byref(lo)))
+    return hi.value, lo.value
+
+
+class SpectralRowsPlan(_Handle):
+    """out[r] = irfft(rfft(x[r]) * H_r): every row its own product of reflection / inverse-reflection / delay terms
+    (`pack_spec_terms`), H formed on the device (wfk_spectral_rows_plan_create).  `batch` = len(terms_rows)."""
+    _destroy = 'wfk_spectral_rows_plan_destroy'
+
+    def __init__(self, terms_rows, n: int, sample_rate: float, dtype=np.float64):
+        terms, counts = pack_spec_terms(terms_rows)
+        self.n, self.batch, self.dtype = int(n), len(counts), np.dtype(dtype)
+        self.sample_rate = float(sample_rate)
+        if self.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError('dtype must be float64 or float32')
+        if self.n < 1 or not (np.isfinite(self.sample_rate) and self.sample_rate > 0):
+            raise ValueError('n >= 1 and a positive sample_rate')
+        check(lib().wfk_spectral_rows_plan_create(self.n, self.batch, _KIND_OF[self.dtype], self.sample_rate,
+                                                  terms.ctypes.data if len(terms) else None, counts.ctypes.data,
+                                                  C.byref(self._h)))
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, stream=0):
+        check(lib().wfk_spectral_rows_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, stream))
 
 
 IN_F64, IN_F32, IN_I16 = 0, 1, 4

@@ -913,6 +913,136 @@ def shift(signal, delay, dt):
     return ret
 
 
+class ReflectionStage:
+    """Device-resident reflection / delay stage for `len(terms_rows)` rows of `n` samples (build once, apply many
+    times), the counterpart of `IirStage` rows for the FFT-domain part of a line's calibration:
+        y[r] = ifft(fft(x[r]) * H_r(f)).real,   H_r = the product of row r's terms
+    with `reflection_filter(f, A, tau)` for ('reflect', A, tau), its inverse for ('correct', A, tau) -- what
+    `reflection` / `correct_reflection` apply to one signal -- and exp(-2j pi f tau) for ('delay', tau), tau of either
+    sign.  A row may carry up to `_engine.SPEC_ROWS_MAX_TERMS` terms (ValueError beyond), or none (it passes unchanged);
+    |A| >= 1 is refused (the reference's filter divides by zero at A = 1).  One transform pair per apply whatever the
+    number of terms; the transfer functions are formed on the device, nothing but the small term table is uploaded.
+
+        st = ReflectionStage([[('correct', A, tau), ('delay', -skew)] for A, tau, skew in lines], n, 2e9)
+        st.apply_torch(x)                      # in place, on torch's current stream
+        st.apply_torch(x, out=y)
+    """
+
+    def __init__(self, terms_rows, n: int, sample_rate: float, dtype=np.float64):
+        self.plan = _engine.SpectralRowsPlan(terms_rows, n, sample_rate, dtype)
+        self.n, self.batch, self.dtype = self.plan.n, self.plan.batch, self.plan.dtype
+        self.sample_rate = self.plan.sample_rate
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, stream=0):
+        self.plan.apply(in_ptr, in_stride, out_ptr, out_stride, stream)
+
+    def apply_torch(self, x, out=None):
+        """x, out: (batch, >= n) row-contiguous device tensors of the stage's dtype (rows may be windows of a wider
+        tensor, any row stride >= n); out=None or out is x: in place.  Asynchronous on torch's current stream; one
+        stage serves one stream at a time (it owns the transform buffers).  -> out"""
+        import torch
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        out = x if out is None else out
+        for t in (x, out):
+            if (not t.is_cuda or t.dtype != want or t.dim() != 2 or t.shape[0] != self.batch or
+                    t.shape[1] < self.n or t.stride(1) != 1 or (self.batch > 1 and t.stride(0) < self.n)):
+                raise ValueError('expected (batch, >=n) row-contiguous device tensors of the stage dtype')
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        self.apply(x.data_ptr(), max(x.stride(0), self.n), out.data_ptr(), max(out.stride(0), self.n), stream)
+        return out
+
+    def close(self):
+        self.plan.close()
+
+
+def _per_row(name, what, value, batch):
+    """a scalar (every row) or one entry per row -> list of `batch` entries"""
+    if not isinstance(value, (list, tuple, np.ndarray)) or (isinstance(value, np.ndarray) and value.ndim == 0):
+        return [value] * batch
+    value = list(value)
+    if len(value) != batch:
+        raise ValueError(f'{name}: {len(value)} {what} entries for {batch} rows')
+    return value
+
+
+def _reflection_rows_terms(name, kind, batch, A_rows, tau_rows):
+    """term lists of reflection_rows / correct_reflection_rows: A and tau each a scalar, or one entry per row, an entry
+    a scalar or a sequence (several reflections on that row); within a row a scalar goes with every entry of the
+    other's sequence"""
+    rows = []
+    for r, (A, tau) in enumerate(zip(_per_row(name, 'A', A_rows, batch), _per_row(name, 'tau', tau_rows, batch))):
+        A, tau = np.atleast_1d(np.asarray(A, dtype=np.float64)), np.atleast_1d(np.asarray(tau, dtype=np.float64))
+        if A.ndim != 1 or tau.ndim != 1 or (len(A) != len(tau) and 1 not in (len(A), len(tau))):
+            raise ValueError(f'{name}: row {r} has {len(A)} amplitudes and {len(tau)} delays')
+        A, tau = np.broadcast_arrays(A, tau)
+        rows.append([(kind, float(a), float(t)) for a, t in zip(A, tau)])
+    return rows
+
+
+def _delay_rows_terms(batch, delays):
+    return [[('delay', float(d))] for d in _per_row('delay_rows', 'delay', delays, batch)]
+
+
+def _rows_signal(name, sig):
+    sig = np.asarray(sig)
+    if sig.ndim != 2:
+        raise ValueError(f'{name}: sig must be 2-D (rows, samples)')
+    if np.iscomplexobj(sig):
+        raise NotImplementedError(f'{name}: complex rows')
+    return np.ascontiguousarray(sig, dtype=np.float64)
+
+
+def _spectral_rows_host(sig2, terms_rows, sample_rate):
+    """NumPy in, NumPy out: upload, one SpectralRowsPlan apply in place, download"""
+    batch, n = sig2.shape
+    if n == 0:
+        _engine.pack_spec_terms(terms_rows)
+        return sig2.copy()
+    plan = _engine.SpectralRowsPlan(terms_rows, n, sample_rate, np.float64)
+    x = None
+    try:
+        x = _engine.DeviceBuffer(sig2.nbytes)
+        x.upload(sig2)
+        plan.apply(x.ptr, n, x.ptr, n)
+        _engine.sync()
+        return x.download(sig2.shape, np.float64)
+    finally:
+        if x is not None:
+            x.close()
+        plan.close()
+
+
+def reflection_rows(sig, A_rows, tau_rows, sample_rate):
+    """`reflection(sig[r], A_rows[r], tau_rows[r], sample_rate)` for every row r of a 2-D `sig` (reference
+    distortion.py:208-210 per row), all rows in one launch, the transfer functions formed on the device.
+    A_rows / tau_rows: a scalar (every row), or one entry per row; an entry may be a sequence: several reflections on
+    that line, their filters multiplied (at most `_engine.SPEC_ROWS_MAX_TERMS`).  ValueError before any device work:
+    sig not 2-D, a row count that does not match, amplitudes and delays of different lengths, |A| >= 1."""
+    sig2 = _rows_signal('reflection_rows', sig)
+    return _spectral_rows_host(
+        sig2, _reflection_rows_terms('reflection_rows', 'reflect', sig2.shape[0], A_rows, tau_rows), sample_rate)
+
+
+def correct_reflection_rows(sig, A_rows, tau_rows, sample_rate):
+    """`correct_reflection(sig[r], A_rows[r], tau_rows[r], sample_rate)` for every row of a 2-D `sig` (reference
+    distortion.py:213-223 per row); arguments and errors as `reflection_rows`, whose inverse it is."""
+    sig2 = _rows_signal('correct_reflection_rows', sig)
+    return _spectral_rows_host(
+        sig2, _reflection_rows_terms('correct_reflection_rows', 'correct', sig2.shape[0], A_rows, tau_rows),
+        sample_rate)
+
+
+def delay_rows(sig, delays, sample_rate):
+    """Row r of a 2-D `sig` delayed by `delays[r]` seconds (a scalar: every row; negative: advanced):
+    ifft(fft(sig[r]) * exp(-2j pi f delays[r])).real -- the BAND-LIMITED, CIRCULAR delay: what leaves at one end of the
+    row comes back in at the other, a whole number of samples is an exact np.roll, a fraction of a sample is the
+    sinc interpolation of the periodic signal.  This is NOT `shift`, which follows the reference's 3-tap linear
+    interpolation and fills with zeros; use `shift` for the reference's results, this for skew correction of
+    rows that are zero (or periodic) at their ends."""
+    sig2 = _rows_signal('delay_rows', sig)
+    return _spectral_rows_host(sig2, _delay_rows_terms(sig2.shape[0], delays), sample_rate)
+
+
 def zDistortKernel(dt, params):
     """FIR kernel of a Z-line distortion model (filter DESIGN: one small FFT on the host,
     reference: distortion.py:52-60)."""
