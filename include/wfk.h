@@ -196,6 +196,10 @@ int wfk_plan_run_host(wfk_plan* plan, void* out_host, int64_t ch_stride,
 
 /* -- FIR stage: out[i] = sum_k ker[k] * sig[i + K/2 - k], zero padded ------- */
 /* replaces predistort(sig, ker=ker), waveforms/distortion.py:329-337          */
+/* Kernels of up to 6148 taps on up to 65535 rows run on the on-chip transform, whatever n.  Anything else runs on
+ * the rocFFT pipeline, which holds one row in at most 65535 blocks of L - K + 1 samples (L the transform length,
+ * the power of two >= 8 K, at least 1024): creation fails with WFK_EINVAL for a longer n, before anything is
+ * allocated.                                                                                                    */
 int wfk_fir_plan_create(const double* ker_host, int32_t K, int64_t n,
                         int32_t batch, int kind /* WFK_OUT_F64|F32 */,
                         wfk_fir_plan** out);
@@ -204,6 +208,10 @@ int wfk_fir_plan_create(const double* ker_host, int32_t K, int64_t n,
 int wfk_fir_plan_create_rows(const double* kers_host, int32_t K, int64_t n,
                              int32_t batch, int kind /* WFK_OUT_F64|F32 */,
                              wfk_fir_plan** out);
+/* Row r: n elements at in_dev + r * in_stride -> out_dev + r * out_stride (strides in elements, >= n).
+ * OUT OF PLACE: workgroups read input that belongs to the blocks of others, and a long kernel reads `in` in
+ * several passes.  WFK_EINVAL if [in, in + (batch-1)*in_stride + n) and [out, out + (batch-1)*out_stride + n)
+ * share a byte.                                                                                            */
 int wfk_fir_apply(wfk_fir_plan* plan, const void* in_dev, int64_t in_stride,
                   void* out_dev, int64_t out_stride, void* hip_stream);
 int wfk_fir_plan_destroy(wfk_fir_plan* plan);
@@ -334,6 +342,8 @@ int wfk_chain_iir_plan_destroy(wfk_chain_iir_plan* plan);
  * reflection / correct_reflection (waveforms/distortion.py:208-223).                  */
 typedef struct wfk_spectral_plan wfk_spectral_plan;
 int wfk_spectral_plan_create(int64_t n, int32_t batch, int kind, wfk_spectral_plan** out);
+/* The one H serves all `batch` rows.  In place (out_dev == in_dev) is allowed: the input is copied to a
+ * staging buffer of the plan before anything is written.  Asynchronous on `hip_stream`.              */
 int wfk_spectral_apply(wfk_spectral_plan* plan, const void* in_dev, void* out_dev,
                        const void* H_dev, void* hip_stream);
 int wfk_spectral_plan_destroy(wfk_spectral_plan* plan);

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cmath>
 #include <complex>
+#include <cstdlib>
 #include <memory>
 #include <new>
 #include <string>
@@ -79,6 +80,8 @@ void put_cx(std::vector<char>& dst, bool f32, size_t at, const std::complex<long
     d[0] = (double)v.real(); d[1] = (double)v.imag();
   }
 }
+
+const char kTooLong[] = "signal too long for one rocFFT FIR plan (blocks > 65535)";
 
 }  // namespace
 
@@ -229,6 +232,8 @@ static int fir_plan_create(const double* ker_host, int32_t K, int64_t n, int32_t
   p->L = L; p->M = L - Kt + 1; p->lead = (Kt - 1) - K / 2;   // fused: + j*Kseg for segment j
   p->nblk = n > 0 ? (n + p->M - 1) / p->M : 0;
   if (n == 0) { *out = p.release(); return WFK_OK; }
+  // gather / scatter put the block in gridDim.y: refuse before any rocFFT plan or buffer is made
+  if (!p->fused && p->nblk > 65535) return wfk_fail(WFK_EINVAL, kTooLong);
   const bool f32 = kind == WFK_OUT_F32;
   const size_t es = f32 ? 4 : 8;
   const size_t nf = p->fused ? (size_t)L : (size_t)L / 2 + 1;   // fused: full complex spectrum
@@ -236,6 +241,13 @@ static int fir_plan_create(const double* ker_host, int32_t K, int64_t n, int32_t
     const double per_ch = (double)p->nblk * ((double)L * es + (double)nf * 2 * es);
     int64_t chunk = (int64_t)(3.0e9 / per_ch);
     chunk = std::max<int64_t>(1, std::min<int64_t>(chunk, batch));
+    chunk = std::min<int64_t>(chunk, 65535);   // gather / scatter put the chunk's row in gridDim.z
+    // WFK_FIR_CHUNK=<rows>: a lower cap, so that the chunk loop and the tail plans run at test sizes
+    if (const char* e = getenv("WFK_FIR_CHUNK")) {
+      char* end = nullptr;
+      const long long v = strtoll(e, &end, 10);
+      if (end != e && *end == '\0' && v >= 1) chunk = std::min<int64_t>(chunk, v);
+    }
     p->chunk = (int32_t)chunk;
     p->tail = batch % p->chunk;
     size_t work_bytes = 0;
@@ -318,6 +330,12 @@ int wfk_fir_apply(wfk_fir_plan* p, const void* in_dev, int64_t in_stride, void* 
   if (p->n == 0) return WFK_OK;
   if (!in_dev || !out_dev) return wfk_fail(WFK_EINVAL, "null buffer");
   if (in_stride < p->n || out_stride < p->n) return wfk_fail(WFK_EINVAL, "stride smaller than n");
+  // no path works in place: the fused kernel reads halos that other workgroups overwrite, passes 2 to 4 of a long
+  // kernel read `in` again, and the pipeline's later chunks gather after the earlier ones have scattered
+  const size_t esz = p->kind == WFK_OUT_F32 ? 4 : 8;
+  const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + ((size_t)(p->batch - 1) * (size_t)in_stride + (size_t)p->n) * esz;
+  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + ((size_t)(p->batch - 1) * (size_t)out_stride + (size_t)p->n) * esz;
+  if (i0 < o1 && o0 < i1) return wfk_fail(WFK_EINVAL, "FIR is out of place: out overlaps in");
   hipStream_t s = (hipStream_t)hip_stream;
   if (p->fused) {
     const size_t seg_bytes = (size_t)p->L * 2 * (p->kind == WFK_OUT_F32 ? 4 : 8);
@@ -328,7 +346,7 @@ int wfk_fir_apply(wfk_fir_plan* p, const void* in_dev, int64_t in_stride, void* 
         return wfk_fail(WFK_EHIP, "fused FIR kernel launch failed");
     return WFK_OK;
   }
-  if (p->nblk > 65535) return wfk_fail(WFK_EINVAL, "signal too long for one rocFFT FIR plan (blocks > 65535)");
+  if (p->nblk > 65535) return wfk_fail(WFK_EINVAL, kTooLong);   // (refused at creation already)
   if (p->kind == WFK_OUT_F32) return fir_run<float, float2>(p, in_dev, in_stride, out_dev, out_stride, s);
   return fir_run<double, double2>(p, in_dev, in_stride, out_dev, out_stride, s);
 }

@@ -34,7 +34,8 @@ struct wfk_spectral_plan {
   int64_t n = 0, nf = 0;
   int32_t batch = 0, kind = 0;
   // (members go in reverse order: the rocFFT plans and the execution info before the work buffer they were given)
-  DevBuf<char> tmp;       // C2R may overwrite its input; R2C input is copied here when in == out
+  DevBuf<char> tmp;       // every apply copies its input here first: rocFFT's real transforms may overwrite their
+                          // input, and it is what makes out == in legal (wfk.h)
   DevBuf<char> spec, work;
   RocfftInfo info;
   RocfftPlan fwd, inv;

@@ -39,8 +39,13 @@ class FirStage:
                     t.shape[0] != self.batch or t.shape[1] < self.n or t.stride(1) != 1):
                 raise ValueError('expected (batch, >=n) row-contiguous device tensors '
                                  'of the plan dtype')
-        if x.data_ptr() == y.data_ptr():
-            raise ValueError('FIR is out of place')
+        # the rows of y may share no memory with the rows of x: [first sample of row 0, end of row batch - 1)
+        es = x.element_size()
+        x0, y0 = x.data_ptr(), y.data_ptr()
+        x1 = x0 + ((self.batch - 1) * x.stride(0) + self.n) * es
+        y1 = y0 + ((self.batch - 1) * y.stride(0) + self.n) * es
+        if x0 == y0 or (x0 < y1 and y0 < x1):
+            raise ValueError('FIR is out of place: y overlaps x')
         stream = torch.cuda.current_stream(x.device).cuda_stream
         self.apply(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), stream)
         return y
