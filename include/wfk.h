@@ -382,6 +382,30 @@ int wfk_spectral_rows_plan_destroy(wfk_spectral_rows_plan* plan);
 /* host only, no device: tau * sample_rate / n in quad precision as the (hi, lo) pair of doubles the plan stores */
 int wfk_spectral_rows_phase_step(double tau, double sample_rate, int64_t n, double* hi_out, double* lo_out);
 
+/* -- per-row shift: the reference's delay in time, one skew per row ----------------------------- */
+/* out[r] = shift(in[r], delay_r, dt) (waveforms/distortion.py:12-39) for `batch` rows of n samples.  The caller
+ * splits every delay with the reference's own expressions, points = int(delay // dt), delta = delay / dt - points
+ * (delta in [0, 1]: Python's floor division makes 1.0 // 0.1 = 9 and delta = 1, which is legal), and the device
+ * computes, with x[k] = 0 for k < 0,
+ *   s[j] = (1 - delta) x[j] + delta x[j - 1]  if delta > 0,   s[j] = x[j] otherwise (a copy, bit for bit),
+ *   y[i] = s[i - points] if 0 <= i - points < n, 0 otherwise
+ * -- linear interpolation and ZERO fill at both ends (not the circular, band-limited WFK_SPEC_DELAY above); rows
+ * with |points| >= n come out all zero.  Unlike the reference, rows keep n samples for n < 3, and the zero tap on
+ * x[j + 1] is not multiplied (an inf there does not make sample j NaN).  points_host / delta_host: `batch` entries.
+ * n < 0, batch < 1, a delta outside [0, 1] or not finite, a kind other than F64 / F32, null pointers: WFK_EINVAL;
+ * no device: WFK_EHIP.  One kernel (shift_rows<T>), one read and one write per sample, float rows computed in
+ * double and rounded once; the plan owns the small row table and nothing else, so it may serve several streams.
+ * wfk_shift_rows_apply() allocates nothing and does not synchronise; strides are in elements, >= n.  OUT OF PLACE
+ * only: if [in, in + (batch - 1) * in_stride + n) overlaps the same range of out, WFK_EINVAL.  n = 0: no-op.   */
+typedef struct wfk_shift_rows_plan wfk_shift_rows_plan;
+int wfk_shift_rows_plan_create(int64_t n, int32_t batch, int kind /* WFK_OUT_F64|F32 */, const int64_t* points_host,
+                               const double* delta_host, wfk_shift_rows_plan** out);
+int wfk_shift_rows_apply(wfk_shift_rows_plan* plan, const void* in_dev, int64_t in_stride, void* out_dev,
+                         int64_t out_stride, void* hip_stream);
+/* "shift_rows<double>" or "shift_rows<float>"; a static string */
+const char* wfk_shift_rows_kernel_name(const wfk_shift_rows_plan* plan);
+int wfk_shift_rows_plan_destroy(wfk_shift_rows_plan* plan);
+
 /* -- readout demodulation (reference utils.py:35-84: traces @ getFTMatrix(...)) ---------------- */
 /* out[s, j] = sum_k x[s, k] * e[k, j] for real traces x (n_shots rows of >= n_points samples, row stride
  * trace_stride elements) and a complex matrix e (n_points x n_freq, complex128 interleaved, point-major: the

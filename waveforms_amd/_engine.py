@@ -121,6 +121,11 @@ def lib():
         l.wfk_spectral_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP]
         l.wfk_spectral_rows_plan_destroy.argtypes = [VP]
         l.wfk_spectral_rows_phase_step.argtypes = [C.c_double, C.c_double, I64, P(C.c_double), P(C.c_double)]
+        l.wfk_shift_rows_plan_create.argtypes = [I64, I32, C.c_int, VP, VP, P(VP)]
+        l.wfk_shift_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP]
+        l.wfk_shift_rows_kernel_name.argtypes = [VP]
+        l.wfk_shift_rows_kernel_name.restype = C.c_char_p
+        l.wfk_shift_rows_plan_destroy.argtypes = [VP]
         l.wfk_demod_plan_create.argtypes = [VP, I64, I32, C.c_int, P(VP)]
         l.wfk_demod_apply.argtypes = [VP, VP, I64, I64, VP, I64, VP]
         l.wfk_demod_kernel_name.argtypes = [VP, I64]
@@ -613,6 +618,39 @@ class SpectralRowsPlan(_Handle):
 
     def apply(self, in_ptr, in_stride, out_ptr, out_stride, stream=0):
         check(lib().wfk_spectral_rows_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, stream))
+
+
+class ShiftRowsPlan(_Handle):
+    """out[r] = the reference's shift of x[r] by points[r] whole samples and the fraction deltas[r] of one (linear
+    interpolation, zero fill; wfk_shift_rows_plan_create).  `batch` = len(points).  ValueError before any device
+    work: no rows, lengths that differ, n < 0, a delta outside [0, 1] or not finite, a dtype other than float64 /
+    float32 (NotImplementedError for a complex one).  |points| is clamped to 2**62: such a row is all zero either way."""
+    _destroy = 'wfk_shift_rows_plan_destroy'
+
+    def __init__(self, points, deltas, n: int, dtype=np.float64):
+        self.n, self.dtype = int(n), np.dtype(dtype)
+        if self.dtype.kind == 'c':
+            raise NotImplementedError('complex rows')
+        if self.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError('dtype must be float64 or float32')
+        pts = [max(-2**62, min(2**62, int(p))) for p in np.asarray(points, dtype=object).reshape(-1)]
+        self.points = np.array(pts, dtype=np.int64)
+        self.deltas = np.ascontiguousarray(deltas, dtype=np.float64).reshape(-1)
+        self.batch = len(self.points)
+        if self.batch < 1 or len(self.deltas) != self.batch:
+            raise ValueError(f'{self.batch} points and {len(self.deltas)} deltas: one of each per row, at least one row')
+        if self.n < 0:
+            raise ValueError('n >= 0')
+        if not np.all((self.deltas >= 0.0) & (self.deltas <= 1.0)):
+            raise ValueError('every delta must lie in [0, 1]')
+        check(lib().wfk_shift_rows_plan_create(self.n, self.batch, _KIND_OF[self.dtype], self.points.ctypes.data,
+                                               self.deltas.ctypes.data, C.byref(self._h)))
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, stream=0):
+        check(lib().wfk_shift_rows_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, stream))
+
+    def kernel_name(self) -> str:
+        return lib().wfk_shift_rows_kernel_name(self._h).decode()
 
 
 IN_F64, IN_F32, IN_I16 = 0, 1, 4

@@ -1042,10 +1042,134 @@ def delay_rows(sig, delays, sample_rate):
     ifft(fft(sig[r]) * exp(-2j pi f delays[r])).real -- the BAND-LIMITED, CIRCULAR delay: what leaves at one end of the
     row comes back in at the other, a whole number of samples is an exact np.roll, a fraction of a sample is the
     sinc interpolation of the periodic signal.  This is NOT `shift`, which follows the reference's 3-tap linear
-    interpolation and fills with zeros; use `shift` for the reference's results, this for skew correction of
-    rows that are zero (or periodic) at their ends."""
+    interpolation and fills with zeros; use `shift_rows` / `ShiftStage` for the reference's results on rows, this for
+    skew correction of rows that are zero (or periodic) at their ends."""
     sig2 = _rows_signal('delay_rows', sig)
     return _spectral_rows_host(sig2, _delay_rows_terms(sig2.shape[0], delays), sample_rate)
+
+
+def _shift_split(name, delays, dt):
+    """delays (a list of numbers) -> (points, deltas) by the reference's own expressions (distortion.py:24-25):
+    points = int(delay // dt), delta = delay / dt - points.  Python's floor division is not floor(delay / dt):
+    1.0 // 0.1 is 9 and delta comes out as exactly 1.0, which the stage takes.  ValueError for a delay or dt that is
+    not finite, dt = 0, or a split that leaves delta outside [0, 1]."""
+    dt = float(dt)
+    if not np.isfinite(dt) or dt == 0.0:
+        raise ValueError(f'{name}: dt must be finite and not zero')
+    points, deltas = [], []
+    for r, d in enumerate(delays):
+        d = float(d)
+        if not np.isfinite(d):
+            raise ValueError(f'{name}: row {r}: delay is not finite')
+        p = int(d // dt)
+        delta = d / dt - p
+        if not 0.0 <= delta <= 1.0:
+            raise ValueError(f'{name}: row {r}: delay / dt = {d / dt!r} does not split into whole samples and a fraction')
+        points.append(p)
+        deltas.append(delta)
+    return points, deltas
+
+
+class ShiftStage:
+    """Device-resident per-row delay in time for `batch` rows of `n` samples (build once, apply many times): the
+    reference's `shift(x[r], delays[r], dt)` (distortion.py:12-39) for every row, one skew per line.  With
+    p = int(delay // dt) and d = delay / dt - p (the reference's expressions, evaluated here on the host):
+        y[r, i] = (1 - d) x[r, i - p] + d x[r, i - p - 1]     samples outside [0, n) are zero, and so is y wherever
+                                                              i - p is outside [0, n)
+    and for d = 0 a plain zero-filled shift by p samples that moves values bit for bit (inf and NaN included).
+    Linear interpolation, zero fill: not the circular band-limited `('delay', tau)` of `ReflectionStage`.
+    Where the reference differs, on purpose: it returns 3 samples for n < 3 with a fractional delay (rows keep n
+    here), and it multiplies x[i + 1] by a zero tap, so an inf there gives NaN at i (not here).
+    `delays`: a scalar (every row; give `batch`) or one value per row.  float32 rows are computed in float64 and
+    rounded once.  `.points` / `.deltas`: the split per row.
+
+        st = ShiftStage(skews, n, 1 / 2e9)
+        st.apply_torch(x, out=y)               # out of place, on torch's current stream
+    """
+
+    def __init__(self, delays, n: int, dt: float, dtype=np.float64, batch=None):
+        scalar = np.ndim(delays) == 0
+        if scalar and batch is None:
+            raise ValueError('ShiftStage: a scalar delay needs batch=')
+        rows = [delays] * int(batch) if scalar else list(np.asarray(delays).reshape(-1))
+        if batch is not None and len(rows) != int(batch):
+            raise ValueError(f'ShiftStage: {len(rows)} delays for {int(batch)} rows')
+        if not rows:
+            raise ValueError('ShiftStage: no rows')
+        points, deltas = _shift_split('ShiftStage', rows, dt)
+        self._set_plan(_engine.ShiftRowsPlan(points, deltas, n, dtype), float(dt))
+
+    def _set_plan(self, plan, dt):
+        self.plan, self.dt = plan, dt
+        self.n, self.batch, self.dtype = plan.n, plan.batch, plan.dtype
+        self.points, self.deltas = plan.points, plan.deltas
+
+    @classmethod
+    def from_split(cls, points, deltas, n: int, dtype=np.float64):
+        """the stage of rows whose delays are already split: points[r] whole samples and deltas[r] in [0, 1] of one"""
+        self = cls.__new__(cls)
+        self._set_plan(_engine.ShiftRowsPlan(points, deltas, n, dtype), None)
+        return self
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, stream=0):
+        self.plan.apply(in_ptr, in_stride, out_ptr, out_stride, stream)
+
+    def kernel_name(self) -> str:
+        return self.plan.kernel_name()
+
+    def apply_torch(self, x, out):
+        """x, out: (batch, >= n) row-contiguous device tensors of the stage's dtype (rows may be windows of a wider
+        tensor); out of place: the rows of `out` may share no memory with the rows of `x` (ValueError).
+        Asynchronous on torch's current stream; one stage may serve several streams.  -> out"""
+        import torch
+        want = torch.float64 if self.dtype == np.float64 else torch.float32
+        for t in (x, out):
+            if (not t.is_cuda or t.dtype != want or t.dim() != 2 or t.shape[0] != self.batch or
+                    t.shape[1] < self.n or t.stride(1) != 1 or (self.batch > 1 and t.stride(0) < self.n)):
+                raise ValueError('expected (batch, >=n) row-contiguous device tensors of the stage dtype')
+        es = x.element_size()
+        xs, os_ = max(x.stride(0), self.n), max(out.stride(0), self.n)
+        x0, y0 = x.data_ptr(), out.data_ptr()
+        x1 = x0 + ((self.batch - 1) * xs + self.n) * es
+        y1 = y0 + ((self.batch - 1) * os_ + self.n) * es
+        if self.n and (x0 == y0 or (x0 < y1 and y0 < x1)):
+            raise ValueError('shift is out of place: out overlaps x')
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        self.apply(x0, xs, y0, os_, stream)
+        return out
+
+    def close(self):
+        self.plan.close()
+
+
+def shift_rows(sig, delays, dt):
+    """`shift(sig[r], delays[r], dt)` for every row r of a 2-D `sig` (reference distortion.py:12-39 per row; `delays`
+    a scalar: every row), all rows in one launch: see `ShiftStage` for the formula and the two places where rows of
+    fewer than 3 samples or with inf in them differ from the reference.  float32 rows stay float32, anything else
+    is computed as float64.  ValueError before any device work: sig not 2-D, a number of delays that does not match,
+    a delay that is not finite.  NotImplementedError: complex rows."""
+    src = np.asarray(sig)
+    if src.ndim == 2 and src.dtype == np.float32:
+        sig2 = np.ascontiguousarray(src)
+    else:
+        sig2 = _rows_signal('shift_rows', sig)
+    batch, n = sig2.shape
+    points, deltas = _shift_split('shift_rows', _per_row('shift_rows', 'delay', delays, batch), dt)
+    if n == 0 or batch == 0:
+        return sig2.copy()
+    plan = _engine.ShiftRowsPlan(points, deltas, n, sig2.dtype)
+    x = y = None
+    try:
+        x, y = _engine.DeviceBuffer(sig2.nbytes), _engine.DeviceBuffer(sig2.nbytes)
+        x.upload(sig2)
+        plan.apply(x.ptr, n, y.ptr, n)
+        _engine.sync()
+        return y.download(sig2.shape, sig2.dtype)
+    finally:
+        for b in (x, y):
+            if b is not None:
+                b.close()
+        plan.close()
 
 
 def zDistortKernel(dt, params):
