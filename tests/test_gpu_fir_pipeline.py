@@ -253,3 +253,86 @@ def test_overlapping_out_is_refused(path, dtype, monkeypatch):
         assert torch.equal(flat[:batch * n], before[:batch * n])
     finally:
         st.close()
+
+
+ROW_STAGES = {
+    'fir': (lambda n, batch, dt: distortion.FirStage(np.arange(1.0, 10.0) / 45.0, n, batch, dt), False),
+    'iir_rows': (lambda n, batch, dt: distortion.IirStage(
+        [[distortion.exp_decay_filter(0.02 * (r + 1), (30 + 10 * r) * 1e-9, 2e9)] for r in range(batch)], n, batch, dt),
+        True),
+    'reflection': (lambda n, batch, dt: distortion.ReflectionStage(
+        [[('correct', 0.1 * (r + 1), (3 + r) * 1e-9), ('delay', 0.7e-9 * r)] for r in range(batch)], n, 2e9, dt), True),
+    'shift': (lambda n, batch, dt: distortion.ShiftStage([0.3e-9 * (r + 1) for r in range(batch)], n, 0.5e-9, dt),
+              False),
+}
+
+
+@pytest.mark.parametrize('name', list(ROW_STAGES))
+@pytest.mark.parametrize('dtype', [np.float64, np.float32])
+def test_row_rule_is_one_rule_for_every_stage(name, dtype):
+    """The shared row check (csrc/wfk_host.h, waveforms_amd/_rows.py) as every per-row stage applies it: a row stride of
+    n - 1 and a null buffer are refused (ValueError from apply_torch, WFK_EINVAL from the raw apply), the out-of-place
+    stages refuse the overlap cases of test_overlapping_out_is_refused with `overlaps` in the text, the in-place stages
+    take out is x; no refusal launches anything, and the stage then computes what a fresh one computes, bit for bit."""
+    make, in_place = ROW_STAGES[name]
+    n, batch = 70, 3
+    tdt = torch.float64 if dtype == np.float64 else torch.float32
+    es = np.dtype(dtype).itemsize
+    st, fresh = make(n, batch, dtype), None
+    try:
+        rng = np.random.default_rng(70)
+        flat = torch.zeros(2 * (batch + 1) * n, dtype=tdt, device=dev())
+        flat[:batch * n] = torch.from_numpy(rng.normal(size=batch * n)).to(dev(), tdt)
+        before = flat.clone()
+        base = flat.data_ptr()
+        x = flat[:batch * n].view(batch, n)
+        y = flat[(batch + 1) * n:][:batch * n].view(batch, n)
+        raw = st.plan.apply
+
+        def refused_raw(*args, match='wfk error -1'):
+            with pytest.raises(_engine.EngineError, match=match) as e:
+                raw(*args)
+            assert 'wfk error -1' in str(e.value)
+
+        # a row stride below n, on either side
+        short = flat.as_strided((batch, n), (n - 1, 1))
+        for xin, yout in ((short, y), (x, y.as_strided((batch, n), (n - 1, 1)))):
+            with pytest.raises(ValueError):
+                st.apply_torch(xin, yout)
+        refused_raw(x.data_ptr(), n - 1, y.data_ptr(), n)
+        refused_raw(x.data_ptr(), n, y.data_ptr(), n - 1)
+        # a null buffer
+        refused_raw(x.data_ptr(), n, None, n)
+        refused_raw(None, n, y.data_ptr(), n)
+        if not in_place:
+            for shift in (0, n * es, 8, batch * n * es - es):      # bytes from in to out; the last: one element shared
+                for a, b in ((base, base + shift), (base + shift, base)):
+                    refused_raw(a, n, b, n, match='overlaps')
+            rows = flat[:(batch + 1) * n].view(batch + 1, n)
+            off = 8 // es
+            wide = flat.view(2, (batch + 1) * n)[0][:batch * (n + 7)].view(batch, n + 7)
+            pairs = [(rows[:batch], rows[:batch]), (rows[:batch], rows[1:]), (rows[1:], rows[:batch]),
+                     (x, flat[off:off + batch * n].view(batch, n)), (flat[off:off + batch * n].view(batch, n), x),
+                     # strided rows: the ranges run to the END of the last row, not to batch * stride
+                     (wide, flat[(batch - 1) * (n + 7) + n - 1:][:batch * n].view(batch, n))]
+            for xin, yout in pairs:
+                with pytest.raises(ValueError, match='overlaps'):
+                    st.apply_torch(xin, yout)
+        torch.cuda.synchronize()
+        assert torch.equal(flat, before)                           # a refusal launches nothing
+        # a valid call afterwards: what a fresh stage gives
+        fresh = make(n, batch, dtype)
+        want = fresh.apply_torch(x, torch.zeros_like(x))
+        assert st.apply_torch(x, y) is y
+        torch.cuda.synchronize()
+        assert torch.equal(y, want) and bool(torch.isfinite(y).all()) and not torch.equal(y, before[:batch * n].view(batch, n))
+        assert torch.equal(flat[:batch * n], before[:batch * n])
+        if in_place:
+            z = x.clone()
+            assert st.apply_torch(z, z) is z and st.apply_torch(x.clone()) is not None
+            torch.cuda.synchronize()
+            assert torch.equal(z, want)
+    finally:
+        st.close()
+        if fresh is not None:
+            fresh.close()

@@ -4,7 +4,7 @@
     tools/kernel_cmp.py A B [object ...]
 
 A, B: two object files, or two trees (then waveforms_amd/csrc/_obj/<object> of each, default every object that is
-built with an offload arch: all but wfk_compile.o).  The code object is taken out of each object file as tools/kernel_regs.sh does, disassembled
+built with an offload arch: the `OBJ :=` line of waveforms_amd/csrc/Makefile but wfk_compile.o).  The code object is taken out of each object file as tools/kernel_regs.sh does, disassembled
 with llvm-objdump -d, and compared per kernel symbol: the encoded instruction words (branches are PC-relative, so
 a kernel that merely moved compares equal) and the metadata kernel_regs.sh prints (VGPR / AGPR / SGPR, spills,
 LDS, scratch).  Exit status 0: same set of kernels, every one identical.
@@ -61,13 +61,20 @@ def kernels(obj):
     return {k: (meta[k], code[k]) for k in meta}
 
 
+def default_objects():
+    """the objects of the Makefile's `OBJ :=` line, minus the one that is host code only"""
+    makefile = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "waveforms_amd", "csrc", "Makefile")
+    with open(makefile) as f:
+        line = next(l for l in f if l.startswith("OBJ :="))
+    return [os.path.basename(o) for o in line.split()[2:] if os.path.basename(o) != "wfk_compile.o"]
+
+
 def main():
     if len(sys.argv) < 3:
         sys.exit(__doc__)
     a, b = sys.argv[1:3]
     if os.path.isdir(a):
-        names = sys.argv[3:] or [f"wfk_{x}.o" for x in ("api", "kernels", "short", "fir", "fir_fused", "fir_sampled", "iir",
-                                                        "iir_rows", "spectral", "spectral_rows", "demod")]
+        names = sys.argv[3:] or default_objects()
         pairs = [(n, *(os.path.join(t, "waveforms_amd/csrc/_obj", n) for t in (a, b))) for n in names]
     else:
         pairs = [(os.path.basename(a), a, b)]

@@ -217,6 +217,12 @@ class _Handle:
 
     __del__ = close
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
 
 class Plan(_Handle):
     """A compiled program bound to a time axis (grid or explicit t)."""
@@ -739,6 +745,12 @@ class DeviceBuffer:
             self.ptr = None
 
     __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 def sync(stream: int = 0):

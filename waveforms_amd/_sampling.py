@@ -10,12 +10,13 @@ API (no reference counterpart): many channels, one launch, output left in HBM.
 from __future__ import annotations
 
 import collections
+import contextlib
 import os
 import threading
 
 import numpy as np
 
-from . import _engine, _flatten
+from . import _engine, _flatten, _rows
 from ._ir import ZERO
 
 
@@ -168,11 +169,8 @@ def call_waveform(w, x, frag=False, out=None, accumulate=False, function_lib=Non
         if runs is not None:
             return _call_runs(w, t, runs, out, accumulate, function_lib)
     plan, owned = _plan_for_axis(w, t, function_lib, grid)
-    try:
+    with plan if owned else contextlib.nullcontext():
         return _finish(w, plan, frag, out, accumulate)
-    finally:
-        if owned:
-            plan.close()
 
 
 _RUN_MIN = 4096      # shortest run worth a plan of its own
@@ -189,16 +187,13 @@ def _call_runs(w, t, runs, out, accumulate, function_lib):
     its part of one result.  Same values as one call per run (reference waveform.py:529-563)."""
     from .waveform import WaveVStack
     ends = [a for a, _ in runs[1:]] + [len(t)]
-    plans = [_engine.Plan(_flatten.flatten([w], g, function_lib), grid=g) for _, g in runs]
-    try:
+    with contextlib.ExitStack() as stack:
+        plans = [stack.enter_context(_engine.Plan(_flatten.flatten([w], g, function_lib), grid=g)) for _, g in runs]
         cplx = (not isinstance(w, WaveVStack)) and any(_is_complex(w, p) for p in plans)
         dtype = np.complex128 if cplx else np.float64
         res = _engine.pinned_empty((len(t), ), dtype)
         for (a, _), b, p in zip(runs, ends, plans):
             p.run_host_into(res[a:b])
-    finally:
-        for p in plans:
-            p.close()
     if out is None or isinstance(w, WaveVStack):
         return res
     if not accumulate:
@@ -219,11 +214,8 @@ def call_vstack(w, x, function_lib=None):
         if runs is not None:
             return _call_runs(w, t, runs, None, False, function_lib)
     plan, owned = _plan_for_axis(w, t, function_lib, grid)
-    try:
+    with plan if owned else contextlib.nullcontext():
         return plan.run_host(np.float64)[0]
-    finally:
-        if owned:
-            plan.close()
 
 
 def _rotated(prog):
@@ -252,17 +244,17 @@ def _sample_filtered(w, plan, sos, initial, zi):
     # input itself when the tree is fully fused (the unfiltered samples never exist in memory), otherwise sampler and
     # filter run back to back on the device buffer
     sections = _engine.sos_sections(sos)
-    chains = [_engine.ChainIirPlan(plan.prog, plan.grid, sections)]
-    D = chains[0].state_dim
-    buf = _engine.DeviceBuffer(max(n, 1) * 8 * rows)
-    dzi = _engine.DeviceBuffer(max(D, 1) * 8 * rows)
-    dzf = _engine.DeviceBuffer(max(D, 1) * 8 * rows)
-    try:
+    with contextlib.ExitStack() as stack:
+        chains = [stack.enter_context(_engine.ChainIirPlan(prog, plan.grid, sections))
+                  for prog in [plan.prog] + ([_rotated(plan.prog)] if cplx else [])]
+        D = chains[0].state_dim
+        buf = stack.enter_context(_engine.DeviceBuffer(max(n, 1) * 8 * rows))
+        dzi = stack.enter_context(_engine.DeviceBuffer(max(D, 1) * 8 * rows))
+        dzf = stack.enter_context(_engine.DeviceBuffer(max(D, 1) * 8 * rows))
         z0 = np.zeros(D, dtype=np.complex128) if zi is None else np.asarray(zi, dtype=np.complex128).reshape(-1)
         init = complex(initial or 0.0)
-        if cplx:
-            chains.append(_engine.ChainIirPlan(_rotated(plan.prog), plan.grid, sections))
         dzi.upload(np.ascontiguousarray(np.concatenate([z0.real, z0.imag])[:D * rows]))
+
         def launch():
             return all([chain.launch(buf.ptr + r * max(n, 1) * 8, max(n, 1), dzi.ptr + r * max(D, 1) * 8,
                                      dzf.ptr + r * max(D, 1) * 8, init.imag if r else init.real)
@@ -279,28 +271,19 @@ def _sample_filtered(w, plan, sos, initial, zi):
             sig = np.zeros(0, dtype=np.complex128 if cplx else np.float64)
         zf = dzf.download((rows, max(D, 1)), np.float64)[:, :D]
         zf = (zf[0] + 1j * zf[1] if cplx else zf[0]).reshape(-1, 2)
-    finally:
-        buf.close()
-        dzi.close()
-        dzf.close()
-        for chain in chains:
-            chain.close()
     return sig, zf
 
 
 def _sample_on_grid(w, grid, out, function_lib, filters=None, zi=None, no_cache=False):
     from .waveform import WaveVStack
     plan, owned = _cached_grid_plan(w, grid, function_lib, no_cache)
-    try:
+    with plan if owned else contextlib.nullcontext():
         if filters is not None:
             sos, initial = filters
             return _sample_filtered(w, plan, sos, initial, zi)
         if isinstance(w, WaveVStack):
             return plan.run_host(np.float64)[0]
         return _finish(w, plan, False, out, False)
-    finally:
-        if owned:
-            plan.close()
 
 
 def sample_waveform(w, sample_rate=None, out=None, chunk_size=None, function_lib=None,
@@ -387,13 +370,12 @@ class BatchSampler:
         """Launch into a CUDA/HIP torch tensor of shape (n_channels, >= n) on the
         current torch stream; returns `out`."""
         import torch
-        if not out.is_cuda or out.dim() != 2 or out.shape[0] != self.n_channels \
-                or out.shape[1] < self.n or out.stride(1) != 1:
-            raise ValueError('out must be a (n_channels, >=n) row-contiguous device tensor')
+        ptr, stride = _rows.check_rows(out, self.n_channels, self.n, None,
+                                       'out must be a (n_channels, >=n) row-contiguous device tensor')
         dtype = {torch.float64: np.float64, torch.float32: np.float32,
                  torch.complex128: np.complex128, torch.complex64: np.complex64}[out.dtype]
         stream = torch.cuda.current_stream(out.device).cuda_stream
-        self.launch(out.data_ptr(), out.stride(0), dtype, accumulate, stream)
+        self.launch(ptr, stride, dtype, accumulate, stream)
         return out
 
     def to_host(self, dtype=np.float64):

@@ -328,14 +328,11 @@ int wfk_fir_apply(wfk_fir_plan* p, const void* in_dev, int64_t in_stride, void* 
                   int64_t out_stride, void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0) return WFK_OK;
-  if (!in_dev || !out_dev) return wfk_fail(WFK_EINVAL, "null buffer");
-  if (in_stride < p->n || out_stride < p->n) return wfk_fail(WFK_EINVAL, "stride smaller than n");
   // no path works in place: the fused kernel reads halos that other workgroups overwrite, passes 2 to 4 of a long
   // kernel read `in` again, and the pipeline's later chunks gather after the earlier ones have scattered
-  const size_t esz = p->kind == WFK_OUT_F32 ? 4 : 8;
-  const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + ((size_t)(p->batch - 1) * (size_t)in_stride + (size_t)p->n) * esz;
-  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + ((size_t)(p->batch - 1) * (size_t)out_stride + (size_t)p->n) * esz;
-  if (i0 < o1 && o0 < i1) return wfk_fail(WFK_EINVAL, "FIR is out of place: out overlaps in");
+  if (const int rc = wfk_check_rows("FIR", p->n, p->kind == WFK_OUT_F32 ? 4 : 8, in_dev, p->batch, in_stride, out_dev,
+                                    p->batch, out_stride, true))
+    return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   if (p->fused) {
     const size_t seg_bytes = (size_t)p->L * 2 * (p->kind == WFK_OUT_F32 ? 4 : 8);

@@ -669,8 +669,9 @@ const char* wfk_chain_kernel_name(const wfk_chain_plan* p) {
 int wfk_chain_launch(wfk_chain_plan* p, void* out_dev, int64_t out_stride, void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0 || p->n_channels == 0) return WFK_OK;
-  if (!out_dev) return wfk_fail(WFK_EINVAL, "null output");
-  if (out_stride < p->n) return wfk_fail(WFK_EINVAL, "out_stride smaller than n");
+  if (const int rc = wfk_check_rows("FIR chain", p->n, p->kind == WFK_OUT_F32 ? 4 : 8, out_dev, p->n_channels, out_stride,
+                                    out_dev, p->n_channels, out_stride))
+    return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   if (!p->fused) {
     int rc = wfk_plan_launch(p->sampler, p->workspace.get(), p->n, p->kind, 0, hip_stream);

@@ -9,6 +9,7 @@
 #include <utility>
 #include <vector>
 
+#include "wfk.h"
 #include "wfk_internal.h"
 
 namespace {
@@ -16,6 +17,31 @@ namespace {
 inline int wfk_fail(int code, const std::string& m) {
   wfk_internal_set_error(m.c_str());
   return code;
+}
+
+// The row rule of every apply (DESIGN.md "The row rule").  A batch of rows of n samples, `stride` samples apart,
+// occupies the bytes from the first sample of row 0 to the END of row batch - 1 -- not batch * stride.
+inline size_t wfk_rows_bytes(int64_t batch, int64_t stride, int64_t n, size_t es) {
+  return ((size_t)(batch - 1) * (size_t)stride + (size_t)n) * es;
+}
+
+// do the half-open byte ranges [a, a + bytes_a) and [b, b + bytes_b) meet
+inline bool wfk_ranges_overlap(const void* a, size_t bytes_a, const void* b, size_t bytes_b) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + bytes_b && b0 < a0 + bytes_a;
+}
+
+// What an apply checks after its own `null plan` / `n == 0` handling: `in` (in_rows rows) and `out` (out_rows rows)
+// are there, no row stride is below n and -- `disjoint`, the out-of-place stages -- the two extents do not meet.
+// A stage whose rows all read ONE input row gives in_rows = 1; a launch without an input gives `out` twice.
+inline int wfk_check_rows(const char* stage, int64_t n, size_t es, const void* in, int64_t in_rows, int64_t in_stride,
+                          const void* out, int64_t out_rows, int64_t out_stride, bool disjoint = false) {
+  if (!in || !out) return wfk_fail(WFK_EINVAL, std::string(stage) + ": null in / out buffer");
+  if (in_stride < n || out_stride < n) return wfk_fail(WFK_EINVAL, std::string(stage) + ": row stride smaller than n");
+  if (disjoint && wfk_ranges_overlap(in, wfk_rows_bytes(in_rows, in_stride, n, es), out,
+                                     wfk_rows_bytes(out_rows, out_stride, n, es)))
+    return wfk_fail(WFK_EINVAL, std::string(stage) + " is out of place: out overlaps in");
+  return WFK_OK;
 }
 
 inline bool wfk_have_device() {

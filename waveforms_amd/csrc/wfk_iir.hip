@@ -1306,8 +1306,9 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0) return WFK_OK;
   if (src) { in_dev = out_dev; in_stride = out_stride; }     // (never read)
-  if (!in_dev || !out_dev) return wfk_fail(WFK_EINVAL, "null buffer");
-  if (in_stride < p->n || out_stride < p->n) return wfk_fail(WFK_EINVAL, "stride smaller than n");
+  if (const int rc = wfk_check_rows("IIR", p->n, p->kind == WFK_OUT_F32 ? 4 : 8, in_dev, p->batch, in_stride, out_dev,
+                                    p->batch, out_stride))
+    return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   if (p->c.D == 0) {
     const dim3 g((unsigned)std::min<int64_t>((p->n + 255) / 256, 4096), (unsigned)p->batch);
@@ -1653,8 +1654,9 @@ int wfk_chain_iir_launch(wfk_chain_iir_plan* p, void* out_dev, int64_t out_strid
                          double* zf_dev, double initial, void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0 || p->n_channels == 0) return WFK_OK;
-  if (!out_dev) return wfk_fail(WFK_EINVAL, "null output");
-  if (out_stride < p->n) return wfk_fail(WFK_EINVAL, "out_stride smaller than n");
+  if (const int rc = wfk_check_rows("IIR chain", p->n, p->kind == WFK_OUT_F32 ? 4 : 8, out_dev, p->n_channels, out_stride,
+                                    out_dev, p->n_channels, out_stride))
+    return rc;
   void* mid = p->fir ? p->workspace.get() : out_dev;
   const int64_t mid_stride = p->fir ? p->n : out_stride;
   int rc;

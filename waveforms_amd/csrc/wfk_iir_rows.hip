@@ -321,8 +321,9 @@ int wfk_iir_rows_apply(wfk_iir_rows_plan* p, const void* in_dev, int64_t in_stri
                        void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0) return WFK_OK;
-  if (!in_dev || !out_dev) return wfk_fail(WFK_EINVAL, "null argument");
-  if (in_stride < p->n || out_stride < p->n) return wfk_fail(WFK_EINVAL, "row stride < n");
+  if (const int rc = wfk_check_rows("per-row IIR", p->n, p->kind == WFK_OUT_F64 ? 8 : 4, in_dev, p->batch, in_stride,
+                                    out_dev, p->batch, out_stride))
+    return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   const int rc = p->kind == WFK_OUT_F64
                      ? irw_launch<double>(p, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial_dev, s)
@@ -337,13 +338,10 @@ int wfk_iir_rows_apply_shared_in(wfk_iir_rows_plan* p, const void* in_dev, void*
                                  void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0) return WFK_OK;
-  if (!in_dev || !out_dev) return wfk_fail(WFK_EINVAL, "null argument");
-  if (out_stride < p->n) return wfk_fail(WFK_EINVAL, "row stride < n");
-  // every row reads the one input row while other rows are already being written: no overlap at all
-  const size_t es = p->kind == WFK_OUT_F64 ? 8 : 4;
-  const uintptr_t i0 = (uintptr_t)in_dev, i1 = i0 + (size_t)p->n * es;
-  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + ((size_t)(p->batch - 1) * (size_t)out_stride + (size_t)p->n) * es;
-  if (i0 < o1 && o0 < i1) return wfk_fail(WFK_EINVAL, "shared input: out overlaps in");
+  // every row reads the one input row (an extent of one row) while other rows are already being written: no overlap
+  if (const int rc = wfk_check_rows("per-row IIR, shared input", p->n, p->kind == WFK_OUT_F64 ? 8 : 4, in_dev, 1, p->n,
+                                    out_dev, p->batch, out_stride, true))
+    return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   const int rc = p->kind == WFK_OUT_F64
                      ? irw_launch<double>(p, in_dev, 0, out_dev, out_stride, zi_dev, zf_dev, initial_dev, s)

@@ -143,10 +143,6 @@ __global__ void __launch_bounds__(kThreads)
     shift_block<T, false, false>(x, y, n, first, p, w0, w1);
 }
 
-inline bool ranges_overlap(const char* a, const char* b, size_t bytes_a, size_t bytes_b) {
-  return a < b + bytes_b && b < a + bytes_a;
-}
-
 }  // namespace
 
 struct wfk_shift_rows_plan {
@@ -206,14 +202,10 @@ int wfk_shift_rows_apply(wfk_shift_rows_plan* p, const void* in_dev, int64_t in_
                          int64_t out_stride, void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0) return WFK_OK;   // nothing to move (the pointers of empty rows may be null)
-  if (!in_dev || !out_dev) return wfk_fail(WFK_EINVAL, "null argument");
-  if (in_stride < p->n || out_stride < p->n) return wfk_fail(WFK_EINVAL, "row stride < n");
   const size_t es = p->kind == WFK_OUT_F32 ? 4 : 8;
   if (((uintptr_t)in_dev | (uintptr_t)out_dev) & (es - 1)) return wfk_fail(WFK_EINVAL, "rows are not aligned to their element");
-  const size_t in_bytes = ((size_t)(p->batch - 1) * (size_t)in_stride + (size_t)p->n) * es;
-  const size_t out_bytes = ((size_t)(p->batch - 1) * (size_t)out_stride + (size_t)p->n) * es;
-  if (ranges_overlap((const char*)in_dev, (const char*)out_dev, in_bytes, out_bytes))
-    return wfk_fail(WFK_EINVAL, "shift rows is out of place: out overlaps in");
+  if (const int rc = wfk_check_rows("shift rows", p->n, es, in_dev, p->batch, in_stride, out_dev, p->batch, out_stride, true))
+    return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   const dim3 grid(p->blocks_per_row * (uint32_t)p->batch);
   const ShiftRow* tab = DevTables::at<const ShiftRow>(p->tables.get(), p->rows_off);

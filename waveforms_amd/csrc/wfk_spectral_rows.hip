@@ -250,10 +250,11 @@ int wfk_spectral_rows_plan_create(int64_t n, int32_t batch, int kind, double sam
 
 int wfk_spectral_rows_apply(wfk_spectral_rows_plan* p, const void* in_dev, int64_t in_stride, void* out_dev,
                             int64_t out_stride, void* hip_stream) {
-  if (!p || !in_dev || !out_dev) return wfk_fail(WFK_EINVAL, "null argument");
-  if (in_stride < p->n || out_stride < p->n) return wfk_fail(WFK_EINVAL, "row stride < n");
-  hipStream_t s = (hipStream_t)hip_stream;
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   const size_t es = p->kind == WFK_OUT_F32 ? 4 : 8;
+  if (const int rc = wfk_check_rows("spectral rows", p->n, es, in_dev, p->batch, in_stride, out_dev, p->batch, out_stride))
+    return rc;
+  hipStream_t s = (hipStream_t)hip_stream;
   const size_t width = (size_t)p->n * es, rows = (size_t)p->batch;
   if (rocfft_execution_info_set_stream(p->info.get(), s) != rocfft_status_success)
     return wfk_fail(WFK_EHIP, "rocfft set_stream failed");

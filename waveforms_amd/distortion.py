@@ -12,11 +12,12 @@ sample) uses NumPy/SciPy exactly as the reference does.
 """
 from __future__ import annotations
 
+import contextlib
 import warnings
 
 import numpy as np
 
-from . import _engine
+from . import _engine, _rows
 
 
 class FirStage:
@@ -33,21 +34,13 @@ class FirStage:
 
     def apply_torch(self, x, y):
         import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
-        for t in (x, y):
-            if (not t.is_cuda or t.dtype != want or t.dim() != 2 or
-                    t.shape[0] != self.batch or t.shape[1] < self.n or t.stride(1) != 1):
-                raise ValueError('expected (batch, >=n) row-contiguous device tensors '
-                                 'of the plan dtype')
-        # the rows of y may share no memory with the rows of x: [first sample of row 0, end of row batch - 1)
-        es = x.element_size()
-        x0, y0 = x.data_ptr(), y.data_ptr()
-        x1 = x0 + ((self.batch - 1) * x.stride(0) + self.n) * es
-        y1 = y0 + ((self.batch - 1) * y.stride(0) + self.n) * es
-        if x0 == y0 or (x0 < y1 and y0 < x1):
+        (x0, xs), (y0, ys) = (_rows.check_rows(
+            t, self.batch, self.n, _rows.torch_dtype(self.dtype),
+            'expected (batch, >=n) row-contiguous device tensors of the plan dtype') for t in (x, y))
+        es = self.dtype.itemsize
+        if not _rows.rows_disjoint((x0, xs, self.batch, self.n, es), (y0, ys, self.batch, self.n, es)):
             raise ValueError('FIR is out of place: y overlaps x')
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        self.apply(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), stream)
+        self.apply(x0, xs, y0, ys, torch.cuda.current_stream(x.device).cuda_stream)
         return y
 
     def close(self):
@@ -116,9 +109,7 @@ class IirStage:
         """None (all zero), or a (batch,) float64 device tensor; a tensor of the last values is kept"""
         import torch
         if isinstance(initial, torch.Tensor):
-            if (not initial.is_cuda or initial.dtype != torch.float64 or tuple(initial.shape) != (self.batch, )
-                    or not initial.is_contiguous()):
-                raise ValueError('initial: a (batch,) contiguous float64 device tensor')
+            _rows.check_state(initial, (self.batch, ), 'initial: a (batch,) contiguous float64 device tensor')
             return initial
         arr = np.asarray(initial, dtype=np.float64)
         if arr.ndim == 0:
@@ -137,33 +128,32 @@ class IirStage:
         tensor); out=None or out is x: in place.  `initial`: a scalar, one value per row, or a (batch,) float64 device
         tensor (per-row values need per-row cascades).  Asynchronous on torch's current stream.  -> out"""
         import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
         out = x if out is None else out
-        for t in (x, out):
-            if (not t.is_cuda or t.dtype != want or t.dim() != 2 or t.shape[0] != self.batch or
-                    t.shape[1] < self.n or t.stride(1) != 1 or (self.batch > 1 and t.stride(0) < self.n)):
-                raise ValueError('expected (batch, >=n) row-contiguous device tensors of the stage dtype')
-        for z in (zi, zf):
-            if z is not None and (not z.is_cuda or z.dtype != torch.float64 or not z.is_contiguous()
-                                  or tuple(z.shape) != (self.batch, self.state_dim)):
-                raise ValueError('zi / zf must be contiguous (batch, state_dim) float64 device tensors')
+        (x0, xs), (y0, ys) = (_rows.check_rows(
+            t, self.batch, self.n, _rows.torch_dtype(self.dtype),
+            'expected (batch, >=n) row-contiguous device tensors of the stage dtype') for t in (x, out))
+        zip_, zfp = (_rows.check_state(z, (self.batch, self.state_dim),
+                                       'zi / zf must be contiguous (batch, state_dim) float64 device tensors')
+                     for z in (zi, zf))
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        zip_, zfp = None if zi is None else zi.data_ptr(), None if zf is None else zf.data_ptr()
         if self.per_row:
             ini = self._initial_tensor(initial, x.device)
-            self.plan.apply(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), zip_, zfp,
-                            None if ini is None else ini.data_ptr(), stream)
+            self.plan.apply(x0, xs, y0, ys, zip_, zfp, None if ini is None else ini.data_ptr(), stream)
             return out
         if isinstance(initial, torch.Tensor) or np.ndim(initial) != 0:
             raise ValueError('a shared cascade takes a scalar `initial`; per-row levels need per-row cascades')
         for attempt in range(2):     # (a look-back timeout of the shared-cascade plan: it has switched form)
-            if self.plan.apply(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), zip_, zfp,
-                               float(initial), stream):
+            if self.plan.apply(x0, xs, y0, ys, zip_, zfp, float(initial), stream):
                 return out
         raise _engine.EngineError('IIR stage refused twice')
 
     def close(self):
         self.plan.close()
+
+
+def _dev(stack, nbytes):
+    """a device buffer of at least 8 bytes that `stack` (a contextlib.ExitStack) frees"""
+    return stack.enter_context(_engine.DeviceBuffer(max(nbytes, 8)))
 
 
 def _nesting(x) -> int:
@@ -200,21 +190,17 @@ class SampledFir:
 
     def launch_torch(self, out):
         import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
-        if (not out.is_cuda or out.dtype != want or out.dim() != 2 or out.shape[0] != self.n_channels
-                or out.shape[1] < self.n or out.stride(1) != 1):
-            raise ValueError('out must be a (n_channels, >=n) row-contiguous device tensor of the plan dtype')
-        self.launch(out.data_ptr(), out.stride(0), torch.cuda.current_stream(out.device).cuda_stream)
+        ptr, stride = _rows.check_rows(
+            out, self.n_channels, self.n, _rows.torch_dtype(self.dtype),
+            'out must be a (n_channels, >=n) row-contiguous device tensor of the plan dtype')
+        self.launch(ptr, stride, torch.cuda.current_stream(out.device).cuda_stream)
         return out
 
     def to_host(self):
-        buf = _engine.DeviceBuffer(max(self.n_channels * self.n, 1) * self.dtype.itemsize)
-        try:
+        with _engine.DeviceBuffer(max(self.n_channels * self.n, 1) * self.dtype.itemsize) as buf:
             self.launch(buf.ptr)
             _engine.sync()
             return buf.download((self.n_channels, self.n), self.dtype)
-        finally:
-            buf.close()
 
     def close(self):
         self.plan.close()
@@ -259,29 +245,25 @@ class SampledIir:
     def launch_torch(self, out, initial=0.0, zi=None, zf=None):
         """zi / zf: optional (n_channels, state_dim) float64 device tensors (initial state in / final state out)"""
         import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
-        if (not out.is_cuda or out.dtype != want or out.dim() != 2 or out.shape[0] != self.n_channels
-                or out.shape[1] < self.n or out.stride(1) != 1):
-            raise ValueError('out must be a (n_channels, >=n) row-contiguous device tensor of the plan dtype')
-        for z in (zi, zf):
-            if z is not None and (not z.is_cuda or z.dtype != torch.float64 or not z.is_contiguous()
-                                  or tuple(z.shape) != (self.n_channels, self.state_dim)):
-                raise ValueError('zi / zf must be contiguous (n_channels, state_dim) float64 device tensors')
+        ptr, stride = _rows.check_rows(
+            out, self.n_channels, self.n, _rows.torch_dtype(self.dtype),
+            'out must be a (n_channels, >=n) row-contiguous device tensor of the plan dtype')
+        zip_, zfp = (_rows.check_state(z, (self.n_channels, self.state_dim),
+                                       'zi / zf must be contiguous (n_channels, state_dim) float64 device tensors')
+                     for z in (zi, zf))
         s = torch.cuda.current_stream(out.device).cuda_stream
         for attempt in range(2):
-            ok = self.launch(out.data_ptr(), out.stride(0), None if zi is None else zi.data_ptr(),
-                             None if zf is None else zf.data_ptr(), initial, s)
-            if ok:
+            if self.launch(ptr, stride, zip_, zfp, initial, s):
                 return out
         raise _engine.EngineError('IIR chain refused twice')
 
     def to_host(self, initial=0.0, zi=None, return_zf=False):
         """NumPy result (n_channels, n); a look-back timeout (outputs NaN) is retried once in the unfused form"""
         D = max(self.state_dim, 1)
-        buf = _engine.DeviceBuffer(max(self.n_channels * self.n, 1) * self.dtype.itemsize)
-        dzi = _engine.DeviceBuffer(self.n_channels * D * 8) if zi is not None else None
-        dzf = _engine.DeviceBuffer(self.n_channels * D * 8) if return_zf else None
-        try:
+        with contextlib.ExitStack() as stack:
+            buf = _dev(stack, max(self.n_channels * self.n, 1) * self.dtype.itemsize)
+            dzi = _dev(stack, self.n_channels * D * 8) if zi is not None else None
+            dzf = _dev(stack, self.n_channels * D * 8) if return_zf else None
             if zi is not None:
                 z = np.broadcast_to(np.asarray(zi, dtype=np.float64).reshape(-1, self.state_dim)
                                     if np.ndim(zi) > 1 else np.asarray(zi, dtype=np.float64),
@@ -295,12 +277,6 @@ class SampledIir:
             if return_zf:
                 return out, dzf.download((self.n_channels, D), np.float64)[:, :self.state_dim]
             return out
-        finally:
-            buf.close()
-            if dzi is not None:
-                dzi.close()
-            if dzf is not None:
-                dzf.close()
 
     def close(self):
         self.plan.close()
@@ -337,19 +313,12 @@ def _fir_host_real(sig: np.ndarray, ker: np.ndarray) -> np.ndarray:
     batch, n = sig2.shape
     if n == 0:
         return np.zeros_like(np.asarray(sig, dtype=np.float64))
-    stage = FirStage(ker, n, batch, np.float64)
-    din = _engine.DeviceBuffer(sig2.nbytes)
-    dout = _engine.DeviceBuffer(sig2.nbytes)
-    try:
+    with _engine.FirPlan(ker, n, batch, np.float64) as plan, _engine.DeviceBuffer(sig2.nbytes) as din, \
+            _engine.DeviceBuffer(sig2.nbytes) as dout:
         din.upload(sig2)
-        stage.apply(din.ptr, n, dout.ptr, n)
+        plan.apply(din.ptr, n, dout.ptr, n)
         _engine.sync()
-        out = dout.download(sig2.shape, np.float64)
-    finally:
-        din.close()
-        dout.close()
-        stage.close()
-    return out.reshape(np.shape(sig))
+        return dout.download(sig2.shape, np.float64).reshape(np.shape(sig))
 
 
 def combine_filters(filters):
@@ -415,43 +384,28 @@ def iir_host(sig, sections, zi=None, initial=0.0, ker=None):
         return y, zf
     sig2 = np.ascontiguousarray(np.atleast_2d(sig), dtype=np.float64)
     batch, n = sig2.shape
-    plan = _engine.IirPlan(sections, n, batch, np.float64)
-    D = plan.state_dim
-    bufs = []
-
-    def dev(nbytes):
-        b = _engine.DeviceBuffer(max(nbytes, 8))
-        bufs.append(b)
-        return b
-
-    fir = None
-    try:
-        x, y = dev(sig2.nbytes), dev(sig2.nbytes)
+    with contextlib.ExitStack() as stack:
+        plan = stack.enter_context(_engine.IirPlan(sections, n, batch, np.float64))
+        D = plan.state_dim
+        x, y = _dev(stack, sig2.nbytes), _dev(stack, sig2.nbytes)
         x.upload(sig2)
         dzi = None
         if zi is not None:
             z = np.ascontiguousarray(np.broadcast_to(np.asarray(zi, dtype=np.float64).reshape(-1),
                                                      (batch, D)))
-            dzi = dev(z.nbytes)
+            dzi = _dev(stack, z.nbytes)
             dzi.upload(z)
-        dzf = dev(batch * D * 8)
+        dzf = _dev(stack, batch * D * 8)
         if not _engine.iir_run_checked(      # (x stays intact: a launch whose look-back timed out can be repeated)
                 lambda: plan.apply(x.ptr, n, y.ptr, n, dzi.ptr if dzi else None, dzf.ptr, initial), plan.status):
             raise _engine.EngineError('IIR stage failed twice')
         res = y
         if ker is not None and n > 0:
-            fir = FirStage(ker, n, batch, np.float64)
-            fir.apply(y.ptr, n, x.ptr, n)
+            stack.enter_context(_engine.FirPlan(ker, n, batch, np.float64)).apply(y.ptr, n, x.ptr, n)
             res = x
         _engine.sync()
         out = res.download(sig2.shape, np.float64) if n else sig2.copy()
         zf = dzf.download((batch, D), np.float64) if n else np.zeros((batch, D))
-    finally:
-        for b in bufs:
-            b.close()
-        plan.close()
-        if fir is not None:
-            fir.close()
     return out.reshape(np.shape(sig)), (zf[0] if np.ndim(sig) == 1 else zf)
 
 
@@ -593,31 +547,18 @@ def _iir_rows_real(sig2, ba, zi):
     """real rows through one IirRowsPlan launch: -> (out, [zf per row]); ba: one combined (b, a) per row"""
     batch, n = sig2.shape
     sig2 = np.ascontiguousarray(sig2, dtype=np.float64)
-    plan = _engine.IirRowsPlan([[s] for s in ba], n, np.float64)
-    D = plan.state_dim
-    bufs = []
-
-    def dev(nbytes):
-        b = _engine.DeviceBuffer(max(nbytes, 8))
-        bufs.append(b)
-        return b
-
-    try:
-        x = dev(sig2.nbytes)
-        x.upload(sig2)
-        z = np.zeros((batch, D))
+    with contextlib.ExitStack() as stack:
+        plan = stack.enter_context(_engine.IirRowsPlan([[s] for s in ba], n, np.float64))
+        z = np.zeros((batch, plan.state_dim))
         for r, zr in enumerate(zi):
             z[r, :len(zr)] = zr
-        dzi, dzf = dev(z.nbytes), dev(z.nbytes)
+        x, dzi, dzf = _dev(stack, sig2.nbytes), _dev(stack, z.nbytes), _dev(stack, z.nbytes)
+        x.upload(sig2)
         dzi.upload(z)
         plan.apply(x.ptr, n, x.ptr, n, dzi.ptr, dzf.ptr)
         _engine.sync()
         out = x.download(sig2.shape, np.float64)
-        zf = dzf.download((batch, D), np.float64)
-    finally:
-        for b in bufs:
-            b.close()
-        plan.close()
+        zf = dzf.download(z.shape, np.float64)
     return out, [zf[r, :plan.own_orders[r][0]] for r in range(batch)]
 
 
@@ -770,9 +711,9 @@ class PhaseCurve:
         P = len(rows)
         if out is None:
             out = torch.empty((P, self.nq), dtype=torch.float64, device=self._dev)
-        elif (not out.is_cuda or out.dtype != torch.float64 or tuple(out.shape) != (P, self.nq)
-              or (self.nq > 1 and out.stride(1) != 1) or (P > 1 and out.stride(0) < self.nq)):
-            raise ValueError(f'out must be a ({P}, {self.nq}) row-contiguous float64 device tensor')
+        out_ptr, out_stride = _rows.check_rows(
+            out, P, self.nq, torch.float64, f'out must be a ({P}, {self.nq}) row-contiguous float64 device tensor',
+            exact=True)
         if self._ws is None or self._ws.shape[0] < P:
             self._ws = None
             self._ws = torch.empty((P, self.num), dtype=torch.float64, device=self._dev)
@@ -797,7 +738,7 @@ class PhaseCurve:
             else:
                 at = ws[lo].data_ptr()
                 plan.apply(at, ws.stride(0), at, ws.stride(0), stream=stream)
-        self.probe.apply(ws.data_ptr(), P, ws.stride(0), out.data_ptr(), max(out.stride(0), self.nq), stream)
+        self.probe.apply(ws.data_ptr(), P, ws.stride(0), out_ptr, out_stride, stream)
         return out
 
     def rows(self, params_rows):
@@ -846,11 +787,8 @@ def phase_curve(t, params, df_dphi, pulse_width, start, wav, sample_rate):
     exp-decay `params`, integrated over `pulse_width` and read off at the delays `t`.  Same signature, same return
     (np.interp's shape and dtype, a scalar t included), ValueError wherever the reference raises.  One `PhaseCurve`
     evaluation; a fit should build a `PhaseCurve` once instead."""
-    pc = PhaseCurve(t, df_dphi, pulse_width, start, wav, sample_rate)
-    try:
+    with contextlib.closing(PhaseCurve(t, df_dphi, pulse_width, start, wav, sample_rate)) as pc:
         return pc(params)
-    finally:
-        pc.close()
 
 
 # --------------------------------------------------------------------------
@@ -867,19 +805,13 @@ def transfer_host(sig, H):
     n = len(sig)
     Hc = np.ascontiguousarray(H, dtype=np.complex128)
     assert Hc.shape == (n // 2 + 1, )
-    plan = _engine.SpectralPlan(n, 1, np.float64)
-    x, y, h = (_engine.DeviceBuffer(n * 8), _engine.DeviceBuffer(n * 8),
-               _engine.DeviceBuffer(Hc.nbytes))
-    try:
+    with _engine.SpectralPlan(n, 1, np.float64) as plan, _engine.DeviceBuffer(n * 8) as x, \
+            _engine.DeviceBuffer(n * 8) as y, _engine.DeviceBuffer(Hc.nbytes) as h:
         x.upload(sig)
         h.upload(Hc)
         plan.apply(x.ptr, y.ptr, h.ptr)
         _engine.sync()
         return y.download((n, ), np.float64)
-    finally:
-        for b in (x, y, h):
-            b.close()
-        plan.close()
 
 
 def reflection(sig, A, tau, sample_rate):
@@ -946,14 +878,11 @@ class ReflectionStage:
         tensor, any row stride >= n); out=None or out is x: in place.  Asynchronous on torch's current stream; one
         stage serves one stream at a time (it owns the transform buffers).  -> out"""
         import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
         out = x if out is None else out
-        for t in (x, out):
-            if (not t.is_cuda or t.dtype != want or t.dim() != 2 or t.shape[0] != self.batch or
-                    t.shape[1] < self.n or t.stride(1) != 1 or (self.batch > 1 and t.stride(0) < self.n)):
-                raise ValueError('expected (batch, >=n) row-contiguous device tensors of the stage dtype')
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        self.apply(x.data_ptr(), max(x.stride(0), self.n), out.data_ptr(), max(out.stride(0), self.n), stream)
+        (x0, xs), (y0, ys) = (_rows.check_rows(
+            t, self.batch, self.n, _rows.torch_dtype(self.dtype),
+            'expected (batch, >=n) row-contiguous device tensors of the stage dtype') for t in (x, out))
+        self.apply(x0, xs, y0, ys, torch.cuda.current_stream(x.device).cuda_stream)
         return out
 
     def close(self):
@@ -1003,18 +932,12 @@ def _spectral_rows_host(sig2, terms_rows, sample_rate):
     if n == 0:
         _engine.pack_spec_terms(terms_rows)
         return sig2.copy()
-    plan = _engine.SpectralRowsPlan(terms_rows, n, sample_rate, np.float64)
-    x = None
-    try:
-        x = _engine.DeviceBuffer(sig2.nbytes)
+    with _engine.SpectralRowsPlan(terms_rows, n, sample_rate, np.float64) as plan, \
+            _engine.DeviceBuffer(sig2.nbytes) as x:
         x.upload(sig2)
         plan.apply(x.ptr, n, x.ptr, n)
         _engine.sync()
         return x.download(sig2.shape, np.float64)
-    finally:
-        if x is not None:
-            x.close()
-        plan.close()
 
 
 def reflection_rows(sig, A_rows, tau_rows, sample_rate):
@@ -1122,20 +1045,13 @@ class ShiftStage:
         tensor); out of place: the rows of `out` may share no memory with the rows of `x` (ValueError).
         Asynchronous on torch's current stream; one stage may serve several streams.  -> out"""
         import torch
-        want = torch.float64 if self.dtype == np.float64 else torch.float32
-        for t in (x, out):
-            if (not t.is_cuda or t.dtype != want or t.dim() != 2 or t.shape[0] != self.batch or
-                    t.shape[1] < self.n or t.stride(1) != 1 or (self.batch > 1 and t.stride(0) < self.n)):
-                raise ValueError('expected (batch, >=n) row-contiguous device tensors of the stage dtype')
-        es = x.element_size()
-        xs, os_ = max(x.stride(0), self.n), max(out.stride(0), self.n)
-        x0, y0 = x.data_ptr(), out.data_ptr()
-        x1 = x0 + ((self.batch - 1) * xs + self.n) * es
-        y1 = y0 + ((self.batch - 1) * os_ + self.n) * es
-        if self.n and (x0 == y0 or (x0 < y1 and y0 < x1)):
+        (x0, xs), (y0, ys) = (_rows.check_rows(
+            t, self.batch, self.n, _rows.torch_dtype(self.dtype),
+            'expected (batch, >=n) row-contiguous device tensors of the stage dtype') for t in (x, out))
+        es = self.dtype.itemsize
+        if not _rows.rows_disjoint((x0, xs, self.batch, self.n, es), (y0, ys, self.batch, self.n, es)):
             raise ValueError('shift is out of place: out overlaps x')
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        self.apply(x0, xs, y0, os_, stream)
+        self.apply(x0, xs, y0, ys, torch.cuda.current_stream(x.device).cuda_stream)
         return out
 
     def close(self):
@@ -1157,19 +1073,12 @@ def shift_rows(sig, delays, dt):
     points, deltas = _shift_split('shift_rows', _per_row('shift_rows', 'delay', delays, batch), dt)
     if n == 0 or batch == 0:
         return sig2.copy()
-    plan = _engine.ShiftRowsPlan(points, deltas, n, sig2.dtype)
-    x = y = None
-    try:
-        x, y = _engine.DeviceBuffer(sig2.nbytes), _engine.DeviceBuffer(sig2.nbytes)
+    with _engine.ShiftRowsPlan(points, deltas, n, sig2.dtype) as plan, _engine.DeviceBuffer(sig2.nbytes) as x, \
+            _engine.DeviceBuffer(sig2.nbytes) as y:
         x.upload(sig2)
         plan.apply(x.ptr, n, y.ptr, n)
         _engine.sync()
         return y.download(sig2.shape, sig2.dtype)
-    finally:
-        for b in (x, y):
-            if b is not None:
-                b.close()
-        plan.close()
 
 
 def zDistortKernel(dt, params):

@@ -121,26 +121,22 @@ class Demodulator:
         without a copy).  Writes `out` (shots, nf) complex128 (allocated when None; any row stride) on
         torch's current stream, asynchronously, and returns it."""
         import torch
-        want = {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32,
-                np.dtype(np.int16): torch.int16}[self.dtype]
+        from . import _rows
         if traces.is_complex():
             raise ValueError('complex traces are not supported')
-        if (not traces.is_cuda or traces.dtype != want or traces.dim() != 2 or traces.shape[1] < self.n
-                or (traces.stride(1) != 1 and traces.shape[1] > 1) or traces.stride(0) < self.n):
-            raise ValueError('traces must be a (shots, >= %d) row-contiguous device tensor of %s'
-                             % (self.n, self.dtype))
+        x_ptr, x_stride = _rows.check_rows(
+            traces, None, self.n, _rows.torch_dtype(self.dtype),
+            'traces must be a (shots, >= %d) row-contiguous device tensor of %s' % (self.n, self.dtype))
         shots = traces.shape[0]
         if out is None:
             out = torch.empty((shots, self.nf), dtype=torch.complex128, device=traces.device)
-        elif (not out.is_cuda or out.dtype != torch.complex128 or out.dim() != 2 or out.shape[0] != shots
-              or out.shape[1] != self.nf or (out.stride(1) != 1 and self.nf > 1)
-              or (shots > 1 and out.stride(0) < self.nf) or out.device != traces.device):
-            raise ValueError('out must be a (shots, %d) row-contiguous complex128 tensor on the traces\' device'
-                             % self.nf)
+        message = 'out must be a (shots, %d) row-contiguous complex128 tensor on the traces\' device' % self.nf
+        out_ptr, out_stride = _rows.check_rows(out, shots, self.nf, torch.complex128, message, exact=True)
+        if out.device != traces.device:
+            raise ValueError(message)
         if shots:
             stream = torch.cuda.current_stream(traces.device).cuda_stream
-            self.plan.apply(traces.data_ptr(), shots, max(traces.stride(0), self.n), out.data_ptr(),
-                            max(out.stride(0), self.nf), stream)
+            self.plan.apply(x_ptr, shots, x_stride, out_ptr, out_stride, stream)
         return out
 
     def __call__(self, signal):
