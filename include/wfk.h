@@ -406,6 +406,37 @@ int wfk_shift_rows_apply(wfk_shift_rows_plan* plan, const void* in_dev, int64_t 
 const char* wfk_shift_rows_kernel_name(const wfk_shift_rows_plan* plan);
 int wfk_shift_rows_plan_destroy(wfk_shift_rows_plan* plan);
 
+/* -- per-row kernel extraction: the reference's extractKernel for every row ---------------------- */
+/* ker[r] = extractKernel(sig_in[r], sig_out[r], sample_rate, bw, skip) (waveforms/distortion.py:42-48) for `batch`
+ * rows of n doubles: the kernel that maps sig_out back onto sig_in, the rows of an FIR plan's kernel matrix.  Per row
+ *   R[k] = rfft(sig_in)[k] / rfft(sig_out)[k] / n, k = 0 .. n/2;   c = irfft(R, n);   s[i] = c[(i + n/2) mod n];
+ *   t[i] = sum_m taps[m] s[i + (n_taps - 1)/2 - m], s = 0 outside [0, n)  (np.convolve(s, taps, 'same'); t = s for
+ *   n_taps = 0);   ker[j] = t[j + skip], 0 <= j < K = max(n - 2 skip, 0).
+ * The caller computes the taps with the reference's expression, M = int(2 * sample_rate / bw) points of
+ * exp(-0.5 * linspace(-3, 3, M)**2) divided by their sum, when bw is given and bw < sample_rate / 2; n_taps = 0
+ * otherwise.  in_rows = 1: ONE sig_in row shared by all rows (it is transformed once per apply); in_rows = batch:
+ * one per row.  Two departures from the reference, on purpose: n_taps > n is refused (np.convolve 'same' returns
+ * n_taps samples there; rows keep their length here) and so is skip < 0 (the reference's slice then means
+ * something else).  n < 1, batch < 1, in_rows not 1 or batch, skip < 0, n_taps < 0 or > n, a tap that is not finite,
+ * null pointers: WFK_EINVAL; no device: WFK_EHIP.  A zero bin in the transform of a sig_out row makes that row's
+ * result non-finite, as in the reference; other rows are not touched by it.
+ * The plan owns the rocFFT plans, the staging and spectrum buffers and the taps.  wfk_extract_rows_apply() allocates
+ * nothing and does not synchronise; strides are in elements, >= n for the signals and >= K for the result; one plan
+ * serves one stream at a time.  Both inputs are staged first, so they may overlap each other in any way; the result
+ * [ker, ker + (batch - 1) * ker_stride + K) may overlap neither input: WFK_EINVAL.  K = 0: a no-op.
+ * Two kernels around rocFFT: extract_ratio (one pass over the two R2C outputs) and extract_smooth (rotation,
+ * smoothing and crop in one pass from the C2R output to ker; without taps it moves values bit for bit; with taps
+ * every output adds its products in ascending m, so a row's result does not depend on the tile or the batch). */
+typedef struct wfk_extract_rows_plan wfk_extract_rows_plan;
+int wfk_extract_rows_plan_create(int64_t n, int32_t batch, int32_t in_rows /* 1 or batch */, const double* taps_host,
+                                 int32_t n_taps /* 0: no smoothing */, int64_t skip, wfk_extract_rows_plan** out);
+int wfk_extract_rows_apply(wfk_extract_rows_plan* plan, const double* sig_in_dev, int64_t in_stride,
+                           const double* sig_out_dev, int64_t out_sig_stride, double* ker_dev, int64_t ker_stride,
+                           void* hip_stream);
+/* "extract_ratio + extract_smooth"; a static string */
+const char* wfk_extract_rows_kernel_name(const wfk_extract_rows_plan* plan);
+int wfk_extract_rows_plan_destroy(wfk_extract_rows_plan* plan);
+
 /* -- readout demodulation (reference utils.py:35-84: traces @ getFTMatrix(...)) ---------------- */
 /* out[s, j] = sum_k x[s, k] * e[k, j] for real traces x (n_shots rows of >= n_points samples, row stride
  * trace_stride elements) and a complex matrix e (n_points x n_freq, complex128 interleaved, point-major: the

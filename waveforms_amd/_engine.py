@@ -126,6 +126,11 @@ def lib():
         l.wfk_shift_rows_kernel_name.argtypes = [VP]
         l.wfk_shift_rows_kernel_name.restype = C.c_char_p
         l.wfk_shift_rows_plan_destroy.argtypes = [VP]
+        l.wfk_extract_rows_plan_create.argtypes = [I64, I32, I32, VP, I32, I64, P(VP)]
+        l.wfk_extract_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, I64, VP]
+        l.wfk_extract_rows_kernel_name.argtypes = [VP]
+        l.wfk_extract_rows_kernel_name.restype = C.c_char_p
+        l.wfk_extract_rows_plan_destroy.argtypes = [VP]
         l.wfk_demod_plan_create.argtypes = [VP, I64, I32, C.c_int, P(VP)]
         l.wfk_demod_apply.argtypes = [VP, VP, I64, I64, VP, I64, VP]
         l.wfk_demod_kernel_name.argtypes = [VP, I64]
@@ -657,6 +662,45 @@ class ShiftRowsPlan(_Handle):
 
     def kernel_name(self) -> str:
         return lib().wfk_shift_rows_kernel_name(self._h).decode()
+
+
+class ExtractRowsPlan(_Handle):
+    """ker[r] = the reference's extractKernel of (sig_in[r], sig_out[r]) for `batch` rows of n doubles
+    (wfk_extract_rows_plan_create): spectral ratio, centred inverse transform, `taps` (None: no smoothing) convolved
+    in 'same' mode, `skip` samples cut at each end; `.k` = max(n - 2 skip, 0) samples per result row.
+    `shared_input`: one sig_in row for all rows.  ValueError before any device work: n < 1, batch < 1, skip < 0,
+    more taps than samples, taps that are not a finite 1-D array."""
+    _destroy = 'wfk_extract_rows_plan_destroy'
+
+    def __init__(self, n: int, batch: int, taps=None, skip: int = 0, shared_input: bool = False):
+        self.n, self.batch, self.skip = int(n), int(batch), int(skip)
+        self.shared_input = bool(shared_input)
+        if self.n < 1 or self.batch < 1:
+            raise ValueError('n >= 1 and batch >= 1')
+        if self.skip < 0:
+            raise ValueError('skip must not be negative (the reference slices ker[skip:len(ker) - skip]; '
+                             'a negative skip is refused here)')
+        if taps is not None:
+            taps = np.ascontiguousarray(taps, dtype=np.float64)
+            if taps.ndim != 1 or not np.all(np.isfinite(taps)):
+                raise ValueError('taps must be a 1-D array of finite values')
+            if len(taps) > self.n:
+                raise ValueError(f'{len(taps)} smoothing taps for rows of {self.n} samples: the reference returns '
+                                 f'{len(taps)} samples there, rows keep their length here, so it is refused')
+            if len(taps) == 0:
+                taps = None
+        self.taps = taps
+        self.k = max(self.n - 2 * self.skip, 0)
+        check(lib().wfk_extract_rows_plan_create(self.n, self.batch, 1 if self.shared_input else self.batch,
+                                                 None if taps is None else taps.ctypes.data,
+                                                 0 if taps is None else len(taps), self.skip, C.byref(self._h)))
+
+    def apply(self, sig_in_ptr, in_stride, sig_out_ptr, out_sig_stride, ker_ptr, ker_stride, stream=0):
+        check(lib().wfk_extract_rows_apply(self._h, sig_in_ptr, in_stride, sig_out_ptr, out_sig_stride, ker_ptr,
+                                           ker_stride, stream))
+
+    def kernel_name(self) -> str:
+        return lib().wfk_extract_rows_kernel_name(self._h).decode()
 
 
 IN_F64, IN_F32, IN_I16 = 0, 1, 4

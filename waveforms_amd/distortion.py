@@ -1081,6 +1081,139 @@ def shift_rows(sig, delays, dt):
         return y.download(sig2.shape, sig2.dtype)
 
 
+def _extract_taps(name, n, sample_rate, bw):
+    """the smoothing taps of extractKernel for rows of n samples, by the reference's own expressions
+    (distortion.py:45-47), or None where it does not smooth (bw is None or bw >= sample_rate / 2).  ValueError: a
+    sample_rate or bw that is not finite, bw <= 0, more taps than samples."""
+    sample_rate = float(sample_rate)
+    if not np.isfinite(sample_rate):
+        raise ValueError(f'{name}: sample_rate is not finite')
+    if bw is None:
+        return None
+    bw = float(bw)
+    if not np.isfinite(bw) or bw <= 0.0:
+        raise ValueError(f'{name}: bw must be finite and positive (or None)')
+    if not bw < 0.5 * sample_rate:
+        return None
+    m = int(2 * sample_rate / bw)
+    if m > n:
+        raise ValueError(f'{name}: bw gives {m} smoothing taps for rows of {n} samples; the reference returns '
+                         f'{m} samples there, rows keep their length here, so it is refused')
+    g = np.exp(-0.5 * np.linspace(-3.0, 3.0, m)**2)
+    return g / g.sum()
+
+
+def _extract_skip(name, skip):
+    skip = int(skip)
+    if skip < 0:
+        raise ValueError(f'{name}: skip must not be negative')
+    return skip
+
+
+class KernelExtractor:
+    """Device-resident `extractKernel` for `batch` rows of `n` float64 samples (build once, apply whenever the lines
+    are measured again): row r of the result is the reference's
+        extractKernel(sig_in[r], sig_out[r], sample_rate, bw, skip)                      (distortion.py:42-48)
+    -- the centred inverse transform of fft(sig_in) / fft(sig_out), smoothed with the reference's +-3 sigma Gaussian
+    of int(2 * sample_rate / bw) points when `bw < sample_rate / 2`, `skip` samples cut at each end -- i.e. the rows
+    of the kernel matrix `FirStage(ker, ...)` takes.  `shared_input`: one `sig_in` (the programmed waveform) for all
+    rows; it is transformed once per apply.  `.k` = max(n - 2 skip, 0) samples per result row, `.taps` the smoothing
+    taps (None: no smoothing; bit for bit the reference's), `.n`, `.batch`.
+    Two departures from the reference, on purpose: a `bw` that gives more taps than a row has samples is refused
+    (np.convolve 'same' returns that many samples there; rows keep their length here), and so is a negative `skip`
+    (ValueError both, before any device work).  A zero bin in the transform of a `sig_out` row makes that row's
+    result non-finite, as in the reference; other rows are not affected.
+
+        ex = KernelExtractor(n, lines, 2e9, bw=0.2e9, skip=(n - 1025) // 2, shared_input=True)
+        ker = ex.apply_torch(programmed, measured)          # (lines, ex.k), on torch's current stream
+        fir = FirStage(ker.cpu().numpy(), n, lines)
+    """
+
+    def __init__(self, n: int, batch: int, sample_rate: float, bw=None, skip: int = 0, shared_input: bool = False):
+        n, batch = int(n), int(batch)
+        if n < 1 or batch < 1:
+            raise ValueError('KernelExtractor: n >= 1 and batch >= 1')
+        skip = _extract_skip('KernelExtractor', skip)
+        taps = _extract_taps('KernelExtractor', n, sample_rate, bw)
+        self.plan = _engine.ExtractRowsPlan(n, batch, taps, skip, shared_input)
+        self.n, self.batch, self.skip, self.k = self.plan.n, self.plan.batch, self.plan.skip, self.plan.k
+        self.taps, self.shared_input = self.plan.taps, self.plan.shared_input
+        self.sample_rate, self.bw = float(sample_rate), bw
+
+    def apply(self, sig_in_ptr, in_stride, sig_out_ptr, out_sig_stride, ker_ptr, ker_stride, stream=0):
+        self.plan.apply(sig_in_ptr, in_stride, sig_out_ptr, out_sig_stride, ker_ptr, ker_stride, stream)
+
+    def kernel_name(self) -> str:
+        return self.plan.kernel_name()
+
+    def apply_torch(self, sig_in, sig_out, out=None):
+        """sig_in, sig_out: (batch, >= n) row-contiguous float64 device tensors (rows may be windows of a wider
+        tensor; they may overlap each other); a shared `sig_in` is 1-D of >= n samples or (1, >= n).  out: None
+        (allocated) or a (batch, >= k) tensor of the same kind whose rows share no memory with an input (ValueError).
+        Asynchronous on torch's current stream; one extractor serves one stream at a time (it owns the transform
+        buffers).  -> out[:, :k]"""
+        import torch
+        f64 = _rows.torch_dtype(np.float64)
+        in_rows = 1 if self.shared_input else self.batch
+        if self.shared_input and sig_in.dim() == 1:
+            sig_in = sig_in[None, :]
+        message = 'expected row-contiguous float64 device tensors: sig_in ({}, >=n), sig_out (batch, >=n)'.format(
+            1 if self.shared_input else 'batch')
+        a0, a_s = _rows.check_rows(sig_in, in_rows, self.n, f64, message)
+        b0, b_s = _rows.check_rows(sig_out, self.batch, self.n, f64, message)
+        if out is None:
+            out = torch.empty((self.batch, self.k), dtype=f64, device=sig_out.device)
+        y0, y_s = _rows.check_rows(out, self.batch, self.k, f64,
+                                   'out must be a (batch, >=k) row-contiguous float64 device tensor')
+        y = (y0, y_s, self.batch, self.k, 8)
+        if not (_rows.rows_disjoint(y, (a0, a_s, in_rows, self.n, 8))
+                and _rows.rows_disjoint(y, (b0, b_s, self.batch, self.n, 8))):
+            raise ValueError('kernel extraction is out of place: out overlaps an input')
+        if self.k:
+            self.apply(a0, a_s, b0, b_s, y0, y_s, torch.cuda.current_stream(sig_out.device).cuda_stream)
+        return out[:, :self.k]
+
+    def close(self):
+        self.plan.close()
+
+
+def extract_kernel_rows(sig_in, sig_out, sample_rate, bw=None, skip=0):
+    """`extractKernel(sig_in[r], sig_out[r], sample_rate, bw, skip)` for every row r of a 2-D `sig_out` (reference
+    distortion.py:42-48 per row), all rows in one apply, NumPy in and out: -> (rows, max(n - 2 skip, 0)) float64.
+    `sig_in`: 2-D of the same shape, or 1-D of n samples (one programmed waveform for all rows).  See
+    `KernelExtractor` for the operation and its two departures from the reference: a `bw` that gives more smoothing
+    taps than a row has samples is refused, and a negative `skip` is refused.  ValueError before any device work:
+    sig_out not 2-D, sig_in neither 1-D nor 2-D or of another shape, skip < 0, more taps than samples, a sample_rate /
+    bw that is not finite, bw <= 0.  NotImplementedError: complex rows.  No rows, no samples or nothing left after
+    the crop: an empty array, without a device."""
+    name = 'extract_kernel_rows'
+    b = np.asarray(sig_out)
+    a = np.asarray(sig_in)
+    if b.ndim != 2:
+        raise ValueError(f'{name}: sig_out must be 2-D (rows, samples)')
+    if a.ndim not in (1, 2):
+        raise ValueError(f'{name}: sig_in must be 2-D like sig_out, or 1-D (one input for all rows)')
+    batch, n = b.shape
+    if (a.ndim == 2 and a.shape != b.shape) or (a.ndim == 1 and a.shape[0] != n):
+        raise ValueError(f'{name}: sig_in has shape {a.shape}, sig_out {b.shape}')
+    if np.iscomplexobj(a) or np.iscomplexobj(b):
+        raise NotImplementedError(f'{name}: complex rows')
+    skip = _extract_skip(name, skip)
+    taps = _extract_taps(name, n, sample_rate, bw)
+    k = max(n - 2 * skip, 0)
+    if n == 0 or batch == 0 or k == 0:
+        return np.empty((batch, k), dtype=np.float64)
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    with _engine.ExtractRowsPlan(n, batch, taps, skip, a.ndim == 1) as plan, _engine.DeviceBuffer(a.nbytes) as xa, \
+            _engine.DeviceBuffer(b.nbytes) as xb, _engine.DeviceBuffer(batch * k * 8) as y:
+        xa.upload(a)
+        xb.upload(b)
+        plan.apply(xa.ptr, n, xb.ptr, n, y.ptr, k)
+        _engine.sync()
+        return y.download((batch, k), np.float64)
+
+
 def zDistortKernel(dt, params):
     """FIR kernel of a Z-line distortion model (filter DESIGN: one small FFT on the host,
     reference: distortion.py:52-60)."""
