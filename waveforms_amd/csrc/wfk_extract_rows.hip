@@ -9,14 +9,12 @@
 // (M = 0) t = s and the last pass only moves values, bit for bit.
 //
 // extract_ratio.  Fin / Fout as Fin conj(Fout) / |Fout|^2, one division per bin, 1/n folded in, written over the
-// spectrum of sig_out.  A sig_in shared by all rows is transformed once and read at `bin` by every row.  Geometry as
-// spec_rows_mul: flat grid, a workgroup never straddles rows, a thread owns kSlots 16-B slots (one bin each) kThreads
-// apart.  A zero bin of sig_out gives inf / NaN and with it a row that is not finite, as in the reference.
+// spectrum of sig_out.  A sig_in shared by all rows is transformed once and read at `bin` by every row.  A row-slot
+// kernel (wfk_rows_dev.h) whose slots are one bin each and start at the row (no lead).  A zero bin of sig_out gives
+// inf / NaN and with it a row that is not finite, as in the reference.
 //
-// extract_smooth.  A workgroup owns kTile consecutive outputs of one row; a lane owns kSlots 16-B slots of them,
-// kThreads slots apart, laid out from the 16-B boundary at or before the first sample of the OUTPUT row (as
-// shift_rows: rows may be windows of a wider buffer), stored whole where they lie inside the row and element by
-// element at its two ends.  The two bodies are chosen by a scalar branch on M.
+// extract_smooth.  A row-slot kernel over the OUTPUT rows: a workgroup owns kTile consecutive outputs of one row.  The
+// two bodies are chosen by a scalar branch on M.
 //   copy body: out[j] = c[(j + skip + n/2) mod n], element loads (the rotation misaligns source and destination).
 //   smoothing body: the taps are walked in blocks of at most kTapBlock.  For a block [m0, m0 + mb) the workgroup
 //   stages s[base .. base + cnt + mb - 1) into LDS, base = (tile's first i) + (M - 1)/2 - m0 - mb + 1: rotation and
@@ -36,13 +34,12 @@
 #include "wfk.h"
 #include "wfk_host.h"
 #include "wfk_rocfft.h"
+#include "wfk_rows_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;                  // threads per workgroup
-constexpr int kSlots = 4;                      // 16-B slots per thread, kThreads slots apart
 constexpr int kTile = kThreads * kSlots * 2;   // outputs of one extract_smooth workgroup
 constexpr int kTapBlock = 1024;                // taps per LDS pass: the halo is at most kTapBlock - 1 samples
 constexpr int kLds = kTile + kTapBlock;        // doubles of LDS (24 KiB): tile + halo, one spare
@@ -51,7 +48,7 @@ constexpr int kLds = kTile + kTapBlock;        // doubles of LDS (24 KiB): tile 
 __global__ void __launch_bounds__(kThreads)
     extract_ratio(double2* __restrict__ spec, const double2* __restrict__ fin, int64_t fin_row_stride, int64_t nf,
                   uint32_t blocks_per_row, double scale) {
-  const uint32_t row = blockIdx.x / blocks_per_row, blk = blockIdx.x - row * blocks_per_row;
+  const auto [row, blk] = row_block(blocks_per_row);
   double2* __restrict__ fo = spec + (int64_t)row * nf;
   const double2* __restrict__ fi = fin + (int64_t)row * fin_row_stride;
 #pragma unroll
@@ -67,8 +64,9 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
-// the two outputs of the slot at output sample j0: whole where the slot lies inside [0, K)
-__device__ __forceinline__ void store_slot(double* __restrict__ y, int64_t K, int64_t j0, double v0, double v1) {
+// store_slot of wfk_rows_dev.h for a pair of doubles, in this kernel's own spelling: under the shared one the compiler
+// lays the two branches out the other way round, and the machine code is kept as it was
+__device__ __forceinline__ void store_pair(double* __restrict__ y, int64_t K, int64_t j0, double v0, double v1) {
   if (j0 >= 0 && j0 + 2 <= K) {
     *reinterpret_cast<double2*>(y + j0) = make_double2(v0, v1);
   } else {
@@ -83,10 +81,10 @@ __global__ void __launch_bounds__(kThreads)
                    const double* __restrict__ taps, int32_t M, int64_t n, int64_t skip, int64_t K,
                    uint32_t blocks_per_row) {
   __shared__ double lds[kLds];
-  const uint32_t row = blockIdx.x / blocks_per_row, blk = blockIdx.x - row * blocks_per_row;
+  const auto [row, blk] = row_block(blocks_per_row);
   const double* __restrict__ x = c + (int64_t)row * n;
   double* __restrict__ y = out + (int64_t)row * out_stride;
-  const int64_t lead = (int64_t)((reinterpret_cast<uintptr_t>(y) / sizeof(double)) & 1);
+  const int64_t lead = row_lead(y);
   const int64_t first = (int64_t)blk * kTile - lead;   // the tile's first output sample (-1: the one before the row)
   if (first >= K) return;
   const int64_t half = n / 2;
@@ -103,7 +101,7 @@ __global__ void __launch_bounds__(kThreads)
         if (src >= n) src -= n;
         v[e] = (j >= 0 && j < K) ? x[src] : 0.0;
       }
-      store_slot(y, K, j0, v[0], v[1]);
+      store_pair(y, K, j0, v[0], v[1]);
     }
     return;
   }
@@ -152,15 +150,8 @@ __global__ void __launch_bounds__(kThreads)
   for (int u = 0; u < kSlots; ++u) {
     const int o0 = (u * kThreads + (int)threadIdx.x) * 2;
     if (o0 >= cnt) break;
-    store_slot(y, K, first + o0, a0[u], a1[u]);
+    store_pair(y, K, first + o0, a0[u], a1[u]);
   }
-}
-
-// rows of `width` bytes, `rows` of them, device to device; one plain copy when both sides are contiguous
-bool copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, hipStream_t s) {
-  if (rows == 1 || (dpitch == width && spitch == width))
-    return hipMemcpyAsync(dst, src, width * rows, hipMemcpyDeviceToDevice, s) == hipSuccess;
-  return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, hipMemcpyDeviceToDevice, s) == hipSuccess;
 }
 
 }  // namespace
@@ -169,14 +160,10 @@ struct wfk_extract_rows_plan {
   int64_t n = 0, nf = 0, skip = 0, K = 0;
   int32_t batch = 0, in_rows = 0, n_taps = 0;
   uint32_t ratio_bpr = 0, smooth_bpr = 0;
-  // (members go in reverse order: the rocFFT plans and the execution info before the work buffer they were given)
   DevBuf<double> taps;
-  DevBuf<char> tmp;        // the staged input of a forward transform (sig_out, then sig_in), then the C2R output
-  DevBuf<char> spec;       // [batch][nf] the transform of sig_out, then the ratio
-  DevBuf<char> spec_in;    // [in_rows][nf] the transform of sig_in
-  DevBuf<char> work;
-  RocfftInfo info;
-  RocfftPlan fwd, fwd_one, inv;   // fwd_one: the batch-1 forward transform of a shared sig_in (batch > 1)
+  // staging rows: sig_out, then sig_in, then the C2R output; spec: the transform of sig_out, then the ratio; spec2:
+  // [in_rows][nf] the transform of sig_in, by a batch-1 forward plan of its own when it is shared (batch > 1)
+  RocfftRows fft;
 };
 
 extern "C" {
@@ -207,45 +194,19 @@ int wfk_extract_rows_plan_create(int64_t n, int32_t batch, int32_t in_rows, cons
     if (!std::isfinite(taps_host[m])) return wfk_fail(WFK_EINVAL, "tap " + std::to_string(m) + " is not finite");
   const int64_t nf = n / 2 + 1;
   const int64_t K = skip < (n + 1) / 2 ? n - 2 * skip : 0;
-  const int64_t ratio_bpr = (nf + (int64_t)kThreads * kSlots - 1) / ((int64_t)kThreads * kSlots);
-  const int64_t smooth_bpr = (K + 1 + kTile - 1) / kTile;   // (+ 1: a row may start inside a slot)
-  if (ratio_bpr * batch > 0x7fffffffLL || smooth_bpr * batch > 0x7fffffffLL)
-    return wfk_fail(WFK_EINVAL, "extract rows plan: batch * n too large for one launch");
+  uint32_t ratio_bpr = 0, smooth_bpr = 0;
+  if (const int rc = wfk_row_blocks("extract rows plan", nf, kThreads * kSlots, 0, batch, &ratio_bpr)) return rc;
+  if (const int rc = wfk_row_blocks("extract rows plan", K, kTile, 1, batch, &smooth_bpr)) return rc;
   if (!wfk_have_device()) return wfk_fail(WFK_EHIP, "no HIP device visible");
   wfk_rocfft_setup_once();
   std::unique_ptr<wfk_extract_rows_plan> p(new wfk_extract_rows_plan());
   p->n = n; p->nf = nf; p->skip = skip; p->K = K;
   p->batch = batch; p->in_rows = in_rows; p->n_taps = n_taps;
-  p->ratio_bpr = (uint32_t)ratio_bpr;
-  p->smooth_bpr = (uint32_t)smooth_bpr;
-  const size_t len[1] = {(size_t)n};
-  const bool shared_one = in_rows == 1 && batch > 1;
-  bool ok = rocfft_plan_create(p->fwd.out(), rocfft_placement_notinplace, rocfft_transform_type_real_forward,
-                               rocfft_precision_double, 1, len, (size_t)batch, nullptr) == rocfft_status_success;
-  if (ok && shared_one)
-    ok = rocfft_plan_create(p->fwd_one.out(), rocfft_placement_notinplace, rocfft_transform_type_real_forward,
-                            rocfft_precision_double, 1, len, 1, nullptr) == rocfft_status_success;
-  ok = ok && rocfft_plan_create(p->inv.out(), rocfft_placement_notinplace, rocfft_transform_type_real_inverse,
-                                rocfft_precision_double, 1, len, (size_t)batch, nullptr) == rocfft_status_success;
-  if (ok) {
-    size_t wbytes = 0, w = 0;
-    for (rocfft_plan q : {p->fwd.get(), p->fwd_one.get(), p->inv.get()}) {
-      if (!q) continue;
-      rocfft_plan_get_work_buffer_size(q, &w);
-      wbytes = w > wbytes ? w : wbytes;
-    }
-    ok = rocfft_execution_info_create(p->info.out()) == rocfft_status_success;
-    if (ok && wbytes)
-      ok = p->work.alloc(wbytes) &&
-           rocfft_execution_info_set_work_buffer(p->info.get(), p->work.get(), wbytes) == rocfft_status_success;
-    ok = ok && p->spec.alloc((size_t)batch * nf * 16);
-    ok = ok && p->spec_in.alloc((size_t)in_rows * nf * 16);
-    ok = ok && p->tmp.alloc((size_t)batch * n * 8);
-    if (ok && n_taps) ok = p->taps.upload(taps_host, (size_t)n_taps * 8);
-  }
-  if (!ok) {
+  p->ratio_bpr = ratio_bpr;
+  p->smooth_bpr = smooth_bpr;
+  if (!(p->fft.create(n, batch, WFK_OUT_F64, in_rows) && (!n_taps || p->taps.upload(taps_host, (size_t)n_taps * 8)))) {
     (void)hipGetLastError();
-    return wfk_fail(WFK_EHIP, "extract rows plan: rocFFT plan / buffer creation failed");
+    return wfk_fft_fail("extract rows plan");
   }
   *out = p.release();
   return WFK_OK;
@@ -268,29 +229,17 @@ int wfk_extract_rows_apply(wfk_extract_rows_plan* p, const double* sig_in_dev, i
       wfk_ranges_overlap(ker_dev, ker_bytes, sig_out_dev, wfk_rows_bytes(p->batch, out_sig_stride, p->n, 8)))
     return wfk_fail(WFK_EINVAL, "extract rows is out of place: the result overlaps an input");
   hipStream_t s = (hipStream_t)hip_stream;
-  const size_t width = (size_t)p->n * 8;
-  if (rocfft_execution_info_set_stream(p->info.get(), s) != rocfft_status_success)
-    return wfk_fail(WFK_EHIP, "rocfft set_stream failed");
+  RocfftRows& f = p->fft;
   // both inputs go through the plan's own contiguous rows: they stay intact, any stride, any overlap between them
-  void* tmp[1] = {p->tmp.get()};
-  void* spec[1] = {p->spec.get()};
-  void* spec_in[1] = {p->spec_in.get()};
-  if (!copy_rows(p->tmp.get(), width, sig_out_dev, (size_t)out_sig_stride * 8, width, (size_t)p->batch, s))
-    return wfk_fail(WFK_EHIP, "copy failed");
-  if (rocfft_execute(p->fwd.get(), tmp, spec, p->info.get()) != rocfft_status_success)
-    return wfk_fail(WFK_EHIP, "rocfft forward failed");
-  if (!copy_rows(p->tmp.get(), width, sig_in_dev, (size_t)in_stride * 8, width, (size_t)p->in_rows, s))
-    return wfk_fail(WFK_EHIP, "copy failed");
-  const rocfft_plan fwd_in = p->fwd_one ? p->fwd_one.get() : p->fwd.get();
-  if (rocfft_execute(fwd_in, tmp, spec_in, p->info.get()) != rocfft_status_success)
-    return wfk_fail(WFK_EHIP, "rocfft forward failed");
+  if (!(f.set_stream(s) && f.stage(sig_out_dev, out_sig_stride, p->batch) && f.forward() &&
+        f.stage(sig_in_dev, in_stride, p->in_rows) && f.forward2()))
+    return wfk_fft_fail("extract rows");
   hipLaunchKernelGGL(extract_ratio, dim3(p->ratio_bpr * (uint32_t)p->batch), dim3(kThreads), 0, s,
-                     (double2*)p->spec.get(), (const double2*)p->spec_in.get(),
-                     p->in_rows == 1 ? (int64_t)0 : p->nf, p->nf, p->ratio_bpr, 1.0 / (double)p->n);
-  if (rocfft_execute(p->inv.get(), spec, tmp, p->info.get()) != rocfft_status_success)
-    return wfk_fail(WFK_EHIP, "rocfft inverse failed");
+                     (double2*)f.spec(), (const double2*)f.spec2(), p->in_rows == 1 ? (int64_t)0 : p->nf, p->nf,
+                     p->ratio_bpr, 1.0 / (double)p->n);
+  if (!f.inverse(f.rows())) return wfk_fft_fail("extract rows");
   hipLaunchKernelGGL(extract_smooth, dim3(p->smooth_bpr * (uint32_t)p->batch), dim3(kThreads), 0, s,
-                     (const double*)p->tmp.get(), ker_dev, ker_stride, (const double*)p->taps.get(), p->n_taps, p->n,
+                     (const double*)f.rows(), ker_dev, ker_stride, (const double*)p->taps.get(), p->n_taps, p->n,
                      p->skip, p->K, p->smooth_bpr);
   if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "extract rows kernel launch failed");
   return WFK_OK;

@@ -83,6 +83,8 @@ void put_cx(std::vector<char>& dst, bool f32, size_t at, const std::complex<long
 
 const char kTooLong[] = "signal too long for one rocFFT FIR plan (blocks > 65535)";
 
+enum { kFwd, kInv, kFwdTail, kInvTail };   // the plans of wfk_fir_plan::fft
+
 }  // namespace
 
 struct wfk_fir_plan {
@@ -94,44 +96,26 @@ struct wfk_fir_plan {
   int32_t tail = 0;  // channels in the last, smaller chunk (0: none)
   int64_t krow = 0;            // per-row kernels (wfk_fir_plan_create_rows): complex elements between the
                                // spectra of consecutive rows; 0: one kernel for every row
-  // (members go in reverse order: the rocFFT plans and the execution info before the work buffer they were given)
   DevBuf<char> tw;             // fused: exp(-2 pi i j / L), j < 256
-  DevBuf<char> kspec, spec, win, work;
-  RocfftInfo info;
-  RocfftPlan fwd, inv, fwd_tail, inv_tail;
+  DevBuf<char> kspec, spec, win;
+  RocfftExec fft;              // the transforms of a chunk and of the smaller last chunk
 };
 
-static int make_plans(wfk_fir_plan* p, int32_t channels, rocfft_plan* fwd, rocfft_plan* inv,
-                      size_t* work_bytes) {
-  const rocfft_precision prec =
-      p->kind == WFK_OUT_F32 ? rocfft_precision_single : rocfft_precision_double;
-  const size_t len[1] = {(size_t)p->L};
-  const size_t nb = (size_t)channels * (size_t)p->nblk;
-  const size_t nf = (size_t)p->L / 2 + 1;
+// the R2C / C2R pair over the windows of `channels` rows, as plans fwd and fwd + 1 of p->fft
+static bool make_plans(wfk_fir_plan* p, int32_t channels, int fwd) {
+  const size_t L = (size_t)p->L, nb = (size_t)channels * (size_t)p->nblk, nf = L / 2 + 1;
   RocfftDesc df, di;
   const size_t one[1] = {1};
-  if (rocfft_plan_description_create(df.out()) != rocfft_status_success) return -1;
-  if (rocfft_plan_description_set_data_layout(df.get(), rocfft_array_type_real,
-                                              rocfft_array_type_hermitian_interleaved, nullptr,
-                                              nullptr, 1, one, (size_t)p->L, 1, one, nf) !=
-      rocfft_status_success)
-    return -1;
-  if (rocfft_plan_create(fwd, rocfft_placement_notinplace, rocfft_transform_type_real_forward, prec,
-                         1, len, nb, df.get()) != rocfft_status_success)
-    return -1;
-  if (rocfft_plan_description_create(di.out()) != rocfft_status_success) return -1;
-  if (rocfft_plan_description_set_data_layout(di.get(), rocfft_array_type_hermitian_interleaved,
-                                              rocfft_array_type_real, nullptr, nullptr, 1, one, nf,
-                                              1, one, (size_t)p->L) != rocfft_status_success)
-    return -1;
-  if (rocfft_plan_create(inv, rocfft_placement_notinplace, rocfft_transform_type_real_inverse, prec,
-                         1, len, nb, di.get()) != rocfft_status_success)
-    return -1;
-  size_t a = 0, b = 0;
-  rocfft_plan_get_work_buffer_size(*fwd, &a);
-  rocfft_plan_get_work_buffer_size(*inv, &b);
-  *work_bytes = std::max(*work_bytes, std::max(a, b));
-  return 0;
+  return rocfft_plan_description_create(df.out()) == rocfft_status_success &&
+         rocfft_plan_description_set_data_layout(df.get(), rocfft_array_type_real,
+                                                 rocfft_array_type_hermitian_interleaved, nullptr, nullptr, 1, one, L,
+                                                 1, one, nf) == rocfft_status_success &&
+         p->fft.make_plan(fwd, true, p->kind, L, nb, df.get()) &&
+         rocfft_plan_description_create(di.out()) == rocfft_status_success &&
+         rocfft_plan_description_set_data_layout(di.get(), rocfft_array_type_hermitian_interleaved,
+                                                 rocfft_array_type_real, nullptr, nullptr, 1, one, nf, 1, one, L) ==
+             rocfft_status_success &&
+         p->fft.make_plan(fwd + 1, false, p->kind, L, nb, di.get());
 }
 
 template <typename T, typename C>
@@ -139,8 +123,7 @@ static int fir_run(wfk_fir_plan* p, const void* in_dev, int64_t in_stride, void*
                    int64_t out_stride, hipStream_t s) {
   const int L = p->L, M = p->M;
   const int64_t nf = L / 2 + 1;
-  if (rocfft_execution_info_set_stream(p->info.get(), s) != rocfft_status_success)
-    return wfk_fail(WFK_EHIP, "rocfft set_stream failed");
+  if (!p->fft.set_stream(s)) return wfk_fft_fail("FIR");
   for (int32_t c0 = 0; c0 < p->batch; c0 += p->chunk) {
     const int32_t nc = std::min(p->chunk, p->batch - c0);
     const bool tail = nc != p->chunk;
@@ -151,17 +134,11 @@ static int fir_run(wfk_fir_plan* p, const void* in_dev, int64_t in_stride, void*
     dim3 gg((L + 255) / 256, (unsigned)p->nblk, (unsigned)nc);
     hipLaunchKernelGGL(fir_gather<T>, gg, dim3(256), 0, s, in, in_stride, win, p->n, L, M, p->lead,
                        p->nblk);
-    void* ib[1] = {win};
-    void* ob[1] = {spec};
-    if (rocfft_execute((tail ? p->fwd_tail : p->fwd).get(), ib, ob, p->info.get()) != rocfft_status_success)
-      return wfk_fail(WFK_EHIP, "rocfft forward execute failed");
+    if (!p->fft.run(tail ? kFwdTail : kFwd, win, spec)) return wfk_fft_fail("FIR");
     const int64_t total = (int64_t)nc * p->nblk * nf;
     hipLaunchKernelGGL(fir_multiply<C>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, spec,
                        reinterpret_cast<const C*>(p->kspec.get()), (int)nf, total);
-    void* ib2[1] = {spec};
-    void* ob2[1] = {win};
-    if (rocfft_execute((tail ? p->inv_tail : p->inv).get(), ib2, ob2, p->info.get()) != rocfft_status_success)
-      return wfk_fail(WFK_EHIP, "rocfft inverse execute failed");
+    if (!p->fft.run(tail ? kInvTail : kInv, spec, win)) return wfk_fft_fail("FIR");
     dim3 gs((M + 255) / 256, (unsigned)p->nblk, (unsigned)nc);
     hipLaunchKernelGGL(fir_scatter<T>, gs, dim3(256), 0, s, win, out, out_stride, p->n, L, M, p->K,
                        p->nblk);
@@ -205,7 +182,7 @@ static int fir_plan_create(const double* ker_host, int32_t K, int64_t n, int32_t
   if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
   if (!ker_host || K < 1 || n < 0 || batch < 1) return wfk_fail(WFK_EINVAL, "bad FIR arguments");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return wfk_fail(WFK_EINVAL, "FIR kind must be F64 or F32");
+  if (const int rc = wfk_check_kind(kind, "FIR ")) return rc;
   if (!wfk_have_device()) return wfk_fail(WFK_EHIP, "no HIP device visible");
   wfk_rocfft_setup_once();
   std::unique_ptr<wfk_fir_plan> p(new wfk_fir_plan());
@@ -235,7 +212,7 @@ static int fir_plan_create(const double* ker_host, int32_t K, int64_t n, int32_t
   // gather / scatter put the block in gridDim.y: refuse before any rocFFT plan or buffer is made
   if (!p->fused && p->nblk > 65535) return wfk_fail(WFK_EINVAL, kTooLong);
   const bool f32 = kind == WFK_OUT_F32;
-  const size_t es = f32 ? 4 : 8;
+  const size_t es = wfk_elem_size(kind);
   const size_t nf = p->fused ? (size_t)L : (size_t)L / 2 + 1;   // fused: full complex spectrum
   if (!p->fused) {
     const double per_ch = (double)p->nblk * ((double)L * es + (double)nf * 2 * es);
@@ -250,17 +227,11 @@ static int fir_plan_create(const double* ker_host, int32_t K, int64_t n, int32_t
     }
     p->chunk = (int32_t)chunk;
     p->tail = batch % p->chunk;
-    size_t work_bytes = 0;
-    if (make_plans(p.get(), p->chunk, p->fwd.out(), p->inv.out(), &work_bytes) ||
-        (p->tail && make_plans(p.get(), p->tail, p->fwd_tail.out(), p->inv_tail.out(), &work_bytes)))
-      return wfk_fail(WFK_EHIP, "rocFFT plan creation failed");
-    bool ok = rocfft_execution_info_create(p->info.out()) == rocfft_status_success;
-    ok = ok && p->win.alloc((size_t)p->chunk * p->nblk * L * es);
-    ok = ok && p->spec.alloc((size_t)p->chunk * p->nblk * nf * 2 * es);
-    if (ok && work_bytes)
-      ok = p->work.alloc(work_bytes) &&
-           rocfft_execution_info_set_work_buffer(p->info.get(), p->work.get(), work_bytes) == rocfft_status_success;
-    if (!ok) return wfk_fail(WFK_ENOMEM, "FIR buffer allocation failed");
+    if (!make_plans(p.get(), p->chunk, kFwd) || (p->tail && !make_plans(p.get(), p->tail, kFwdTail)))
+      return wfk_fft_fail("FIR plan");
+    if (const int rc = p->fft.bind()) return wfk_fft_fail("FIR plan", rc);
+    if (!p->win.alloc((size_t)p->chunk * p->nblk * L * es) || !p->spec.alloc((size_t)p->chunk * p->nblk * nf * 2 * es))
+      return wfk_fft_fail("FIR plan", WFK_ENOMEM);
   }
   const size_t nrow = per_row ? (size_t)batch : 1;
   p->krow = per_row ? (int64_t)((size_t)p->nseg * nf) : 0;
@@ -330,12 +301,12 @@ int wfk_fir_apply(wfk_fir_plan* p, const void* in_dev, int64_t in_stride, void* 
   if (p->n == 0) return WFK_OK;
   // no path works in place: the fused kernel reads halos that other workgroups overwrite, passes 2 to 4 of a long
   // kernel read `in` again, and the pipeline's later chunks gather after the earlier ones have scattered
-  if (const int rc = wfk_check_rows("FIR", p->n, p->kind == WFK_OUT_F32 ? 4 : 8, in_dev, p->batch, in_stride, out_dev,
+  if (const int rc = wfk_check_rows("FIR", p->n, wfk_elem_size(p->kind), in_dev, p->batch, in_stride, out_dev,
                                     p->batch, out_stride, true))
     return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   if (p->fused) {
-    const size_t seg_bytes = (size_t)p->L * 2 * (p->kind == WFK_OUT_F32 ? 4 : 8);
+    const size_t seg_bytes = (size_t)p->L * 2 * wfk_elem_size(p->kind);
     for (int sg = 0; sg < p->nseg; ++sg)
       if (wfk_internal_fir_fused_launch(p->kind, in_dev, in_stride, out_dev, out_stride,
                                         p->kspec.get() + sg * seg_bytes, p->tw.get(), p->n, p->M,

@@ -514,7 +514,7 @@ static int chain_plan_create(const wfk_program* prog, const wfk_grid* grid, cons
   if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
   if (!prog || !grid || !ker_host) return wfk_fail(WFK_EINVAL, "null argument");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return wfk_fail(WFK_EINVAL, "chain kind must be F64 or F32");
+  if (const int rc = wfk_check_kind(kind, "chain ")) return rc;
   std::unique_ptr<wfk_chain_plan> p(new wfk_chain_plan());
   p->kind = kind;
   wfk_internal_keep_mixed_short(true);       // (fir_short samples the short pieces itself: a mixed short plan stays one)
@@ -596,7 +596,7 @@ static int chain_plan_create(const wfk_program* prog, const wfk_grid* grid, cons
         if (hs->mixed) {
           // the general kernel's pieces (few, by construction: a plan dominated by them is not short) travel
           // through rows of a workspace, written sparsely in a launch of their own
-          const size_t es = kind == WFK_OUT_F32 ? 4 : 8;
+          const size_t es = wfk_elem_size(kind);
           if (!p->workspace.alloc((size_t)p->n_channels * (size_t)p->n * es))
             return wfk_fail(WFK_ENOMEM, "chain workspace allocation failed");
           p->hybrid = true;
@@ -635,7 +635,7 @@ static int chain_plan_create(const wfk_program* prog, const wfk_grid* grid, cons
     p->fused = true;
   } else {
     // unfused: the samples go through a workspace owned by the plan (no allocation at launch)
-    const size_t es = kind == WFK_OUT_F32 ? 4 : 8;
+    const size_t es = wfk_elem_size(kind);
     if (!p->workspace.alloc((size_t)p->n_channels * (size_t)p->n * es))
       return wfk_fail(WFK_ENOMEM, "chain workspace allocation failed");
   }
@@ -669,7 +669,7 @@ const char* wfk_chain_kernel_name(const wfk_chain_plan* p) {
 int wfk_chain_launch(wfk_chain_plan* p, void* out_dev, int64_t out_stride, void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0 || p->n_channels == 0) return WFK_OK;
-  if (const int rc = wfk_check_rows("FIR chain", p->n, p->kind == WFK_OUT_F32 ? 4 : 8, out_dev, p->n_channels, out_stride,
+  if (const int rc = wfk_check_rows("FIR chain", p->n, wfk_elem_size(p->kind), out_dev, p->n_channels, out_stride,
                                     out_dev, p->n_channels, out_stride))
     return rc;
   hipStream_t s = (hipStream_t)hip_stream;

@@ -1,6 +1,7 @@
-// wfk_host.h -- what the host side of every stage shares: the error helper, the device probe, the owners of a
-// plan's device memory (DevBuf, MappedWord), the packer of several host tables into one device block (DevTables),
-// next to the prototypes of the functions one stage's file calls in another's (wfk_internal.h).  Host code only.
+// wfk_host.h -- what the host side of every stage shares: the error helper, the element kind and its size, the launch
+// arithmetic of the row-slot kernels, the row rule, the device probe, the owners of a plan's device memory (DevBuf,
+// MappedWord), the packer of several host tables into one device block (DevTables), next to the prototypes of the
+// functions one stage's file calls in another's (wfk_internal.h).  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,27 @@ namespace {
 inline int wfk_fail(int code, const std::string& m) {
   wfk_internal_set_error(m.c_str());
   return code;
+}
+
+// bytes of one real sample of a plan's kind
+inline size_t wfk_elem_size(int kind) { return kind == WFK_OUT_F32 ? 4 : 8; }
+
+// the kinds a stage takes; `who` ("", "IIR ", ...) goes in front of the text
+inline int wfk_check_kind(int kind, const char* who = "") {
+  if (kind == WFK_OUT_F64 || kind == WFK_OUT_F32) return WFK_OK;
+  return wfk_fail(WFK_EINVAL, std::string(who) + "kind must be F64 or F32");
+}
+
+// Workgroups per row of a row-slot kernel (wfk_rows_dev.h): ceil((n + lead) / per_block) for rows of n >= 0 elements,
+// a workgroup covering per_block of them.  `lead`: the elements a row may start into its first slot, V - 1 where the
+// slots are laid out from a 16-byte boundary, 0 where they start at the row.  The grid is flat, batch >= 1 rows times
+// these blocks in x: more than 2^31 - 1 is refused.  (Written so that no n overflows.)
+inline int wfk_row_blocks(const char* stage, int64_t n, int64_t per_block, int64_t lead, int64_t batch,
+                          uint32_t* blocks_per_row) {
+  const int64_t bpr = n ? (n - 1) / per_block + ((n - 1) % per_block + lead) / per_block + 1 : 0;
+  if (bpr > 0x7fffffffLL / batch) return wfk_fail(WFK_EINVAL, std::string(stage) + ": batch * n too large for one launch");
+  *blocks_per_row = (uint32_t)bpr;
+  return WFK_OK;
 }
 
 // The row rule of every apply (DESIGN.md "The row rule").  A batch of rows of n samples, `stride` samples apart,

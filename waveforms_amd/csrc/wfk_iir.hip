@@ -1083,7 +1083,7 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
   if (n_sections < 1 || n_sections > 4096 || !orders || !b || !a || n < 0 || batch < 1 ||
       batch > 65535)
     return wfk_fail(WFK_EINVAL, "bad IIR arguments");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return wfk_fail(WFK_EINVAL, "IIR kind must be F64 or F32");
+  if (const int rc = wfk_check_kind(kind, "IIR ")) return rc;
   std::unique_ptr<wfk_iir_plan> p(new wfk_iir_plan());
   IirCoef& c = p->c;
   std::memset(&c, 0, sizeof c);
@@ -1306,7 +1306,7 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0) return WFK_OK;
   if (src) { in_dev = out_dev; in_stride = out_stride; }     // (never read)
-  if (const int rc = wfk_check_rows("IIR", p->n, p->kind == WFK_OUT_F32 ? 4 : 8, in_dev, p->batch, in_stride, out_dev,
+  if (const int rc = wfk_check_rows("IIR", p->n, wfk_elem_size(p->kind), in_dev, p->batch, in_stride, out_dev,
                                     p->batch, out_stride))
     return rc;
   hipStream_t s = (hipStream_t)hip_stream;
@@ -1511,7 +1511,7 @@ int wfk_chain_iir_plan_create(const wfk_program* prog, const wfk_grid* grid, int
   if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
   if (!prog || !grid) return wfk_fail(WFK_EINVAL, "null argument");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return wfk_fail(WFK_EINVAL, "chain kind must be F64 or F32");
+  if (const int rc = wfk_check_kind(kind, "chain ")) return rc;
   if (ker_host && K < 1) return wfk_fail(WFK_EINVAL, "empty FIR kernel");
   try {
     std::unique_ptr<wfk_chain_iir_plan> p(new wfk_chain_iir_plan());
@@ -1525,7 +1525,7 @@ int wfk_chain_iir_plan_create(const wfk_program* prog, const wfk_grid* grid, int
                        : wfk_fir_plan_create(ker_host, K, grid->n, std::max(1, prog->n_channels), kind, &p->fir);
     if (rc) return rc;
     if (p->n == 0 || p->n_channels == 0) { *out = p.release(); return WFK_OK; }
-    const size_t es = kind == WFK_OUT_F32 ? 4 : 8;
+    const size_t es = wfk_elem_size(kind);
     if (p->fir && !p->workspace.alloc((size_t)p->n_channels * (size_t)p->n * es))
       return wfk_fail(WFK_ENOMEM, "chain workspace allocation failed");
     // ---- can the sampler run inside the first IIR pass? ----------------------------------------------
@@ -1654,7 +1654,7 @@ int wfk_chain_iir_launch(wfk_chain_iir_plan* p, void* out_dev, int64_t out_strid
                          double* zf_dev, double initial, void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0 || p->n_channels == 0) return WFK_OK;
-  if (const int rc = wfk_check_rows("IIR chain", p->n, p->kind == WFK_OUT_F32 ? 4 : 8, out_dev, p->n_channels, out_stride,
+  if (const int rc = wfk_check_rows("IIR chain", p->n, wfk_elem_size(p->kind), out_dev, p->n_channels, out_stride,
                                     out_dev, p->n_channels, out_stride))
     return rc;
   void* mid = p->fir ? p->workspace.get() : out_dev;

@@ -247,7 +247,7 @@ int wfk_iir_rows_plan_create(int32_t n_sections, const int32_t* orders, const do
   *out = nullptr;
   if (n_sections < 1 || !orders || !b_rows || !a_rows || n < 0 || batch < 1)
     return wfk_fail(WFK_EINVAL, "bad per-row IIR arguments");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return wfk_fail(WFK_EINVAL, "IIR kind must be F64 or F32");
+  if (const int rc = wfk_check_kind(kind, "IIR ")) return rc;
   bool equal = true;
   int64_t Dtot = 0;
   for (int s = 0; s < n_sections; ++s) {

@@ -9,14 +9,10 @@
 // Departures from the reference, on purpose: rows keep n samples for n < 3 (np.convolve 'same' returns 3 there), and
 // the reference's zero tap on x[j + 1] is not multiplied (an inf at j + 1 does not turn sample j into NaN).
 //
-// Execution form.  A workgroup never straddles rows (blockIdx.x = row * blocks_per_row + block in row), so the row's
-// table entry (p, 1 - delta, delta, has_frac) sits at a wave-uniform address and arrives by scalar loads; the
-// delta = 0 path is a wave-uniform branch into a loop that only copies.  A lane owns the outputs of kSlots 16-B slots,
-// kThreads slots apart, and stores each with one 16-B store.  Slots are laid out from the 16-B boundary at or before
-// the first sample of the OUTPUT row (lead = that sample's offset into its slot, taken from the address: rows may be
-// windows of a wider buffer), so full slots are aligned whatever the row's start; the first and the last slot of a
-// row may be partial and are stored element by element.  The source index i - p is misaligned against the
-// destination whenever p is not a multiple of the slot: the loads are element loads.  A lane needs one sample more
+// Execution form.  A row-slot kernel (wfk_rows_dev.h) over the OUTPUT rows: the row's table entry (p, 1 - delta,
+// delta, has_frac) arrives by scalar loads, and the delta = 0 path is a wave-uniform branch into a loop that only
+// copies.  The source index i - p is misaligned against the destination whenever p is not a multiple of the slot: the
+// loads are element loads.  A lane needs one sample more
 // than it stores, x[j0 - 1]: it loads it (the neighbouring lane has just pulled the same line into the cache; a
 // cross-lane move costs more instructions than the load).  A workgroup whose outputs are all zero fill
 // (the head or the tail of a shifted row, every block of a row with |p| >= n) stores zeros and issues no loads.
@@ -30,6 +26,7 @@
 
 #include "wfk.h"
 #include "wfk_host.h"
+#include "wfk_rows_dev.h"
 
 #pragma clang fp contract(off)   // two rounded products and one rounded sum, as the host formula
 
@@ -40,9 +37,6 @@ namespace {
 #define WFK_SHIFT_NEIGHBOUR_SHFL 0
 #endif
 
-constexpr int kThreads = 256;   // threads per workgroup
-constexpr int kSlots = 4;       // 16-B stores per thread, kThreads slots apart
-
 // one row as the device reads it
 struct ShiftRow {
   int64_t p;        // whole samples (either sign)
@@ -50,10 +44,6 @@ struct ShiftRow {
   int32_t frac;     // delta > 0
   int32_t pad;
 };
-
-template <typename T> struct Slot;
-template <> struct Slot<double> { typedef double2 type; };
-template <> struct Slot<float> { typedef float4 type; };
 
 // the V outputs of the slot that starts at output sample i0 (source sample j0 = i0 - p); ZERO: all zero fill
 template <typename T, bool FRAC, bool ZERO>
@@ -91,19 +81,7 @@ __device__ __forceinline__ void shift_slot(const T* __restrict__ x, T* __restric
       v[e] = (j >= 0 && j < n) ? x[j] : T(0);
     }
   }
-  if (i0 >= 0 && i0 + V <= n) {
-    typename Slot<T>::type q;
-    if constexpr (V == 2) {
-      q.x = v[0]; q.y = v[1];
-    } else {
-      q.x = v[0]; q.y = v[1]; q.z = v[2]; q.w = v[3];
-    }
-    *reinterpret_cast<typename Slot<T>::type*>(y + i0) = q;
-  } else {
-#pragma unroll
-    for (int e = 0; e < V; ++e)
-      if (i0 + e >= 0 && i0 + e < n) y[i0 + e] = v[e];
-  }
+  store_slot(y, n, i0, v);
 }
 
 template <typename T, bool FRAC, bool ZERO>
@@ -124,13 +102,13 @@ __global__ void __launch_bounds__(kThreads)
     shift_rows(const T* __restrict__ in, int64_t in_stride, T* __restrict__ out, int64_t out_stride,
                const ShiftRow* __restrict__ tab, int64_t n, uint32_t blocks_per_row) {
   constexpr int V = 16 / sizeof(T);
-  const uint32_t row = blockIdx.x / blocks_per_row, blk = blockIdx.x - row * blocks_per_row;
+  const auto [row, blk] = row_block(blocks_per_row);
   const int64_t p = tab[row].p;
   const double w0 = tab[row].w0, w1 = tab[row].w1;
   const bool frac = tab[row].frac != 0;
   const T* __restrict__ x = in + (int64_t)row * in_stride;
   T* __restrict__ y = out + (int64_t)row * out_stride;
-  const int64_t lead = (int64_t)((reinterpret_cast<uintptr_t>(y) / sizeof(T)) & (V - 1));
+  const int64_t lead = row_lead(y);
   const int64_t first = (int64_t)blk * (kSlots * kThreads * V) - lead;   // the block's first output sample
   if (first >= n) return;
   // sources of the block's outputs: [first - p, first - p + block span); none inside [0, n): zero fill, no loads
@@ -170,11 +148,10 @@ int wfk_shift_rows_plan_create(int64_t n, int32_t batch, int kind, const int64_t
   if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
   if (n < 0 || batch < 1 || !points_host || !delta_host) return wfk_fail(WFK_EINVAL, "bad shift rows plan arguments");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return wfk_fail(WFK_EINVAL, "kind must be F64 or F32");
-  const int V = kind == WFK_OUT_F32 ? 4 : 2;
-  const int64_t per_block = (int64_t)V * kThreads * kSlots;
-  const int64_t bpr = n ? (n + (V - 1) + per_block - 1) / per_block : 0;   // (V - 1: a row may start inside a slot)
-  if (bpr * batch > 0x7fffffffLL) return wfk_fail(WFK_EINVAL, "shift rows plan: batch * n too large for one launch");
+  if (const int rc = wfk_check_kind(kind)) return rc;
+  const int V = 16 / (int)wfk_elem_size(kind);
+  uint32_t bpr = 0;
+  if (const int rc = wfk_row_blocks("shift rows plan", n, V * kThreads * kSlots, V - 1, batch, &bpr)) return rc;
   std::vector<ShiftRow> rows((size_t)batch);
   for (int32_t r = 0; r < batch; ++r) {
     const double d = delta_host[r];
@@ -185,7 +162,7 @@ int wfk_shift_rows_plan_create(int64_t n, int32_t batch, int kind, const int64_t
   if (!wfk_have_device()) return wfk_fail(WFK_EHIP, "no HIP device visible");
   std::unique_ptr<wfk_shift_rows_plan> p(new wfk_shift_rows_plan());
   p->n = n; p->batch = batch; p->kind = kind;
-  p->blocks_per_row = (uint32_t)bpr;
+  p->blocks_per_row = bpr;
   DevTables tab;
   p->rows_off = tab.add(rows);
   if (!(p->tables.alloc(tab.total()) && tab.upload(p->tables.get()))) {
@@ -202,7 +179,7 @@ int wfk_shift_rows_apply(wfk_shift_rows_plan* p, const void* in_dev, int64_t in_
                          int64_t out_stride, void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0) return WFK_OK;   // nothing to move (the pointers of empty rows may be null)
-  const size_t es = p->kind == WFK_OUT_F32 ? 4 : 8;
+  const size_t es = wfk_elem_size(p->kind);
   if (((uintptr_t)in_dev | (uintptr_t)out_dev) & (es - 1)) return wfk_fail(WFK_EINVAL, "rows are not aligned to their element");
   if (const int rc = wfk_check_rows("shift rows", p->n, es, in_dev, p->batch, in_stride, out_dev, p->batch, out_stride, true))
     return rc;

@@ -15,9 +15,8 @@
 // below 2^53: exact in a double.  (The file is compiled with contraction off: a contracted k * hi - rint(p) would
 // count the product's rounding error twice.)
 //
-// Table access.  A workgroup never straddles rows (blockIdx.x = row * blocks_per_row + block in row), so the row's
-// term count and terms sit at wave-uniform addresses: the compiler fetches them with scalar loads, once per wave, and
-// the branch on a term's kind is a scalar branch.
+// Table access.  spec_rows_mul is a row-slot kernel (wfk_rows_dev.h): the row's term count and terms arrive by scalar
+// loads, once per wave, and the branch on a term's kind is a scalar branch.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -28,13 +27,12 @@
 #include "wfk.h"
 #include "wfk_host.h"
 #include "wfk_rocfft.h"
+#include "wfk_rows_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kThreads = 256;   // threads per workgroup
-constexpr int kSlots = 4;       // 16-B accesses per thread, kThreads apart
 constexpr int kMaxTerms = WFK_SPEC_ROWS_MAX_TERMS;
 
 // one term as the device reads it: c = tau fs / n as (hi, lo); g = 1 - A (REFLECT), 1 / (1 - A) (CORRECT)
@@ -92,16 +90,14 @@ __device__ __forceinline__ void cmul(R& x, R& y, const double2 h) {
   y = (R)(a * h.y + b * h.x);
 }
 
-// spec: [batch][nf] complex (C = double2 or float2), multiplied in place.  A thread owns kSlots 16-B slots of its
-// row.  With float2 a slot is two bins, and a row that starts at an odd element (nf odd, odd row) starts 8 B past
-// a 16-B boundary: its slots are laid out from the boundary before it (lead = 1), the bin before the row and the
-// bins past its end are left alone.
+// spec: [batch][nf] complex (C = double2 or float2), multiplied in place.  With float2 a slot is two bins, and a row
+// that starts at an odd element (nf odd, odd row) has lead = 1; the slot is loaded as it is stored, whole or one bin.
 template <typename C>
 __global__ void __launch_bounds__(kThreads)
     spec_rows_mul(C* __restrict__ spec, const SpecTerm* __restrict__ terms, const int32_t* __restrict__ counts,
                   int64_t nf, uint32_t blocks_per_row, double scale) {
   constexpr int V = 16 / sizeof(C);   // bins per slot
-  const uint32_t row = blockIdx.x / blocks_per_row, blk = blockIdx.x - row * blocks_per_row;
+  const auto [row, blk] = row_block(blocks_per_row);
   const int T = counts[row];
   const SpecTerm* __restrict__ tt = terms + (size_t)row * kMaxTerms;
   const int64_t base = (int64_t)row * nf;
@@ -140,13 +136,6 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
-// rows of `width` bytes, `rows` of them, device to device; one plain copy when both sides are contiguous
-bool copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, hipStream_t s) {
-  if (rows == 1 || (dpitch == width && spitch == width))
-    return hipMemcpyAsync(dst, src, width * rows, hipMemcpyDeviceToDevice, s) == hipSuccess;
-  return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, rows, hipMemcpyDeviceToDevice, s) == hipSuccess;
-}
-
 }  // namespace
 
 struct wfk_spectral_rows_plan {
@@ -154,12 +143,8 @@ struct wfk_spectral_rows_plan {
   int32_t batch = 0, kind = 0;
   uint32_t blocks_per_row = 0;
   size_t terms_off = 0, counts_off = 0;
-  // (members go in reverse order: the rocFFT plans and the execution info before the work buffer they were given)
   DevBuf<char> tables;    // SpecTerm [batch][kMaxTerms], int32 counts [batch]
-  DevBuf<char> tmp;       // the staged input (rocFFT may overwrite the input of a real transform); the C2R output when out_stride != n
-  DevBuf<char> spec, work;
-  RocfftInfo info;
-  RocfftPlan fwd, inv;
+  RocfftRows fft;         // its staging rows take the C2R output too when out_stride != n
 };
 
 extern "C" {
@@ -181,13 +166,12 @@ int wfk_spectral_rows_plan_create(int64_t n, int32_t batch, int kind, double sam
   if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
   if (n < 1 || batch < 1 || !n_terms_per_row_host) return wfk_fail(WFK_EINVAL, "bad spectral rows plan arguments");
-  if (kind != WFK_OUT_F64 && kind != WFK_OUT_F32) return wfk_fail(WFK_EINVAL, "kind must be F64 or F32");
+  if (const int rc = wfk_check_kind(kind)) return rc;
   if (!std::isfinite(sample_rate) || sample_rate <= 0) return wfk_fail(WFK_EINVAL, "sample_rate must be positive");
   const int64_t nf = n / 2 + 1;
-  const int V = kind == WFK_OUT_F32 ? 2 : 1;
-  const int64_t per_block = (int64_t)V * kThreads * kSlots;
-  const int64_t bpr = (nf + (V - 1) + per_block - 1) / per_block;   // (V - 1: a row may start one bin into a slot)
-  if (bpr * batch > 0x7fffffffLL) return wfk_fail(WFK_EINVAL, "spectral rows plan: batch * n too large for one launch");
+  const int V = 8 / (int)wfk_elem_size(kind);   // bins per slot
+  uint32_t bpr = 0;
+  if (const int rc = wfk_row_blocks("spectral rows plan", nf, V * kThreads * kSlots, V - 1, batch, &bpr)) return rc;
   std::vector<SpecTerm> terms((size_t)batch * kMaxTerms, SpecTerm{0, 0, 0, 0, 0, 0});
   std::vector<int32_t> counts(n_terms_per_row_host, n_terms_per_row_host + batch);
   const wfk_spec_term* src = terms_host;
@@ -214,33 +198,13 @@ int wfk_spectral_rows_plan_create(int64_t n, int32_t batch, int kind, double sam
   wfk_rocfft_setup_once();
   std::unique_ptr<wfk_spectral_rows_plan> p(new wfk_spectral_rows_plan());
   p->n = n; p->nf = nf; p->batch = batch; p->kind = kind;
-  p->blocks_per_row = (uint32_t)bpr;
+  p->blocks_per_row = bpr;
   DevTables tab;
   p->terms_off = tab.add(terms);
   p->counts_off = tab.add(counts);
-  const rocfft_precision prec = kind == WFK_OUT_F32 ? rocfft_precision_single : rocfft_precision_double;
-  const size_t es = kind == WFK_OUT_F32 ? 4 : 8;
-  const size_t len[1] = {(size_t)n};
-  bool ok = rocfft_plan_create(p->fwd.out(), rocfft_placement_notinplace, rocfft_transform_type_real_forward,
-                               prec, 1, len, (size_t)batch, nullptr) == rocfft_status_success;
-  ok = ok && rocfft_plan_create(p->inv.out(), rocfft_placement_notinplace, rocfft_transform_type_real_inverse,
-                                prec, 1, len, (size_t)batch, nullptr) == rocfft_status_success;
-  size_t wa = 0, wb = 0;
-  if (ok) {
-    rocfft_plan_get_work_buffer_size(p->fwd.get(), &wa);
-    rocfft_plan_get_work_buffer_size(p->inv.get(), &wb);
-    const size_t wbytes = wa > wb ? wa : wb;
-    ok = rocfft_execution_info_create(p->info.out()) == rocfft_status_success;
-    if (ok && wbytes)
-      ok = p->work.alloc(wbytes) &&
-           rocfft_execution_info_set_work_buffer(p->info.get(), p->work.get(), wbytes) == rocfft_status_success;
-    ok = ok && p->spec.alloc((size_t)batch * nf * 2 * es);
-    ok = ok && p->tmp.alloc((size_t)batch * n * es);
-    ok = ok && p->tables.alloc(tab.total()) && tab.upload(p->tables.get());
-  }
-  if (!ok) {
+  if (!(p->fft.create(n, batch, kind) && p->tables.alloc(tab.total()) && tab.upload(p->tables.get()))) {
     (void)hipGetLastError();
-    return wfk_fail(WFK_EHIP, "rocFFT plan / buffer creation failed");
+    return wfk_fft_fail("spectral rows plan");
   }
   *out = p.release();
   return WFK_OK;
@@ -251,36 +215,25 @@ int wfk_spectral_rows_plan_create(int64_t n, int32_t batch, int kind, double sam
 int wfk_spectral_rows_apply(wfk_spectral_rows_plan* p, const void* in_dev, int64_t in_stride, void* out_dev,
                             int64_t out_stride, void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
-  const size_t es = p->kind == WFK_OUT_F32 ? 4 : 8;
-  if (const int rc = wfk_check_rows("spectral rows", p->n, es, in_dev, p->batch, in_stride, out_dev, p->batch, out_stride))
+  if (const int rc = wfk_check_rows("spectral rows", p->n, wfk_elem_size(p->kind), in_dev, p->batch, in_stride, out_dev,
+                                    p->batch, out_stride))
     return rc;
   hipStream_t s = (hipStream_t)hip_stream;
-  const size_t width = (size_t)p->n * es, rows = (size_t)p->batch;
-  if (rocfft_execution_info_set_stream(p->info.get(), s) != rocfft_status_success)
-    return wfk_fail(WFK_EHIP, "rocfft set_stream failed");
+  RocfftRows& f = p->fft;
   // the transforms work on contiguous rows the plan owns: the caller's input stays intact (or is `out`), any stride
-  if (!copy_rows(p->tmp.get(), width, in_dev, (size_t)in_stride * es, width, rows, s))
-    return wfk_fail(WFK_EHIP, "copy failed");
-  void* ib[1] = {p->tmp.get()};
-  void* ob[1] = {p->spec.get()};
-  if (rocfft_execute(p->fwd.get(), ib, ob, p->info.get()) != rocfft_status_success)
-    return wfk_fail(WFK_EHIP, "rocfft forward failed");
+  if (!(f.set_stream(s) && f.stage(in_dev, in_stride, p->batch) && f.forward())) return wfk_fft_fail("spectral rows");
   const dim3 grid(p->blocks_per_row * (uint32_t)p->batch);
   const SpecTerm* terms = DevTables::at<const SpecTerm>(p->tables.get(), p->terms_off);
   const int32_t* counts = DevTables::at<const int32_t>(p->tables.get(), p->counts_off);
   if (p->kind == WFK_OUT_F32)
-    hipLaunchKernelGGL(spec_rows_mul<float2>, grid, dim3(kThreads), 0, s, (float2*)p->spec.get(), terms, counts,
-                       p->nf, p->blocks_per_row, 1.0 / (double)p->n);
+    hipLaunchKernelGGL(spec_rows_mul<float2>, grid, dim3(kThreads), 0, s, (float2*)f.spec(), terms, counts, p->nf,
+                       p->blocks_per_row, 1.0 / (double)p->n);
   else
-    hipLaunchKernelGGL(spec_rows_mul<double2>, grid, dim3(kThreads), 0, s, (double2*)p->spec.get(), terms, counts,
-                       p->nf, p->blocks_per_row, 1.0 / (double)p->n);
-  const bool direct = rows == 1 || out_stride == p->n;
-  void* ib2[1] = {p->spec.get()};
-  void* ob2[1] = {direct ? out_dev : (void*)p->tmp.get()};
-  if (rocfft_execute(p->inv.get(), ib2, ob2, p->info.get()) != rocfft_status_success)
-    return wfk_fail(WFK_EHIP, "rocfft inverse failed");
-  if (!direct && !copy_rows(out_dev, (size_t)out_stride * es, p->tmp.get(), width, width, rows, s))
-    return wfk_fail(WFK_EHIP, "copy failed");
+    hipLaunchKernelGGL(spec_rows_mul<double2>, grid, dim3(kThreads), 0, s, (double2*)f.spec(), terms, counts, p->nf,
+                       p->blocks_per_row, 1.0 / (double)p->n);
+  const bool direct = p->batch == 1 || out_stride == p->n;
+  if (!(f.inverse(direct ? out_dev : (void*)f.rows()) && (direct || f.unstage(out_dev, out_stride))))
+    return wfk_fft_fail("spectral rows");
   if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "spectral rows kernel launch failed");
   return WFK_OK;
 }
