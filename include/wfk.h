@@ -315,7 +315,7 @@ int wfk_iir_rows_plan_destroy(wfk_iir_rows_plan* plan);
  * wfk_fir_plan_create (ker_per_row != 0: kers_host[channel * K + k]) -- predistort(wav(t), filters, ker)
  * (waveforms/distortion.py:298-337).  Everything stays on the device.  When the program is fully fused (carrier-envelope
  * ops only, real amplitudes, no clip) and the cascade's first pass is in the single-pass form (state dimension <= 4),
- * the wave that owns a 2048-sample chunk of the scan EVALUATES its input instead of loading it (iir_sampled): the
+ * the wave that owns a chunk of the scan (8192 or 16384 samples) EVALUATES its input instead of loading it (iir_sampled): the
  * unfiltered samples never touch HBM and the pass moves the 8 (4) B/sample of its output only.  Otherwise
  * sampler -> (in place) IIR.  The FIR stage reads the filtered rows from a workspace the plan owns.
  * wfk_chain_iir_launch() allocates nothing and does not synchronise; status / timeout semantics as wfk_iir_status

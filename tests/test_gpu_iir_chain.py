@@ -60,6 +60,8 @@ def test_fused_chain_matches_oracle_and_scipy(shape):
     si = SampledIir(chans, grid, secs)
     assert si.fused, si.why_not
     assert si.plan.kernel_name().startswith('iir_sampled<double,'), si.plan.kernel_name()
+    if shape == 'two_biquads':      # butter(4, 0.03): the sweep form, and the name says which instantiation was launched
+        assert si.plan.kernel_name() == 'iir_sampled<double,2,2,false>'
     x = _samples(chans, grid)
     want = np.stack([_cascade(secs, row)[0] for row in x])
     got, zf = si.to_host(return_zf=True)

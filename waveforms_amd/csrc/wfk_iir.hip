@@ -28,6 +28,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "wfk.h"
@@ -345,80 +346,38 @@ __device__ __forceinline__ void matvec_add_plain(double (&v)[IIR_MAXD], const do
   }
 }
 
-template <typename T, int NSEC, int ORD, bool PLAIN>
-__global__ void __launch_bounds__(64, OP_WAVES) iir_onepass(const IirCoef c, const T* __restrict__ in, int64_t in_stride,
-                                                  T* __restrict__ out, int64_t out_stride,
-                                                  unsigned* __restrict__ status, double* __restrict__ aggbuf,
-                                                  double* __restrict__ prefbuf, unsigned* __restrict__ ticket,
-                                                  const double* __restrict__ pw1, const double* __restrict__ lanep1,
-                                                  const double* __restrict__ lanepU, const double* __restrict__ zi,
-                                                  double* __restrict__ zf, int64_t n, int64_t nchunks, int rows,
-                                                  unsigned epoch, double pre_sub, double post_add, int persist,
-                                                  unsigned* __restrict__ fault, int spin_limit) {
-  constexpr int DD = NSEC * ORD;       // state dimension (<= 4)
-  __shared__ T tile[64][OP_LB + 1];
-  const int lane = threadIdx.x;
-  // one ticket counter per row (64 B apart): a single counter for all rows serialises 3e5 atomics on
-  // one address -- measured 5.2 ms for the whole kernel against 3.1 ms of the three-launch form
-  const int row = (int)(blockIdx.x % (unsigned)rows);
-  // persist != 0: the grid holds a bounded number of waves per row and each walks the ticket counter
-  // until the row is used up (few long rows: otherwise hundreds of chunks of one row are in flight
-  // and every look-back reads all of them); persist == 0: one chunk per workgroup
-  for (;;) {
+// ---- the chained scan's protocol, written once for iir_onepass and iir_sampled: ticket, flags, look-back, fault ----
+
+// the row's next chunk (wave-uniform)
+__device__ __forceinline__ int64_t op_take_chunk(unsigned* ticket, int row, int lane) {
   unsigned t = 0;
   if (lane == 0) t = atomicAdd(ticket + 16 * row, 1u);
   t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
-  const int64_t chunk = t;
-  if (chunk >= nchunks) return;
-  const T* x = in + (int64_t)row * in_stride + chunk * OP_CHUNK;
-  T* y = out + (int64_t)row * out_stride + chunk * OP_CHUNK;
-  const int64_t left = n - chunk * OP_CHUNK;                 // samples of this row from the chunk's start
-  const int cnt = (int)(left - (int64_t)lane * OP_LB < 0 ? 0 : (left - (int64_t)lane * OP_LB > OP_LB ? OP_LB : left - (int64_t)lane * OP_LB));
-  const bool whole = left >= OP_CHUNK;                       // wave-uniform
+  return t;
+}
 
-  // ---- load: sample j = i*64 + lane of the chunk belongs to block j / OP_LB, position j % OP_LB
-  // (a whole chunk loads unconditionally: with the bounds test inside the loop every load sits in
-  //  its own branch and is waited for before the next one is issued -- the whole kernel then runs
-  //  at a fraction of the copy rate, the stream probe of round 2, HISTORY)
-  if (whole) {
-    T v[OP_LB];
+// lane 0 publishes a chunk's DD-vector under `flag`: the values are acknowledged (vmcnt 0) before the flag store is issued
+template <int DD>
+__device__ __forceinline__ void op_publish(double* buf, unsigned* status, int64_t slot,
+                                           unsigned flag, const double* v) {
 #pragma unroll
-    for (int i = 0; i < OP_LB; ++i) v[i] = x[i * 64 + lane];
-#pragma unroll
-    for (int i = 0; i < OP_LB; ++i) {
-      const int j = i * 64 + lane;
-      tile[j / OP_LB][j % OP_LB] = v[i];
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < OP_LB; ++i) {
-      const int64_t j = (int64_t)i * 64 + lane;
-      tile[(int)(j / OP_LB)][(int)(j % OP_LB)] = j < left ? x[j] : (T)0;
-    }
-  }
-  __syncthreads();
-  double xr[OP_LB];
-#pragma unroll
-  for (int i = 0; i < OP_LB; ++i) xr[i] = (double)tile[lane][i] - pre_sub;
-  __syncthreads();
+  for (int i = 0; i < DD; ++i) op_store(buf + slot * DD + i, v[i]);
+  __builtin_amdgcn_s_waitcnt(0);                             // the state is in memory before the flag is
+  __hip_atomic_store(status + slot, flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 
-  // ---- sweep 1: zero state -> local final state; scan over the 64 blocks
-  double z[IIR_MAXD];
-#pragma unroll
-  for (int i = 0; i < IIR_MAXD; ++i) z[i] = 0.0;
-  if (whole) {
-#pragma unroll
-    for (int i = 0; i < OP_LB; ++i) (void)iir_step_t<NSEC, ORD>(c, xr[i], z);
-  } else {
-#pragma unroll
-    for (int i = 0; i < OP_LB; ++i)
-      if (i < cnt) (void)iir_step_t<NSEC, ORD>(c, xr[i], z);
-  }
-  // (a block past the end of the row leaves its state alone: T1^0; the scan below still multiplies
-  //  by T1 per block, which only matters AFTER the last sample -- nothing there is used)
-  if (PLAIN) wave_scan_plain<DD>(z, pw1, lane);
-  else wave_scan<DD>(z, pw1, DD, lane);                      // z = v_l (inclusive)
-  double vprev[DD], agg[DD];
+// State at the chunk's start.  z: the inclusive in-wave scan v_l of the 64 lane states from a zero state at the chunk's
+// start.  Publishes the chunk's aggregate v_63 (flag 1), looks back over the row's preceding chunks (chunk 0: reads zi),
+// raises the fault word if that timed out, publishes the prefix agg + U S_in (flag 2).  -> vprev = v_(l-1) (lane 0: zero),
+// sin_ = S_in; returns `poisoned` (wave-uniform): the look-back ran out of polls, the chunk's outputs must be NaN.
+template <int DD>
+__device__ __forceinline__ bool op_chunk_start(const double (&z)[IIR_MAXD], int lane, int row, int64_t chunk,
+                                               int64_t nchunks, unsigned epoch, unsigned* status,
+                                               double* aggbuf, double* prefbuf,
+                                               const double* lanepU, const double* zi,
+                                               unsigned* fault, int spin_limit, double (&vprev)[DD],
+                                               double (&sin_)[IIR_MAXD]) {
+  double agg[DD];
 #pragma unroll
   for (int i = 0; i < DD; ++i) {
     const double up = __shfl_up(z[i], 1);
@@ -427,15 +386,9 @@ __global__ void __launch_bounds__(64, OP_WAVES) iir_onepass(const IirCoef c, con
   }
   const int64_t slot = ((int64_t)row * nchunks + chunk);
   const unsigned F_AGG = epoch * 4u + 1u, F_PRE = epoch * 4u + 2u;
-  if (chunk > 0 && lane == 0) {
-#pragma unroll
-    for (int i = 0; i < DD; ++i) op_store(aggbuf + slot * DD + i, agg[i]);
-    __builtin_amdgcn_s_waitcnt(0);                           // the state is in memory before the flag is
-    __hip_atomic_store(status + slot, F_AGG, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (chunk > 0 && lane == 0) op_publish<DD>(aggbuf, status, slot, F_AGG, agg);
 
   // ---- state at the chunk's start
-  double sin_[IIR_MAXD];
 #pragma unroll
   for (int i = 0; i < IIR_MAXD; ++i) sin_[i] = 0.0;
   bool poisoned = false;
@@ -529,25 +482,102 @@ __global__ void __launch_bounds__(64, OP_WAVES) iir_onepass(const IirCoef c, con
 #pragma unroll
     for (int i = 0; i < IIR_MAXD; ++i) so[i] = i < DD ? agg[i < DD ? i : 0] : 0.0;
     dd_matvec_add<DD>(so, so, lanepU, sin_, DD);                 // U^1 (plain double where PLAIN allows it: 9.82 -> 9.65 ms at 256 x 1e7, inside the noise; not kept)
-    if (chunk + 1 < nchunks) {
-#pragma unroll
-      for (int i = 0; i < DD; ++i) op_store(prefbuf + slot * DD + i, so[i]);
-      __builtin_amdgcn_s_waitcnt(0);
-      __hip_atomic_store(status + slot, F_PRE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (chunk + 1 < nchunks) op_publish<DD>(prefbuf, status, slot, F_PRE, so);
   }
+  return poisoned;
+}
 
-  // ---- sweep 2 from the true block states: v_{l-1} + T1^l * S_in
+// lane start state of the second sweep: v_(l-1) + B^l S_in (lanep: B^(l+1), B the lane run's transition)
+template <int DD, bool PLAIN>
+__device__ __forceinline__ void op_lane_start(double (&z)[IIR_MAXD], const double (&vprev)[DD],
+                                              const double* lanep, const double (&sin_)[IIR_MAXD], int lane) {
 #pragma unroll
   for (int i = 0; i < IIR_MAXD; ++i) z[i] = i < DD ? vprev[i < DD ? i : 0] : 0.0;
   if (lane == 0) {
 #pragma unroll
     for (int i = 0; i < DD; ++i) z[i] = sin_[i];
   } else if (PLAIN) {
-    matvec_add_plain<DD>(z, lanep1 + (int64_t)(lane - 1) * DD * DD * 2, sin_);
+    matvec_add_plain<DD>(z, lanep + (int64_t)(lane - 1) * DD * DD * 2, sin_);
   } else {
-    dd_matvec_add<DD>(z, z, lanep1 + (int64_t)(lane - 1) * DD * DD * 2, sin_, DD);
+    dd_matvec_add<DD>(z, z, lanep + (int64_t)(lane - 1) * DD * DD * 2, sin_, DD);
   }
+}
+
+template <typename T, int NSEC, int ORD, bool PLAIN>
+__global__ void __launch_bounds__(64, OP_WAVES) iir_onepass(const IirCoef c, const T* __restrict__ in, int64_t in_stride,
+                                                  T* __restrict__ out, int64_t out_stride,
+                                                  unsigned* __restrict__ status, double* __restrict__ aggbuf,
+                                                  double* __restrict__ prefbuf, unsigned* __restrict__ ticket,
+                                                  const double* __restrict__ pw1, const double* __restrict__ lanep1,
+                                                  const double* __restrict__ lanepU, const double* __restrict__ zi,
+                                                  double* __restrict__ zf, int64_t n, int64_t nchunks, int rows,
+                                                  unsigned epoch, double pre_sub, double post_add, int persist,
+                                                  unsigned* __restrict__ fault, int spin_limit) {
+  constexpr int DD = NSEC * ORD;       // state dimension (<= 4)
+  __shared__ T tile[64][OP_LB + 1];
+  const int lane = threadIdx.x;
+  // one ticket counter per row (64 B apart): a single counter for all rows serialises 3e5 atomics on
+  // one address -- measured 5.2 ms for the whole kernel against 3.1 ms of the three-launch form
+  const int row = (int)(blockIdx.x % (unsigned)rows);
+  // persist != 0: the grid holds a bounded number of waves per row and each walks the ticket counter
+  // until the row is used up (few long rows: otherwise hundreds of chunks of one row are in flight
+  // and every look-back reads all of them); persist == 0: one chunk per workgroup
+  for (;;) {
+  const int64_t chunk = op_take_chunk(ticket, row, lane);
+  if (chunk >= nchunks) return;
+  const T* x = in + (int64_t)row * in_stride + chunk * OP_CHUNK;
+  T* y = out + (int64_t)row * out_stride + chunk * OP_CHUNK;
+  const int64_t left = n - chunk * OP_CHUNK;                 // samples of this row from the chunk's start
+  const int cnt = (int)(left - (int64_t)lane * OP_LB < 0 ? 0 : (left - (int64_t)lane * OP_LB > OP_LB ? OP_LB : left - (int64_t)lane * OP_LB));
+  const bool whole = left >= OP_CHUNK;                       // wave-uniform
+
+  // ---- load: sample j = i*64 + lane of the chunk belongs to block j / OP_LB, position j % OP_LB
+  // (a whole chunk loads unconditionally: with the bounds test inside the loop every load sits in
+  //  its own branch and is waited for before the next one is issued -- the whole kernel then runs
+  //  at a fraction of the copy rate, the stream probe of round 2, HISTORY)
+  if (whole) {
+    T v[OP_LB];
+#pragma unroll
+    for (int i = 0; i < OP_LB; ++i) v[i] = x[i * 64 + lane];
+#pragma unroll
+    for (int i = 0; i < OP_LB; ++i) {
+      const int j = i * 64 + lane;
+      tile[j / OP_LB][j % OP_LB] = v[i];
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < OP_LB; ++i) {
+      const int64_t j = (int64_t)i * 64 + lane;
+      tile[(int)(j / OP_LB)][(int)(j % OP_LB)] = j < left ? x[j] : (T)0;
+    }
+  }
+  __syncthreads();
+  double xr[OP_LB];
+#pragma unroll
+  for (int i = 0; i < OP_LB; ++i) xr[i] = (double)tile[lane][i] - pre_sub;
+  __syncthreads();
+
+  // ---- sweep 1: zero state -> local final state; scan over the 64 blocks
+  double z[IIR_MAXD];
+#pragma unroll
+  for (int i = 0; i < IIR_MAXD; ++i) z[i] = 0.0;
+  if (whole) {
+#pragma unroll
+    for (int i = 0; i < OP_LB; ++i) (void)iir_step_t<NSEC, ORD>(c, xr[i], z);
+  } else {
+#pragma unroll
+    for (int i = 0; i < OP_LB; ++i)
+      if (i < cnt) (void)iir_step_t<NSEC, ORD>(c, xr[i], z);
+  }
+  // (a block past the end of the row leaves its state alone: T1^0; the scan below still multiplies
+  //  by T1 per block, which only matters AFTER the last sample -- nothing there is used)
+  if (PLAIN) wave_scan_plain<DD>(z, pw1, lane);
+  else wave_scan<DD>(z, pw1, DD, lane);                      // z = v_l (inclusive)
+  // ---- state at the chunk's start (aggregate, look-back, prefix), then sweep 2 from the true block states v_{l-1} + T1^l * S_in
+  double vprev[DD], sin_[IIR_MAXD];
+  const bool poisoned = op_chunk_start<DD>(z, lane, row, chunk, nchunks, epoch, status, aggbuf, prefbuf, lanepU, zi, fault,
+                                           spin_limit, vprev, sin_);
+  op_lane_start<DD, PLAIN>(z, vprev, lanep1, sin_, lane);
   const double bad = poisoned ? __builtin_nan("") : 0.0;
   if (whole) {
 #pragma unroll
@@ -767,10 +797,7 @@ __global__ void __launch_bounds__(64, OPS_WAVES) iir_sampled(const IirCoef c, co
   const double xoff = C.offset - pre_sub;                      // sample + channel offset - initial: what the filter sees
   if (lane <= OP_LB) reinterpret_cast<double2*>(s_par + OPS_PAR)[lane] = make_double2(1.0, 0.0);   // phasor table of ops without a carrier
   for (;;) {
-  unsigned t = 0;
-  if (lane == 0) t = atomicAdd(ticket + 16 * row, 1u);
-  t = (unsigned)__builtin_amdgcn_readfirstlane((int)t);
-  const int64_t chunk = t;
+  const int64_t chunk = op_take_chunk(ticket, row, lane);
   if (chunk >= nchunks) return;
   const int64_t base = chunk * (64 * RUN), chunk_end = base + (64 * RUN);
   const int jrun = lane * RUN;                             // first sample of this lane's run, relative to the chunk
@@ -848,126 +875,12 @@ __global__ void __launch_bounds__(64, OPS_WAVES) iir_sampled(const IirCoef c, co
   //  AFTER the last sample -- nothing there is used)
   if (PLAIN) wave_scan_plain<DD>(z, pwL, lane);
   else wave_scan<DD>(z, pwL, DD, lane);                        // z = v_l (inclusive)
-  double vprev[DD], agg[DD];
-#pragma unroll
-  for (int i = 0; i < DD; ++i) {
-    const double up = __shfl_up(z[i], 1);
-    vprev[i] = lane == 0 ? 0.0 : up;
-    agg[i] = __shfl(z[i], 63);
-  }
-  const int64_t slot = ((int64_t)row * nchunks + chunk);
-  const unsigned F_AGG = epoch * 4u + 1u, F_PRE = epoch * 4u + 2u;
-  if (chunk > 0 && lane == 0) {
-#pragma unroll
-    for (int i = 0; i < DD; ++i) op_store(aggbuf + slot * DD + i, agg[i]);
-    __builtin_amdgcn_s_waitcnt(0);                             // the state is in memory before the flag is
-    __hip_atomic_store(status + slot, F_AGG, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-
-  // ---- state at the chunk's start: decoupled look-back, window by window (see iir_onepass)
-  double sin_[IIR_MAXD];
-#pragma unroll
-  for (int i = 0; i < IIR_MAXD; ++i) sin_[i] = 0.0;
-  bool poisoned = false;
-  if (chunk == 0) {
-#pragma unroll
-    for (int i = 0; i < DD; ++i) sin_[i] = zi ? zi[(int64_t)row * DD + i] : 0.0;
-  } else {
-    double hop[IIR_MAXD];
-#pragma unroll
-    for (int i = 0; i < IIR_MAXD; ++i) hop[i] = 0.0;
-    int spins = 0;
-    for (int w = 0;; ++w) {
-      const int64_t pc = chunk - 1 - 64 * (int64_t)w - lane;
-      const unsigned* f = status + (int64_t)row * nchunks + (pc >= 0 ? pc : 0);
-      unsigned st = 0;
-      int kstop = -1;
-      bool whole_window = false;
-      for (; spins < spin_limit; ++spins) {
-        if (pc >= 0 && !(st == F_PRE)) st = __hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool pre = pc >= 0 && st == F_PRE;
-        const bool ag = pc >= 0 && (st == F_AGG || st == F_PRE);
-        const unsigned long long has_pre = __ballot(pre), has_agg = __ballot(ag);
-        if (has_pre != 0ull) {
-          const int k = __ffsll((long long)has_pre) - 1;       // nearest chunk with a prefix
-          const unsigned long long need = k == 0 ? 0ull : (~0ull >> (64 - k));   // lanes 0 .. k-1
-          if ((has_agg & need) == need) { kstop = k; break; }
-        } else if (has_agg == ~0ull && w < OP_WINDOWS - 1) {
-          whole_window = true;
-          kstop = 64;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-      if (kstop < 0) { poisoned = true; kstop = 0; }
-      double contrib[IIR_MAXD];
-#pragma unroll
-      for (int i = 0; i < IIR_MAXD; ++i) contrib[i] = 0.0;
-      if (lane <= kstop && pc >= 0) {
-        const double* src = (lane == kstop ? prefbuf : aggbuf) + ((int64_t)row * nchunks + pc) * DD;
-        double v[IIR_MAXD];
-#pragma unroll
-        for (int i = 0; i < IIR_MAXD; ++i) v[i] = i < DD ? op_load(src + i) : 0.0;
-        if (lane == 0) {
-#pragma unroll
-          for (int i = 0; i < DD; ++i) contrib[i] = v[i];     // U^0
-        } else {
-          dd_matvec_add<DD>(contrib, contrib, lanepU + (int64_t)(lane - 1) * DD * DD * 2, v, DD);   // U^lane
-        }
-      }
-      double wsum[IIR_MAXD];
-#pragma unroll
-      for (int i = 0; i < IIR_MAXD; ++i) wsum[i] = 0.0;
-#pragma unroll
-      for (int i = 0; i < DD; ++i) {
-        double sum = contrib[i];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) sum += __shfl_xor(sum, o);
-        wsum[i] = sum;
-      }
-      for (int q = 0; q < w; ++q) {                            // this window lies 64 w chunks back: U^(64 w)
-        double nx[IIR_MAXD];
-#pragma unroll
-        for (int i = 0; i < IIR_MAXD; ++i) nx[i] = 0.0;
-        dd_matvec_add<DD>(nx, nx, lanepU + (int64_t)63 * DD * DD * 2, wsum, DD);
-#pragma unroll
-        for (int i = 0; i < IIR_MAXD; ++i) wsum[i] = nx[i];
-      }
-#pragma unroll
-      for (int i = 0; i < DD; ++i) hop[i] += wsum[i];
-      if (!whole_window) break;
-    }
-#pragma unroll
-    for (int i = 0; i < DD; ++i) sin_[i] = hop[i];
-  }
-  poisoned = __any(poisoned);
-  if (poisoned && lane == 0) __hip_atomic_fetch_or(fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-
-  // ---- publish the inclusive prefix: agg + U * S_in
-  if (lane == 0) {
-    double so[IIR_MAXD];
-#pragma unroll
-    for (int i = 0; i < IIR_MAXD; ++i) so[i] = i < DD ? agg[i < DD ? i : 0] : 0.0;
-    dd_matvec_add<DD>(so, so, lanepU, sin_, DD);
-    if (chunk + 1 < nchunks) {
-#pragma unroll
-      for (int i = 0; i < DD; ++i) op_store(prefbuf + slot * DD + i, so[i]);
-      __builtin_amdgcn_s_waitcnt(0);
-      __hip_atomic_store(status + slot, F_PRE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-
-  // ---- pass 2: the run again from its true state v_(l-1) + TL^l S_in: evaluate, sweep, store
-#pragma unroll
-  for (int i = 0; i < IIR_MAXD; ++i) z[i] = i < DD ? vprev[i < DD ? i : 0] : 0.0;
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < DD; ++i) z[i] = sin_[i];
-  } else if (PLAIN) {
-    matvec_add_plain<DD>(z, lanepL + (int64_t)(lane - 1) * DD * DD * 2, sin_);
-  } else {
-    dd_matvec_add<DD>(z, z, lanepL + (int64_t)(lane - 1) * DD * DD * 2, sin_, DD);
-  }
+  // ---- state at the chunk's start (aggregate, look-back, prefix), then pass 2: the run again from its true state
+  // v_(l-1) + TL^l S_in: evaluate, sweep, store
+  double vprev[DD], sin_[IIR_MAXD];
+  const bool poisoned = op_chunk_start<DD>(z, lane, row, chunk, nchunks, epoch, status, aggbuf, prefbuf, lanepU, zi, fault,
+                                           spin_limit, vprev, sin_);
+  op_lane_start<DD, PLAIN>(z, vprev, lanepL, sin_, lane);
   const double bad = poisoned ? __builtin_nan("") : 0.0;
 #pragma unroll 1
   for (int r = 0; r < (RUN / OP_LB); ++r) {
@@ -1025,6 +938,18 @@ __global__ void __launch_bounds__(256) iir_scale(const T* __restrict__ in, int64
     out[row * out_stride + j] = (T)(g * ((double)in[row * in_stride + j] - pre) + post);
 }
 
+// a table set on the device (IirScanTables, wfk_iir_common.h): what one of the two single-pass kernels is launched with
+struct OpTables {
+  DevBuf<double> pw, lanep, lanepU, wdot;
+  int run = 0;
+  bool plain = false;                // the PLAIN argument of the kernel's template
+  bool upload(const IirScanTables& h) {
+    run = h.run;
+    plain = h.plain;
+    return pw.upload(h.pw) && lanep.upload(h.lanep) && lanepU.upload(h.lanepU) && (h.wdot.empty() || wdot.upload(h.wdot));
+  }
+};
+
 }  // namespace
 
 struct wfk_iir_plan {
@@ -1047,27 +972,29 @@ struct wfk_iir_plan {
   DevBuf<double> zf_tmp;
   double gain = 1.0;             // D == 0: y = gain * (x - pre) + post
   // single-pass form (biquad cascades with <= 4 states): chunk flags / aggregates / prefixes, ticket,
-  // and the tables of the 32-step block transition T1 and of U = T1^64
+  // and one table set per kernel (T1: the transition over OP_LB samples)
   bool onepass = false;
-  bool op_plain = false;         // in-wave scan in plain double (entries of T1^1..T1^64 of order 1)
   int64_t op_chunks = 0;
   unsigned epoch = 0;
   DevBuf<unsigned> op_status;
   DevBuf<unsigned> op_ticket;
   DevBuf<double> op_agg;
   DevBuf<double> op_pref;
-  DevBuf<double> op_pw1;
-  DevBuf<double> op_lanep1;
-  DevBuf<double> op_lanepU;
-  // iir_sampled: a lane owns a run of op_run samples: TL = T1^(op_run / OP_LB), UL = TL^64
-  DevBuf<double> op_pwL;             // TL^(2^k)
-  DevBuf<double> op_lanepL;          // TL^(l+1)
-  DevBuf<double> op_lanepUL;         // UL^(l+1)
-  DevBuf<double> op_wdot;            // [op_run][4]: end state of a run from zero state per unit sample at position k (dot-product form)
-  int op_run = 0;                    // samples per lane run of iir_sampled: OPS_RUN (dot-product form) | OPS_RUN_SWEEP
-  bool op_plainL = false;
+  OpTables op1;                      // iir_onepass: lane blocks of OP_LB samples, B = T1
+  OpTables opL;                      // iir_sampled: lane runs of OPS_RUN (dot-product form) | OPS_RUN_SWEEP samples
   MappedWord op_fault;               // host memory, mapped: raised by a chunk whose look-back timed out
 };
+
+// A look-back of `p` or of one of its parts timed out: clear the fault words, and serve the plan and every part of it in
+// the three-launch form from here on (no chained waits: neither this part nor another can time out again)
+static void iir_leave_onepass(wfk_iir_plan* p) {
+  auto leave = [](wfk_iir_plan* q) {
+    if (q->op_fault.host()) *q->op_fault.host() = 0;
+    q->onepass = false;
+  };
+  leave(p);
+  for (auto& q : p->parts) leave(q.get());
+}
 
 extern "C" {
 
@@ -1212,50 +1139,24 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
     const bool want = on ? on[0] != '0' : !band;
     if (biq && n >= 4 * OP_CHUNK && want) {
       const std::vector<quad> T1 = transition(OP_LB);
-      std::vector<double> pw1, lanep1, pwU, lanepU;
-      const std::vector<quad> U1 = tables(T1, pw1, lanep1);    // U1 = T1^64: one chunk
-      tables(U1, pwU, lanepU);                                  // U1^(l+1), l < 64: the look-back window
-      std::vector<double> pwL, lanepL, pwUL, lanepUL;           // the same for the long runs of iir_sampled
-      // (runs of OPS_RUN samples; where their transition powers rule out the dot-product form, of OPS_RUN_SWEEP)
-      p->op_run = OPS_RUN;
-      for (int attempt = 0; attempt < 2; ++attempt) {
-        pwL.clear(); lanepL.clear(); pwUL.clear(); lanepUL.clear();
-        std::vector<quad> TL = T1, nxt;
-        for (int k = 1; k < p->op_run / OP_LB; ++k) { iir_qmatmul(TL, T1, nxt, D); TL.swap(nxt); }
-        const std::vector<quad> UL = tables(TL, pwL, lanepL);
-        tables(UL, pwUL, lanepUL);
-        double tm = 0.0;
-        for (size_t e = 0; e < lanepL.size(); e += 2) tm = std::max(tm, std::fabs(lanepL[e]));
-        const char* dde = getenv("WFK_IIR_DD");
-        p->op_plainL = attempt == 0 && tm < 16.0 && !(dde && dde[0] == '1');
-        if (p->op_plainL || p->op_run == OPS_RUN_SWEEP) break;
-        p->op_run = OPS_RUN_SWEEP;
-      }
-      std::vector<double> wdot((size_t)p->op_run * 4, 0.0);
-      for (int k = 0; k < p->op_run && p->op_plainL; ++k) {
-        quad z[IIR_MAXD];
-        for (int r = 0; r < IIR_MAXD; ++r) z[r] = 0;
-        for (int t = k; t < p->op_run; ++t)
-          iir_quad_step(n_sections, orders, bn.data(), an.data(), t == k ? (quad)1 : (quad)0, z);
-        for (int r = 0; r < D && r < 4; ++r) wdot[(size_t)k * 4 + r] = (double)z[r];
-      }
-      double tmax = 0.0;                                        // largest entry of T1^1 .. T1^64 (hi words)
-      for (size_t e = 0; e < lanep1.size(); e += 2) tmax = std::max(tmax, std::fabs(lanep1[e]));
-      const char* ddenv = getenv("WFK_IIR_DD");
-      p->op_plain = tmax < 16.0 && !(ddenv && ddenv[0] == '1');
+      auto table_set = [&](int run, bool may_plain, bool dot) {
+        return iir_scan_tables(n_sections, orders, bn.data(), an.data(), D, T1, OP_LB, run, may_plain, dot);
+      };
+      const IirScanTables t1 = table_set(OP_LB, true, false);
+      // iir_sampled: runs of OPS_RUN samples; where their transition powers rule out the dot-product form, of OPS_RUN_SWEEP
+      IirScanTables tL = table_set(OPS_RUN, true, true);
+      if (!tL.plain) tL = table_set(OPS_RUN_SWEEP, false, true);
       p->op_chunks = (n + OP_CHUNK - 1) / OP_CHUNK;
       const size_t slots = (size_t)batch * (size_t)p->op_chunks;
       if (!p->op_status.alloc(slots * 4) || hipMemset(p->op_status.get(), 0, slots * 4) != hipSuccess ||
           !p->op_ticket.alloc((size_t)batch * 64) || !p->op_agg.alloc(slots * D * 8) ||
-          !p->op_pref.alloc(slots * D * 8) || !p->op_pw1.upload(pw1) || !p->op_lanep1.upload(lanep1) ||
-          !p->op_lanepU.upload(lanepU) || !p->op_pwL.upload(pwL) || !p->op_lanepL.upload(lanepL) ||
-          !p->op_lanepUL.upload(lanepUL) || !p->op_wdot.upload(wdot) || !p->op_fault.alloc())
+          !p->op_pref.alloc(slots * D * 8) || !p->op1.upload(t1) || !p->opL.upload(tL) || !p->op_fault.alloc())
         return wfk_fail(WFK_ENOMEM, "IIR single-pass buffer allocation failed");
       // ONE section of order 3 / 4 whose transition powers grow past 1e3 (clustered poles: butter(4, 0.022) as a single
       // (b, a), 3.2e3): the block start states this form re-injects every 32 samples as doubles cost it a digit against
       // the three-launch form (iirchain_soak seed 12713, against a long-double recursion: 1.1e-10 vs 2.4e-11 of peak;
       // SciPy 1.7e-11) -- such sections take that form unless WFK_IIR_ONEPASS=1 insists
-      p->onepass = (on && on[0] == '1') || !(orders[0] >= 3 && tmax > 1e3);
+      p->onepass = (on && on[0] == '1') || !(orders[0] >= 3 && t1.tmax > 1e3);
     }
   }
   *out = p.release();
@@ -1294,6 +1195,57 @@ static void iir_launch(wfk_iir_plan* p, const void* in, int64_t is, void* out, i
 #undef IIR_CASE
   iir_launch_t<T, 0, 0>(p, in, is, out, os, zi, zf, initial, post, s);
 }
+
+// one launch of the single-pass form
+struct OpCall {
+  const IirSampArgs* src;      // iir_sampled evaluates its input | null: iir_onepass reads `in`
+  const void* in;
+  int64_t in_stride;
+  void* out;
+  int64_t out_stride;
+  const double* zi;
+  double* zf;
+  double initial, post;
+  unsigned total;              // workgroups
+  int64_t nchunks;
+  unsigned epoch;
+  int persist, spin_limit;
+  hipStream_t s;
+};
+
+// either kernel, with the PLAIN of that kernel's own table set
+template <typename T, int NSEC, int ORD>
+static void op_launch(wfk_iir_plan* p, const OpCall& k) {
+  const OpTables& t = k.src ? p->opL : p->op1;
+  auto go = [&](auto plain) {
+    constexpr bool PLAIN = decltype(plain)::value;
+    if (k.src)
+      hipLaunchKernelGGL((iir_sampled<T, NSEC, ORD, PLAIN>), dim3(k.total), dim3(64), 0, k.s, p->c, *k.src, (T*)k.out,
+                         k.out_stride, p->op_status.get(), p->op_agg.get(), p->op_pref.get(), p->op_ticket.get(),
+                         t.pw.get(), t.lanep.get(), t.lanepU.get(), t.wdot.get(), k.zi, k.zf, p->n, k.nchunks,
+                         (int)p->batch, k.epoch, k.initial, k.post, k.persist, p->op_fault.dev(), k.spin_limit);
+    else
+      hipLaunchKernelGGL((iir_onepass<T, NSEC, ORD, PLAIN>), dim3(k.total), dim3(64), 0, k.s, p->c, (const T*)k.in,
+                         k.in_stride, (T*)k.out, k.out_stride, p->op_status.get(), p->op_agg.get(), p->op_pref.get(),
+                         p->op_ticket.get(), t.pw.get(), t.lanep.get(), t.lanepU.get(), k.zi, k.zf, p->n, k.nchunks,
+                         (int)p->batch, k.epoch, k.initial, k.post, k.persist, p->op_fault.dev(), k.spin_limit);
+  };
+  if (t.plain) go(std::true_type{}); else go(std::false_type{});
+}
+
+#ifndef OPS_ONLY_22
+template <typename T>
+static void op_launch_shape(wfk_iir_plan* p, const OpCall& k) {
+  const int ns = p->c.nsec, od = p->c.ord[0];
+  if (od == 2) return ns == 1 ? op_launch<T, 1, 2>(p, k) : op_launch<T, 2, 2>(p, k);
+  if (od == 3) return op_launch<T, 1, 3>(p, k);
+  if (od == 4) return op_launch<T, 1, 4>(p, k);
+  if (ns == 1) return op_launch<T, 1, 1>(p, k);
+  if (ns == 2) return op_launch<T, 2, 1>(p, k);
+  if (ns == 3) return op_launch<T, 3, 1>(p, k);
+  return op_launch<T, 4, 1>(p, k);
+}
+#endif
 
 extern "C" {
 
@@ -1337,8 +1289,7 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
       int rc = iir_apply_impl(q, first ? in_dev : out_dev, first ? in_stride : out_stride, out_dev,
                               out_stride, zi_dev ? p->zi_tmp.get() : nullptr, zf_dev ? p->zf_tmp.get() : nullptr,
                               first ? initial : 0.0, last ? post : 0.0, hip_stream, first ? src : nullptr);
-      if (rc == WFK_ETIMEOUT)   // a part reported an earlier stall: no part of this plan may wait on a chain again
-        for (auto& r : p->parts) r->onepass = false;
+      if (rc == WFK_ETIMEOUT) iir_leave_onepass(p);   // a part reported an earlier stall
       if (rc) return rc;
       if (zf_dev && Di > 0 &&
           hipMemcpy2DAsync(zf_dev + off, D * 8, p->zf_tmp.get(), Di * 8, Di * 8, (size_t)p->batch,
@@ -1348,10 +1299,8 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
     return WFK_OK;
   }
   if (p->onepass && *p->op_fault.host() != 0) {
-    // an earlier launch of this plan timed out in a look-back (its outputs hold NaN): say so now, and
-    // serve this plan in the three-launch form from here on (no chained waits, cannot time out)
-    *p->op_fault.host() = 0;
-    p->onepass = false;
+    // an earlier launch of this plan timed out in a look-back (its outputs hold NaN): say so now
+    iir_leave_onepass(p);
     return wfk_fail(WFK_ETIMEOUT, "IIR single pass: a look-back timed out in an EARLIER launch of this plan (a stalled or "
                                   "preempted predecessor chunk); its outputs hold NaN. The plan now runs in the three-launch form: launch again");
   }
@@ -1366,7 +1315,7 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
     // Few long rows: with one chunk per workgroup 2304 / rows chunks of a row are in flight, and a
     // look-back reads every one of them.  Below OP_DEPTH_ROWS rows the grid is op_depth persistent waves
     // per row instead (WFK_IIR_OP_DEPTH: experiments).
-    const int64_t ops_chunk = 64 * (int64_t)p->op_run;
+    const int64_t ops_chunk = 64 * (int64_t)p->opL.run;
     const int64_t nchunks = src ? (p->n + ops_chunk - 1) / ops_chunk : p->op_chunks;   // (iir_sampled: long chunks)
     unsigned total = (unsigned)(nchunks * p->batch);
     int persist = 0;
@@ -1386,45 +1335,13 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
         persist = 1;
       }
     }
-#define OP_LAUNCH_K(KERNEL, PL, FIRST, TABS, NCH, TT, NS, OR)                                                     \
-    if (PL)                                                                                                   \
-    hipLaunchKernelGGL((KERNEL<TT, NS, OR, true>), dim3(total), dim3(64), 0, s, p->c, FIRST,                   \
-                       (TT*)out_dev, out_stride, p->op_status.get(), p->op_agg.get(), p->op_pref.get(), p->op_ticket.get(),             \
-                       TABS, zi_dev, zf_dev, p->n, NCH, (int)p->batch, epoch,                                     \
-                       initial, post, persist, p->op_fault.dev(), spin_limit);                                            \
-    else                                                                                                       \
-    hipLaunchKernelGGL((KERNEL<TT, NS, OR, false>), dim3(total), dim3(64), 0, s, p->c, FIRST,                  \
-                       (TT*)out_dev, out_stride, p->op_status.get(), p->op_agg.get(), p->op_pref.get(), p->op_ticket.get(),             \
-                       TABS, zi_dev, zf_dev, p->n, NCH, (int)p->batch, epoch,                                     \
-                       initial, post, persist, p->op_fault.dev(), spin_limit)
-#define OP_COMMA ,
-#define OP_LAUNCH(TT, NS, OR)                                                                                     \
-    if (src) { OP_LAUNCH_K(iir_sampled, p->op_plainL, *src, p->op_pwL.get() OP_COMMA p->op_lanepL.get() OP_COMMA p->op_lanepUL.get() OP_COMMA p->op_wdot.get(), nchunks, TT, NS, OR); } \
-    else { OP_LAUNCH_K(iir_onepass, p->op_plain, (const TT*)in_dev OP_COMMA in_stride, p->op_pw1.get() OP_COMMA p->op_lanep1.get() OP_COMMA p->op_lanepU.get(), p->op_chunks, TT, NS, OR); }
+    const OpCall call{src, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial, post, total, nchunks, epoch,
+                      persist, spin_limit, s};
 #ifdef OPS_ONLY_22     /* A/B builds (tools/iirchain_ablate.sh): one shape, a third of the compile time */
-#define OP_SHAPES(TT)  do { OP_LAUNCH(TT, 2, 2); } while (0)
+    op_launch<double, 2, 2>(p, call);
 #else
-#define OP_SHAPES(TT)                                                                              \
-    do {                                                                                           \
-      const int ns_ = p->c.nsec, or_ = p->c.ord[0];                                                \
-      if (or_ == 2) { if (ns_ == 1) { OP_LAUNCH(TT, 1, 2); } else { OP_LAUNCH(TT, 2, 2); } }       \
-      else if (or_ == 3) { OP_LAUNCH(TT, 1, 3); }                                                  \
-      else if (or_ == 4) { OP_LAUNCH(TT, 1, 4); }                                                  \
-      else if (ns_ == 1) { OP_LAUNCH(TT, 1, 1); }                                                  \
-      else if (ns_ == 2) { OP_LAUNCH(TT, 2, 1); }                                                  \
-      else if (ns_ == 3) { OP_LAUNCH(TT, 3, 1); }                                                  \
-      else { OP_LAUNCH(TT, 4, 1); }                                                                \
-    } while (0)
+    if (p->kind == WFK_OUT_F32) op_launch_shape<float>(p, call); else op_launch_shape<double>(p, call);
 #endif
-#ifdef OPS_ONLY_22
-    OP_SHAPES(double);
-#else
-    if (p->kind == WFK_OUT_F32) OP_SHAPES(float); else OP_SHAPES(double);
-#endif
-#undef OP_SHAPES
-#undef OP_LAUNCH
-#undef OP_LAUNCH_K
-#undef OP_COMMA
     if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "IIR kernel launch failed");
     return WFK_OK;
   }
@@ -1441,25 +1358,13 @@ extern "C" int wfk_iir_status(wfk_iir_plan* p, void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (hipStreamSynchronize((hipStream_t)hip_stream) != hipSuccess) return wfk_fail(WFK_EHIP, "stream synchronisation failed");
 
-  bool fault = false;
-  auto look = [&](wfk_iir_plan* q) {
-    if (q->op_fault.host() && *q->op_fault.host() != 0) {
-      *q->op_fault.host() = 0;
-      q->onepass = false;
-      fault = true;
-    }
-  };
-  look(p);
-  for (auto& q : p->parts) look(q.get());
-  if (fault) {
-    // one chunk chain stalled: the retry must not be able to time out in ANOTHER part either
-    p->onepass = false;
-    for (auto& q : p->parts) q->onepass = false;
-  }
-  if (fault)
-    return wfk_fail(WFK_ETIMEOUT, "IIR single pass: a look-back timed out (a stalled or preempted predecessor chunk); the outputs "
+  auto raised = [](const wfk_iir_plan* q) { return q->op_fault.host() && *q->op_fault.host() != 0; };
+  bool fault = raised(p);
+  for (auto& q : p->parts) fault = fault || raised(q.get());
+  if (!fault) return WFK_OK;
+  iir_leave_onepass(p);
+  return wfk_fail(WFK_ETIMEOUT, "IIR single pass: a look-back timed out (a stalled or preempted predecessor chunk); the outputs "
                                   "of that launch hold NaN. The plan now runs in the three-launch form: launch again");
-  return WFK_OK;
 }
 
 extern "C" int wfk_iir_apply(wfk_iir_plan* p, const void* in_dev, int64_t in_stride, void* out_dev,
@@ -1534,7 +1439,7 @@ int wfk_chain_iir_plan_create(const wfk_program* prog, const wfk_grid* grid, int
     HostPlan H;
     std::string err;
     const int par_cap = OPS_PAR;     // doubles of LDS the kernel stages a piece's parameter block in
-    const int64_t ops_chunk = 64 * (int64_t)(first->op_run > 0 ? first->op_run : OPS_RUN);      // samples per chunk of the fused scan
+    const int64_t ops_chunk = 64 * (int64_t)(first->opL.run > 0 ? first->opL.run : OPS_RUN);      // samples per chunk of the fused scan
     if (off && off[0] == '1') p->why = "disabled by WFK_CHAIN_UNFUSED";
     else if (!first->onepass) p->why = "the first IIR pass is not in the single-pass form (state dimension > 4, mixed orders, a short or a mid-sized batch of long rows)";
     else if (p->n < 4 * ops_chunk) p->why = "rows shorter than four chunks of the fused scan";
@@ -1641,7 +1546,7 @@ const char* wfk_chain_iir_kernel_name(const wfk_chain_iir_plan* p) {
   if (wfk_chain_iir_is_fused(p)) {
     const wfk_iir_plan* f = chain_first_stage(const_cast<wfk_chain_iir_plan*>(p));
     name = std::string("iir_sampled<") + T + "," + std::to_string(f->c.nsec) + "," + std::to_string(f->c.ord[0]) + "," +
-           (f->op_plain ? "true" : "false") + ">";
+           (f->opL.plain ? "true" : "false") + ">";
     if (!p->iir->parts.empty() && p->iir->parts.size() > 1) name += " + IIR passes";
   } else {
     name = std::string(wfk_plan_kernel_name(p->sampler, p->kind)) + " + IIR";

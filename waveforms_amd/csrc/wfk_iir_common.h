@@ -1,9 +1,13 @@
 // wfk_iir_common.h -- what every IIR form shares (wfk_iir.hip: three-launch scan, iir_onepass, iir_sampled;
 // wfk_iir_rows.hip: one cascade per row): the cascade step, the double-double mat-vec that applies the
-// transition tables, and the quad-precision builder of those tables.  (Errors, device memory: wfk_host.h.)
+// transition tables, the quad-precision builder of those tables, and the table set of a chained scan.  (Errors,
+// device memory: wfk_host.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
 #include <vector>
 
 #include "wfk_host.h"
@@ -134,6 +138,44 @@ inline std::vector<quad> iir_power_tables(const std::vector<quad>& B, int D, int
     cur.swap(nxt);
   }
   return cur;
+}
+
+// The table set of a chained scan (iir_onepass, iir_sampled) whose lanes own runs of `run` samples: B = T1^(run / block)
+// is the run's transition (T1: `block` samples, multiplied on from the right), U = B^64 a chunk's.
+struct IirScanTables {
+  std::vector<double> pw, lanep;   // B^(2^k), k < 7; B^(l+1), l < 64
+  std::vector<double> lanepU;      // U^(l+1), l < 64: the look-back window
+  std::vector<double> wdot;        // [run][4], on request: a run's end state from zero state per unit sample at
+                                   // position k (the dot-product form of pass 1); zeros unless `plain`
+  int run = 0;
+  double tmax = 0.0;               // largest entry of B^1 .. B^64 (hi words)
+  bool plain = false;              // entries of order 1, nothing cancels: scan and mat-vec in plain double
+};
+
+// b, a: as iir_quad_step.  may_plain = false: never plain.  WFK_IIR_DD=1 keeps every set in double-double.
+inline IirScanTables iir_scan_tables(int nsec, const int32_t* orders, const double* b, const double* a, int D,
+                                     const std::vector<quad>& T1, int block, int run, bool may_plain, bool dot) {
+  IirScanTables t;
+  t.run = run;
+  const size_t MM = (size_t)D * D * 2;
+  std::vector<double> pwU(7 * MM, 0.0);
+  t.pw.assign(7 * MM, 0.0);
+  t.lanep.assign(64 * MM, 0.0);
+  t.lanepU.assign(64 * MM, 0.0);
+  std::vector<quad> B = T1, nxt;
+  for (int k = 1; k < run / block; ++k) { iir_qmatmul(B, T1, nxt, D); B.swap(nxt); }
+  const std::vector<quad> U = iir_power_tables(B, D, 1, t.pw.data(), t.lanep.data());
+  iir_power_tables(U, D, 1, pwU.data(), t.lanepU.data());
+  for (size_t e = 0; e < t.lanep.size(); e += 2) t.tmax = std::max(t.tmax, std::fabs(t.lanep[e]));
+  const char* dd = getenv("WFK_IIR_DD");
+  t.plain = may_plain && t.tmax < 16.0 && !(dd && dd[0] == '1');
+  if (dot) t.wdot.assign((size_t)run * 4, 0.0);
+  for (int k = 0; k < run && dot && t.plain; ++k) {
+    std::vector<quad> z((size_t)D, (quad)0);
+    for (int s = k; s < run; ++s) iir_quad_step(nsec, orders, b, a, s == k ? (quad)1 : (quad)0, z.data());
+    for (int r = 0; r < D && r < 4; ++r) t.wdot[(size_t)k * 4 + r] = (double)z[r];
+  }
+  return t;
 }
 
 }  // namespace
