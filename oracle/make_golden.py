@@ -468,6 +468,12 @@ def make_spectral(ref, gold):
     np.savez_compressed(os.path.join(gold, 'spectral.npz'), **spec)
 
 
+def make_names(ref, gold):
+    """kernel_name() of the plans of tests/test_kernel_names.py, from the library in the tree (no reference involved)"""
+    import test_kernel_names
+    test_kernel_names.record(os.path.join(gold, 'kernel_names.json'))
+
+
 # fixture group -> (generator, files it writes); `python oracle/make_golden.py NAME...` runs only those
 FIXTURES = {
     'design': (make_design, ['design.npz']),
@@ -484,6 +490,7 @@ FIXTURES = {
     'late': (make_late, ['late.npz']),
     'awg': (make_awg, ['awg.npz', 'awg_c4.npz']),
     'n4': (make_n4, ['n4.npz']),
+    'names': (make_names, ['kernel_names.json']),
 }
 
 

@@ -215,3 +215,38 @@ def test_more_ranks_than_samples_and_tiny_slices():
             tf.close()
         assert np.max(np.abs(got - ref)) <= 1e-12, (n, world)
         assert np.max(np.abs(fgot - fref)) <= 1e-12, (n, world)
+
+
+def _slice_rows(kind):
+    """two channels (one with a complex amplitude) whose slice runs the general kernel's build `kind`"""
+    if kind == 'fused':       # fused ops only (the lean tier switched off)
+        chans = [wl.sum_channel(wf, 6, 1000), (0.4 - 0.7j) * wl.sum_channel(wf, 6, 1001)]
+        return chans, ('linspace', 0.0, 6 * wl.SPAN, 50000, False), {'WFK_DISABLE_LEAN': '1'}, ',false,false,false,16>'
+    if kind == 'generic':     # two tables in one piece: generic terms, nothing for the direct tier
+        hann = lambda m: wf.samplingPoints(-wl.SPAN / 2, wl.SPAN / 2, np.hanning(m))
+        w = ((hann(1000) * (wf.cos(2e9) + wf.cos(2.5e9))) >> 40e-9) + (hann(100) >> 44e-9)
+        return [w, (0.3 + 0.2j) * w], ('linspace', 0.0, 80e-9, 40000, False), {'WFK_DISABLE_MIXED': '1'}, ',false,true,false,16>'
+    return [_rows('generic')[0][0], (1 - 0.5j) * _rows('generic')[0][0]], ('linspace', 0.0, 300e-9, 25003, False), {}, ',false,true,true,16>'
+
+
+@pytest.mark.parametrize('kind', ['fused', 'generic', 'direct'])
+def test_float_and_complex_slices_of_the_general_kernel(kind, monkeypatch):
+    """wfk_sample_slice / wfk_sample_wide_slice for every output kind: three tiles of a grid from a sample index that is
+    no multiple of the tile, against the NumPy oracle at the slice's own times"""
+    from oracle import np_oracle
+    chans, grid, env, tail = _slice_rows(kind)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    g = _flatten.grid_slice(_flatten.grid_from_desc(grid), 5001, 5001 + 3 * 4096 + 37)
+    plan = _engine.Plan(_flatten.flatten(chans), grid=g)
+    t = _flatten.grid_values(g)
+    ref = np.stack([np_oracle.call(w, t) for w in chans])
+    pk = max(1.0, float(np.abs(ref).max()))
+    for dt, tol in ((np.float64, 1e-9), (np.float32, cases.FP32_TOL), (np.complex128, 1e-9), (np.complex64, cases.FP32_TOL)):
+        name = plan.kernel_name(dt)
+        assert name.startswith(('wfk_sample<', 'wfk_sample_wide<')) and name.endswith(tail), name
+        want = ref if np.dtype(dt).kind == 'c' else ref.real
+        err = float(np.max(np.abs(plan.run_host(dt) - want)))
+        print(kind, np.dtype(dt).name, name, 'err / peak %.3g' % (err / pk))
+        assert err <= tol * pk, (kind, dt, err)
+    plan.close()

@@ -5,8 +5,9 @@
 
 A, B: two object files, or two trees (then waveforms_amd/csrc/_obj/<object> of each, default every object that is
 built with an offload arch: the `OBJ :=` line of waveforms_amd/csrc/Makefile but wfk_compile.o).  The code object is taken out of each object file as tools/kernel_regs.sh does, disassembled
-with llvm-objdump -d, and compared per kernel symbol: the encoded instruction words (branches are PC-relative, so
-a kernel that merely moved compares equal) and the metadata kernel_regs.sh prints (VGPR / AGPR / SGPR, spills,
+with llvm-objdump -d, and compared per function symbol (kernels and the device functions they call): the encoded
+instruction words (branches are PC-relative and a reference to another function is compared by what it reaches, so
+a kernel that merely moved compares equal) and, for kernels, the metadata kernel_regs.sh prints (VGPR / AGPR / SGPR, spills,
 LDS, scratch).  Exit status 0: same set of kernels, every one identical.
 """
 import os
@@ -25,7 +26,7 @@ def run(*cmd):
 
 
 def kernels(obj):
-    """{kernel symbol: (metadata tuple, [encoded instruction words])}"""
+    """{function symbol: (metadata tuple of a kernel or None, [encoded instruction words])}"""
     with tempfile.TemporaryDirectory() as tmp:
         fat, co = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "k.co")
         if ".hip_fatbin" not in run(f"{B}/llvm-readelf", "-S", obj):
@@ -45,20 +46,33 @@ def kernels(obj):
                 meta[cur["name"]] = tuple(cur.get(x) for x in META)
             cur = {}
         cur[m.group(2)] = m.group(3).strip()
-    code, sym = {}, None
+    # every function of the code object (kernels and the device functions they call): its address, its words.  A
+    # reference from one function to another -- s_getpc_b64, then s_add_u32 with the 32-bit distance -- is recorded as
+    # the function and offset it reaches: which functions come first in the object is not part of a kernel's code
+    code, start, refs, sym, prev = {}, {}, [], None, ""
     for line in dis.splitlines():
-        m = re.match(r"[0-9a-f]+ <(.+)>:$", line)
+        m = re.match(r"([0-9a-f]+) <(.+)>:$", line)
         if m:
-            sym = m.group(1)
-            code[sym] = []
+            sym = m.group(2)
+            code[sym], start[sym] = [], int(m.group(1), 16)
             continue
-        m = re.search(r"// [0-9A-F]+: ([0-9A-F ]+)$", line)
+        m = re.search(r"^\s*(\S+).*// ([0-9A-F]+): ([0-9A-F ]+)$", line)
         if m and sym is not None:
-            code[sym].extend(m.group(1).split())
+            words = m.group(3).split()
+            if m.group(1) == "s_add_u32" and prev == "s_getpc_b64" and len(words) == 2:
+                dist = int(words[1], 16) - (1 << 32 if words[1][0] in "89ABCDEF" else 0)
+                refs.append((sym, len(code[sym]) + 1, int(m.group(2), 16) + dist))
+            code[sym].extend(words)
+            prev = m.group(1)
+    by_addr = sorted((a, k) for k, a in start.items())
+    for sym, at, target in refs:
+        a, k = max((x for x in by_addr if x[0] <= target), default=(0, None))
+        if k is not None and target < a + 4 * len(code[k]):
+            code[sym][at] = f"{k}+{target - a}"
     missing = [k for k in meta if k not in code]
     if missing:
         sys.exit(f"{obj}: no code found for {missing[:3]}")
-    return {k: (meta[k], code[k]) for k in meta}
+    return {k: (meta.get(k), code[k]) for k in code}
 
 
 def default_objects():
@@ -100,7 +114,7 @@ def main():
                 print(f"    code {len(ca)} -> {len(cb)} words, first difference at word {first}")
         bad += len(only)
         words = sum(len(c) for _, c in ka.values())
-        print(f"{label}: {len(ka)} kernels in A, {len(kb)} in B, {same} identical "
+        print(f"{label}: {len(ka)} functions in A, {len(kb)} in B, {same} identical "
               f"(instruction words and registers / spills / LDS / scratch), {words} instruction words in A")
     print("IDENTICAL" if not bad else f"{bad} DIFFERENCE(S)")
     return 1 if bad else 0

@@ -16,6 +16,7 @@
 #include "wfk.h"
 #include "wfk_host.h"
 #include "wfk_internal.h"
+#include "wfk_pick.h"
 
 static thread_local std::string g_err;
 
@@ -357,42 +358,33 @@ int64_t wfk_plan_table_bytes(const wfk_plan* p) {
 }
 
 const char* wfk_plan_kernel_name(const wfk_plan* p, int out_kind) {
-  if (!p || out_kind < 0 || out_kind > 3) return "";
   static thread_local std::string name;
-  const char* T = (out_kind == WFK_OUT_F32 || out_kind == WFK_OUT_C64) ? "float" : "double";
-  const char* cplx = (out_kind == WFK_OUT_C128 || out_kind == WFK_OUT_C64) ? "true" : "false";
-  const HostPlan& h = p->h;
-  const bool f32 = out_kind == WFK_OUT_F32 || out_kind == WFK_OUT_C64;
-  // the general kernel's symbol: float outputs of plans with generic terms and of time lists run the builds with
-  // double arithmetic (wfk_sample_wide)
-  auto general = [&](bool tl, bool g, bool d, int ns) {
-    const std::string tail = std::string(cplx) + "," + (tl ? "true" : "false") + "," + (g ? "true" : "false") + "," +
-                             (d ? "true" : "false") + "," + std::to_string(ns) + ">";
-    return f32 && (tl || g || d) ? "wfk_sample_wide<" + tail : std::string("wfk_sample<") + T + "," + tail;
-  };
-  if (h.shortp) {
-    name = std::string("wfk_sample_short<") + T + "," + cplx + ",false," + std::to_string(WFK_SH_R) + "," +
-           std::to_string(h.short_fam == 0 && out_kind == WFK_OUT_F32 && !(std::getenv("WFK_SH_NO_PK") && std::getenv("WFK_SH_NO_PK")[0] == '1') ? 3 : h.short_fam) + ">";
-    if (h.mixed)      // pieces the short tier cannot take: a second launch of the general kernel
-      name += " + " + general(false, h.n_direct > 0 || h.n_generic > 0, h.n_direct > 0, h.ns);
-    return name.c_str();
-  }
-  const std::string lean_name = std::string("wfk_sample_lean<") + T + "," + cplx + "," + std::to_string(h.ns) +
-      (h.n_corr > 0 && out_kind != WFK_OUT_F32 && out_kind != WFK_OUT_C64
-           ? std::string(",true,") + std::to_string(h.lean_fam >= 1 ? 1 : 0) + ">"
-           : std::string(",false,") + std::to_string(h.lean_fam) + ">");
-  if (!h.tlist && h.lean) {
-    name = lean_name;
-  } else {
-    // (a time-list plan whose every term fused runs the pointwise-ops-only build; any generic term brings
-    //  the build with the direct tier, as before)
-    const bool tl_full = h.tlist && (h.n_direct > 0 || h.n_generic > 0);
-    const bool direct = tl_full || (!h.tlist && h.n_direct > 0), generic = direct || (!h.tlist && h.n_generic > 0);
-    name = general(h.tlist, generic, direct, h.ns);
-    if (h.mixed && h.tlist) name = general(true, false, false, h.ns) + " + " + name;
-    else if (h.mixed) name = lean_name + " + " + name;   // two launches over disjoint pieces
-  }
+  SamplerPicks picks; std::string err;
+  name.clear();
+  if (p && wfk_sampler_picks(p->h, out_kind, wfk_short_packed(), picks, err) == WFK_OK)
+    for (int i = 0; i < picks.n; ++i) name += (i ? " + " : "") + wfk_pick_name(picks.pick[i]);
   return name.c_str();
+}
+
+// the arguments of a pick's launch on the general / lean kernels: the chunk table it walks, the rest from the plan
+static KArgs sampler_args(const wfk_plan* p, const SamplerPick& k, void* out_dev, int64_t ch_stride, uint32_t flags) {
+  const HostPlan& h = p->h;
+  KArgs a{};
+  a.channels = p->d_channels; a.pieces = p->d_pieces; a.params = p->d_params; a.pool = p->d_pool; a.tlist = p->d_tlist;
+  a.out = out_dev; a.ch_stride = ch_stride; a.n = h.n; a.accumulate = (flags & WFK_ACCUMULATE) ? 1 : 0;
+  a.t0 = h.t0; a.i0 = h.i0; a.step = h.step; a.last = h.last; a.has_last = h.has_last;
+  a.lean_par = h.lean_par; a.lean_ops = h.lean_ops; a.corr = h.n_corr > 0 ? 1 : 0; a.lean_fam = h.lean_fam;
+  a.wavepriv = (h.tlist && h.ns == WFK_NS_TLIST_SMALL && h.max_block_len <= WFK_LDS_DOUBLES / 4 &&
+                !std::getenv("WFK_NO_WAVEPRIV")) ? 1 : 0;
+  a.mixed = h.mixed ? 1 : 0;   // two launches, one output: each skips the other's pieces (a short plan's first launch also wrote the zero stretches)
+  a.reseed = WFK_LEAN_RESEED;
+  switch (k.table) {
+    case ChunkTable::Lean: a.chunk_first = p->d_lean_chunk_first; a.chunks_per_ch = h.lean_chunks_per_ch; a.tiles_per_chunk = h.lean_tiles_per_chunk; break;
+    case ChunkTable::F32: a.chunk_first = p->d_f32_chunk_first; a.chunks_per_ch = h.f32_chunks_per_ch; a.tiles_per_chunk = h.f32_tiles_per_chunk; a.reseed = WFK_LEAN_RESEED_F32; break;
+    default: a.chunk_first = p->d_chunk_first; a.chunks_per_ch = h.chunks_per_ch; a.tiles_per_chunk = h.tiles_per_chunk;
+  }
+  a.n_chunks = a.chunks_per_ch * h.n_channels;
+  return a;
 }
 
 // Launch the plan, or part `part` of `nparts` of it (single-channel plans only: the part's chunks are
@@ -410,114 +402,43 @@ static int plan_launch_part(wfk_plan* p, void* out_dev, int64_t ch_stride, int o
     base = total * part / nparts;
     count = total * (part + 1) / nparts - base;
   };
-  if (p->h.shortp) {
-    SArgs sa{};
-    sa.channels = p->d_channels;
-    sa.units = p->d_units;
-    sa.slots = p->d_slots;
-    sa.recs = p->d_params;
-    sa.out = out_dev;
-    sa.ch_stride = ch_stride;
-    sa.n_units = (int64_t)p->h.s_units.size();
-    sa.units_per_chunk = p->h.s_units_per_chunk;
-    const int64_t all = (sa.n_units + sa.units_per_chunk - 1) / sa.units_per_chunk;
-    sub(all, sa.chunk_base, sa.n_chunks);
-    sa.accumulate = (flags & WFK_ACCUMULATE) ? 1 : 0;
-    sa.lds_samples = p->h.s_lds_samples;
-    sa.fam = p->h.short_fam;
-    sa.t0 = p->h.t0; sa.last = p->h.last;
-    sa.dlast = p->h.has_last ? (double)(p->h.i0 + p->h.n - 1) : -1.0;
-    sa.di0 = (double)p->h.i0;
-    { const char* e = std::getenv("WFK_SH_NO_PK"); sa.pk = (e && e[0] == '1') ? 0 : 1; }
-    sa.step = p->h.step;
-    sa.pool = p->d_pool;
-    if (s_lo && nparts > 1) {
-      const int64_t u0 = sa.chunk_base * sa.units_per_chunk, u1 = (sa.chunk_base + sa.n_chunks) * sa.units_per_chunk;
-      *s_lo = u0 < sa.n_units ? p->h.s_units[(size_t)u0].j0 : p->h.n;
-      *s_hi = u1 < sa.n_units ? p->h.s_units[(size_t)u1].j0 : p->h.n;
-    }
-    if (hip_stream) p->async_launch = true;
-    std::string serr;
-    const bool foreign_only = (flags & WFK_PLAN_FOREIGN_ONLY) && p->h.mixed;   // (the chain at AWG rates samples the short pieces itself)
-    const int src = sa.n_chunks > 0 && !foreign_only ? wfk_launch_short(sa, out_kind, hip_stream, serr) : WFK_OK;
-    if (src) return wfk_fail(src, serr);
-    if (!p->h.mixed) return WFK_OK;
-  }
-  KArgs a{};
-  a.channels = p->d_channels;
-  a.pieces = p->d_pieces;
-  a.params = p->d_params;
-  a.pool = p->d_pool;
-  a.chunk_first = p->d_chunk_first;
-  a.tlist = p->d_tlist;
-  a.out = out_dev;
-  a.ch_stride = ch_stride;
-  a.n = p->h.n;
-  a.chunks_per_ch = p->h.chunks_per_ch;
-  a.n_chunks = p->h.chunks_per_ch * p->h.n_channels;
-  a.tiles_per_chunk = p->h.tiles_per_chunk;
-  a.accumulate = (flags & WFK_ACCUMULATE) ? 1 : 0;
-  a.t0 = p->h.t0;
-  a.i0 = p->h.i0;
-  a.step = p->h.step;
-  a.last = p->h.last;
-  a.has_last = p->h.has_last;
-  a.lean_par = p->h.lean_par;
-  a.lean_ops = p->h.lean_ops;
-  a.corr = p->h.n_corr > 0 ? 1 : 0;
-  a.lean_fam = p->h.lean_fam;
-  a.wavepriv = (p->h.tlist && p->h.ns == WFK_NS_TLIST_SMALL && p->h.max_block_len <= WFK_LDS_DOUBLES / 4 &&
-                !std::getenv("WFK_NO_WAVEPRIV")) ? 1 : 0;
-  a.reseed = WFK_LEAN_RESEED;
-  // float outputs of the lean launch: longer chunks, rarer exact reseeds (HostPlan::f32_*)
-  const bool f32_lean = (out_kind == WFK_OUT_F32 || out_kind == WFK_OUT_C64) && p->h.f32_tiles_per_chunk > 0;
-  auto use_f32_chunks = [&](KArgs& k) {
-    k.chunk_first = p->d_f32_chunk_first;
-    k.chunks_per_ch = p->h.f32_chunks_per_ch;
-    k.n_chunks = p->h.f32_chunks_per_ch * p->h.n_channels;
-    k.tiles_per_chunk = p->h.f32_tiles_per_chunk;
-    k.reseed = WFK_LEAN_RESEED_F32;
-  };
-  if (f32_lean && p->h.lean) use_f32_chunks(a);
   if (hip_stream) p->async_launch = true;
-  std::string err;
-  int rc = WFK_OK;
-  if (p->h.shortp) {
-    a.mixed = 1;      // the short launch above wrote its pieces and the zero stretches; now the rest
-  } else if (p->h.mixed && p->h.tlist) {
-    // time list: the fully fused and the zero pieces on the pointwise-ops build (same chunking) ...
-    KArgs l = a;
-    l.mixed = 1;
-    rc = wfk_launch_sampler(l, p->h.n_channels, out_kind, true, p->h.ns, false, false, false, hip_stream, err);
-    if (rc) return wfk_fail(rc, err);
-    a.mixed = 1;   // ... then the pieces with generic terms on the build with the direct tier
-  } else if (p->h.mixed) {
-    // lean and zero pieces first (own chunking: one wave per workgroup) ...
-    KArgs l = a;
-    l.mixed = 1;
-    l.chunk_first = p->d_lean_chunk_first;
-    l.chunks_per_ch = p->h.lean_chunks_per_ch;
-    l.n_chunks = p->h.lean_chunks_per_ch * p->h.n_channels;
-    l.tiles_per_chunk = p->h.lean_tiles_per_chunk;
-    if (f32_lean) use_f32_chunks(l);
-    rc = wfk_launch_sampler(l, p->h.n_channels, out_kind, false, p->h.ns, true, false, false, hip_stream, err);
-    if (rc) return wfk_fail(rc, err);
-    a.mixed = 1;   // ... then the pieces with generic terms
-  }
-  if (nparts > 1) {
-    const int64_t all = a.n_chunks;
-    sub(all, a.chunk_base, a.n_chunks);
-    const int64_t tile = (int64_t)(p->h.lean ? 64 : WFK_WG) * p->h.ns, span = tile * a.tiles_per_chunk;
-    if (s_lo) {
-      *s_lo = std::min<int64_t>(p->h.n, a.chunk_base * span);
-      *s_hi = std::min<int64_t>(p->h.n, (a.chunk_base + a.n_chunks) * span);
+  SamplerPicks picks; std::string err;
+  const bool packed = wfk_short_packed();
+  int rc = wfk_sampler_picks(p->h, out_kind, packed, picks, err);
+  for (int i = 0; i < picks.n && !rc; ++i) {
+    const SamplerPick& k = picks.pick[i];
+    if (k.tier == SamplerTier::Short) {
+      SArgs sa{};
+      sa.channels = p->d_channels; sa.units = p->d_units; sa.slots = p->d_slots; sa.recs = p->d_params; sa.pool = p->d_pool;
+      sa.out = out_dev; sa.ch_stride = ch_stride; sa.accumulate = (flags & WFK_ACCUMULATE) ? 1 : 0;
+      sa.n_units = (int64_t)p->h.s_units.size();
+      sa.units_per_chunk = p->h.s_units_per_chunk;
+      sub((sa.n_units + sa.units_per_chunk - 1) / sa.units_per_chunk, sa.chunk_base, sa.n_chunks);
+      sa.lds_samples = p->h.s_lds_samples; sa.fam = p->h.short_fam; sa.pk = packed ? 1 : 0;
+      sa.t0 = p->h.t0; sa.last = p->h.last; sa.step = p->h.step; sa.di0 = (double)p->h.i0;
+      sa.dlast = p->h.has_last ? (double)(p->h.i0 + p->h.n - 1) : -1.0;
+      if (s_lo && nparts > 1) {
+        const int64_t u0 = sa.chunk_base * sa.units_per_chunk, u1 = (sa.chunk_base + sa.n_chunks) * sa.units_per_chunk;
+        *s_lo = u0 < sa.n_units ? p->h.s_units[(size_t)u0].j0 : p->h.n;
+        *s_hi = u1 < sa.n_units ? p->h.s_units[(size_t)u1].j0 : p->h.n;
+      }
+      const bool foreign_only = (flags & WFK_PLAN_FOREIGN_ONLY) && p->h.mixed;   // (the chain at AWG rates samples the short pieces itself)
+      if (sa.n_chunks > 0 && !foreign_only) rc = wfk_launch_short(sa, k, hip_stream, err);
+      continue;
     }
-    if (a.n_chunks == 0) return WFK_OK;
+    KArgs a = sampler_args(p, k, out_dev, ch_stride, flags);
+    if (nparts > 1) {
+      sub(a.n_chunks, a.chunk_base, a.n_chunks);
+      const int64_t tile = (int64_t)(k.tier == SamplerTier::Lean ? 64 : WFK_WG) * p->h.ns, span = tile * a.tiles_per_chunk;
+      if (s_lo) {
+        *s_lo = std::min<int64_t>(p->h.n, a.chunk_base * span);
+        *s_hi = std::min<int64_t>(p->h.n, (a.chunk_base + a.n_chunks) * span);
+      }
+      if (a.n_chunks == 0) return WFK_OK;
+    }
+    rc = wfk_launch_sampler(a, k, p->h.n_channels, hip_stream, err);
   }
-  rc = wfk_launch_sampler(a, p->h.n_channels, out_kind, p->h.tlist, p->h.ns, p->h.lean,
-                          p->h.n_generic > 0 || (p->h.tlist && p->h.n_direct > 0),   // (time lists: either generic + direct or neither)
-                          p->h.n_direct > 0 || (p->h.tlist && p->h.n_generic > 0),
-                          hip_stream, err);
   return rc ? wfk_fail(rc, err) : WFK_OK;
 }
 

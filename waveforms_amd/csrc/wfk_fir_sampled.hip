@@ -654,12 +654,26 @@ int64_t wfk_chain_table_bytes(const wfk_chain_plan* p) {
   return p->fused ? p->table_bytes : wfk_plan_table_bytes(p->sampler);
 }
 
+}  // extern "C"
+
+// The build a fused chain runs, chosen once for the launch and the name: f(T{}, hop in blocks of 256 as an integral
+// constant) for float / double x hop 12 / 10.
+template <typename F>
+static auto chain_build(const wfk_chain_plan* p, F&& f) {
+  using H12 = std::integral_constant<int, 12>; using H10 = std::integral_constant<int, 10>;
+  if (p->kind == WFK_OUT_F32) return p->hopb == 12 ? f(float{}, H12{}) : f(float{}, H10{});
+  return p->hopb == 12 ? f(double{}, H12{}) : f(double{}, H10{});
+}
+
+extern "C" {
+
 const char* wfk_chain_kernel_name(const wfk_chain_plan* p) {
   if (!p) return "";
   static thread_local std::string name;
-  const char* T = p->kind == WFK_OUT_F32 ? "float" : "double";
   if (p->fused) {
-    name = std::string(p->shortw ? "fir_short<" : "fir_sampled<") + T + "," + std::to_string(p->hopb) + ">";
+    name = chain_build(p, [&](auto t, auto hop) {
+      return std::string(p->shortw ? "fir_short<" : "fir_sampled<") + (sizeof(t) == 4 ? "float" : "double") + "," + std::to_string(hop()) + ">";
+    });
     if (p->hybrid) name = "wfk_sample<...> (pieces without a short form) + " + name;
   }
   else name = std::string(wfk_plan_kernel_name(p->sampler, p->kind)) + " + FIR";
@@ -693,13 +707,7 @@ int wfk_chain_launch(wfk_chain_plan* p, void* out_dev, int64_t out_stride, void*
     a.hspec = kspec; a.tw = tw; a.step = p->step; a.hrow = wfk_internal_fir_krow(p->fir);
     a.hop = 256 * p->hopb; a.K = K; a.lead = lead;
     const dim3 grid((unsigned)p->npairs, (unsigned)p->n_channels);
-    if (p->kind == WFK_OUT_F32) {
-      if (p->hopb == 12) hipLaunchKernelGGL((fir_short<float, 12>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((fir_short<float, 10>), grid, dim3(256), 0, s, a);
-    } else {
-      if (p->hopb == 12) hipLaunchKernelGGL((fir_short<double, 12>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((fir_short<double, 10>), grid, dim3(256), 0, s, a);
-    }
+    chain_build(p, [&](auto t, auto hop) { hipLaunchKernelGGL((fir_short<decltype(t), decltype(hop)::value>), grid, dim3(256), 0, s, a); });
     if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "fused sampler->FIR kernel launch failed");
     return WFK_OK;
   }
@@ -710,13 +718,7 @@ int wfk_chain_launch(wfk_chain_plan* p, void* out_dev, int64_t out_stride, void*
   a.t0 = p->t0; a.step = p->step; a.last = p->last; a.has_last = p->has_last; a.i0 = p->i0;
   a.hop = 256 * p->hopb; a.K = K; a.lead = lead;
   const dim3 grid((unsigned)((p->npairs + WFK_FIRS_PPW - 1) / WFK_FIRS_PPW), (unsigned)p->n_channels);
-  if (p->kind == WFK_OUT_F32) {
-    if (p->hopb == 12) hipLaunchKernelGGL((fir_sampled<float, 12>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((fir_sampled<float, 10>), grid, dim3(256), 0, s, a);
-  } else {
-    if (p->hopb == 12) hipLaunchKernelGGL((fir_sampled<double, 12>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((fir_sampled<double, 10>), grid, dim3(256), 0, s, a);
-  }
+  chain_build(p, [&](auto t, auto hop) { hipLaunchKernelGGL((fir_sampled<decltype(t), decltype(hop)::value>), grid, dim3(256), 0, s, a); });
   if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "fused sampler->FIR kernel launch failed");
   return WFK_OK;
 }

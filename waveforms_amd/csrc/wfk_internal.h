@@ -278,8 +278,8 @@ struct HostPlan {
   int32_t n_corr = 0;          // fused ops carrying the grid-rounding correction
   bool lean = false;           // wave-per-workgroup fused kernel (see WFK_LEAN_*)
   int32_t lean_fam = 0;        // instantiation of that kernel the plan needs: 0 plain ops, 1 + closing ops (erf
-                               // edges, shared envelopes), 2 + chirps -- a shape added to one family cannot move
-                               // the code generation of the others
+                               // edges, shared envelopes), 2 + chirps, 3 + stateless multipliers, 4 + own-term ops -- a
+                               // shape added to one family cannot move the code generation of the others
   bool mixed = false;          // lean pieces go to the lean kernel, the rest to the general kernel
   int32_t lean_tile = 0, lean_tiles_per_chunk = 1;   // mixed: the lean launch's own chunking
   int64_t lean_chunks_per_ch = 0;
@@ -301,7 +301,8 @@ struct HostPlan {
   bool short_has_fmul = false;     // some short piece holds an op wfk_sample_short evaluates and fir_short does not (table / mollifier multipliers, chirps)
   int32_t short_fam = 0;           // instantiation of wfk_sample_short the plan needs: 0 carrier-envelope ops only, 1 + erf edges, chirps and
                                    // shared Gaussians, 2 + table / mollifier envelopes (closing multipliers, own-term ops), 4 + exponential / hyperbolic chirp
-                                   // multipliers (3 is family 0 in packed fp32, picked at launch)
+                                   // multipliers, 6 family 0 + the grid-rounding correction (3 is family 0 in packed fp32, picked at launch).
+                                   // The compiler produces 0, 1, 2, 4 and 6 and nothing else; the pick (wfk_pick.h) rejects any other value
   bool short_corr = false;         // some short op carries the grid-rounding correction (family 6: wfk_short_dev.h short_op_corr)
   bool short_needs_corr = false;   // some carrier wanted the grid-rounding correction, which only the lean kernel has
   bool pool_real = false;          // `pool` holds tables the parameter blocks point into (INTERP / mollifier / SAMPLED)
@@ -345,11 +346,10 @@ void wfk_internal_grid_times(const wfk_grid* g, double* out);         // out[g->
 // this thread's next plan compiles keep table / mollifier multipliers out of short pieces (the FIR chain's sampler plan)
 void wfk_internal_no_short_fmul(bool on);
 
-// kernels (wfk_kernels.hip)
-int wfk_launch_sampler(const KArgs& a, int32_t n_channels, int out_kind, bool tlist, int ns,
-                       bool lean, bool generic, bool direct, void* stream, std::string& err);
-// (a.corr selects the lean kernel variant with the per-sample grid-rounding correction)
-int wfk_launch_short(const SArgs& a, int out_kind, void* stream, std::string& err);
+// kernels (wfk_kernels.hip, wfk_short.hip): the launch of one pick of a plan (wfk_pick.h)
+struct SamplerPick;
+int wfk_launch_sampler(const KArgs& a, const SamplerPick& k, int32_t n_channels, void* stream, std::string& err);
+int wfk_launch_short(const SArgs& a, const SamplerPick& k, void* stream, std::string& err);
 
 // functions one stage's file calls in another's, exported but not part of include/wfk.h
 extern "C" {

@@ -28,6 +28,7 @@
 
 #include "wfk.h"
 #include "wfk_internal.h"
+#include "wfk_pick.h"
 
 namespace {
 
@@ -1857,90 +1858,68 @@ __global__ void __launch_bounds__(WFK_WG, WFK_SLICE_WGS(CPLX, GENERIC, DIRECT)) 
   wfk_sample_body<double, float, CPLX, false, GENERIC, DIRECT, NS, true>(a);
 }
 
+// The builds of one output kind and geometry, and the launch of the one the pick names.  Rows of three are indexed by
+// what the plan's pieces hold: [0] fused ops only, [1] + generic terms, [2] + the direct tier (a time list has [0] or [2]).
 template <typename T, bool CPLX, bool TLIST, int NS>
-int launch(const KArgs& a, int64_t blocks, hipStream_t s, bool lean, bool generic, bool direct) {
-  const dim3 g((unsigned)blocks), b(WFK_WG);
-  if constexpr (!TLIST) {   // (the lean kernel exists for grid plans only)
+bool launch(const KArgs& a, const SamplerPick& k, int64_t blocks, hipStream_t s) {
+  using Kernel = void (*)(const KArgs);
+  constexpr bool kF32 = sizeof(T) == 4;
+  const int gd = k.direct ? 2 : k.generic ? 1 : 0;
+  const bool lean = !TLIST && k.tier == SamplerTier::Lean, slice = !TLIST && k.slice;
+  Kernel fn = nullptr;
+  dim3 wg(WFK_WG); size_t lds = 0;
+  if constexpr (!TLIST) {   // (the lean kernel and the slice builds exist for grid plans only)
     if (lean) {
-      const size_t lds = (size_t)(a.lean_par + 128 * a.lean_ops) * sizeof(double);
-      if constexpr (sizeof(T) == 8) {
-        if (a.corr) {      // (corrected carriers and chirps never share a plan's lean pieces: family <= 1 here)
-          if (a.lean_fam >= 1) hipLaunchKernelGGL((wfk_sample_lean<T, CPLX, NS, true, 1>), g, dim3(64), lds, s, a);
-          else hipLaunchKernelGGL((wfk_sample_lean<T, CPLX, NS, true, 0>), g, dim3(64), lds, s, a);
-          return hipGetLastError() == hipSuccess ? 0 : -1;
-        }
+      static constexpr Kernel plain[5] = {wfk_sample_lean<T, CPLX, NS, false, 0>, wfk_sample_lean<T, CPLX, NS, false, 1>, wfk_sample_lean<T, CPLX, NS, false, 2>,
+                                          wfk_sample_lean<T, CPLX, NS, false, 3>, wfk_sample_lean<T, CPLX, NS, false, 4>};
+      if (!k.corr && k.fam >= 0 && k.fam <= 4) fn = plain[k.fam];
+      if constexpr (!kF32) {      // (the corrected build: double only, families 0 and 1)
+        static constexpr Kernel corr[2] = {wfk_sample_lean<T, CPLX, NS, true, 0>, wfk_sample_lean<T, CPLX, NS, true, 1>};
+        if (k.corr && k.fam >= 0 && k.fam <= 1) fn = corr[k.fam];
       }
-      if (a.lean_fam >= 4) hipLaunchKernelGGL((wfk_sample_lean<T, CPLX, NS, false, 4>), g, dim3(64), lds, s, a);
-      else if (a.lean_fam == 3) hipLaunchKernelGGL((wfk_sample_lean<T, CPLX, NS, false, 3>), g, dim3(64), lds, s, a);
-      else if (a.lean_fam == 2) hipLaunchKernelGGL((wfk_sample_lean<T, CPLX, NS, false, 2>), g, dim3(64), lds, s, a);
-      else if (a.lean_fam == 1) hipLaunchKernelGGL((wfk_sample_lean<T, CPLX, NS, false, 1>), g, dim3(64), lds, s, a);
-      else hipLaunchKernelGGL((wfk_sample_lean<T, CPLX, NS, false, 0>), g, dim3(64), lds, s, a);
-      return hipGetLastError() == hipSuccess ? 0 : -1;
+      wg = dim3(64); lds = (size_t)(a.lean_par + 128 * a.lean_ops) * sizeof(double);
+    } else if (slice) {           // a time slice of a longer grid: the builds that offset the sample index
+      static constexpr Kernel sliced[3] = {wfk_sample_slice<T, CPLX, false, false, NS>, wfk_sample_slice<T, CPLX, true, false, NS>, wfk_sample_slice<T, CPLX, true, true, NS>};
+      fn = sliced[gd];
+      if constexpr (kF32) {
+        static constexpr Kernel wide[3] = {nullptr, wfk_sample_wide_slice<CPLX, true, false, NS>, wfk_sample_wide_slice<CPLX, true, true, NS>};
+        if (k.tier == SamplerTier::Wide) fn = wide[gd];
+      }
     }
   }
-  if constexpr (!TLIST) {
-    if (a.i0 != 0) {                     // a time slice of a longer grid: the builds that offset the sample index
-      if constexpr (sizeof(T) == 4) {
-        if (direct) { hipLaunchKernelGGL((wfk_sample_wide_slice<CPLX, true, true, NS>), g, b, 0, s, a); return hipGetLastError() == hipSuccess ? 0 : -1; }
-        if (generic) { hipLaunchKernelGGL((wfk_sample_wide_slice<CPLX, true, false, NS>), g, b, 0, s, a); return hipGetLastError() == hipSuccess ? 0 : -1; }
-      }
-      if (direct) hipLaunchKernelGGL((wfk_sample_slice<T, CPLX, true, true, NS>), g, b, 0, s, a);
-      else if (generic) hipLaunchKernelGGL((wfk_sample_slice<T, CPLX, true, false, NS>), g, b, 0, s, a);
-      else hipLaunchKernelGGL((wfk_sample_slice<T, CPLX, false, false, NS>), g, b, 0, s, a);
-      return hipGetLastError() == hipSuccess ? 0 : -1;
+  if (!lean && !slice) {
+    // ([3], the grid's fused-only build, is what [0] is for a grid plan; no pick reaches it at a time list's NS, nor the
+    //  float forms of [1] and [2], which run wide.  The ladder this table replaced instantiated them, and so does the
+    //  table: the object's kernels stay the same set, symbol for symbol)
+    static constexpr Kernel base[4] = {wfk_sample<T, CPLX, TLIST, false, false, NS>, wfk_sample<T, CPLX, false, true, false, NS>,
+                                       wfk_sample<T, CPLX, TLIST, true, true, NS>, wfk_sample<T, CPLX, false, false, false, NS>};
+    fn = base[gd];
+    if constexpr (kF32) {         // float / complex64 outputs of these tiers: double arithmetic (wfk_sample_wide)
+      static constexpr Kernel wide[3] = {wfk_sample_wide<CPLX, TLIST, false, false, NS>, wfk_sample_wide<CPLX, false, true, false, NS>,
+                                         wfk_sample_wide<CPLX, TLIST, true, true, NS>};
+      if (k.tier == SamplerTier::Wide) fn = wide[gd];
     }
   }
-  if constexpr (sizeof(T) == 4) {        // float / complex64 outputs of these tiers: double arithmetic (wfk_sample_wide)
-    if (TLIST && !generic && !direct) { hipLaunchKernelGGL((wfk_sample_wide<CPLX, TLIST, false, false, NS>), g, b, 0, s, a); return hipGetLastError() == hipSuccess ? 0 : -1; }
-    if (TLIST || direct) { hipLaunchKernelGGL((wfk_sample_wide<CPLX, TLIST, true, true, NS>), g, b, 0, s, a); return hipGetLastError() == hipSuccess ? 0 : -1; }
-    if (generic) { hipLaunchKernelGGL((wfk_sample_wide<CPLX, false, true, false, NS>), g, b, 0, s, a); return hipGetLastError() == hipSuccess ? 0 : -1; }
-  }
-  if (TLIST && !generic && !direct)      // every term of the plan fused: pointwise ops only, no libm shapes of the direct tier
-    hipLaunchKernelGGL((wfk_sample<T, CPLX, TLIST, false, false, NS>), g, b, 0, s, a);
-  else if (TLIST || direct)
-    hipLaunchKernelGGL((wfk_sample<T, CPLX, TLIST, true, true, NS>), g, b, 0, s, a);
-  else if (generic)
-    hipLaunchKernelGGL((wfk_sample<T, CPLX, false, true, false, NS>), g, b, 0, s, a);
-  else
-    hipLaunchKernelGGL((wfk_sample<T, CPLX, false, false, false, NS>), g, b, 0, s, a);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  if (!fn || (TLIST && gd == 1)) return false;
+  hipLaunchKernelGGL(fn, dim3((unsigned)blocks), wg, lds, s, a);
+  return true;
 }
 
 }  // namespace
 
-int wfk_launch_sampler(const KArgs& a, int32_t n_channels, int out_kind, bool tlist, int ns, bool lean,
-                       bool generic, bool direct, void* stream, std::string& err) {
+int wfk_launch_sampler(const KArgs& a, const SamplerPick& k, int32_t n_channels, void* stream, std::string& err) {
   if (a.chunk_base < 0 || a.chunk_base + a.n_chunks > (int64_t)n_channels * a.chunks_per_ch) { err = "chunk range outside the plan"; return WFK_EINVAL; }
   const int64_t blocks = ((a.n_chunks + 7) >> 3) << 3;   // see xcd_chunk()
   if (blocks == 0) return WFK_OK;
   if (blocks > 0x7fffffffLL) { err = "grid too large"; return WFK_EINVAL; }
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  if (!tlist) {
-    switch (out_kind) {
-      case WFK_OUT_F64: rc = launch<double, false, false, WFK_NS_GRID>(a, blocks, s, lean, generic, direct); break;
-      case WFK_OUT_F32: rc = launch<float, false, false, WFK_NS_GRID>(a, blocks, s, lean, generic, direct); break;
-      case WFK_OUT_C128: rc = launch<double, true, false, WFK_NS_GRID>(a, blocks, s, lean, generic, direct); break;
-      case WFK_OUT_C64: rc = launch<float, true, false, WFK_NS_GRID>(a, blocks, s, lean, generic, direct); break;
-      default: err = "bad out_kind"; return WFK_EINVAL;
-    }
-  } else if (ns == WFK_NS_TLIST_SMALL) {
-    switch (out_kind) {
-      case WFK_OUT_F64: rc = launch<double, false, true, WFK_NS_TLIST_SMALL>(a, blocks, s, false, generic, direct); break;
-      case WFK_OUT_F32: rc = launch<float, false, true, WFK_NS_TLIST_SMALL>(a, blocks, s, false, generic, direct); break;
-      case WFK_OUT_C128: rc = launch<double, true, true, WFK_NS_TLIST_SMALL>(a, blocks, s, false, generic, direct); break;
-      case WFK_OUT_C64: rc = launch<float, true, true, WFK_NS_TLIST_SMALL>(a, blocks, s, false, generic, direct); break;
-      default: err = "bad out_kind"; return WFK_EINVAL;
-    }
-  } else {
-    switch (out_kind) {
-      case WFK_OUT_F64: rc = launch<double, false, true, WFK_NS_TLIST>(a, blocks, s, false, generic, direct); break;
-      case WFK_OUT_F32: rc = launch<float, false, true, WFK_NS_TLIST>(a, blocks, s, false, generic, direct); break;
-      case WFK_OUT_C128: rc = launch<double, true, true, WFK_NS_TLIST>(a, blocks, s, false, generic, direct); break;
-      case WFK_OUT_C64: rc = launch<float, true, true, WFK_NS_TLIST>(a, blocks, s, false, generic, direct); break;
-      default: err = "bad out_kind"; return WFK_EINVAL;
-    }
-  }
-  if (rc) { err = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()); return WFK_EHIP; }
+  const bool built = wfk_with_kind(k.f32, k.cplx, [&](auto t, auto c) {
+    using T = decltype(t); constexpr bool CPLX = decltype(c)::value;
+    if (!k.tlist) return launch<T, CPLX, false, WFK_NS_GRID>(a, k, blocks, s);
+    if (k.ns == WFK_NS_TLIST_SMALL) return launch<T, CPLX, true, WFK_NS_TLIST_SMALL>(a, k, blocks, s);
+    return launch<T, CPLX, true, WFK_NS_TLIST>(a, k, blocks, s);
+  });
+  if (!built) { err = "no sampler build for " + wfk_pick_name(k); return WFK_EINVAL; }
+  if (hipGetLastError() != hipSuccess) { err = std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()); return WFK_EHIP; }
   return WFK_OK;
 }

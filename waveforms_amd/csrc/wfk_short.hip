@@ -35,6 +35,7 @@
 
 #include "wfk.h"
 #include "wfk_internal.h"
+#include "wfk_pick.h"
 #include "wfk_short_dev.h"
 
 namespace {
@@ -410,40 +411,35 @@ __global__ void __launch_bounds__(64, CPLX ? 2 : (FAM == 6 ? WFK_SH_WAVES6 : WFK
   }
 }
 
-template <typename T, bool CPLX>
-int launch_short(const SArgs& a, hipStream_t s) {
-  const int64_t blocks = ((a.n_chunks + 7) >> 3) << 3;
-  if (blocks == 0) return 0;
-  if (blocks > 0x7fffffffLL) return -2;
-  if (a.lds_samples > WFK_SH_LCAP) return -3;
-#define SH_LAUNCH(ACCV, FAMV) hipLaunchKernelGGL((wfk_sample_short<T, CPLX, ACCV, WFK_SH_R, FAMV>), dim3((unsigned)blocks), dim3(64), 0, s, a)
-  // (real float launches of family 0 run its packed-fp32 build, "family 3")
-  constexpr bool kPk = std::is_same<T, float>::value && !CPLX;
-  if (a.accumulate) {
-    if (a.fam <= 0) { if constexpr (kPk) { if (a.pk) SH_LAUNCH(true, 3); else SH_LAUNCH(true, 0); } else SH_LAUNCH(true, 0); }
-    else if (a.fam == 1) SH_LAUNCH(true, 1); else if (a.fam == 2) SH_LAUNCH(true, 2); else if (a.fam == 6) SH_LAUNCH(true, 6); else SH_LAUNCH(true, 4);
-  } else {
-    if (a.fam <= 0) { if constexpr (kPk) { if (a.pk) SH_LAUNCH(false, 3); else SH_LAUNCH(false, 0); } else SH_LAUNCH(false, 0); }
-    else if (a.fam == 1) SH_LAUNCH(false, 1); else if (a.fam == 2) SH_LAUNCH(false, 2); else if (a.fam == 6) SH_LAUNCH(false, 6); else SH_LAUNCH(false, 4);
+// one build of the kernel, the pick's: 0 / 1 / 2 / 4 / 6, and 3 = family 0 in packed fp32 (real float outputs only)
+template <typename T, bool CPLX, bool ACC>
+bool launch_short(const SArgs& a, int build, unsigned blocks, hipStream_t s) {
+#define SH_LAUNCH(FAMV) hipLaunchKernelGGL((wfk_sample_short<T, CPLX, ACC, WFK_SH_R, FAMV>), dim3(blocks), dim3(64), 0, s, a)
+  switch (build) {
+    case 0: SH_LAUNCH(0); return true;
+    case 1: SH_LAUNCH(1); return true;
+    case 2: SH_LAUNCH(2); return true;
+    case 3: if constexpr (std::is_same<T, float>::value && !CPLX) { SH_LAUNCH(3); return true; } return false;
+    case 4: SH_LAUNCH(4); return true;
+    case 6: SH_LAUNCH(6); return true;
   }
 #undef SH_LAUNCH
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  return false;
 }
 
 }  // namespace
 
-int wfk_launch_short(const SArgs& a, int out_kind, void* stream, std::string& err) {
+int wfk_launch_short(const SArgs& a, const SamplerPick& k, void* stream, std::string& err) {
   hipStream_t s = (hipStream_t)stream;
-  int rc;
-  switch (out_kind) {
-    case WFK_OUT_F64: rc = launch_short<double, false>(a, s); break;
-    case WFK_OUT_F32: rc = launch_short<float, false>(a, s); break;
-    case WFK_OUT_C128: rc = launch_short<double, true>(a, s); break;
-    case WFK_OUT_C64: rc = launch_short<float, true>(a, s); break;
-    default: err = "bad out_kind"; return WFK_EINVAL;
-  }
-  if (rc == -2) { err = "grid too large"; return WFK_EINVAL; }
-  if (rc == -3) { err = "short plan: unit longer than the staging array"; return WFK_EINVAL; }
-  if (rc) { err = std::string("short kernel launch failed: ") + hipGetErrorString(hipGetLastError()); return WFK_EHIP; }
+  const int64_t blocks = ((a.n_chunks + 7) >> 3) << 3;
+  if (blocks == 0) return WFK_OK;
+  if (blocks > 0x7fffffffLL) { err = "grid too large"; return WFK_EINVAL; }
+  if (a.lds_samples > WFK_SH_LCAP) { err = "short plan: unit longer than the staging array"; return WFK_EINVAL; }
+  const bool built = wfk_with_kind(k.f32, k.cplx, [&](auto t, auto c) {
+    return a.accumulate ? launch_short<decltype(t), decltype(c)::value, true>(a, k.fam, (unsigned)blocks, s)
+                        : launch_short<decltype(t), decltype(c)::value, false>(a, k.fam, (unsigned)blocks, s);
+  });
+  if (!built) { err = "short plan: no build for op family " + std::to_string(k.fam); return WFK_EINVAL; }
+  if (hipGetLastError() != hipSuccess) { err = std::string("short kernel launch failed: ") + hipGetErrorString(hipGetLastError()); return WFK_EHIP; }
   return WFK_OK;
 }
