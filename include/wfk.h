@@ -271,6 +271,12 @@ int wfk_iir_apply(wfk_iir_plan* plan, const void* in_dev, int64_t in_stride, voi
  * out of look-back polls (its outputs then hold NaN -- never silently: the same condition also fails the
  * NEXT wfk_iir_apply of the plan).  The plan switches to the three-launch form, so launching again works. */
 int wfk_iir_status(wfk_iir_plan* plan, void* hip_stream);
+/* What the next wfk_iir_apply launches, one entry per pass of a cut cascade, joined with " + ":
+ * "iir_onepass<T,NSEC,ORD,PLAIN>" (" persistent" behind it when the grid is a bounded set of waves per row),
+ * "iir_pass<T,NSEC,ORD>" for the three-launch form (0,0: the runtime-shaped build), "iir_scale<T>" for a pure gain,
+ * "" for n == 0.  The apply and the name read one decision; once a look-back timeout has been reported the name is
+ * that of the three-launch form.  The string belongs to the calling thread and lasts until its next call.         */
+const char* wfk_iir_kernel_name(const wfk_iir_plan* plan);
 int wfk_iir_plan_destroy(wfk_iir_plan* plan);
 
 /* -- IIR stage with one cascade PER ROW ------------------------------------------------------- */

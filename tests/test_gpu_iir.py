@@ -2,12 +2,15 @@
 initial)) [scipy.signal.sosfilt semantics] and predistort(filters=...) [lfilter +
 lfiltic], against golden outputs of the real reference (tests/golden/iir.npz), the
 oracle, and the reference's own test_filters closed form."""
+import functools
+import os
+
 import numpy as np
 import pytest
 from scipy.signal import butter, lfilter, lfiltic, sosfilt, tf2sos
 
 import cases
-from cases import FP32_TOL
+from cases import FP32_TOL, FP64_IIR_ORDER34_TOL, FP64_IIR_TOL
 import golden_io
 import waveforms_amd as wf
 from oracle import np_oracle
@@ -20,7 +23,6 @@ pytestmark = pytest.mark.gpu
 def _iir_form(request):
     """every test runs with the library's own choice (single pass where the shape allows: one or two
     biquads on rows of >= 8192 samples) and with the three-launch block scan forced"""
-    import os
     if request.param == 'three-launch':
         os.environ['WFK_IIR_ONEPASS'] = '0'
     yield
@@ -28,25 +30,51 @@ def _iir_form(request):
 IIR = golden_io.npz('iir.npz')
 
 
-def _lfilter_longdouble(b, a, x, initial):
-    """The lfilter recurrence (direct form II transposed, zi from lfiltic) in np.longdouble."""
+def _section_longdouble(b, a, x, zi, at=()):
+    """One direct-form-II-transposed section in np.longdouble: x (rows, n) -> y (rows, n), rows side by side, from the
+    state zi (rows, order).  -> (y, zf, {t: state after t samples for t in `at`}), all np.longdouble."""
     ld = np.longdouble
-    zi = lfiltic(b, a, np.full(len(a) - 1, initial), np.full(len(b) - 1, initial))
     m = max(len(a), len(b)) - 1
     bb = np.zeros(m + 1, dtype=ld)
     aa = np.zeros(m + 1, dtype=ld)
     bb[:len(b)] = np.asarray(b, dtype=ld) / ld(a[0])
     aa[:len(a)] = np.asarray(a, dtype=ld) / ld(a[0])
-    z = np.asarray(zi, dtype=ld).copy()
-    y = np.empty(len(x), dtype=ld)
-    for t in range(len(x)):
-        xx = ld(x[t])
-        yy = bb[0] * xx + z[0]
+    x = np.asarray(x, dtype=ld)
+    z = np.array(zi, dtype=ld).reshape(x.shape[0], m)
+    y = np.empty(x.shape, dtype=ld)
+    at, states = set(at), {}
+    for t in range(x.shape[1]):
+        xx = x[:, t]
+        yy = bb[0] * xx + z[:, 0] if m else bb[0] * xx
         for j in range(m - 1):
-            z[j] = bb[j + 1] * xx - aa[j + 1] * yy + z[j + 1]
-        z[m - 1] = bb[m] * xx - aa[m] * yy
-        y[t] = yy
-    return y.astype(np.float64)
+            z[:, j] = bb[j + 1] * xx - aa[j + 1] * yy + z[:, j + 1]
+        if m:
+            z[:, m - 1] = bb[m] * xx - aa[m] * yy
+        y[:, t] = yy
+        if t + 1 in at:
+            states[t + 1] = z.copy()
+    return y, z, states
+
+
+def _lfilter_longdouble(b, a, x, initial):
+    """The lfilter recurrence (direct form II transposed, zi from lfiltic) in np.longdouble."""
+    zi = lfiltic(b, a, np.full(len(a) - 1, initial), np.full(len(b) - 1, initial))
+    m = max(len(a), len(b)) - 1
+    zi = np.concatenate([zi, np.zeros(m - len(zi))])
+    return _section_longdouble(b, a, np.asarray(x)[None, :], zi[None, :])[0][0].astype(np.float64)
+
+
+def _three_launch():
+    """the module fixture's `three-launch` parameter (or a test's own cross-check) is in force"""
+    return os.environ.get('WFK_IIR_ONEPASS') == '0'
+
+
+def _assert_form(plan, single_pass='iir_onepass<'):
+    """every pass of the plan's next apply is in the form this run is about: the single pass under the library's own
+    choice (the caller has picked a shape that qualifies), iir_pass under WFK_IIR_ONEPASS=0"""
+    want = 'iir_pass<' if _three_launch() else single_pass
+    name = plan.kernel_name()
+    assert name and all(part.startswith(want) for part in name.split(' + ')), (name, want)
 
 
 def _configure(name):
@@ -190,6 +218,13 @@ def test_iir_batch_shapes_and_properties():
                     off += m
                 want[r] = y
             plan = _engine.IirPlan(sec, n, batch, np.float64)
+            # which form runs: rows below 8192 samples and sections of order > 4 take iir_pass; at 150_001 every cut
+            # of a cascade of first- and second-order sections has a state dimension <= 4 and takes the single pass
+            orders = [max(len(b), len(a)) - 1 for b, a in sec]
+            if n < 8192 or min(orders) > 4:
+                _assert_form(plan, single_pass='iir_pass<')
+            elif max(orders) <= 2:
+                _assert_form(plan)
             xd = torch.from_numpy(x).cuda()
             yd = torch.empty_like(xd)
             zid = torch.from_numpy(zi).cuda()
@@ -337,7 +372,6 @@ def test_single_pass_chained_scan(nsec, n, rows):
     read once; the default for these shapes).  Against scipy.signal.sosfilt with random initial state,
     final state, DC offset, in place, float32, and the three-launch form of the same plan
     (WFK_IIR_ONEPASS=0)."""
-    import os
     rng = np.random.default_rng(n + nsec)
     sos = butter(2 * nsec, 0.07, output='sos')
     secs = [(r[:3], r[3:]) for r in sos]
@@ -351,6 +385,7 @@ def test_single_pass_chained_scan(nsec, n, rows):
 
     def run(dtype, inplace=False):
         plan = _engine.IirPlan(secs, n, rows, dtype)
+        _assert_form(plan)
         es = np.dtype(dtype).itemsize
         dx, dy = _engine.DeviceBuffer(rows * n * es), _engine.DeviceBuffer(rows * n * es)
         dzi, dzf = _engine.DeviceBuffer(zi.nbytes), _engine.DeviceBuffer(zi.nbytes)
@@ -415,6 +450,7 @@ def test_first_order_cascades(nsec, n, rows):
     def run(dtype):
         plan = _engine.IirPlan(secs, n, rows, dtype)
         assert plan.state_dim == nsec
+        _assert_form(plan, single_pass=f'iir_onepass<{"double" if dtype is np.float64 else "float"},{nsec},1,')
         es = np.dtype(dtype).itemsize
         dx, dy = _engine.DeviceBuffer(rows * n * es), _engine.DeviceBuffer(rows * n * es)
         dzi, dzf = _engine.DeviceBuffer(zi.nbytes), _engine.DeviceBuffer(zi.nbytes)
@@ -438,13 +474,92 @@ def test_first_order_cascades(nsec, n, rows):
     assert np.max(np.abs(g32 - want)) <= FP32_TOL * pk
 
 
+TAIL_N = (8192, 8193, 8223, 8224, 8225, 10239, 10240, 10241)
+TAIL_SHAPES = {
+    'two_biquads': lambda: [(r[:3], r[3:]) for r in butter(4, 0.07, output='sos')],
+    'four_first_order': lambda: [distortion.exp_decay_filter(A, tau, 2e9)
+                                 for A, tau in ((0.03, 40e-9), (0.01, 900e-9), (-0.005, 20e-6), (0.02, 3e-7))],
+    'order3': lambda: [butter(3, 0.05)],
+}
+TAIL_ROWS, TAIL_INITIAL = 3, 0.25
+
+
+@functools.lru_cache(maxsize=None)
+def _tail_reference(shape):
+    """x (rows, max n), zi, and the np.longdouble recurrence on it, section by section from zi: y at the longest n and
+    the cascade's state after every n of TAIL_N.  The filter is causal, so the answer for a shorter n is the prefix:
+    one recurrence per shape serves all lengths and both dtypes.  -> (secs, x, zi, y, {n: zf})"""
+    secs = TAIL_SHAPES[shape]()
+    rng = np.random.default_rng(sorted(TAIL_SHAPES).index(shape) + 77)
+    x = rng.normal(size=(TAIL_ROWS, max(TAIL_N)))
+    orders = [max(len(b), len(a)) - 1 for b, a in secs]
+    zi = rng.normal(size=(TAIL_ROWS, sum(orders))) * 0.1
+    y = np.asarray(x, dtype=np.longdouble) - np.longdouble(TAIL_INITIAL)
+    zf, off = {n: [] for n in TAIL_N}, 0
+    for (b, a), m in zip(secs, orders):
+        y, _, states = _section_longdouble(b, a, y, zi[:, off:off + m], at=TAIL_N)
+        for n in TAIL_N:
+            zf[n].append(states[n])
+        off += m
+    y = (y + np.longdouble(TAIL_INITIAL)).astype(np.float64)
+    for arr in (x, zi, y):
+        arr.setflags(write=False)
+    return secs, x, zi, y, {n: np.concatenate(zf[n], axis=1).astype(np.float64) for n in TAIL_N}
+
+
+@pytest.mark.parametrize('n', TAIL_N)
+@pytest.mark.parametrize('shape', sorted(TAIL_SHAPES))
+def test_single_pass_tail_edges(shape, n):
+    """The single pass at its own edges: its chunk is 2048 samples, its lane block 32, and it starts at n = 8192.
+    Four whole chunks, a tail of one sample, a last block of 31 / 32 / 33 samples, a chunk edge -1 / 0 / +1: the
+    tail decides `cnt`, the `whole` split, and the lane that writes zf.  fp64 and fp32 against the np.longdouble
+    recurrence (random zi, zf, a DC level, applied twice for the epoch) and against the three-launch form."""
+    if _three_launch():
+        pytest.skip('three-launch form: the single pass is what this test is about')
+    secs, x, zi, ywant, zfwant = _tail_reference(shape)
+    x, want, wzf = x[:, :n], ywant[:, :n], zfwant[n]
+    rows = TAIL_ROWS
+
+    def run(dtype):
+        plan = _engine.IirPlan(secs, n, rows, dtype)
+        _assert_form(plan)
+        es = np.dtype(dtype).itemsize
+        dx, dy = _engine.DeviceBuffer(rows * n * es), _engine.DeviceBuffer(rows * n * es)
+        dzi, dzf = _engine.DeviceBuffer(zi.nbytes), _engine.DeviceBuffer(zi.nbytes)
+        dx.upload(np.ascontiguousarray(x.astype(dtype)))
+        dzi.upload(zi)
+        for _ in range(2):
+            dzf.upload(np.full(zi.shape, np.nan))           # (a lane that never writes zf must show)
+            assert plan.apply(dx.ptr, n, dy.ptr, n, dzi.ptr, dzf.ptr, TAIL_INITIAL)
+            assert plan.status()
+        got, zf = dy.download((rows, n), dtype), dzf.download(zi.shape, np.float64)
+        for b_ in (dx, dy, dzi, dzf):
+            b_.close()
+        plan.close()
+        return got, zf
+
+    tol = FP64_IIR_ORDER34_TOL if shape == 'order3' else FP64_IIR_TOL
+    pk, zpk = max(1.0, np.abs(want).max()), max(1.0, np.abs(wzf).max())
+    got, zf = run(np.float64)
+    g32, zf32 = run(np.float32)
+    err = (np.max(np.abs(got - want)) / pk, np.max(np.abs(zf - wzf)) / zpk,
+           np.max(np.abs(g32 - want)) / pk, np.max(np.abs(zf32 - wzf)) / zpk)
+    print(f'tail edges {shape} n={n}: y {err[0]:.3g} zf {err[1]:.3g} of peak; float y {err[2]:.3g} zf {err[3]:.3g}')
+    assert err[0] <= tol and err[1] <= tol, err
+    assert err[2] <= FP32_TOL and err[3] <= FP32_TOL, err
+    os.environ['WFK_IIR_ONEPASS'] = '0'        # the three-launch form of the same plan
+    try:
+        three, zf3 = run(np.float64)
+    finally:
+        del os.environ['WFK_IIR_ONEPASS']
+    assert np.max(np.abs(three - got)) <= 1e-12 * pk and np.max(np.abs(zf3 - zf)) <= 1e-12 * zpk
+
+
 @pytest.mark.parametrize('rows,n,first', [(64, 200_003, False), (130, 150_001, True)])
 def test_single_pass_persistent_waves(rows, n, first):
     """From 64 rows on the single pass runs as a bounded set of persistent waves per row walking the
     ticket counter (more chunks per row than waves per row): sosfilt / lfilter per row, in place,
     twice in a row (epochs), against the three-launch form."""
-    import os
-    from scipy.signal import lfilter
     rng = np.random.default_rng(rows)
     if first:
         secs = [(np.array([1.0 + 0.01 * k, -0.9 - 0.01 * k]), np.array([1.0, -0.95 + 0.02 * k])) for k in range(3)]
@@ -460,6 +575,8 @@ def test_single_pass_persistent_waves(rows, n, first):
 
     def run():
         plan = _engine.IirPlan(secs, n, rows, np.float64)
+        _assert_form(plan)
+        assert _three_launch() or plan.kernel_name().endswith(' persistent'), plan.kernel_name()
         dx = _engine.DeviceBuffer(rows * n * 8)
         for _ in range(2):
             dx.upload(x)
@@ -485,8 +602,7 @@ def test_lookback_timeout_is_an_error_not_silent_nans():
     forced here with WFK_IIR_SPIN=0 (no poll at all).  The launch's outputs hold NaN, wfk_iir_status says
     so, the plan switches to the three-launch form, and the second launch is correct; the Python stages
     (predistort, sample(filters=)) recover by themselves."""
-    import os
-    if os.environ.get('WFK_IIR_ONEPASS') == '0':
+    if _three_launch():
         pytest.skip('three-launch form: nothing to time out')
     rng = np.random.default_rng(3)
     n, rows = 300_000, 3
@@ -495,12 +611,14 @@ def test_lookback_timeout_is_an_error_not_silent_nans():
     x = rng.normal(size=(rows, n))
     want = np.stack([sosfilt(sos, r) for r in x])
     plan = _engine.IirPlan(secs, n, rows, np.float64)
+    assert plan.kernel_name().startswith('iir_onepass<double,2,2,'), plan.kernel_name()
     dx, dy = _engine.DeviceBuffer(x.nbytes), _engine.DeviceBuffer(x.nbytes)
     dx.upload(x)
     os.environ['WFK_IIR_SPIN'] = '0'
     try:
         plan.apply(dx.ptr, n, dy.ptr, n)
         assert plan.status() is False                       # reported ...
+        assert plan.kernel_name() == 'iir_pass<double,2,2>'  # ... and the name is that of the form the plan switched to
         assert np.isnan(dy.download((rows, n), np.float64)).any()   # ... and nothing plausible was written
         assert plan.status() is True                        # (the word is cleared by the check)
         plan.apply(dx.ptr, n, dy.ptr, n)                    # three-launch form now

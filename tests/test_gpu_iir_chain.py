@@ -133,6 +133,50 @@ def test_ragged_rows_piece_edges_inside_chunks_offsets_and_shifts(n, endpoint):
     si.close()
 
 
+# iir_sampled takes its chunks of 64 lane runs in rounds of 32 samples: 8192 samples in the dot-product form (runs of 128),
+# 16384 in the sweep form (runs of 256), and fuses from four chunks on.  Four whole chunks, a tail of one sample, a
+# last round of 31 / 32 / 33 samples, a chunk edge -1 / 0 / +1.
+_TAILS = [(0.1, 'iir_sampled<double,2,2,true>', n) for n in (32768, 32769, 32895, 32896, 32897, 40959, 40960, 40961)] + \
+         [(0.03, 'iir_sampled<double,2,2,false>', n) for n in (65536, 65537, 65791, 65792, 65793, 81919, 81920, 81921)]
+
+
+@pytest.mark.parametrize('fc,name,n', _TAILS)
+def test_fused_scan_tail_edges(fc, name, n):
+    """rows that end on and around the edges of the fused scan's own geometry, both scan forms, zf included: against
+    the oracle's samples through SciPy, and against the unfused path of the same plan type.
+
+    MI355X, fused - reference in fractions of the peak: dot-product form (lane runs of 128 samples) 5.6e-14 .. 4.0e-13,
+    sweep form (runs of 256) 1.7e-13 .. 3.0e-13, zf <= 8.8e-16.  The unfused path sits 1e-14 from the reference, so these
+    figures are also the distance between the two paths.  The sweep form measured 5.9e-13 .. 1.3e-12 and missed the
+    1e-12 cross-check at n = 65536, 65537 and 81920 while iir_sampled carried its Gaussian recurrence over a whole
+    256-sample run (the drift grows with the square of the steps); it restarts from exact seeds every 128 samples now."""
+    secs = [(r[:3], r[3:]) for r in butter(4, fc, output='sos')]
+    chans = [wl.sum_channel(wf, 6, 1000 + c) for c in range(2)]
+    grid = ('linspace', 0.0, 6 * wl.SPAN, n, False)
+    si = SampledIir(chans, grid, secs)
+    assert si.fused, si.why_not
+    assert si.plan.kernel_name() == name
+    x = _samples(chans, grid)
+    ref = [_cascade(secs, row) for row in x]
+    want, wzf = np.stack([r[0] for r in ref]), np.stack([r[1] for r in ref])
+    pk, zpk = max(1.0, np.abs(want).max()), max(1.0, np.abs(wzf).max())
+    got, zf = si.to_host(return_zf=True)
+    si.close()
+    os.environ['WFK_CHAIN_UNFUSED'] = '1'
+    try:
+        su = SampledIir(chans, grid, secs)
+        assert not su.fused and 'WFK_CHAIN_UNFUSED' in su.why_not
+        ugot, uzf = su.to_host(return_zf=True)
+        su.close()
+    finally:
+        del os.environ['WFK_CHAIN_UNFUSED']
+    err = (np.max(np.abs(got - want)) / pk, np.max(np.abs(zf - wzf)) / zpk,
+           np.max(np.abs(ugot - got)) / pk, np.max(np.abs(uzf - zf)) / zpk)
+    print(f'fused tail edges {name} n={n}: y {err[0]:.3g} zf {err[1]:.3g} of peak; unfused - fused y {err[2]:.3g} zf {err[3]:.3g}')
+    assert err[0] <= TOL and err[1] <= TOL, err
+    assert err[2] <= 1e-12 and err[3] <= 1e-12, err
+
+
 def test_run_length_follows_the_scan_form_and_short_rows_fall_back():
     """the dot-product form (transition powers of order 1: butter(4, 0.1)) runs 128 samples per lane and fuses from 32768
     samples on; the sweep form (slow poles: butter(4, 0.03)) runs 256 per lane and needs 65536 -- shorter rows take

@@ -107,6 +107,8 @@ def lib():
         l.wfk_iir_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP, C.c_double, VP]
         l.wfk_iir_plan_destroy.argtypes = [VP]
         l.wfk_iir_status.argtypes = [VP, VP]
+        l.wfk_iir_kernel_name.argtypes = [VP]
+        l.wfk_iir_kernel_name.restype = C.c_char_p
         l.wfk_iir_rows_plan_create.argtypes = [I32, VP, VP, VP, I64, I32, C.c_int, P(VP)]
         l.wfk_iir_rows_state_dim.argtypes = [VP]
         l.wfk_iir_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP, VP, VP]
@@ -485,6 +487,11 @@ class IirPlan(_Handle):
         """Synchronise `stream`; False if a single-pass launch since the last check ran into a look-back
         timeout (its outputs hold NaN; the plan has switched to the three-launch form: apply again)."""
         return _accepted(lib().wfk_iir_status(self._h, stream))
+
+    def kernel_name(self) -> str:
+        """what the next apply launches, one entry per pass of a cut cascade joined with ' + ':
+        'iir_onepass<T,NSEC,ORD,PLAIN>' (+ ' persistent'), 'iir_pass<T,NSEC,ORD>' (three launches), 'iir_scale<T>'"""
+        return lib().wfk_iir_kernel_name(self._h).decode()
 
 
 def pack_sections_rows(sections_per_row):

@@ -626,7 +626,9 @@ __global__ void __launch_bounds__(64, OP_WAVES) iir_onepass(const IirCoef c, con
 // OPS_RUN_SWEEP = 256 where it is the sweep (slow poles; double-double scans) -- taken in rounds of 32 with the sampler's
 // op state (phasor, Gaussian pair) and the filter state carried from round to round.  A sample costs ~10 VALU
 // instructions to evaluate, so the chunk is not kept between the two sweeps (that would be 64 KB per wave), it is
-// evaluated TWICE:
+// evaluated TWICE.  The carried op state starts from exact seeds every FOUR rounds (128 samples), in both run lengths: the
+// Gaussian pair g *= r, r *= q drifts with the square of the steps taken (8e-15 of peak at a run's first sample, 8e-14
+// at its 128th; carried over 256 it put the sweep form 1.3e-12 from the unfused path, 2.5e-13 since; +1.3 % on 256 x 1e6):
 //   pass 1  RUN / 32 rounds: evaluate 32, sweep on from the running state (zero at the run's start); then the in-wave
 //           scan of the 64 run states (TL = RUN-step transition), aggregate, look-back (as iir_onepass);
 //   pass 2  the rounds again from the true state v_(l-1) + TL^l S_in: evaluate, sweep, transpose through LDS, store.
@@ -852,7 +854,7 @@ __global__ void __launch_bounds__(64, OPS_WAVES) iir_sampled(const IirCoef c, co
     const int js = jrun + r * OP_LB;
     if (r * OP_LB >= nrel) break;                          // (wave-uniform: no lane has a sample in this round)
     T acc[OP_LB];
-    ops_round<T>(sa, C, s_par, pd, m, nops, shape_off, deg1, js, dbase, nrel, r == 0, prev_p, car, acc);
+    ops_round<T>(sa, C, s_par, pd, m, nops, shape_off, deg1, js, dbase, nrel, (r & 3) == 0, prev_p, car, acc);
     const int rest = nrel - js;
     if (PLAIN && chunk_end <= n) {                             // (wave-uniform: every run of the chunk is whole)
       const double* w = s_w + r * OP_LB * 4;
@@ -887,7 +889,7 @@ __global__ void __launch_bounds__(64, OPS_WAVES) iir_sampled(const IirCoef c, co
     const int js = jrun + r * OP_LB;
     if (r * OP_LB >= nrel) break;                          // (wave-uniform)
     T acc[OP_LB];
-    ops_round<T>(sa, C, s_par, pd, m, nops, shape_off, deg1, js, dbase, nrel, r == 0, prev_p, car, acc);
+    ops_round<T>(sa, C, s_par, pd, m, nops, shape_off, deg1, js, dbase, nrel, (r & 3) == 0, prev_p, car, acc);
     const int rest = nrel - js;                                // samples of the row from this lane's segment on
     if (rest >= OP_LB) {
 #pragma unroll
@@ -1181,19 +1183,27 @@ static void iir_launch_t(wfk_iir_plan* p, const void* in, int64_t is, void* out,
                      post);
 }
 
+// Does the three-launch form have a compile-time shaped iir_pass for this cascade?  (One to four biquads: sosfilt
+// cascades; one section of order 1..8: lfilter -- predistort(filters=) combines its sections into ONE polynomial.)
+// Otherwise the runtime-shaped build <T,0,0> runs it.  Read by the launch and by the name.
+static bool iir_pass_shaped(const IirCoef& c) {
+  for (int k = 1; k < c.nsec; ++k)
+    if (c.ord[k] != c.ord[0]) return false;
+  const int ns = c.nsec, od = c.ord[0];
+  return (od == 2 && ns >= 1 && ns <= 4) || (ns == 1 && od >= 1 && od <= 8);
+}
+
 template <typename T>
 static void iir_launch(wfk_iir_plan* p, const void* in, int64_t is, void* out, int64_t os,
                        const double* zi, double* zf, double initial, double post, hipStream_t s) {
   const IirCoef& c = p->c;
-  bool uniform = true;
-  for (int k = 1; k < c.nsec; ++k) uniform = uniform && c.ord[k] == c.ord[0];
   const int ns = c.nsec, od = c.ord[0];
-#define IIR_CASE(NS, OD) if (uniform && ns == NS && od == OD) return iir_launch_t<T, NS, OD>(p, in, is, out, os, zi, zf, initial, post, s)
-  IIR_CASE(1, 2); IIR_CASE(2, 2); IIR_CASE(3, 2); IIR_CASE(4, 2);      // sosfilt cascades
-  IIR_CASE(1, 1); IIR_CASE(1, 3); IIR_CASE(1, 4); IIR_CASE(1, 5); IIR_CASE(1, 6);  // lfilter
-  IIR_CASE(1, 7); IIR_CASE(1, 8);   // predistort(filters=) combines its sections into ONE polynomial
+  if (!iir_pass_shaped(c)) return iir_launch_t<T, 0, 0>(p, in, is, out, os, zi, zf, initial, post, s);
+#define IIR_CASE(NS, OD) if (ns == NS && od == OD) return iir_launch_t<T, NS, OD>(p, in, is, out, os, zi, zf, initial, post, s)
+  IIR_CASE(1, 2); IIR_CASE(2, 2); IIR_CASE(3, 2); IIR_CASE(4, 2);
+  IIR_CASE(1, 1); IIR_CASE(1, 3); IIR_CASE(1, 4); IIR_CASE(1, 5); IIR_CASE(1, 6);
+  IIR_CASE(1, 7); IIR_CASE(1, 8);
 #undef IIR_CASE
-  iir_launch_t<T, 0, 0>(p, in, is, out, os, zi, zf, initial, post, s);
 }
 
 // one launch of the single-pass form
@@ -1246,6 +1256,57 @@ static void op_launch_shape(wfk_iir_plan* p, const OpCall& k) {
   return op_launch<T, 4, 1>(p, k);
 }
 #endif
+
+// The grid of the next single-pass launch of `p`, decided once: iir_apply_impl launches it, wfk_iir_kernel_name names it.
+// sampled: iir_sampled (long chunks of 64 lane runs) instead of iir_onepass.
+struct OpShape {
+  int64_t nchunks;             // chunks per row
+  unsigned total;              // workgroups
+  int persist;                 // the grid is a bounded set of waves per row, each walking the row's ticket counter
+};
+
+static OpShape iir_op_shape(const wfk_iir_plan* p, bool sampled) {
+  // Few long rows: with one chunk per workgroup 2304 / rows chunks of a row are in flight, and a
+  // look-back reads every one of them.  Below OP_DEPTH_ROWS rows the grid is op_depth persistent waves
+  // per row instead (WFK_IIR_OP_DEPTH: experiments).
+  const int64_t ops_chunk = 64 * (int64_t)p->opL.run;
+  OpShape sh;
+  sh.nchunks = sampled ? (p->n + ops_chunk - 1) / ops_chunk : p->op_chunks;   // (iir_sampled: long chunks)
+  sh.total = (unsigned)(sh.nchunks * p->batch);
+  sh.persist = 0;
+  // from 64 rows on: about two waves per SIMD's worth of persistent waves (same box, 2 biquads, one
+  // chunk per workgroup vs this: 128 x 1e7 5.86 vs 5.41 ms, 256 x 1e7 10.8 vs 9.6, 512 x 1e6 2.15 vs
+  // 2.03, 1024 x 1e6 3.82 vs 3.74); fewer rows run faster with everything in flight
+  int depth = 0;
+  // (float rows under two biquads are the exception: 256 x 1e7 7.4 vs 8.4 ms)
+  if (p->batch >= 64 && p->batch <= 1152 && !(p->kind == WFK_OUT_F32 && p->c.nsec == 2)) {
+    depth = (int)((4608 + p->batch - 1) / p->batch);
+    depth = depth < 4 ? 4 : (depth > 36 ? 36 : depth);
+  }
+  if (const char* e = getenv("WFK_IIR_OP_DEPTH")) depth = atoi(e);
+  if (depth > 0 && (int64_t)depth < sh.nchunks) {
+    sh.total = (unsigned)(depth * p->batch);
+    sh.persist = 1;
+  }
+  return sh;
+}
+
+// What the next apply of `p` launches, one entry per pass of a cut cascade (wfk_iir_kernel_name)
+static std::string iir_plan_name(const wfk_iir_plan* p) {
+  if (p->n == 0) return "";
+  const std::string T = p->kind == WFK_OUT_F32 ? "float" : "double";
+  if (p->c.D == 0) return "iir_scale<" + T + ">";
+  if (!p->parts.empty()) {
+    std::string name;
+    for (const auto& q : p->parts) name += (name.empty() ? "" : " + ") + iir_plan_name(q.get());
+    return name;
+  }
+  const std::string shape = std::to_string(p->c.nsec) + "," + std::to_string(p->c.ord[0]);
+  if (p->onepass)
+    return "iir_onepass<" + T + "," + shape + "," + (p->op1.plain ? "true" : "false") + ">" +
+           (iir_op_shape(p, false).persist ? " persistent" : "");
+  return "iir_pass<" + T + "," + (iir_pass_shaped(p->c) ? shape : std::string("0,0")) + ">";
+}
 
 extern "C" {
 
@@ -1312,31 +1373,9 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
     if (hipMemsetAsync(p->op_ticket.get(), 0, (size_t)p->batch * 64, s) != hipSuccess)
       return wfk_fail(WFK_EHIP, "IIR ticket reset failed");
     const unsigned epoch = ++p->epoch;
-    // Few long rows: with one chunk per workgroup 2304 / rows chunks of a row are in flight, and a
-    // look-back reads every one of them.  Below OP_DEPTH_ROWS rows the grid is op_depth persistent waves
-    // per row instead (WFK_IIR_OP_DEPTH: experiments).
-    const int64_t ops_chunk = 64 * (int64_t)p->opL.run;
-    const int64_t nchunks = src ? (p->n + ops_chunk - 1) / ops_chunk : p->op_chunks;   // (iir_sampled: long chunks)
-    unsigned total = (unsigned)(nchunks * p->batch);
-    int persist = 0;
-    {
-      // from 64 rows on: about two waves per SIMD's worth of persistent waves (same box, 2 biquads, one
-      // chunk per workgroup vs this: 128 x 1e7 5.86 vs 5.41 ms, 256 x 1e7 10.8 vs 9.6, 512 x 1e6 2.15 vs
-      // 2.03, 1024 x 1e6 3.82 vs 3.74); fewer rows run faster with everything in flight
-      int depth = 0;
-      // (float rows under two biquads are the exception: 256 x 1e7 7.4 vs 8.4 ms)
-      if (p->batch >= 64 && p->batch <= 1152 && !(p->kind == WFK_OUT_F32 && p->c.nsec == 2)) {
-        depth = (int)((4608 + p->batch - 1) / p->batch);
-        depth = depth < 4 ? 4 : (depth > 36 ? 36 : depth);
-      }
-      if (const char* e = getenv("WFK_IIR_OP_DEPTH")) depth = atoi(e);
-      if (depth > 0 && (int64_t)depth < nchunks) {
-        total = (unsigned)(depth * p->batch);
-        persist = 1;
-      }
-    }
-    const OpCall call{src, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial, post, total, nchunks, epoch,
-                      persist, spin_limit, s};
+    const OpShape sh = iir_op_shape(p, src != nullptr);
+    const OpCall call{src, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial, post, sh.total, sh.nchunks, epoch,
+                      sh.persist, spin_limit, s};
 #ifdef OPS_ONLY_22     /* A/B builds (tools/iirchain_ablate.sh): one shape, a third of the compile time */
     op_launch<double, 2, 2>(p, call);
 #else
@@ -1372,6 +1411,14 @@ extern "C" int wfk_iir_apply(wfk_iir_plan* p, const void* in_dev, int64_t in_str
                              double initial, void* hip_stream) {
   return iir_apply_impl(p, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial, initial,
                         hip_stream);
+}
+
+/* what the next wfk_iir_apply launches; after a look-back timeout has been reported, the three-launch form */
+extern "C" const char* wfk_iir_kernel_name(const wfk_iir_plan* p) {
+  if (!p) return "";
+  static thread_local std::string name;
+  name = iir_plan_name(p);
+  return name.c_str();
 }
 
 }  // extern "C"

@@ -94,8 +94,9 @@ class IirStage:
         self.state_dim = self.plan.state_dim
 
     def kernel_name(self) -> str:
-        """'iir_rows_tile<T,NSEC,ORD>' for per-row cascades; the shared-cascade plan picks its kernels per launch"""
-        return self.plan.kernel_name() if self.per_row else 'iir_plan'
+        """'iir_rows_tile<T,NSEC,ORD>' for per-row cascades; for a shared cascade what its next apply launches
+        (`_engine.IirPlan.kernel_name`: 'iir_onepass<...>', 'iir_pass<...>', 'iir_scale<T>', one per pass)"""
+        return self.plan.kernel_name()
 
     def row_state(self, z, r: int):
         """row r's own state (scipy layout, its sections back to back) out of a (batch, state_dim) host array"""
