@@ -200,16 +200,8 @@ int wfk_set_device(int ordinal) {
   return WFK_OK;
 }
 
-namespace {
-// resets the compiler's thread-local "samples per lane of the time-list tier" on every way out of a scope
-struct TlistNsGuard {
-  explicit TlistNsGuard(int ns) { wfk_internal_tlist_ns(ns); }
-  ~TlistNsGuard() { wfk_internal_tlist_ns(0); }
-};
-}  // namespace
-
 static int plan_create_impl(const wfk_program* prog, const wfk_grid* grid, const double* tlist,
-                            int64_t n, wfk_plan** out) {
+                            int64_t n, const CompileRequest& req, wfk_plan** out) {
   wfk_plan* p = new (std::nothrow) wfk_plan();
   if (!p) return wfk_fail(WFK_ENOMEM, "out of host memory");
   std::string err;
@@ -220,9 +212,9 @@ static int plan_create_impl(const wfk_program* prog, const wfk_grid* grid, const
       int nt = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
       if (const char* e = std::getenv("WFK_COMPILE_THREADS")) nt = std::atoi(e);
       nt = std::min(nt, prog->n_channels / 8);
-      if (nt > 1) rc = wfk_compile_blocks(prog, grid, nt, p->h, err);
+      if (nt > 1) rc = wfk_compile_blocks(prog, grid, nt, p->h, err, req);
     }
-    if (rc == WFK_RETRY_STD) rc = wfk_compile(prog, grid, tlist, n, p->h, err);
+    if (rc == WFK_RETRY_STD) rc = wfk_compile(prog, grid, tlist, n, p->h, err, req);
   } catch (...) {
     delete p;
     throw;
@@ -246,8 +238,9 @@ static int plan_create_impl(const wfk_program* prog, const wfk_grid* grid, const
       wfk_internal_grid_times(grid, grid_t.data());
       HostPlan h2;
       std::string err2;
-      TlistNsGuard ns_guard(WFK_NS_TLIST_SMALL);
-      const int rc2 = wfk_compile(prog, nullptr, grid_t.data(), grid->n, h2, err2);
+      CompileRequest pointwise = req;
+      pointwise.tlist_ns = WFK_NS_TLIST_SMALL;
+      const int rc2 = wfk_compile(prog, nullptr, grid_t.data(), grid->n, h2, err2, pointwise);
       if (rc2 == WFK_OK) {
         h2.grid_as_tlist = true;
         h2.t0 = p->h.t0; h2.step = p->h.step; h2.last = p->h.last;     // introspection: the grid it stands for
@@ -274,12 +267,12 @@ static int plan_create_impl(const wfk_program* prog, const wfk_grid* grid, const
 }
 
 // No exception crosses the C boundary: the compiler and the upload allocate host vectors.
-static int plan_create(const wfk_program* prog, const wfk_grid* grid, const double* tlist,
-                       int64_t n, wfk_plan** out) {
+int wfk_internal_plan_create(const wfk_program* prog, const wfk_grid* grid, const double* tlist, int64_t n,
+                             const CompileRequest& req, wfk_plan** out) {
   if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
   try {
-    return plan_create_impl(prog, grid, tlist, n, out);
+    return plan_create_impl(prog, grid, tlist, n, req, out);
   } catch (const std::bad_alloc&) {
     return wfk_fail(WFK_ENOMEM, "out of host memory while compiling the plan");
   } catch (const std::exception& e) {
@@ -289,14 +282,14 @@ static int plan_create(const wfk_program* prog, const wfk_grid* grid, const doub
 
 int wfk_plan_create_grid(const wfk_program* prog, const wfk_grid* grid, wfk_plan** out) {
   if (!grid) return wfk_fail(WFK_EINVAL, "null grid");
-  return plan_create(prog, grid, nullptr, 0, out);
+  return wfk_internal_plan_create(prog, grid, nullptr, 0, CompileRequest(), out);
 }
 
 int wfk_plan_create_tlist(const wfk_program* prog, const double* t_host, int64_t n,
                           wfk_plan** out) {
   if (!t_host && n > 0) return wfk_fail(WFK_EINVAL, "null t_host");
   static const double dummy = 0.0;
-  return plan_create(prog, nullptr, t_host ? t_host : &dummy, n, out);
+  return wfk_internal_plan_create(prog, nullptr, t_host ? t_host : &dummy, n, CompileRequest(), out);
 }
 
 int wfk_plan_destroy(wfk_plan* p) {

@@ -131,28 +131,72 @@ struct BlockBuilder {
   size_t size() const { return WFK_BLK_HDR + body.size() + tables.size() + 1; }
 };
 
+// What one compile of the retry ladder (compile_ladder) runs with, next to the caller's CompileRequest
+struct Attempt {
+  bool allow_corr;         // far carriers may stay fused with the per-sample rounding correction (false: they go to libm)
+  int want_short;          // -1 = decide the short tier from the mean live piece length (grid plans), 0 = never
+  bool no_short_corr;      // second attempt at a short plan whose corrected carriers met ops family 6 does not hold
+  bool no_chirp;           // second compile of a plan that mixes corrected carriers and chirps
+  int lane_stride = 64;    // samples between a lane's consecutive samples ...
+  int ns_override = 0;     // ... and samples per lane (0: the tier's own): wfk_compile_geom
+};
+
+// ---- environment switches: experiment, validation and tuning knobs, read once per plan ------------------------------
+// Three parsing rules, one per switch as it always was: "set at all", "first character is 1", integer in a range.
+bool env_set(const char* name) { return std::getenv(name) != nullptr; }
+bool env_is1(const char* name) { const char* e = std::getenv(name); return e && e[0] == '1'; }
+int env_1_to_64(const char* name) {          // 0: unset or out of range (the switch is ignored then)
+  const char* e = std::getenv(name); const int v = e ? std::atoi(e) : 0; return v >= 1 && v <= 64 ? v : 0;
+}
+struct CompileEnv {
+  bool no_sinc_tab = env_set("WFK_NO_SINC_TAB");
+  bool no_moll_rec = env_set("WFK_NO_MOLL_REC");
+  bool no_interp_grid = env_set("WFK_NO_INTERP_GRID");
+  bool no_interp_lin = env_set("WFK_NO_INTERP_LIN");
+  bool no_short_cmul = env_set("WFK_NO_SHORT_CMUL");
+  bool no_short_chirp = env_set("WFK_NO_SHORT_CHIRP");
+  bool no_short_multi = env_set("WFK_NO_SHORT_MULTI");
+  bool no_lean_multi = env_set("WFK_NO_LEAN_MULTI");
+  bool no_short_envmul = env_set("WFK_NO_SHORT_ENVMUL");
+  bool no_bank = env_set("WFK_NO_BANK");
+  bool no_short_xchirp = env_set("WFK_NO_SHORT_XCHIRP");
+  bool no_short_erftab = env_set("WFK_NO_SHORT_ERFTAB");
+  bool no_short_corr = env_set("WFK_NO_SHORT_CORR");
+  bool keep_mixed_short = env_set("WFK_KEEP_MIXED_SHORT");   // a short plan that hands many samples on stays a short plan
+  bool has_tlsmall_limit = env_set("WFK_TLSMALL_LIMIT");     // time lists: the phase bound of the cheap reduction ...
+  double tlsmall_limit = has_tlsmall_limit ? std::atof(std::getenv("WFK_TLSMALL_LIMIT")) : 0.0;   // ... overridden
+  bool disable_fast = env_is1("WFK_DISABLE_FAST");           // validation / A-B: every factor with device libm even on a grid
+  bool disable_corr = env_is1("WFK_DISABLE_CORR");
+  bool disable_chirp = env_is1("WFK_DISABLE_CHIRP");
+  bool disable_lean = env_is1("WFK_DISABLE_LEAN");
+  bool disable_fuse = env_is1("WFK_DISABLE_FUSE");
+  bool disable_tlfuse = env_is1("WFK_DISABLE_TLFUSE");       // time lists: every factor on device libm, as before they fused
+  bool disable_expfuse = env_is1("WFK_DISABLE_EXPFUSE");
+  bool disable_erfmul = env_is1("WFK_DISABLE_ERFMUL");
+  bool disable_fmul = env_is1("WFK_DISABLE_FMUL");
+  bool disable_mixed = env_is1("WFK_DISABLE_MIXED");
+  int short_mode = std::getenv("WFK_SHORT") ? std::atoi(std::getenv("WFK_SHORT")) : -1;   // 0: never, 1: whatever the piece length
+  int64_t short_maxlen = std::getenv("WFK_SHORT_MAXLEN") ? std::atoll(std::getenv("WFK_SHORT_MAXLEN")) : 1536;   // tools/short_crossover.py
+  int tpc = env_1_to_64("WFK_TPC");                          // tuning overrides: tiles per chunk, ...
+  int tpc_f32 = env_1_to_64("WFK_TPC_F32");                  // ... the float launch's cap on them, ...
+  int sh_upc = env_1_to_64("WFK_SH_UPC");                    // ... the short tier's units per chunk
+};
+struct ChunkRule {             // what a launch's chunking depends on beyond the plan's own tables
+  int32_t total_channels;      // channels of the whole job (wfk_compile_blocks: of all blocks, so that their tables concatenate)
+  int32_t lean_units_max;      // most state units of a lean piece (phasors + envelopes)
+  bool has_bank;               // some piece holds a run of bare carriers (tone loop): longer chunks pay there
+  int tpc;                     // WFK_TPC (0: none)
+};
+struct ShortCounts { int64_t short_pieces, foreign_pieces, short_samples, foreign_samples; };   // what the piece loop took / handed on
+
 }  // namespace
 
-static thread_local bool g_no_short_corr = false;   // second attempt at a short plan whose corrected carriers met ops family 6 does not hold
-static thread_local bool g_no_short_fmul = false;   // the FIR chain's sampler plan: fir_short has no table / mollifier multipliers, such pieces stay with the general kernel
-void wfk_internal_no_short_fmul(bool on) { g_no_short_fmul = on; }
-static thread_local bool g_no_chirp = false;   // second compile of a plan that mixes corrected carriers and chirps
-static thread_local bool g_keep_mixed_short = false;   // the FIR chain's sampler plan: fir_short fuses the short pieces, the rest is copied in
-void wfk_internal_keep_mixed_short(bool on) { g_keep_mixed_short = on; }
-static thread_local int g_tlist_ns = 0;        // samples per lane of this thread's next time-list compiles (0: by size)
-// wfk_compile_blocks: this thread compiles a BLOCK of the channels of a bigger job -- the program's channel arrays are
-// views into the job's (ch_member_off does not start at 0), the job was validated once by the caller, and the
-// launch geometry (tiles per chunk) is decided on the job's channel count, so that the blocks' tables concatenate
-static thread_local int32_t g_block_total_channels = 0;
-void wfk_internal_tlist_ns(int ns) { g_tlist_ns = ns; }
 // the sample times of a grid, as NumPy forms them (this file is built -ffp-contract=off)
 void wfk_internal_grid_times(const wfk_grid* g, double* out) {
   const TimeAxis ax{g, nullptr, g->n};
   for (int64_t i = 0; i < g->n; ++i) out[i] = ax.at(i);
 }
 
-// want_short: -1 = decide from the mean live piece length (grid plans), 0 = never.  Returns
-// WFK_RETRY_STD when the short geometry was chosen but some piece cannot run in it.
 // a vector of at most N elements on the stack (the fusion pass runs per term: heap traffic there was a third of a compile)
 template <class T, int N>
 struct SmallVec {
@@ -189,119 +233,8 @@ struct PhaseTimer {
   ~PhaseTimer() { mark("rest"); }
 };
 
-static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double* tlist,
-                        int64_t n_tlist, HostPlan& H, std::string& err, bool allow_corr,
-                        int lane_stride = 64, int ns_override = 0, int want_short = 0);
-
-// Grid plan for another evaluation geometry: lanes `lane_stride` samples apart, `ns` samples per
-// lane (the sampler fused into the FIR transform walks a window with stride 256, wfk_fir_sampled.hip).
-// Only the piece / parameter tables are meaningful in the result; H.lean tells whether every piece
-// is one block of fused ops (the only form that kernel evaluates).
-int wfk_compile_geom(const wfk_program* P, const wfk_grid* grid, int lane_stride, int ns, HostPlan& H,
-                     std::string& err) {
-  return compile_impl(P, grid, nullptr, 0, H, err, false, lane_stride, ns);
-}
-
-int wfk_compile(const wfk_program* P, const wfk_grid* grid, const double* tlist,
-                int64_t n_tlist, HostPlan& H, std::string& err) {
-  // Carriers whose phase is sensitive to NumPy's grid rounding (far from t = 0) stay fused with a
-  // first-order per-sample correction, which only the lean kernel implements.  A plan that turns
-  // out not to be lean is compiled again with such carriers on the exact (libm) path.
-  // Plans whose live pieces are short (AWG sample rates: tens to hundreds of samples per pulse) are
-  // compiled for the contiguous-lane geometry of wfk_short.hip first; a piece that tier cannot take
-  // (generic terms, erf edges, corrected carriers) sends the whole plan back to the standard tiers.
-  int rc = compile_impl(P, grid, tlist, n_tlist, H, err, true, 64, 0, -1);
-  if (rc == WFK_OK && H.shortp && H.short_corr && H.short_fam != 6) {
-    // corrected carriers next to closing ops / chirps / tables: no family of the short tier holds both -- the attempt
-    // again without the tier's correction (those carriers' pieces then go the way they went before family 6)
-    g_no_short_corr = true;
-    H = HostPlan();
-    rc = compile_impl(P, grid, tlist, n_tlist, H, err, true, 64, 0, -1);
-    g_no_short_corr = false;
-  }
-  const bool gave_up = rc == WFK_RETRY_STD;
-  const double mean_len = H.mean_piece_len;      // (of the first compile: the later ones do not take the short-tier decision)
-  if (rc == WFK_RETRY_STD) rc = compile_impl(P, grid, tlist, n_tlist, H, err, true);
-  else if (rc == WFK_OK && H.shortp && H.short_needs_corr) {
-    // far from t = 0 fast carriers need the per-sample rounding correction, which only the lean kernel
-    // has: where the standard tiers can run the plan lean (pieces long enough for its recurrences) they
-    // win; otherwise the short tier keeps what it can take and libm serves those carriers either way
-    HostPlan S;
-    std::string e2;
-    if (compile_impl(P, grid, tlist, n_tlist, S, e2, true) == WFK_OK && (S.lean || S.mixed)) H = std::move(S);
-  }
-  if (rc == WFK_OK && !H.shortp && H.n_corr > 0 && !H.lean && !H.mixed) rc = compile_impl(P, grid, tlist, n_tlist, H, err, false);
-  if (rc == WFK_OK && !H.shortp && H.n_corr > 0 && H.lean_fam >= 2) {
-    // corrected carriers (far from t = 0) and fused chirps in one plan: the lean kernel is not instantiated
-    // for that combination; the chirps take the general path
-    g_no_chirp = true;
-    rc = compile_impl(P, grid, tlist, n_tlist, H, err, true);
-    if (rc == WFK_OK && H.n_corr > 0 && !H.lean && !H.mixed) rc = compile_impl(P, grid, tlist, n_tlist, H, err, false);
-    g_no_chirp = false;
-  }
-  // pieces of AWG-rate length that the short tier could not take: the standard tiers walk every piece over whole wave
-  // tiles of 1024 samples (wfk_api.cpp: such grid plans are evaluated pointwise instead)
-  // (not where the standard compile came out lean: chirp pulses stay on the lean kernel's chirp family, measured
-  //  12.6 ms against 17.6 pointwise on 2048 x 1e5 at 2 GS/s)
-  //  12.6 ms against 17.6 pointwise on 2048 x 1e5 at 2 GS/s; and only for pieces well below a wave tile: from a few
-  //  hundred samples per piece on, the general kernel's per-factor fast paths cost less than pointwise libm)
-  if (rc == WFK_OK) H.short_gave_up = gave_up && grid != nullptr && !H.lean && !H.mixed && mean_len > 0.0 && mean_len < 192.0;
-  // A short plan that hands more than a few per cent of its samples on: on 2e8 samples the general kernel's launch over those
-  // pieces costs ~1.25 ms per per cent (every piece over a wave tile) next to 0.4 ms for the short pieces; evaluated pointwise
-  // the fused pieces take ~4.5 ms and the rest 0.34 ms per per cent (rocprofv3 --stats, one exponential chirp in ten
-  // pulses: 12.9 -> 7.9 ms) -- break-even near 4.5 %
-  if (rc == WFK_OK && grid && H.shortp && H.mixed && H.foreign_frac >= 0.05 && mean_len > 0.0 && mean_len < 192.0 &&
-      !g_keep_mixed_short && !std::getenv("WFK_KEEP_MIXED_SHORT"))
-    H.short_gave_up = true;
-  return rc;
-}
-
-static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double* tlist,
-                        int64_t n_tlist, HostPlan& H, std::string& err, bool allow_corr,
-                        int lane_stride, int ns_override, int want_short) {
-  PhaseTimer ptimer;
-  if (!P || (!grid && !tlist && n_tlist != 0)) { err = "null program or time axis"; return WFK_EINVAL; }
-  if (P->n_channels < 0 || P->n_members < 0) { err = "negative counts"; return WFK_EINVAL; }
-  TimeAxis ax{grid, tlist, grid ? grid->n : n_tlist};
-  if (ax.n < 0) { err = "negative sample count"; return WFK_EINVAL; }
-  H = HostPlan();
-  H.tlist = grid == nullptr;
-  H.n_channels = P->n_channels;
-  H.n = ax.n;
-  if (grid) {
-    H.t0 = grid->t0; H.step = grid->step; H.last = grid->last; H.has_last = grid->has_last; H.i0 = grid->i0;
-    if (grid->i0 < 0) { err = "negative grid.i0"; return WFK_EINVAL; }
-    if (ax.n > 1 && !(grid->step > 0)) { err = "grid step must be positive"; return WFK_EINVAL; }
-  }
-  H.ns = H.tlist ? (g_tlist_ns > 0 ? g_tlist_ns : (ax.n < WFK_TLIST_SMALL_N ? WFK_NS_TLIST_SMALL : WFK_NS_TLIST)) : WFK_NS_GRID;
-  if (ns_override > 0 && !H.tlist) H.ns = ns_override;
-  H.tile = WFK_WG * H.ns;
-  int NS = H.ns;
-  double dstride = grid ? (double)lane_stride * grid->step : 0.0;  // time between a lane's samples
-  bool shortm = false;          // the plan is compiled for the short tier (decided after the piece search)
-  bool cur_short = false;       // ... and the piece being built uses its contiguous-lane geometry
-  const int lean_par_cap = ns_override > 0 ? WFK_CHAIN_PAR : WFK_LEAN_PAR;
-  // (experiment switches, read once per compile: a getenv per piece is a scan of the environment per piece)
-  const bool env_no_sinc_tab = std::getenv("WFK_NO_SINC_TAB") != nullptr;
-  const bool env_no_moll_rec = std::getenv("WFK_NO_MOLL_REC") != nullptr;
-  const bool env_no_interp_grid = std::getenv("WFK_NO_INTERP_GRID") != nullptr;
-  const bool env_no_interp_lin = std::getenv("WFK_NO_INTERP_LIN") != nullptr;
-  const bool env_no_short_cmul = std::getenv("WFK_NO_SHORT_CMUL") != nullptr;
-  const bool env_no_short_chirp = std::getenv("WFK_NO_SHORT_CHIRP") != nullptr;
-  const bool env_no_short_multi = std::getenv("WFK_NO_SHORT_MULTI") != nullptr;
-  const bool env_no_lean_multi = std::getenv("WFK_NO_LEAN_MULTI") != nullptr;
-  const bool env_no_short_envmul = std::getenv("WFK_NO_SHORT_ENVMUL") != nullptr;
-  const bool env_no_bank = std::getenv("WFK_NO_BANK") != nullptr;
-  const char* const env_tlsmall_limit = std::getenv("WFK_TLSMALL_LIMIT");
-  const bool env_no_short_xchirp = std::getenv("WFK_NO_SHORT_XCHIRP") != nullptr;
-  const bool env_no_short_erftab = std::getenv("WFK_NO_SHORT_ERFTAB") != nullptr;
-  const bool env_no_short_corr = std::getenv("WFK_NO_SHORT_CORR") != nullptr || g_no_short_corr;
-  // validation / A-B switch: evaluate every factor with device libm even on a grid
-  const char* nofast_env = std::getenv("WFK_DISABLE_FAST");
-  const bool nofast = nofast_env && nofast_env[0] == '1';
-
-  if (g_block_total_channels == 0) {
-  // ---- validate structure ----------------------------------------------------
+// ---- validate structure ----------------------------------------------------
+static int validate_program(const wfk_program* P, std::string& err) {
   auto offsets_ok = [](const auto* off, int64_t count, int64_t total) {
     if (off[0] != 0 || off[count] != total) return false;
     for (int64_t i = 0; i < count; ++i)
@@ -317,10 +250,9 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
     err = "offset arrays must start at 0, be non-decreasing and end at the element counts";
     return WFK_EINVAL;
   }
-  for (int32_t c = 0; c < P->n_channels; ++c) {
+  for (int32_t c = 0; c < P->n_channels; ++c)
     if (P->ch_member_off[c] > P->ch_member_off[c + 1]) { err = "ch_member_off not monotone"; return WFK_EINVAL; }
-    if (std::isnan(P->ch_clip_lo[c]) || std::isnan(P->ch_clip_hi[c])) { err = "NaN clip"; return WFK_EINVAL; }
-  }
+    else if (std::isnan(P->ch_clip_lo[c]) || std::isnan(P->ch_clip_hi[c])) { err = "NaN clip"; return WFK_EINVAL; }
   for (int32_t m = 0; m < P->n_members; ++m) {
     int32_t a = P->mb_piece_off[m], b = P->mb_piece_off[m + 1];
     if (b <= a) { err = "member without pieces"; return WFK_EINVAL; }
@@ -364,10 +296,12 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
       err = "derivative order out of range"; return WFK_EINVAL;
     }
   }
+  return WFK_OK;
+}
 
-  }
-  ptimer.mark("validate");
-  // ---- searchsorted per member ----------------------------------------------
+// ---- searchsorted per member, then the geometry: short tier? -------------------------------------
+// Writes H.member_idx and H.mean_piece_len; returns whether the plan is compiled for the short tier.
+static bool search_members(const wfk_program* P, const TimeAxis& ax, const CompileEnv& env, const Attempt& at, HostPlan& H) {
   H.member_idx.resize(P->n_members);
   for (int32_t c = 0; c < P->n_channels; ++c)
     for (int32_t m = P->ch_member_off[c]; m < P->ch_member_off[c + 1]; ++m) {
@@ -375,38 +309,197 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
       for (int32_t p = P->mb_piece_off[m]; p < P->mb_piece_off[m + 1]; ++p)
         idx.push_back(ax.search_left(P->ch_tshift[c], P->pc_bound[p]));
     }
-
-  ptimer.mark("searchsorted");
-  // ---- geometry: short tier? ---------------------------------------------------------------------
   // Mean length of the live member pieces (samples).  Below WFK_SH_MAXLEN the plan is compiled for
   // the contiguous-lane geometry: lane stride = one sample, WFK_SH_R samples per lane.
   // (the tier's records and the fir_short window entries hold sample indices as 32-bit words: a row of
   // 2^31 samples or more stays on the standard tiers, which index in 64 bits)
-  if (want_short != 0 && grid && !H.tlist && !nofast && ns_override == 0 && ax.n > 0 && ax.n < ((int64_t)1 << 31)) {
-    const char* e = std::getenv("WFK_SHORT");          // 0: never, 1: whatever the piece length
-    const int mode = e ? std::atoi(e) : -1;
-    int64_t live = 0, live_samples = 0;
-    for (int32_t m = 0; m < P->n_members; ++m) {
-      const auto& idx = H.member_idx[m];
-      int64_t prev = 0;
-      for (size_t k = 0; k < idx.size(); ++k) {
-        const int32_t p = P->mb_piece_off[m] + (int32_t)k;
-        if (idx[k] > prev && P->pc_term_off[p + 1] > P->pc_term_off[p]) { ++live; live_samples += idx[k] - prev; }
-        prev = std::max(prev, idx[k]);
+  if (at.want_short == 0 || !ax.g || env.disable_fast || at.ns_override != 0 || ax.n <= 0 || ax.n >= ((int64_t)1 << 31))
+    return false;
+  int64_t live = 0, live_samples = 0;
+  for (int32_t m = 0; m < P->n_members; ++m) {
+    const auto& idx = H.member_idx[m];
+    int64_t prev = 0;
+    for (size_t k = 0; k < idx.size(); ++k) {
+      const int32_t p = P->mb_piece_off[m] + (int32_t)k;
+      if (idx[k] > prev && P->pc_term_off[p + 1] > P->pc_term_off[p]) { ++live; live_samples += idx[k] - prev; }
+      prev = std::max(prev, idx[k]);
+    }
+  }
+  H.mean_piece_len = live > 0 ? (double)live_samples / (double)live : 0.0;
+  return env.short_mode != 0 && live > 0 && (env.short_mode == 1 || live_samples < env.short_maxlen * live);
+}
+
+// ---- workgroup chunking ------------------------------------------------------
+static void chunking(const HostPlan& H, const ChunkRule& R, bool lean_geom, int32_t& tile, int32_t& tiles_per_chunk,
+                     int64_t& chunks_per_ch, std::vector<int32_t>& chunk_first, int lean_cap = WFK_LEAN_TPC, int64_t lean_div = 2048) {
+  tile = (lean_geom ? 64 : WFK_WG) * H.ns;
+  const int64_t tiles_per_ch = (H.n + tile - 1) / tile;
+  const int64_t total_tiles = tiles_per_ch * R.total_channels;
+  // lean: one wave per workgroup; ~2-3k workgroups already fill 256 CUs x 12 waves.  Longer
+  // chunks amortise the exact seeds, shorter ones keep the set of regions being written at
+  // any moment compact, which is what the HBM write rate depends on:
+  // measured best at 8 tiles (= one seed per chunk) on the headline config while a degree-1 op cost
+  // 12 instructions per sample, at 5 since the phasor fold (8: same box 3.19 / 6: 3.11 / 5: 3.07 / 4: 3.16 ms);
+  // 4 on C2.
+  // Pieces of many ops (multi-tone pulses): a chunk's first tile seeds EVERY op exactly (libm: ~200 instructions
+  // each), which at 5 tiles per chunk is as much work as the ops' own arithmetic -- longer chunks there
+  // (ten tones per pulse, same box: 5 / 10 / 20 / 40 tiles 2.16 / 1.95 / 1.87 / 1.84 ms; four tones 1.34 / 1.27 / 1.22)
+  if (lean_geom && lean_cap == WFK_LEAN_TPC && R.lean_units_max >= 5 && R.has_bank) lean_cap = 20;
+  const int64_t tpc = total_tiles / (lean_geom ? lean_div : 8192);
+  tiles_per_chunk = (int32_t)std::min<int64_t>(lean_geom ? lean_cap : 16, std::max<int64_t>(1, tpc));
+  if (R.tpc) tiles_per_chunk = R.tpc;   // tuning override (WFK_TPC)
+  chunks_per_ch = (tiles_per_ch + tiles_per_chunk - 1) / tiles_per_chunk;
+  chunk_first.assign((size_t)(chunks_per_ch * H.n_channels), 0);
+  const int64_t chunk_samples = (int64_t)tiles_per_chunk * tile;
+  for (int32_t c = 0; c < H.n_channels; ++c) {
+    int32_t p = H.channels[c].piece_begin;
+    for (int64_t k = 0; k < chunks_per_ch; ++k) {
+      int64_t g0 = k * chunk_samples;
+      while (p < H.channels[c].piece_end - 1 && H.pieces[p].stop <= g0) ++p;
+      chunk_first[(size_t)(c * chunks_per_ch + k)] = p;
+    }
+  }
+}
+
+// ---- short tier: wave units and lane slots ------------------------------------
+static void short_chunks(HostPlan& H, const CompileEnv& env) {   // workgroup = one wave walking `units_per_chunk` consecutive units
+  if (H.s_slots.empty()) H.s_slots.push_back(0);
+  H.s_units_per_chunk = env.sh_upc ? env.sh_upc : (int32_t)std::min<int64_t>(6, std::max<int64_t>(1, (int64_t)H.s_units.size() / 8192));
+}
+static int short_tier_tables(HostPlan& H, const ShortCounts& N, const ChunkRule& R, const CompileEnv& env) {
+  // Mostly pieces the short tier cannot take (e.g. carriers that need the lean kernel's grid-rounding
+  // correction far from t = 0): the standard tiers serve the whole plan better
+  if (N.foreign_samples > N.short_samples || (N.short_pieces == 0 && N.foreign_pieces > 0)) return WFK_RETRY_STD;
+  H.shortp = true;
+  H.lean = false;
+  // corrected carriers live in family 6 = family 0 + the correction: with closing ops, chirps or tables in the same plan
+  // the carriers go back to the tiers that have both
+  if (H.short_corr && H.short_fam != 0) H.short_needs_corr = true;
+  if (H.short_corr && H.short_fam == 0) H.short_fam = 6;
+  H.mixed = N.foreign_pieces > 0;       // foreign pieces: a second launch of the general kernel
+  H.foreign_frac = N.short_samples > 0 ? (double)N.foreign_samples / (double)(N.short_samples + N.foreign_samples) : 0.0;
+  H.tile = 64 * WFK_SH_R;
+  for (int32_t c = 0; c < H.n_channels; ++c) {
+    ShortUnit U{};
+    auto fresh = [&](int64_t j0) {
+      U = ShortUnit{};
+      U.ch = c; U.j0 = j0; U.slot0 = (int32_t)H.s_slots.size(); U.rec0 = -1;
+      U.offset = H.channels[c].offset; U.clip_lo = H.channels[c].clip_lo; U.clip_hi = H.channels[c].clip_hi;
+      U.do_clip = H.channels[c].do_clip;
+    };
+    fresh(0);
+    auto close = [&](int64_t next_j0) {
+      if (U.n_samples > 0) {
+        if (U.n_slots > 0) H.s_lds_samples = std::max(H.s_lds_samples, U.n_samples);
+        if (U.rec0 < 0) U.rec0 = 0;
+        if (U.n_slots > 0) {
+          // LDS staging layout of this unit (wfk_short.hip): plain or padded by one element per 16,
+          // whichever spreads the lanes' first elements over more of the 16 bank pairs
+          int plain[16] = {0}, padded[16] = {0}, wp = 0, wq = 0;
+          for (int32_t k = 0; k < U.n_slots; ++k) {
+            const int o = (int)((H.s_slots[(size_t)U.slot0 + k] >> 16) & 0x3ff);
+            wp = std::max(wp, ++plain[o & 15]);
+            wq = std::max(wq, ++padded[(o + (o >> 4)) & 15]);
+          }
+          if (wq < wp) U.gaps |= 2;
+        }
+        H.s_units.push_back(U);
+      }
+      fresh(next_j0);
+    };
+    for (int32_t pi = H.channels[c].piece_begin; pi < H.channels[c].piece_end; ++pi) {
+      const DevPiece& D = H.pieces[pi];
+      if (D.n_blk != 0 && !(D.flags & WFK_PF_SHORT)) {   // the general kernel's piece: no unit covers it
+        close(D.stop);
+        continue;
+      }
+      if (D.n_blk == 0) {
+        // zero stretch: rides in the current unit's range while it fits, long ones as pure-fill units
+        int64_t z0 = D.start, left = D.stop - D.start;
+        if (U.n_slots > 0) {
+          const int64_t take = std::min<int64_t>(left, WFK_SH_LCAP - U.n_samples);
+          U.n_samples += (int32_t)take; U.gaps |= 1;
+          z0 += take; left -= take;
+          if (left > 0) close(z0);
+        }
+        while (left >= WFK_SH_LCAP / 2) {
+          const int64_t take = std::min<int64_t>(left, WFK_SH_FILL);
+          if (U.n_samples > 0) close(z0);
+          U.n_samples = (int32_t)take;
+          z0 += take; left -= take;
+          close(z0);
+        }
+        if (left > 0) { U.n_samples += (int32_t)left; U.gaps |= 1; }
+        continue;
+      }
+      int32_t rec = 0;
+      for (int64_t r0 = D.start; r0 < D.stop; r0 += WFK_SH_SUB, ++rec) {
+        const int64_t len = std::min<int64_t>(WFK_SH_SUB, D.stop - r0);
+        const int64_t nseg = (len + WFK_SH_R - 1) / WFK_SH_R, base = len / nseg, rem = len % nseg;
+        const int64_t rec16 = (D.par_off + (int64_t)rec * D.first_len) / 2;
+        int64_t k0 = 0;
+        for (int64_t sgi = 0; sgi < nseg; ++sgi) {
+          const int64_t sl = base + (sgi < rem ? 1 : 0);
+          if (U.n_slots == 64 || U.n_samples + sl > WFK_SH_LCAP ||
+              (U.rec0 >= 0 && rec16 - U.rec0 > WFK_SH_DREC_MAX)) close(r0 + k0);
+          if (U.rec0 < 0) U.rec0 = rec16;
+          H.s_slots.push_back(WFK_SH_SLOT(rec16 - U.rec0, U.n_samples, sl));
+          ++U.n_slots;
+          U.n_samples += (int32_t)sl;
+          k0 += sl;
+        }
       }
     }
-    int64_t maxlen = 1536;                              // tools/short_crossover.py
-    if (const char* m = std::getenv("WFK_SHORT_MAXLEN")) maxlen = std::atoll(m);
-    if (mode != 0 && live > 0 && (mode == 1 || live_samples < maxlen * live)) {
-      shortm = true;
-    }
-    H.mean_piece_len = live > 0 ? (double)live_samples / (double)live : 0.0;
+    close(H.n);
   }
+  short_chunks(H, env);
+  H.chunks_per_ch = 0;
+  H.pool_real = !H.pool.empty();
+  if (H.pool.empty()) H.pool.push_back(0.0);
+  H.params.resize(H.params.size() + 16, 0.0);   // (the kernel reads one op record past the last real one)
+  if (H.mixed) {   // the general kernel's launch over the foreign pieces: the grid tier's geometry
+    H.ns = WFK_NS_GRID;
+    chunking(H, R, false, H.tile, H.tiles_per_chunk, H.chunks_per_ch, H.chunk_first);
+  }
+  return WFK_OK;
+}
+
+// One compile.  Returns WFK_RETRY_STD when the short geometry was chosen but some piece cannot run in it.
+static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double* tlist, int64_t n_tlist, HostPlan& H,
+                        std::string& err, const CompileRequest& req, const Attempt& at, const CompileEnv& env) {
+  PhaseTimer ptimer;
+  if (!P || (!grid && !tlist && n_tlist != 0)) { err = "null program or time axis"; return WFK_EINVAL; }
+  if (P->n_channels < 0 || P->n_members < 0) { err = "negative counts"; return WFK_EINVAL; }
+  TimeAxis ax{grid, tlist, grid ? grid->n : n_tlist};
+  if (ax.n < 0) { err = "negative sample count"; return WFK_EINVAL; }
+  H = HostPlan();
+  H.tlist = grid == nullptr;
+  H.n_channels = P->n_channels;
+  H.n = ax.n;
+  if (grid) {
+    H.t0 = grid->t0; H.step = grid->step; H.last = grid->last; H.has_last = grid->has_last; H.i0 = grid->i0;
+    if (grid->i0 < 0) { err = "negative grid.i0"; return WFK_EINVAL; }
+    if (ax.n > 1 && !(grid->step > 0)) { err = "grid step must be positive"; return WFK_EINVAL; }
+  }
+  H.ns = H.tlist ? (req.tlist_ns > 0 ? req.tlist_ns : (ax.n < WFK_TLIST_SMALL_N ? WFK_NS_TLIST_SMALL : WFK_NS_TLIST)) : WFK_NS_GRID;
+  if (at.ns_override > 0 && !H.tlist) H.ns = at.ns_override;
+  H.tile = WFK_WG * H.ns;
+  int NS = H.ns;
+  double dstride = grid ? (double)at.lane_stride * grid->step : 0.0;  // time between a lane's samples
+  bool cur_short = false;       // the piece being built uses the short tier's contiguous-lane geometry
+  const int lean_par_cap = at.ns_override > 0 ? WFK_CHAIN_PAR : WFK_LEAN_PAR;
+  const bool env_no_short_corr = env.no_short_corr || at.no_short_corr;
+  const bool nofast = env.disable_fast;
+  if (!req.program_validated)
+    if (const int rc = validate_program(P, err)) return rc;
+  ptimer.mark("validate");
+  const bool shortm = search_members(P, ax, env, at, H);   // the plan is compiled for the short tier
+  ptimer.mark("searchsorted");
   // geometry of the piece being built: lanes one sample apart (short tier) or `lane_stride` apart
   auto set_geom = [&](bool sh) {
     cur_short = sh;
     NS = sh ? WFK_SH_R : H.ns;
-    dstride = grid ? (sh ? 1.0 : (double)lane_stride) * grid->step : 0.0;
+    dstride = grid ? (sh ? 1.0 : (double)at.lane_stride) * grid->step : 0.0;
   };
   set_geom(shortm);
 
@@ -489,12 +582,10 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
   // may join only if their weight times the phase noise stays inside the budget; what is left
   // after the correction is d^2 / 2.  (fl(x - s_m) is not exact when the carrier is referenced to
   // t = 0, as mixing()'s is: what the subtraction rounds away is recovered with a TwoSum.)
-  const char* nocorr_env = std::getenv("WFK_DISABLE_CORR");
   // (short tier: family 6 evaluates corrected carriers of degree <= 1 on channels without a pending shift)
-  const bool corr_enabled = allow_corr && (!shortm || !env_no_short_corr) && !H.tlist && !(nocorr_env && nocorr_env[0] == '1');
+  const bool corr_enabled = at.allow_corr && (!shortm || !env_no_short_corr) && !H.tlist && !env.disable_corr;
   bool piece_corr_ok = true;   // cleared for the second attempt at a piece that turned out not to be lean
-  const char* nochirp_env = std::getenv("WFK_DISABLE_CHIRP");
-  const bool chirp_base = !H.tlist && ns_override == 0 && !g_no_chirp && !(nochirp_env && nochirp_env[0] == '1');
+  const bool chirp_base = !H.tlist && at.ns_override == 0 && !at.no_chirp && !env.disable_chirp;
   bool piece_chirp_ok = true;  // likewise: the fused chirp op exists in the lean kernel only
   bool piece_fuse_ok = true;   // time lists: cleared for the second attempt at a piece that kept a generic term (see below)
   bool chirp_ok = false;
@@ -543,7 +634,7 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
           fast = true;
         }
       } else if (type == WFK_SINC && std::isfinite(a[0]) && a[0] != 0.0 && rate_safe(3.141592653589793 * a[0], s0, s1) &&
-                 !env_no_sinc_tab) {
+                 !env.no_sinc_tab) {
         // sin(pi b u) from the phasor table, the argument pi b u advanced by the very same phase step (so the two
         // stay consistent where the argument passes through zero), one reciprocal per sample instead of libm's
         // sin + a division (reference _waveform.pyx:303-305: np.sinc)
@@ -551,7 +642,7 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
         rec[0] = WFK_M_SINC_TAB; rec[3] = a[0]; rec[4] = dphase; fast = true;
         table = table_for(B, dphase);
       } else if (type == WFK_MOLLIFIER && a[1] == 0.0 && std::isfinite(a[0]) && a[0] > 0.0 && rate_safe(4.0 / a[0], s0, s1) &&
-                 !env_no_moll_rec) {
+                 !env.no_moll_rec) {
         // exp(1 / (x^2 - 1) + 1), x = u / r (reference _waveform.pyx:359-363): the exponent is <= 0 inside the
         // support; Newton reciprocal + inline exponential instead of an IEEE division and libm's exp
         rec[0] = WFK_M_MOLL_REC; rec[3] = a[0]; rec[4] = dstride; fast = true;
@@ -594,7 +685,7 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
             H.pool.push_back(0.0);
             // grid mode: same arithmetic, but the knot/slope loads (L2 latency) of four samples
             // are in flight together instead of one dependent load pair per sample
-            if (!H.tlist && !nofast && pw == 1.0 && m < (int64_t(1) << 31) && !env_no_interp_grid) {
+            if (!H.tlist && !nofast && pw == 1.0 && m < (int64_t(1) << 31) && !env.no_interp_grid) {
               rec[0] = WFK_M_INTERP_GRID;
               // A finite table is a CONTINUOUS piecewise-linear function: next to a knot the two adjoining
               // segments agree to rounding, so the knot index may come straight from the O(1) guess, without
@@ -610,7 +701,7 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
                 finite = std::isfinite(sl);
                 smax = std::max(smax, std::fabs(sl));
               }
-              if (finite && s1 > s0 && rate_safe(4.0 * smax, s0, s1) && !env_no_interp_lin) {
+              if (finite && s1 > s0 && rate_safe(4.0 * smax, s0, s1) && !env.no_interp_lin) {
                 rec[0] = WFK_M_INTERP_LIN;
                 interp_lin = true;
               }
@@ -691,26 +782,17 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
   };
 
   // ---- fusion: terms -> carrier-envelope groups ---------------------------------
-  const char* nolean_env = std::getenv("WFK_DISABLE_LEAN");
-  const bool nolean = nolean_env && nolean_env[0] == '1';
-  const char* nofuse_env = std::getenv("WFK_DISABLE_FUSE");
+  const bool nolean = env.disable_lean;
   // (time-list plans fuse too: their ops are evaluated pointwise -- one sincos + one exp per group and
   //  sample instead of a libm call per factor; WFK_DISABLE_TLFUSE=1: every factor on device libm, as before)
-  const char* notlfuse_env = std::getenv("WFK_DISABLE_TLFUSE");
-  const bool can_fuse = (!H.tlist || !(notlfuse_env && notlfuse_env[0] == '1')) && !nofast &&
-                        !(nofuse_env && nofuse_env[0] == '1');
+  const bool can_fuse = (!H.tlist || !env.disable_tlfuse) && !nofast && !env.disable_fuse;
 
-  const char* noexp_env = std::getenv("WFK_DISABLE_EXPFUSE");
-  const bool expfuse = !(noexp_env && noexp_env[0] == '1');
-  const char* noerf_env = std::getenv("WFK_DISABLE_ERFMUL");
-  const bool erfmod_base = can_fuse && !H.tlist && ns_override == 0 && !(noerf_env && noerf_env[0] == '1');
+  const bool expfuse = !env.disable_expfuse;
+  const bool erfmod_base = can_fuse && !H.tlist && at.ns_override == 0 && !env.disable_erfmul;
   // stateless closing multipliers (INTERP tables, mollifiers): ops of the lean kernel's family 3 ONLY, so they
   // exist where every piece flagged lean is certain to run on that kernel (lean or mixed plans in the standard
   // geometry, no corrected carriers: that instantiation has families 0 / 1 only)
-  const char* nofmul_env = std::getenv("WFK_DISABLE_FMUL");
-  const char* nomix_env0 = std::getenv("WFK_DISABLE_MIXED");
-  const bool fmul_base = erfmod_base && !nolean && !g_no_chirp && !(nofmul_env && nofmul_env[0] == '1') &&
-                         !(nomix_env0 && nomix_env0[0] == '1');
+  const bool fmul_base = erfmod_base && !nolean && !at.no_chirp && !env.disable_fmul && !env.disable_mixed;
   bool piece_fmul_ok = true;   // cleared for the second attempt at a piece that turned out not to be lean
   bool plan_has_bank = false;  // some piece holds a run of bare carriers (tone loop): longer chunks pay there
 
@@ -1256,7 +1338,7 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
       //  by a multiplication, one rounding off the reference's division: 2 v^2 ulp <= 1.5e-13 relative at |v| = 26)
       if (G.has_env && !G.has_exp) rec[WFK_FCE_H] = 1.0 / G.sigma;
       double lim = 1.6e6;       // (tests: WFK_TLSMALL_LIMIT=0 sends every carrier through the two-term 1/pi reduction)
-      if (env_tlsmall_limit) lim = std::atof(env_tlsmall_limit);
+      if (env.has_tlsmall_limit) lim = env.tlsmall_limit;
       if (G.tl_thmax <= lim) rec[WFK_FCE_DEG] += (double)WFK_FCE_TLSMALL;
     }
     if (G.chirp) {
@@ -1341,7 +1423,7 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
     // 12-double record: the op adds envelope x carrier itself (word bit 7; bit 8: mollifier) instead of a carrier
     // op followed by the closing multiplier in a record of its own (a dependent load per piece)
     const bool one = groups.size() >= 2 && (groups[1].fmul == 2 || groups[1].fmul == 3) && groups[0].deg == 0 && !groups[0].has_env && !groups[0].has_exp &&
-                     !groups[0].erfmul && !groups[0].envmul && !groups[0].chirp && !groups[0].fmul && !env_no_short_cmul;
+                     !groups[0].erfmul && !groups[0].envmul && !groups[0].chirp && !groups[0].fmul && !env.no_short_cmul;
     // (several envelopes in one piece: the host marked every (group, multiplier) pair -- FceGroup::fmul_own)
     auto own_pair = [&](size_t gi) { return gi + 1 < groups.size() && groups[gi + 1].fmul && (groups[gi + 1].fmul_own || (one && gi == 0)); };
     int32_t rec_len = 0;
@@ -1352,7 +1434,7 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
     // one carrier (or a constant) under a flat-top edge of at most WFK_SH_ERFTAB samples: ONE own-term op over the edge's
     // sampled table (erf_table above), read at whole knots -- position k, step 1 (not for the FIR chain's sampler plan:
     // fir_short evaluates the erf closing op only)
-    if (groups.size() == 2 && groups[1].erfmul && s1 - s0 <= WFK_SH_ERFTAB && !g_no_short_fmul && !env_no_short_erftab &&
+    if (groups.size() == 2 && groups[1].erfmul && s1 - s0 <= WFK_SH_ERFTAB && !req.no_short_fmul && !env.no_short_erftab &&
         groups[0].deg == 0 && !groups[0].has_env && !groups[0].has_exp && !groups[0].erfmul && !groups[0].envmul && !groups[0].chirp &&
         !groups[0].fmul && !groups[0].corr) {
       const FceGroup& G = groups[0];
@@ -1620,7 +1702,7 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
       for (int attempt = 0; attempt < 2 && !live.empty(); ++attempt) {
         const int32_t corr_before = H.n_corr;
         // (a short plan: in its short pieces only -- the pieces that tier hands on run on the general kernel, which has no chirp op)
-        chirp_ok = chirp_base && piece_chirp_ok && can_fuse && (!shortm || (cur_short && !g_no_short_fmul && !env_no_short_chirp));
+        chirp_ok = chirp_base && piece_chirp_ok && can_fuse && (!shortm || (cur_short && !req.no_short_fmul && !env.no_short_chirp));
         D.flags |= WFK_PF_HAS_TERMS;
         BlockBuilder B;
         auto room_for = [&](size_t need) -> int {
@@ -1669,13 +1751,13 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
         int mod_kind = 0;             // 1: erf edge, 2: INTERP table, 3: mollifier (the closing multiplier of this piece)
         int32_t mod_f = -1;           // the first term's factor of that kind (later terms must carry an equal one)
         // (a short plan: in its short pieces only -- the pieces that tier hands on go to the general kernel)
-        const bool fmul_now = fmul_base && piece_fmul_ok && (!shortm || (cur_short && !g_no_short_fmul)) && std::isfinite(ax.at(s0)) && std::isfinite(ax.at(s1 - 1));
+        const bool fmul_now = fmul_base && piece_fmul_ok && (!shortm || (cur_short && !req.no_short_fmul)) && std::isfinite(ax.at(s0)) && std::isfinite(ax.at(s1 - 1));
         // a term's ONE factor of a kind the closing multipliers take (power 1); -1: none, or not admissible here
         // Short pieces may hold SEVERAL envelopes (overlapping pulses of different shapes: crosstalk-compensated channels),
         // as long as each stands over one plain carrier: every such term is an own-term op, acc += F (A cos + B sin).
         struct XMod { int kind; int32_t f; std::vector<FceGroup> g; };
         std::vector<XMod> xmods;      // the envelopes after the first one
-        const bool multi_ok = !(cur_short ? env_no_short_multi : env_no_lean_multi);
+        const bool multi_ok = !(cur_short ? env.no_short_multi : env.no_lean_multi);
         auto same_mod = [&](int32_t a_, int32_t b_) {
           const int64_t na = P->fc_arg_off[a_ + 1] - P->fc_arg_off[a_];
           if (P->fc_type[a_] != P->fc_type[b_] || P->fc_shift[a_] != P->fc_shift[b_] || na != P->fc_arg_off[b_ + 1] - P->fc_arg_off[b_]) return false;
@@ -1689,7 +1771,7 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
           int32_t at = -1;
           for (int32_t f = P->tm_factor_off[k]; f < P->tm_factor_off[k + 1]; ++f)
             if (P->fc_type[f] == WFK_INTERP || P->fc_type[f] == WFK_MOLLIFIER ||
-                (cur_short && !env_no_short_xchirp && (P->fc_type[f] == WFK_EXPONENTIALCHIRP || P->fc_type[f] == WFK_HYPERBOLICCHIRP))) {
+                (cur_short && !env.no_short_xchirp && (P->fc_type[f] == WFK_EXPONENTIALCHIRP || P->fc_type[f] == WFK_HYPERBOLICCHIRP))) {
               if (at >= 0 || P->fc_power[f] != 1.0) return -1;
               at = f;
             } else if (P->fc_type[f] == WFK_ERF) return -1;
@@ -1902,7 +1984,7 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
         // (From four carriers on: the extra op costs a pair of pieces what it saves them.)
         // (short pieces too: a tone costs a phasor seed and 7 instructions per sample there instead of the seeds of its own
         //  Gaussian and 13; not for the FIR chain's sampler plan, whose fir_short does not know the closing op)
-        if (groups.size() >= 4 && !mod_on && (!cur_short || (!g_no_short_fmul && !env_no_short_envmul))) {
+        if (groups.size() >= 4 && !mod_on && (!cur_short || (!req.no_short_fmul && !env.no_short_envmul))) {
           bool shared = true, e32 = true;
           for (const FceGroup& g : groups) {
             shared = shared && g.has_env && !g.has_exp && g.sigma == groups[0].sigma && g.sg == groups[0].sg;
@@ -1919,7 +2001,7 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
         // tones): marked for the lean kernel's compact tone loop -- per tone and tile two state reads, the products
         // with the amplitude, the phasor advance; no per-op dispatch (wfk_kernels.hip: fce_bank)
         bool piece_has_bank = false;
-        if (!cur_short && !H.tlist && ns_override == 0 && !env_no_bank) {
+        if (!cur_short && !H.tlist && at.ns_override == 0 && !env.no_bank) {
           auto bare = [](const FceGroup& g) {
             return g.W != 0.0 && !g.chirp && g.deg == 0 && !g.has_env && !g.has_exp && !g.envmul && !g.erfmul && !g.fmul && !g.corr;
           };
@@ -2066,9 +2148,7 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
   // mixed plans: some pieces are lean, some are not (the erf edges of a flat-top pulse next to its
   // multi-tone plateau).  Two launches over the same output: the lean kernel takes the lean and the
   // zero pieces, the general kernel the rest -- every sample is still written exactly once.
-  const char* nomix_env = std::getenv("WFK_DISABLE_MIXED");
-  H.mixed = !H.lean && !H.tlist && can_fuse && !nolean && n_lean_pieces > 0 && ns_override == 0 &&
-            !(nomix_env && nomix_env[0] == '1');
+  H.mixed = !H.lean && !H.tlist && can_fuse && !nolean && n_lean_pieces > 0 && at.ns_override == 0 && !env.disable_mixed;
   // time lists: fully fused pieces on the pointwise build, the others on the build with the direct tier
   // (same chunking for both launches); all of one kind: a single launch of that build
   const bool tl_mixed = H.tlist && n_lean_pieces > 0 && !lean_ok;
@@ -2076,163 +2156,20 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
   H.lean_par = std::max(256, (H.lean_par + 63) / 64 * 64);      // >= the 2 KB every plan had so far
   const int32_t lean_units_max = H.lean_ops;                     // most state units of a lean piece (phasors + envelopes)
   H.lean_ops = std::max(8, H.lean_ops);                          // likewise: 8 units = 8 KB of state
-  auto chunking = [&](bool lean_geom, int32_t& tile, int32_t& tiles_per_chunk, int64_t& chunks_per_ch,
-                      std::vector<int32_t>& chunk_first, int lean_cap = WFK_LEAN_TPC, int64_t lean_div = 2048) {
-    // general kernel: workgroup = 4 waves, tile = 256*NS samples, chunk = tiles_per_chunk tiles
-    // lean kernel   : workgroup = 1 wave,  tile = 64*NS samples (a wave owns a contiguous span)
-    tile = (lean_geom ? 64 : WFK_WG) * H.ns;
-    const int64_t tiles_per_ch = (ax.n + tile - 1) / tile;
-    const int64_t total_tiles = tiles_per_ch * (g_block_total_channels > 0 ? g_block_total_channels : P->n_channels);
-    // lean: one wave per workgroup; ~2-3k workgroups already fill 256 CUs x 12 waves.  Longer
-    // chunks amortise the exact seeds, shorter ones keep the set of regions being written at
-    // any moment compact, which is what the HBM write rate depends on:
-    // measured best at 8 tiles (= one seed per chunk) on the headline config while a degree-1 op cost
-    // 12 instructions per sample, at 5 since the phasor fold (8: same box 3.19 / 6: 3.11 / 5: 3.07 / 4: 3.16 ms);
-    // 4 on C2.
-    // Pieces of many ops (multi-tone pulses): a chunk's first tile seeds EVERY op exactly (libm: ~200 instructions
-    // each), which at 5 tiles per chunk is as much work as the ops' own arithmetic -- longer chunks there
-    // (ten tones per pulse, same box: 5 / 10 / 20 / 40 tiles 2.16 / 1.95 / 1.87 / 1.84 ms; four tones 1.34 / 1.27 / 1.22)
-    if (lean_geom && lean_cap == WFK_LEAN_TPC && lean_units_max >= 5 && plan_has_bank) lean_cap = 20;
-    const int64_t tpc = total_tiles / (lean_geom ? lean_div : 8192);
-    tiles_per_chunk = (int32_t)std::min<int64_t>(lean_geom ? lean_cap : 16, std::max<int64_t>(1, tpc));
-    if (const char* e = std::getenv("WFK_TPC")) {   // tuning override
-      int v = std::atoi(e);
-      if (v >= 1 && v <= 64) tiles_per_chunk = v;
-    }
-    chunks_per_ch = (tiles_per_ch + tiles_per_chunk - 1) / tiles_per_chunk;
-    chunk_first.assign((size_t)(chunks_per_ch * P->n_channels), 0);
-    const int64_t chunk_samples = (int64_t)tiles_per_chunk * tile;
-    for (int32_t c = 0; c < P->n_channels; ++c) {
-      int32_t p = H.channels[c].piece_begin;
-      for (int64_t k = 0; k < chunks_per_ch; ++k) {
-        int64_t g0 = k * chunk_samples;
-        while (p < H.channels[c].piece_end - 1 && H.pieces[p].stop <= g0) ++p;
-        chunk_first[(size_t)(c * chunks_per_ch + k)] = p;
-      }
-    }
-  };
+  const ChunkRule R = {req.block_total_channels > 0 ? req.block_total_channels : P->n_channels, lean_units_max, plan_has_bank, env.tpc};
   ptimer.mark("chunking");
-  // ---- short tier: wave units and lane slots ------------------------------------
-  if (shortm) {
-    // Mostly pieces the short tier cannot take (e.g. carriers that need the lean kernel's grid-rounding
-    // correction far from t = 0): the standard tiers serve the whole plan better
-    if (n_foreign_samples > n_short_samples || (n_short_pieces == 0 && n_foreign_pieces > 0)) return WFK_RETRY_STD;
-    H.shortp = true;
-    H.lean = false;
-    // corrected carriers live in family 6 = family 0 + the correction: with closing ops, chirps or tables in the same plan
-    // the carriers go back to the tiers that have both
-    if (H.short_corr && H.short_fam != 0) H.short_needs_corr = true;
-    if (H.short_corr && H.short_fam == 0) H.short_fam = 6;
-    H.mixed = n_foreign_pieces > 0;       // foreign pieces: a second launch of the general kernel
-    H.foreign_frac = n_short_samples > 0 ? (double)n_foreign_samples / (double)(n_short_samples + n_foreign_samples) : 0.0;
-    H.tile = 64 * WFK_SH_R;
-    for (int32_t c = 0; c < P->n_channels; ++c) {
-      ShortUnit U{};
-      auto fresh = [&](int64_t j0) {
-        U = ShortUnit{};
-        U.ch = c; U.j0 = j0; U.slot0 = (int32_t)H.s_slots.size(); U.rec0 = -1;
-        U.offset = H.channels[c].offset; U.clip_lo = H.channels[c].clip_lo; U.clip_hi = H.channels[c].clip_hi;
-        U.do_clip = H.channels[c].do_clip;
-      };
-      fresh(0);
-      auto close = [&](int64_t next_j0) {
-        if (U.n_samples > 0) {
-          if (U.n_slots > 0) H.s_lds_samples = std::max(H.s_lds_samples, U.n_samples);
-          if (U.rec0 < 0) U.rec0 = 0;
-          if (U.n_slots > 0) {
-            // LDS staging layout of this unit (wfk_short.hip): plain or padded by one element per 16,
-            // whichever spreads the lanes' first elements over more of the 16 bank pairs
-            int plain[16] = {0}, padded[16] = {0}, wp = 0, wq = 0;
-            for (int32_t k = 0; k < U.n_slots; ++k) {
-              const int o = (int)((H.s_slots[(size_t)U.slot0 + k] >> 16) & 0x3ff);
-              wp = std::max(wp, ++plain[o & 15]);
-              wq = std::max(wq, ++padded[(o + (o >> 4)) & 15]);
-            }
-            if (wq < wp) U.gaps |= 2;
-          }
-          H.s_units.push_back(U);
-        }
-        fresh(next_j0);
-      };
-      for (int32_t pi = H.channels[c].piece_begin; pi < H.channels[c].piece_end; ++pi) {
-        const DevPiece& D = H.pieces[pi];
-        if (D.n_blk != 0 && !(D.flags & WFK_PF_SHORT)) {   // the general kernel's piece: no unit covers it
-          close(D.stop);
-          continue;
-        }
-        if (D.n_blk == 0) {
-          // zero stretch: rides in the current unit's range while it fits, long ones as pure-fill units
-          int64_t z0 = D.start, left = D.stop - D.start;
-          if (U.n_slots > 0) {
-            const int64_t take = std::min<int64_t>(left, WFK_SH_LCAP - U.n_samples);
-            U.n_samples += (int32_t)take; U.gaps |= 1;
-            z0 += take; left -= take;
-            if (left > 0) close(z0);
-          }
-          while (left >= WFK_SH_LCAP / 2) {
-            const int64_t take = std::min<int64_t>(left, WFK_SH_FILL);
-            if (U.n_samples > 0) close(z0);
-            U.n_samples = (int32_t)take;
-            z0 += take; left -= take;
-            close(z0);
-          }
-          if (left > 0) { U.n_samples += (int32_t)left; U.gaps |= 1; }
-          continue;
-        }
-        int32_t rec = 0;
-        for (int64_t r0 = D.start; r0 < D.stop; r0 += WFK_SH_SUB, ++rec) {
-          const int64_t len = std::min<int64_t>(WFK_SH_SUB, D.stop - r0);
-          const int64_t nseg = (len + WFK_SH_R - 1) / WFK_SH_R, base = len / nseg, rem = len % nseg;
-          const int64_t rec16 = (D.par_off + (int64_t)rec * D.first_len) / 2;
-          int64_t k0 = 0;
-          for (int64_t sgi = 0; sgi < nseg; ++sgi) {
-            const int64_t sl = base + (sgi < rem ? 1 : 0);
-            if (U.n_slots == 64 || U.n_samples + sl > WFK_SH_LCAP ||
-                (U.rec0 >= 0 && rec16 - U.rec0 > WFK_SH_DREC_MAX)) close(r0 + k0);
-            if (U.rec0 < 0) U.rec0 = rec16;
-            H.s_slots.push_back(WFK_SH_SLOT(rec16 - U.rec0, U.n_samples, sl));
-            ++U.n_slots;
-            U.n_samples += (int32_t)sl;
-            k0 += sl;
-          }
-        }
-      }
-      close(ax.n);
-    }
-    if (H.s_slots.empty()) H.s_slots.push_back(0);
-    // workgroup = one wave walking `units_per_chunk` consecutive units
-    const int64_t nu = (int64_t)H.s_units.size();
-    H.s_units_per_chunk = (int32_t)std::min<int64_t>(6, std::max<int64_t>(1, nu / 8192));
-    if (const char* e = std::getenv("WFK_SH_UPC")) {   // tuning override
-      const int v = std::atoi(e);
-      if (v >= 1 && v <= 64) H.s_units_per_chunk = v;
-    }
-    H.chunks_per_ch = 0;
-    H.pool_real = !H.pool.empty();
-    if (H.pool.empty()) H.pool.push_back(0.0);
-    H.params.resize(H.params.size() + 16, 0.0);   // (the kernel reads one op record past the last real one)
-    if (H.mixed) {
-      set_geom(false);
-      H.ns = WFK_NS_GRID;
-      chunking(false, H.tile, H.tiles_per_chunk, H.chunks_per_ch, H.chunk_first);
-    }
-    return WFK_OK;
-  }
+  if (shortm) return short_tier_tables(H, {n_short_pieces, n_foreign_pieces, n_short_samples, n_foreign_samples}, R, env);
 
-  chunking(H.lean, H.tile, H.tiles_per_chunk, H.chunks_per_ch, H.chunk_first);
-  if (H.mixed && !H.tlist) chunking(true, H.lean_tile, H.lean_tiles_per_chunk, H.lean_chunks_per_ch, H.lean_chunk_first);
-  if ((H.lean || H.mixed) && ns_override == 0 && !H.tlist) {
+  chunking(H, R, H.lean, H.tile, H.tiles_per_chunk, H.chunks_per_ch, H.chunk_first);
+  if (H.mixed && !H.tlist) chunking(H, R, true, H.lean_tile, H.lean_tiles_per_chunk, H.lean_chunks_per_ch, H.lean_chunk_first);
+  if ((H.lean || H.mixed) && at.ns_override == 0 && !H.tlist) {
     // the lean launch's chunking for float outputs (longer chunks, see HostPlan)
     int32_t tile32 = 0;
-    int cap32 = WFK_LEAN_TPC_F32;
-    if (const char* e = std::getenv("WFK_TPC_F32")) {   // tuning override
-      const int v = std::atoi(e);
-      if (v >= 1 && v <= 64) cap32 = v;
-    }
+    const int cap32 = env.tpc_f32 ? env.tpc_f32 : WFK_LEAN_TPC_F32;   // (tuning override)
     // (beyond the double table's 8 tiles only where at least ~8 chunks per resident wave remain: C3's
     //  250 k tiles run best at 8-10 tiles per chunk -- 0.201 ms against 0.219 at 20 -- the 2.5 M tiles of
     //  256 x 1e7 at 16-20)
-    chunking(true, tile32, H.f32_tiles_per_chunk, H.f32_chunks_per_ch, H.f32_chunk_first, cap32, 24576);
+    chunking(H, R, true, tile32, H.f32_tiles_per_chunk, H.f32_chunks_per_ch, H.f32_chunk_first, cap32, 24576);
     if (H.f32_tiles_per_chunk <= (H.mixed ? H.lean_tiles_per_chunk : H.tiles_per_chunk)) {
       H.f32_chunk_first.clear();      // nothing to gain: the double table serves
       H.f32_tiles_per_chunk = 0;
@@ -2244,22 +2181,92 @@ static int compile_impl(const wfk_program* P, const wfk_grid* grid, const double
   return WFK_OK;
 }
 
+// Grid plan for another evaluation geometry: lanes `lane_stride` samples apart, `ns` samples per
+// lane (the sampler fused into the FIR transform walks a window with stride 256, wfk_fir_sampled.hip).
+// Only the piece / parameter tables are meaningful in the result; H.lean tells whether every piece
+// is one block of fused ops (the only form that kernel evaluates).
+int wfk_compile_geom(const wfk_program* P, const wfk_grid* grid, int lane_stride, int ns, HostPlan& H, std::string& err) {
+  const Attempt geom = {/*allow_corr*/ false, /*want_short*/ 0, /*no_short_corr*/ false, /*no_chirp*/ false, lane_stride, ns};
+  return compile_impl(P, grid, nullptr, 0, H, err, CompileRequest(), geom, CompileEnv());
+}
+
+// The retry ladder: a plan is compiled for the most specific tier first, and again for a more general one where it does not fit.
+//  * Carriers whose phase is sensitive to NumPy's grid rounding (far from t = 0) stay fused with a
+//    first-order per-sample correction, which only the lean kernel implements.  A plan that turns
+//    out not to be lean is compiled again with such carriers on the exact (libm) path.
+//  * Plans whose live pieces are short (AWG sample rates: tens to hundreds of samples per pulse) are
+//    compiled for the contiguous-lane geometry of wfk_short.hip first; a piece that tier cannot take
+//    (generic terms, erf edges, corrected carriers) sends the whole plan back to the standard tiers.
+static int compile_ladder(const wfk_program* P, const wfk_grid* grid, const double* tlist, int64_t n_tlist, HostPlan& H,
+                          std::string& err, const CompileRequest& req, const CompileEnv& env) {
+  auto attempt = [&](HostPlan& out, std::string& e, const Attempt& at) { return compile_impl(P, grid, tlist, n_tlist, out, e, req, at, env); };
+  int rc = attempt(H, err, {/*allow_corr*/ true, /*want_short*/ -1, /*no_short_corr*/ false, /*no_chirp*/ false});
+  if (rc == WFK_OK && H.shortp && H.short_corr && H.short_fam != 6) {
+    // corrected carriers next to closing ops / chirps / tables: no family of the short tier holds both -- the attempt
+    // again without the tier's correction (those carriers' pieces then go the way they went before family 6)
+    H = HostPlan();
+    rc = attempt(H, err, {/*allow_corr*/ true, /*want_short*/ -1, /*no_short_corr*/ true, /*no_chirp*/ false});
+  }
+  const bool gave_up = rc == WFK_RETRY_STD;
+  const double mean_len = H.mean_piece_len;      // (of the first compile: the later ones do not take the short-tier decision)
+  if (rc == WFK_RETRY_STD)
+    rc = attempt(H, err, {/*allow_corr*/ true, /*want_short*/ 0, /*no_short_corr*/ false, /*no_chirp*/ false});
+  else if (rc == WFK_OK && H.shortp && H.short_needs_corr) {
+    // far from t = 0 fast carriers need the per-sample rounding correction, which only the lean kernel
+    // has: where the standard tiers can run the plan lean (pieces long enough for its recurrences) they
+    // win; otherwise the short tier keeps what it can take and libm serves those carriers either way
+    HostPlan S; std::string e2;
+    const int rcs = attempt(S, e2, {/*allow_corr*/ true, /*want_short*/ 0, /*no_short_corr*/ false, /*no_chirp*/ false});
+    if (rcs == WFK_OK && (S.lean || S.mixed)) H = std::move(S);
+  }
+  if (rc == WFK_OK && !H.shortp && H.n_corr > 0 && !H.lean && !H.mixed)
+    rc = attempt(H, err, {/*allow_corr*/ false, /*want_short*/ 0, /*no_short_corr*/ false, /*no_chirp*/ false});
+  if (rc == WFK_OK && !H.shortp && H.n_corr > 0 && H.lean_fam >= 2) {
+    // corrected carriers (far from t = 0) and fused chirps in one plan: the lean kernel is not instantiated
+    // for that combination; the chirps take the general path
+    rc = attempt(H, err, {/*allow_corr*/ true, /*want_short*/ 0, /*no_short_corr*/ false, /*no_chirp*/ true});
+    if (rc == WFK_OK && H.n_corr > 0 && !H.lean && !H.mixed)
+      rc = attempt(H, err, {/*allow_corr*/ false, /*want_short*/ 0, /*no_short_corr*/ false, /*no_chirp*/ true});
+  }
+  // pieces of AWG-rate length that the short tier could not take: the standard tiers walk every piece over whole wave
+  // tiles of 1024 samples (wfk_api.cpp: such grid plans are evaluated pointwise instead)
+  // (not where the standard compile came out lean: chirp pulses stay on the lean kernel's chirp family, measured
+  //  12.6 ms against 17.6 pointwise on 2048 x 1e5 at 2 GS/s; and only for pieces well below a wave tile: from a few
+  //  hundred samples per piece on, the general kernel's per-factor fast paths cost less than pointwise libm)
+  if (rc == WFK_OK) H.short_gave_up = gave_up && grid != nullptr && !H.lean && !H.mixed && mean_len > 0.0 && mean_len < 192.0;
+  // A short plan that hands more than a few per cent of its samples on: on 2e8 samples the general kernel's launch over those
+  // pieces costs ~1.25 ms per per cent (every piece over a wave tile) next to 0.4 ms for the short pieces; evaluated pointwise
+  // the fused pieces take ~4.5 ms and the rest 0.34 ms per per cent (rocprofv3 --stats, one exponential chirp in ten
+  // pulses: 12.9 -> 7.9 ms) -- break-even near 4.5 %
+  if (rc == WFK_OK && grid && H.shortp && H.mixed && H.foreign_frac >= 0.05 && mean_len > 0.0 && mean_len < 192.0 &&
+      !req.keep_mixed_short && !env.keep_mixed_short)
+    H.short_gave_up = true;
+  return rc;
+}
+
+int wfk_compile(const wfk_program* P, const wfk_grid* grid, const double* tlist, int64_t n_tlist, HostPlan& H, std::string& err, const CompileRequest& req) {
+  return compile_ladder(P, grid, tlist, n_tlist, H, err, req, CompileEnv());
+}
 
 // ---- big batches: channel blocks compiled on host threads ---------------------------------------
 // The compile is O(#pieces) of scalar work with long-double seeds per op (2 us per piece): a fresh AWG sequence of
 // 2048 rows x 1668 pulses is 7 s on one core.  Channels are independent (reference: one Waveform per channel,
 // waveforms/waveform.py:529-563), so the job is cut into contiguous channel blocks, every block is compiled by
-// wfk_compile on its own thread into its own HostPlan, and the plans are concatenated (indices rebased).  Taken for the
+// compile_ladder on its own thread into its own HostPlan, and the plans are concatenated (indices rebased).  Taken for the
 // two bulk shapes -- pure short-tier plans (their tables move with them) and pure lean plans without pool tables; anything
 // else (mixed tiers, lean plans with INTERP / mollifier / SAMPLED tables, blocks that chose different tiers) returns WFK_RETRY_STD and the caller compiles in one piece.
-int wfk_compile_blocks(const wfk_program* P, const wfk_grid* grid, int nthreads, HostPlan& H, std::string& err) {
+int wfk_compile_blocks(const wfk_program* P, const wfk_grid* grid, int nthreads, HostPlan& H, std::string& err,
+                       const CompileRequest& req) {
   if (!P || !grid || nthreads < 2 || P->n_channels < 2 * nthreads) return WFK_RETRY_STD;
+  const CompileEnv env;
   {
-    // validate the whole program once, here (a block skips it): a grid of zero points is enough for that
+    // validate the whole program once, here (a block skips it): a grid of zero points is enough for that (a whole compile, not
+    // validate_program alone: compile_impl's own refusals of negative counts and of a negative grid.i0 are reached on zero points too)
     HostPlan V;
     wfk_grid g0 = *grid;
     g0.n = 0; g0.has_last = 0;
-    const int rc = compile_impl(P, &g0, nullptr, 0, V, err, true);
+    const int rc = compile_impl(P, &g0, nullptr, 0, V, err, req,
+                                {/*allow_corr*/ true, /*want_short*/ 0, /*no_short_corr*/ false, /*no_chirp*/ false}, env);
     if (rc != WFK_OK && rc != WFK_RETRY_STD) return rc;
   }
   const int K = nthreads;
@@ -2268,21 +2275,22 @@ int wfk_compile_blocks(const wfk_program* P, const wfk_grid* grid, int nthreads,
   std::vector<int> rcs((size_t)K, WFK_OK);
   std::vector<int32_t> first((size_t)K + 1);
   for (int k = 0; k <= K; ++k) first[k] = (int32_t)((int64_t)P->n_channels * k / K);
-  const bool t_fmul = g_no_short_fmul, t_mixed = g_keep_mixed_short, t_chirp = g_no_chirp;
+  // a block: the program's channel arrays are views into the job's (ch_member_off does not start at 0), the job was
+  // validated above, and the launch geometry (tiles per chunk) is decided on the job's channel count
+  CompileRequest block = req;
+  block.block_total_channels = P->n_channels;
+  block.program_validated = true;
   auto work = [&](int k) {
-    g_no_short_fmul = t_fmul; g_keep_mixed_short = t_mixed; g_no_chirp = t_chirp;
-    g_block_total_channels = P->n_channels;
     wfk_program Q = *P;
     const int32_t a = first[k];
     Q.n_channels = first[k + 1] - a;
     Q.ch_member_off += a; Q.ch_offset += a; Q.ch_tshift += a; Q.ch_clip_lo += a; Q.ch_clip_hi += a;
     try {
-      rcs[k] = wfk_compile(&Q, grid, nullptr, 0, parts[k], errs[k]);
+      rcs[k] = compile_ladder(&Q, grid, nullptr, 0, parts[k], errs[k], block, env);
     } catch (...) {
       rcs[k] = WFK_ENOMEM;
       errs[k] = "out of host memory while compiling a channel block";
     }
-    g_block_total_channels = 0;
   };
   {
     std::vector<std::thread> th;
@@ -2375,15 +2383,7 @@ int wfk_compile_blocks(const wfk_program* P, const wfk_grid* grid, int nthreads,
   H.foreign_frac = frac_sum / (double)P->n_channels;
   H.pool_real = !H.pool.empty();
   if (H.pool.empty()) H.pool.assign(1, 0.0);
-  if (H.shortp) {
-    const int64_t nu = (int64_t)H.s_units.size();
-    H.s_units_per_chunk = (int32_t)std::min<int64_t>(6, std::max<int64_t>(1, nu / 8192));
-    if (const char* e = std::getenv("WFK_SH_UPC")) {
-      const int v = std::atoi(e);
-      if (v >= 1 && v <= 64) H.s_units_per_chunk = v;
-    }
-    if (H.s_slots.empty()) H.s_slots.push_back(0);
-  }
+  if (H.shortp) short_chunks(H, env);
   return WFK_OK;
 }
 

@@ -517,9 +517,9 @@ static int chain_plan_create(const wfk_program* prog, const wfk_grid* grid, cons
   if (const int rc = wfk_check_kind(kind, "chain ")) return rc;
   std::unique_ptr<wfk_chain_plan> p(new wfk_chain_plan());
   p->kind = kind;
-  wfk_internal_keep_mixed_short(true);       // (fir_short samples the short pieces itself: a mixed short plan stays one)
-  int rc = wfk_plan_create_grid(prog, grid, &p->sampler);
-  wfk_internal_keep_mixed_short(false);
+  CompileRequest req;
+  req.keep_mixed_short = true;               // (fir_short samples the short pieces itself: a mixed short plan stays one)
+  int rc = wfk_internal_plan_create(prog, grid, nullptr, 0, req, &p->sampler);
   if (rc) return rc;
   {
     // pieces that close with a table / mollifier multiplier: fir_short does not evaluate those, the general kernel
@@ -530,11 +530,8 @@ static int chain_plan_create(const wfk_program* prog, const wfk_grid* grid, cons
     if (h0 && h0->shortp && h0->short_has_fmul) {
       wfk_plan_destroy(p->sampler);
       p->sampler = nullptr;
-      wfk_internal_no_short_fmul(true);
-      wfk_internal_keep_mixed_short(true);
-      rc = wfk_plan_create_grid(prog, grid, &p->sampler);
-      wfk_internal_keep_mixed_short(false);
-      wfk_internal_no_short_fmul(false);
+      req.no_short_fmul = true;
+      rc = wfk_internal_plan_create(prog, grid, nullptr, 0, req, &p->sampler);
       if (rc) return rc;
     }
   }

@@ -311,17 +311,28 @@ struct HostPlan {
   int32_t s_lds_samples = 0, s_units_per_chunk = 1;
 };
 
+// What a caller may ask of a compile beyond the program and the time axis.  The defaults are the plain compile; the
+// compiler's experiment switches are environment variables, read once per plan (CompileEnv in wfk_compile.cpp).
+struct CompileRequest {
+  bool keep_mixed_short = false;      // the FIR chain's sampler plan: fir_short fuses the short pieces, the rest is copied in -- a mixed short plan stays one
+  bool no_short_fmul = false;         // likewise: fir_short has no table / mollifier multipliers, such pieces stay with the general kernel
+  int tlist_ns = 0;                   // samples per lane of a time-list compile (0: by size)
+  int32_t block_total_channels = 0;   // the program is a block of the channels of a job of so many (0: it is the whole job): wfk_compile_blocks
+  bool program_validated = false;     // the caller has validated the program's structure already: the compile does not look again
+};
+
 // host compiler: flattened program + time axis -> device tables.  Returns 0 or a
 // negative WFK_E* code with a message in err.
 int wfk_compile(const wfk_program* prog, const wfk_grid* grid, const double* tlist,
-                int64_t n, HostPlan& out, std::string& err);
+                int64_t n, HostPlan& out, std::string& err, const CompileRequest& req = {});
 
 int wfk_compile_geom(const wfk_program* prog, const wfk_grid* grid, int lane_stride, int ns,
                      HostPlan& out, std::string& err);
 #define WFK_RETRY_STD 1      // (not an error: compile again another way)
 // big batches: contiguous channel blocks compiled on `nthreads` host threads, plans concatenated; WFK_RETRY_STD when
 // the plan is not of a shape this takes (compile it in one piece then)
-int wfk_compile_blocks(const wfk_program* prog, const wfk_grid* grid, int nthreads, HostPlan& out, std::string& err);
+int wfk_compile_blocks(const wfk_program* prog, const wfk_grid* grid, int nthreads, HostPlan& out, std::string& err,
+                       const CompileRequest& req = {});
 
 // Sampler fused into the FIR transform at AWG rates (fir_short, wfk_fir_sampled.hip): the pieces of a pure
 // short plan cut into per-half-window entry lists.  Window pair `pr` of a row starts at sample
@@ -340,11 +351,7 @@ struct ShortWin {        // one half of one pair of windows of one channel
 int wfk_chain_windows(const HostPlan& H, int64_t n, int64_t hop, int64_t lead, int64_t half, int64_t npairs,
                       std::vector<ShortWin>& wins, std::vector<uint32_t>& entries, std::string& err);
 
-void wfk_internal_keep_mixed_short(bool on);                          // this thread's next compiles keep mixed short plans (the FIR chain's sampler)
-void wfk_internal_tlist_ns(int ns);                                   // samples per lane of this thread's next time-list compiles (0: by size)
 void wfk_internal_grid_times(const wfk_grid* g, double* out);         // out[g->n]: the grid's sample times, as NumPy forms them
-// this thread's next plan compiles keep table / mollifier multipliers out of short pieces (the FIR chain's sampler plan)
-void wfk_internal_no_short_fmul(bool on);
 
 // kernels (wfk_kernels.hip, wfk_short.hip): the launch of one pick of a plan (wfk_pick.h)
 struct SamplerPick;
@@ -356,6 +363,9 @@ extern "C" {
 void wfk_internal_set_error(const char* msg);   // wfk_api.cpp: this thread's text behind wfk_last_error
 // wfk_api.cpp: the compiled plan and its parameter table on the device; launch of a mixed short plan's general-kernel part
 void wfk_internal_plan_tables(const wfk_plan* p, const HostPlan** h, const double** d_params);
+// wfk_api.cpp: wfk_plan_create_grid (tlist == NULL) / wfk_plan_create_tlist (grid == NULL) with a request to the compiler
+int wfk_internal_plan_create(const wfk_program* prog, const wfk_grid* grid, const double* tlist, int64_t n,
+                             const CompileRequest& req, wfk_plan** out);
 int wfk_internal_plan_launch_foreign(wfk_plan* p, void* out_dev, int64_t ch_stride, int out_kind, void* hip_stream);
 // wfk_fir.hip: kernel spectrum and twiddles of a plan that runs as ONE pass of the on-chip transform; its row stride
 void wfk_internal_fir_tables(const wfk_fir_plan* p, const void** kspec, const void** tw, int* fused, int* nseg,
