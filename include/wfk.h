@@ -342,6 +342,35 @@ int wfk_chain_iir_launch(wfk_chain_iir_plan* plan, void* out_dev, int64_t out_st
 int wfk_chain_iir_status(wfk_chain_iir_plan* plan, void* hip_stream);
 int wfk_chain_iir_plan_destroy(wfk_chain_iir_plan* plan);
 
+/* ---- sampler -> per-row IIR chain: every row its own waveform AND its own cascade ------------------------------
+ * predistort(wav(t), filters=[exp_decay_filter(...), ...], initial=level) per flux line (reference
+ * waveforms/distortion.py:100-185, :298-321), device-resident:  out[c] = F_c(wav_c(t) - initial[c]) + initial[c] for
+ * the channels c of `prog` on `grid`.  The batch is the program's channel count; coefficient layout (b_rows / a_rows:
+ * n_channels rows of the sections back to back, each orders[s] + 1 long), the shape limits, zi / zf / initial_dev
+ * are those of wfk_iir_rows_plan_create / wfk_iir_rows_apply.
+ * Fused, ONE kernel: the workgroup that owns a row evaluates each tile of 4096 samples into LDS and filters it there
+ * -- "iir_rows_sampled<T,NSEC,ORD>" on fine grids (fully fused real channels without clip whose parameter blocks
+ * fit 2048 doubles of LDS: stride-256 chains), "iir_rows_short<T,NSEC,ORD>" at AWG sample rates (a pure short-tier
+ * plan of real channels: runs of one piece).  The unfiltered samples never touch HBM, the launch moves the 8 (4)
+ * B/sample of its output, and rows of any length fuse.  Everything else -- complex channels, generic terms, clip on a
+ * fine grid, table / mollifier envelopes and corrected carriers at AWG rates, mixed plans, WFK_CHAIN_UNFUSED=1 --
+ * runs the sampler into `out` and iir_rows_tile in place on it; the name is then the two kernels joined with " + "
+ * and the reason is never empty.  The decision is taken once, at creation.
+ * wfk_chain_iir_rows_launch() allocates nothing and does not synchronise; n == 0 launches nothing.  The strings
+ * live as long as the plan.                                                                                      */
+typedef struct wfk_chain_iir_rows_plan wfk_chain_iir_rows_plan;
+int wfk_chain_iir_rows_plan_create(const wfk_program* prog, const wfk_grid* grid, int32_t n_sections,
+                                   const int32_t* orders, const double* b_rows, const double* a_rows,
+                                   int kind /* WFK_OUT_F64|F32 */, wfk_chain_iir_rows_plan** out);
+int wfk_chain_iir_rows_is_fused(const wfk_chain_iir_rows_plan* plan);
+const char* wfk_chain_iir_rows_unfused_reason(const wfk_chain_iir_rows_plan* plan);
+const char* wfk_chain_iir_rows_kernel_name(const wfk_chain_iir_rows_plan* plan);
+int64_t wfk_chain_iir_rows_table_bytes(const wfk_chain_iir_rows_plan* plan);
+int wfk_chain_iir_rows_state_dim(const wfk_chain_iir_rows_plan* plan);
+int wfk_chain_iir_rows_launch(wfk_chain_iir_rows_plan* plan, void* out_dev, int64_t out_stride, const double* zi_dev,
+                              double* zf_dev, const double* initial_dev, void* hip_stream);
+int wfk_chain_iir_rows_plan_destroy(wfk_chain_iir_rows_plan* plan);
+
 /* -- whole-signal transfer function ------------------- */
 /* out = irfft(rfft(in) * H) per row; rows contiguous (stride n); H_dev = n/2+1 complex128
  * bins on the device (f_k = k*fs/n).  Replaces the scipy.fftpack calls of

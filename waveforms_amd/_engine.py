@@ -102,6 +102,17 @@ def lib():
         l.wfk_chain_iir_launch.argtypes = [VP, VP, I64, VP, VP, C.c_double, VP]
         l.wfk_chain_iir_status.argtypes = [VP, VP]
         l.wfk_chain_iir_plan_destroy.argtypes = [VP]
+        l.wfk_chain_iir_rows_plan_create.argtypes = [P(wfk_program), P(wfk_grid), I32, VP, VP, VP, C.c_int, P(VP)]
+        l.wfk_chain_iir_rows_is_fused.argtypes = [VP]
+        l.wfk_chain_iir_rows_unfused_reason.argtypes = [VP]
+        l.wfk_chain_iir_rows_unfused_reason.restype = C.c_char_p
+        l.wfk_chain_iir_rows_kernel_name.argtypes = [VP]
+        l.wfk_chain_iir_rows_kernel_name.restype = C.c_char_p
+        l.wfk_chain_iir_rows_table_bytes.argtypes = [VP]
+        l.wfk_chain_iir_rows_table_bytes.restype = I64
+        l.wfk_chain_iir_rows_state_dim.argtypes = [VP]
+        l.wfk_chain_iir_rows_launch.argtypes = [VP, VP, I64, VP, VP, VP, VP]
+        l.wfk_chain_iir_rows_plan_destroy.argtypes = [VP]
         l.wfk_iir_plan_create.argtypes = [I32, VP, VP, VP, I64, I32, C.c_int, P(VP)]
         l.wfk_iir_state_dim.argtypes = [VP]
         l.wfk_iir_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP, C.c_double, VP]
@@ -561,6 +572,42 @@ class IirRowsPlan(_Handle):
 
     def kernel_name(self) -> str:
         return lib().wfk_iir_rows_kernel_name(self._h).decode()
+
+
+class ChainIirRowsPlan(_Handle):
+    """sampler -> per-row IIR for every channel of `prog` on `grid` (wfk_chain_iir_rows_*), the twin of ChainIirPlan
+    with one cascade PER CHANNEL: `sections_per_row[c]` is the list of (b, a) sections of channel c, packed by
+    `pack_sections_rows` (IirRowsPlan's shapes and limits).  Fused, the workgroup that owns a row evaluates each tile
+    of the row in LDS and filters it there ('iir_rows_sampled<...>' on fine grids, 'iir_rows_short<...>' at AWG
+    rates): the unfiltered samples never touch HBM (`fused`, `why_not`, `kernel_name()`)."""
+    _destroy = 'wfk_chain_iir_rows_plan_destroy'
+
+    def __init__(self, prog: Program, grid: wfk_grid, sections_per_row, dtype=np.float64, packed=None):
+        """packed: what pack_sections_rows(sections_per_row) gave a caller that has packed the cascades already"""
+        orders, bm, am, self.own_orders = pack_sections_rows(sections_per_row) if packed is None else packed
+        if bm.shape[0] != prog.n_channels:
+            raise ValueError(f'{bm.shape[0]} cascades for {prog.n_channels} rows')
+        self.prog, self.grid, self.dtype = prog, grid, np.dtype(dtype)
+        self.n, self.n_channels = int(grid.n), prog.n_channels
+        self.orders = orders
+        bm, am = np.ascontiguousarray(bm), np.ascontiguousarray(am)
+        check(lib().wfk_chain_iir_rows_plan_create(C.byref(prog.struct), C.byref(grid), len(orders), orders.ctypes.data,
+                                                   bm.ctypes.data, am.ctypes.data, _KIND_OF[self.dtype],
+                                                   C.byref(self._h)))
+        self.state_dim = int(orders.sum())
+        self.fused = bool(lib().wfk_chain_iir_rows_is_fused(self._h))
+        self.why_not = lib().wfk_chain_iir_rows_unfused_reason(self._h).decode()
+
+    def launch(self, out_ptr: int, out_stride: int, zi_ptr=None, zf_ptr=None, initial_ptr=None, stream: int = 0):
+        """initial_ptr: device array of `n_channels` doubles (one level per row) or None"""
+        check(lib().wfk_chain_iir_rows_launch(self._h, out_ptr, out_stride, zi_ptr, zf_ptr, initial_ptr, stream))
+
+    def kernel_name(self) -> str:
+        """'iir_rows_sampled<T,NSEC,ORD>', 'iir_rows_short<T,NSEC,ORD>', or the unfused pair joined with ' + '"""
+        return lib().wfk_chain_iir_rows_kernel_name(self._h).decode()
+
+    def table_bytes(self) -> int:
+        return int(lib().wfk_chain_iir_rows_table_bytes(self._h))
 
 
 class SpectralPlan(_Handle):

@@ -37,51 +37,18 @@
 
 #include "wfk.h"
 #include "wfk_iir_common.h"
+#include "wfk_iir_rows_dev.h"
 
-#define IRW_RUN 16                        // samples per lane and tile
-#define IRW_THREADS 256
-#define IRW_WAVES (IRW_THREADS / 64)
-#define IRW_TILE (IRW_RUN * IRW_THREADS)  // 4096 samples: 34 KB of LDS in fp64, four workgroups per CU
-#define IRW_PITCH (IRW_RUN + 1)           // elements between the runs of neighbouring lanes
-#define IRW_MAXD 4                        // state dimension limit
-#define IRW_NPW 7                         // T^(2^k), k = 0 .. 6 (k = 6: one wave)
+#define IRW_LOADS_INPUT          // for wfk_iir_rows_head.inc: this file's kernel loads its tiles (it holds T^lane, has x)
 
 namespace {
-
-// per-row table (doubles): b[NC] a[NC] | pw[IRW_NPW][D][D][2] | lanep[64][D][D][2] (T^l, l = 0 .. 63)
-__host__ __device__ constexpr int irw_row_doubles(int nsec, int ord) {
-  return 2 * nsec * (ord + 1) + (IRW_NPW + 64) * (nsec * ord) * (nsec * ord) * 2;
-}
 
 template <typename T, int NSEC, int ORD>
 __global__ void __launch_bounds__(IRW_THREADS) iir_rows_tile(const T* in, int64_t in_stride, T* out,
                                                              int64_t out_stride, const double* __restrict__ tab,
                                                              const double* __restrict__ zi, double* __restrict__ zf,
                                                              const double* __restrict__ initial, int64_t n) {
-  constexpr int D = NSEC * ORD, NC = NSEC * (ORD + 1), MM = D * D * 2;
-  __shared__ T tile[IRW_THREADS * IRW_PITCH];
-  __shared__ double s_tot[IRW_WAVES][D];
-  __shared__ double s_carry[2][D];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int64_t row = blockIdx.x;
-  const double* rt = tab + row * (int64_t)irw_row_doubles(NSEC, ORD);   // workgroup-uniform: scalar loads
-  double cb[NC], ca[NC];
-#pragma unroll
-  for (int i = 0; i < NC; ++i) { cb[i] = rt[i]; ca[i] = rt[NC + i]; }
-  const auto B = [&](int s, int i) { return cb[s * (ORD + 1) + i]; };
-  const auto A = [&](int s, int i) { return ca[s * (ORD + 1) + i]; };
-  const double* pw = rt + 2 * NC;
-  const double* W = pw + (IRW_NPW - 1) * MM;                            // T^64
-  double L[MM];                                                         // T^lane, kept for the whole row
-#pragma unroll
-  for (int e = 0; e < MM; ++e) L[e] = pw[(IRW_NPW + lane) * MM + e];
-  const double pre = initial ? initial[row] : 0.0;
-  if (tid < D) s_carry[0][tid] = zi ? zi[row * D + tid] : 0.0;
-  const T* x = in + row * in_stride;
-  T* y = out + row * out_stride;
-  const int64_t ntile = (n + IRW_TILE - 1) / IRW_TILE;
-  T* const my = tile + tid * IRW_PITCH;
+#include "wfk_iir_rows_head.inc"
 
   T nxt[IRW_RUN];
   auto fetch = [&](int64_t t) {
@@ -107,91 +74,8 @@ __global__ void __launch_bounds__(IRW_THREADS) iir_rows_tile(const T* in, int64_
     }
     if (t + 1 < ntile) fetch(t + 1);
     __syncthreads();
-    const int64_t mine = left - (int64_t)tid * IRW_RUN;                 // samples of the row from this lane's run on
-    const int cnt = (int)(mine < 0 ? 0 : (mine > IRW_RUN ? IRW_RUN : mine));
-
-    // ---- sweep 1: zero state -> local end state; inclusive scan over the wave
-    double z[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) z[i] = 0.0;
-    if (cnt == IRW_RUN) {
-#pragma unroll
-      for (int i = 0; i < IRW_RUN; ++i) (void)iir_cascade_step<NSEC, ORD>(B, A, (double)my[i] - pre, z);
-    } else {
-      for (int i = 0; i < cnt; ++i) (void)iir_cascade_step<NSEC, ORD>(B, A, (double)my[i] - pre, z);
-    }
-    // (a lane past the end of the row keeps a zero state; the scan still multiplies by T per lane, which only
-    //  matters AFTER the last sample -- nothing there is used)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      const int d = 1 << k;
-      double u[D], r[D];
-#pragma unroll
-      for (int i = 0; i < D; ++i) u[i] = __shfl_up(z[i], d);
-      dd_matvec_add<D>(r, z, pw + k * MM, u);
-#pragma unroll
-      for (int i = 0; i < D; ++i) z[i] = lane >= d ? r[i] : z[i];
-    }
-    double vprev[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-      const double up = __shfl_up(z[i], 1);
-      vprev[i] = lane == 0 ? 0.0 : up;
-    }
-    if (lane == 63) {
-#pragma unroll
-      for (int i = 0; i < D; ++i) s_tot[wv][i] = z[i];
-    }
-    __syncthreads();
-
-    // ---- state at this wave's start: the carry pushed through the waves before it
-    double S[D];
-#pragma unroll
-    for (int i = 0; i < D; ++i) S[i] = s_carry[t & 1][i];
-    for (int w = 0; w < wv; ++w) {
-      double tot[D], r[D];
-#pragma unroll
-      for (int i = 0; i < D; ++i) tot[i] = s_tot[w][i];
-      dd_matvec_add<D>(r, tot, W, S);
-#pragma unroll
-      for (int i = 0; i < D; ++i) S[i] = r[i];
-    }
-    if (wv == IRW_WAVES - 1) {     // the next tile's carry (double-buffered: the other waves still read this tile's)
-      double r[D];
-      dd_matvec_add<D>(r, z, W, S);                                    // lane 63: z = this wave's total
-      if (lane == 63) {
-#pragma unroll
-        for (int i = 0; i < D; ++i) s_carry[(t + 1) & 1][i] = r[i];
-      }
-    }
-
-    // ---- sweep 2 from the true start state v_(l-1) + T^l S_w, y over x in LDS
-    dd_matvec_add<D>(z, vprev, L, S);
-    if (cnt == IRW_RUN) {
-#pragma unroll
-      for (int i = 0; i < IRW_RUN; ++i) my[i] = (T)(iir_cascade_step<NSEC, ORD>(B, A, (double)my[i] - pre, z) + pre);
-    } else {
-      for (int i = 0; i < cnt; ++i) my[i] = (T)(iir_cascade_step<NSEC, ORD>(B, A, (double)my[i] - pre, z) + pre);
-    }
-    if (zf && cnt > 0 && mine <= IRW_RUN) {                             // the lane that holds the row's last sample
-#pragma unroll
-      for (int i = 0; i < D; ++i) zf[row * D + i] = z[i];
-    }
-    __syncthreads();
-    if (left >= IRW_TILE) {
-#pragma unroll
-      for (int i = 0; i < IRW_RUN; ++i) {
-        const int j = i * IRW_THREADS + tid;
-        y[base + j] = tile[(j / IRW_RUN) * IRW_PITCH + (j % IRW_RUN)];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < IRW_RUN; ++i) {
-        const int j = i * IRW_THREADS + tid;
-        if (j < left) y[base + j] = tile[(j / IRW_RUN) * IRW_PITCH + (j % IRW_RUN)];
-      }
-    }
-    __syncthreads();
+    // ---- steps 2-4 on the tile in LDS: the text the evaluating kernels share
+#include "wfk_iir_rows_body.inc"
   }
 }
 
@@ -315,6 +199,8 @@ int wfk_iir_rows_plan_create(int32_t n_sections, const int32_t* orders, const do
 int wfk_iir_rows_state_dim(const wfk_iir_rows_plan* p) { return p ? p->D : WFK_EINVAL; }
 
 const char* wfk_iir_rows_kernel_name(const wfk_iir_rows_plan* p) { return p ? p->name.c_str() : ""; }
+
+const double* wfk_internal_iir_rows_table(const wfk_iir_rows_plan* p) { return p ? p->tab.get() : nullptr; }
 
 int wfk_iir_rows_apply(wfk_iir_rows_plan* p, const void* in_dev, int64_t in_stride, void* out_dev,
                        int64_t out_stride, const double* zi_dev, double* zf_dev, const double* initial_dev,

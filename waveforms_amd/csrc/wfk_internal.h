@@ -258,6 +258,7 @@ struct wfk_program;
 struct wfk_grid;
 struct wfk_plan;
 struct wfk_fir_plan;
+struct wfk_iir_rows_plan;
 
 struct HostPlan {
   bool tlist = false;
@@ -376,5 +377,7 @@ int wfk_internal_fir_fused_launch(int kind, const void* in, int64_t in_stride, v
                                   const void* hspec, const void* tw, int64_t n, int M, int K, int lead, int64_t nblk,
                                   int32_t batch, int accumulate, void* stream, int64_t hspec_row_stride);
 int wfk_internal_fir_fused_len(void);
+// wfk_iir_rows.hip: the rows' tables on the device ([batch][irw_row_doubles], wfk_iir_rows_dev.h)
+const double* wfk_internal_iir_rows_table(const wfk_iir_rows_plan* p);
 }
 #endif

@@ -47,6 +47,33 @@ class FirStage:
         self.plan.close()
 
 
+def _row_state(z, r, own_orders, section_order):
+    """row r's own state out of a (rows, state_dim) host array of per-row cascades padded to a common shape
+    (`_engine.pack_sections_rows`): section s sits at s * section_order and is own_orders[r][s] long"""
+    z, m = np.asarray(z), section_order
+    return np.concatenate([z[r, s * m:s * m + o] for s, o in enumerate(own_orders[r])] or [z[r, :0]])
+
+
+def _initial_rows(owner, rows, initial, device):
+    """the per-row `initial` of a stage: a scalar, one value per row, or a (rows,) float64 device tensor -> None (all
+    zero) or a (rows,) float64 device tensor; a tensor of the last values is kept in `owner._initial_cache`"""
+    import torch
+    if isinstance(initial, torch.Tensor):
+        _rows.check_state(initial, (rows, ), 'initial: a (batch,) contiguous float64 device tensor')
+        return initial
+    arr = np.asarray(initial, dtype=np.float64)
+    if arr.ndim == 0:
+        arr = np.full(rows, float(arr))
+    if arr.shape != (rows, ):
+        raise ValueError('initial: a scalar or one value per row')
+    if not arr.any():
+        return None
+    c = owner._initial_cache
+    if c is None or c[1] != device or not np.array_equal(c[0], arr):
+        owner._initial_cache = c = (arr.copy(), device, torch.from_numpy(arr.copy()).to(device))
+    return c[2]
+
+
 class IirStage:
     """Device-resident IIR stage for `batch` rows of `n` samples (build once, apply many times), the
     counterpart of `FirStage`:  y[r] = F_r(x[r] - initial[r]) + initial[r].
@@ -100,29 +127,10 @@ class IirStage:
 
     def row_state(self, z, r: int):
         """row r's own state (scipy layout, its sections back to back) out of a (batch, state_dim) host array"""
-        z = np.asarray(z)
-        if not self.per_row:
-            return z[r]
-        m = self.section_order
-        return np.concatenate([z[r, s * m:s * m + o] for s, o in enumerate(self.own_orders[r])] or [z[r, :0]])
+        return _row_state(z, r, self.own_orders, self.section_order) if self.per_row else np.asarray(z)[r]
 
     def _initial_tensor(self, initial, device):
-        """None (all zero), or a (batch,) float64 device tensor; a tensor of the last values is kept"""
-        import torch
-        if isinstance(initial, torch.Tensor):
-            _rows.check_state(initial, (self.batch, ), 'initial: a (batch,) contiguous float64 device tensor')
-            return initial
-        arr = np.asarray(initial, dtype=np.float64)
-        if arr.ndim == 0:
-            arr = np.full(self.batch, float(arr))
-        if arr.shape != (self.batch, ):
-            raise ValueError('initial: a scalar or one value per row')
-        if not arr.any():
-            return None
-        c = self._initial_cache
-        if c is None or c[1] != device or not np.array_equal(c[0], arr):
-            self._initial_cache = c = (arr.copy(), device, torch.from_numpy(arr.copy()).to(device))
-        return c[2]
+        return _initial_rows(self, self.batch, initial, device)
 
     def apply_torch(self, x, out=None, initial=0.0, zi=None, zf=None):
         """x, out: (batch, >= n) row-contiguous device tensors of the stage's dtype (rows may be windows of a wider
@@ -274,6 +282,99 @@ class SampledIir:
                     lambda: self.launch(buf.ptr, None, None if dzi is None else dzi.ptr,
                                         None if dzf is None else dzf.ptr, initial), self.plan.status):
                 raise _engine.EngineError('IIR chain failed twice')
+            out = buf.download((self.n_channels, self.n), self.dtype)
+            if return_zf:
+                return out, dzf.download((self.n_channels, D), np.float64)[:, :self.state_dim]
+            return out
+
+    def close(self):
+        self.plan.close()
+
+
+class SampledIirRows:
+    """`predistort(wav_r(t), filters=cascade_r, initial=level_r)` for many channels on one uniform grid, every row
+    its own waveform AND its own cascade (every flux line its own exp-decay correction; reference waveform.py:529-563
+    -> distortion.py:100-185, 298-321), device-resident -- `BatchSampler.launch_torch(z)` followed by
+    `IirStage([...one cascade per row...]).apply_torch(z)` in ONE kernel: the workgroup that owns a row evaluates each
+    tile of 4096 samples in LDS and filters it there, so the unfiltered samples never touch HBM (`fused`;
+    `kernel_name()` is 'iir_rows_sampled<...>' on fine grids, 'iir_rows_short<...>' at AWG sample rates).  Plans the
+    fused kernels do not take (`why_not`) run the two launches.  `sections_rows`: one cascade [(b, a), ...] per
+    resulting row, with `IirStage`'s per-row rules (padded to a common shape: sections of equal order, total state
+    dimension <= 4).  Build once, launch many times.
+
+        sr = SampledIirRows(channels, wl.awg_grid(n, 2e9), [[exp_decay_filter(A, tau, 2e9)] for A, tau in lines])
+        sr.launch_torch(out, initial=levels, zf=zf)     # (n_channels, >= n) device tensor of the plan dtype
+    """
+
+    def __init__(self, channels, grid, sections_rows, dtype=np.float64, function_lib=None, tile=1):
+        """`tile` > 1 repeats the channel list that many times (synthetic batches, as BatchSampler's)"""
+        from . import _flatten
+        self.dtype = np.dtype(dtype)
+        if self.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise ValueError('SampledIirRows: dtype must be float64 or float32')
+        channels, sections_rows = list(channels), list(sections_rows)
+        rows = len(channels) * max(int(tile), 1)
+        if len(sections_rows) != rows:
+            raise ValueError(f'SampledIirRows: {len(sections_rows)} cascades for {rows} rows')
+        packed = _engine.pack_sections_rows(sections_rows)         # argument errors before any device work
+        if not isinstance(grid, _flatten.wfk_grid):
+            grid = _flatten.grid_from_desc(grid)
+        self.prog = _flatten.tile_program(_flatten.flatten(channels, grid, function_lib), tile)
+        if self.prog.n_channels != rows:
+            raise ValueError(f'SampledIirRows: {len(sections_rows)} cascades for {self.prog.n_channels} rows')
+        self.plan = _engine.ChainIirRowsPlan(self.prog, grid, sections_rows, self.dtype, packed=packed)
+        self.n, self.n_channels = self.plan.n, self.plan.n_channels
+        self.state_dim = self.plan.state_dim
+        self.own_orders, self.section_order = packed[3], int(packed[0][0])
+        self.fused, self.why_not = self.plan.fused, self.plan.why_not
+        self._initial_cache = None
+
+    def row_state(self, z, r: int):
+        """row r's own state (scipy layout, its sections back to back) out of a (n_channels, state_dim) host array"""
+        return _row_state(z, r, self.own_orders, self.section_order)
+
+    def kernel_name(self) -> str:
+        """'iir_rows_sampled<T,NSEC,ORD>' | 'iir_rows_short<T,NSEC,ORD>' | '<sampler kernels> + iir_rows_tile<T,NSEC,ORD>'"""
+        return self.plan.kernel_name()
+
+    def launch(self, out_ptr, out_stride=None, zi_ptr=None, zf_ptr=None, initial_ptr=None, stream=0):
+        """raw pointers; initial_ptr: device array of n_channels doubles or None"""
+        self.plan.launch(out_ptr, self.n if out_stride is None else out_stride, zi_ptr, zf_ptr, initial_ptr, stream)
+
+    def launch_torch(self, out, initial=0.0, zi=None, zf=None):
+        """out: (n_channels, >= n) row-contiguous device tensor of the plan dtype (rows may be windows of a wider
+        tensor); `initial`: a scalar, one value per row, or a (n_channels,) float64 device tensor; zi / zf: optional
+        (n_channels, state_dim) float64 device tensors.  Asynchronous on torch's current stream.  -> out"""
+        import torch
+        ptr, stride = _rows.check_rows(
+            out, self.n_channels, self.n, _rows.torch_dtype(self.dtype),
+            'out must be a (n_channels, >=n) row-contiguous device tensor of the plan dtype')
+        zip_, zfp = (_rows.check_state(z, (self.n_channels, self.state_dim),
+                                       'zi / zf must be contiguous (n_channels, state_dim) float64 device tensors')
+                     for z in (zi, zf))
+        ini = _initial_rows(self, self.n_channels, initial, out.device)
+        self.launch(ptr, stride, zip_, zfp, None if ini is None else ini.data_ptr(),
+                    torch.cuda.current_stream(out.device).cuda_stream)
+        return out
+
+    def to_host(self, initial=0.0, zi=None, return_zf=False):
+        """NumPy result (n_channels, n) [, zf (n_channels, state_dim)]; initial: a scalar or one value per row;
+        zi: (n_channels, state_dim)"""
+        D = max(self.state_dim, 1)
+        ini = np.broadcast_to(np.asarray(initial, dtype=np.float64), (self.n_channels, ))
+        with contextlib.ExitStack() as stack:
+            buf = _dev(stack, max(self.n_channels * self.n, 1) * self.dtype.itemsize)
+            dzi = _dev(stack, self.n_channels * D * 8) if zi is not None else None
+            dzf = _dev(stack, self.n_channels * D * 8) if return_zf else None
+            dini = _dev(stack, self.n_channels * 8) if ini.any() else None
+            if zi is not None:
+                dzi.upload(np.ascontiguousarray(np.broadcast_to(np.asarray(zi, dtype=np.float64),
+                                                                (self.n_channels, self.state_dim))))
+            if dini is not None:
+                dini.upload(np.ascontiguousarray(ini))
+            self.launch(buf.ptr, None, None if dzi is None else dzi.ptr, None if dzf is None else dzf.ptr,
+                        None if dini is None else dini.ptr)
+            _engine.sync()
             out = buf.download((self.n_channels, self.n), self.dtype)
             if return_zf:
                 return out, dzf.download((self.n_channels, D), np.float64)[:, :self.state_dim]
