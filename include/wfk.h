@@ -441,6 +441,37 @@ int wfk_shift_rows_apply(wfk_shift_rows_plan* plan, const void* in_dev, int64_t 
 const char* wfk_shift_rows_kernel_name(const wfk_shift_rows_plan* plan);
 int wfk_shift_rows_plan_destroy(wfk_shift_rows_plan* plan);
 
+/* -- per-row DAC codes: scale, round and saturate rows to int16 ---------------------------------- */
+/* `batch` real rows of n samples (kind: WFK_OUT_F64 or WFK_OUT_F32, the INPUT rows) become int16 DAC codes.  Input
+ * row r has gain_host[r] (LSB per unit of the signal) and offset_host[r] (LSB), both finite.  Per sample, in double
+ * (a float sample is widened first) and without a fused multiply-add,
+ *   v = fl(fl(x * gain) + offset),   q = rint(v) (half to even),   lo = -2^(bits - 1),   hi = 2^(bits - 1) - 1,
+ *   c = 0 if v is NaN (counted as nan), lo if q < lo (below; -inf too), hi if q > hi (above; +inf too), q otherwise,
+ *   word = c * 2^shift as int16   (2 <= bits <= 16, 0 <= shift <= 16 - bits: the low `shift` bits are zero).
+ * interleave = k in {1, 2}, batch a multiple of k: output row g holds the input rows g k .. g k + k - 1 sample by
+ * sample, out[g, i k + j] = word[g k + j, i] (k = 2: rows [I, Q] become I0 Q0 I1 Q1 ...); there are batch / k output
+ * rows of k n codes.  n < 0, batch < 1, a gain or offset that is not finite (the row is named), bits / shift /
+ * interleave out of range, a batch that is no multiple of the interleave, a kind other than F64 / F32, null
+ * pointers, more than 2^31 - 1 workgroups: WFK_EINVAL, before any device work; no device: WFK_EHIP.
+ * wfk_dac_rows_apply() allocates nothing and does not synchronise.  in_stride is in samples, >= n; out_stride in
+ * codes, >= k n where there is more than one output row.  counts_dev: NULL, or batch * 3 int64 on the device,
+ * [below, above, nan] per INPUT row; every apply OVERWRITES them (zeroed on the stream, then added to with integer
+ * atomics: bitwise reproducible); without them the kernel does no counting.  OUT OF PLACE only, and the input is
+ * never written: an output extent that meets the input extent, or counts that meet either, WFK_EINVAL.  n = 0:
+ * a no-op that still zeroes the counts.  The plan owns the small row table and nothing else, so it may serve
+ * several streams. */
+typedef struct wfk_dac_rows_plan wfk_dac_rows_plan;
+int wfk_dac_rows_plan_create(int64_t n, int32_t batch, int kind /* WFK_OUT_F64|F32: the INPUT rows */,
+                             const double* gain_host, const double* offset_host, int bits, int shift,
+                             int interleave, wfk_dac_rows_plan** out);
+int wfk_dac_rows_apply(wfk_dac_rows_plan* plan, const void* in_dev, int64_t in_stride,
+                       int16_t* out_dev, int64_t out_stride /* in codes, >= interleave * n */,
+                       int64_t* counts_dev /* batch * 3, or NULL */, void* hip_stream);
+/* "dac_rows<double>" / "dac_rows<float>", or with counts "dac_rows_count<double>" / "dac_rows_count<float>" (the
+ * interleave is an argument of the kernel, not part of its name); a static string */
+const char* wfk_dac_rows_kernel_name(const wfk_dac_rows_plan* plan, int with_counts);
+int wfk_dac_rows_plan_destroy(wfk_dac_rows_plan* plan);
+
 /* -- per-row kernel extraction: the reference's extractKernel for every row ---------------------- */
 /* ker[r] = extractKernel(sig_in[r], sig_out[r], sample_rate, bw, skip) (waveforms/distortion.py:42-48) for `batch`
  * rows of n doubles: the kernel that maps sig_out back onto sig_in, the rows of an FIR plan's kernel matrix.  Per row

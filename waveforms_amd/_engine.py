@@ -139,6 +139,11 @@ def lib():
         l.wfk_shift_rows_kernel_name.argtypes = [VP]
         l.wfk_shift_rows_kernel_name.restype = C.c_char_p
         l.wfk_shift_rows_plan_destroy.argtypes = [VP]
+        l.wfk_dac_rows_plan_create.argtypes = [I64, I32, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, P(VP)]
+        l.wfk_dac_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP]
+        l.wfk_dac_rows_kernel_name.argtypes = [VP, C.c_int]
+        l.wfk_dac_rows_kernel_name.restype = C.c_char_p
+        l.wfk_dac_rows_plan_destroy.argtypes = [VP]
         l.wfk_extract_rows_plan_create.argtypes = [I64, I32, I32, VP, I32, I64, P(VP)]
         l.wfk_extract_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, I64, VP]
         l.wfk_extract_rows_kernel_name.argtypes = [VP]
@@ -716,6 +721,63 @@ class ShiftRowsPlan(_Handle):
 
     def kernel_name(self) -> str:
         return lib().wfk_shift_rows_kernel_name(self._h).decode()
+
+
+def dac_rows_arguments(gain, offset, n, bits=16, shift=0, interleave=1, dtype=np.float64):
+    """the arguments of a DacRowsPlan, checked on the host -> (gain, offset: float64 arrays of one length, n, bits,
+    shift, interleave, dtype).  ValueError / NotImplementedError as DacRowsPlan lists them."""
+    n, bits, shift, interleave, dtype = int(n), int(bits), int(shift), int(interleave), np.dtype(dtype)
+    if dtype.kind == 'c':
+        raise NotImplementedError('complex rows')
+    if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError('dtype must be float64 or float32')
+    gain = np.ascontiguousarray(gain, dtype=np.float64).reshape(-1)
+    offset = np.ascontiguousarray(offset, dtype=np.float64).reshape(-1)
+    if len(gain) < 1 or len(offset) != len(gain):
+        raise ValueError(f'{len(gain)} gains and {len(offset)} offsets: one of each per row, at least one row')
+    if n < 0:
+        raise ValueError('n >= 0')
+    if not 2 <= bits <= 16:
+        raise ValueError('bits must lie in [2, 16]')
+    if not 0 <= shift <= 16 - bits:
+        raise ValueError(f'shift must lie in [0, 16 - bits] = [0, {16 - bits}]')
+    if interleave not in (1, 2):
+        raise ValueError('interleave must be 1 or 2')
+    if len(gain) % interleave:
+        raise ValueError(f'{len(gain)} rows are no multiple of the interleave {interleave}')
+    for name, a in (('gain', gain), ('offset', offset)):
+        bad = np.flatnonzero(~np.isfinite(a))
+        if len(bad):
+            raise ValueError(f'row {int(bad[0])}: {name} is not finite')
+    return gain, offset, n, bits, shift, interleave, dtype
+
+
+class DacRowsPlan(_Handle):
+    """codes[r] = saturate(rint(x[r] * gain[r] + offset[r])) * 2**shift as int16 for `batch` = len(gain) rows of n
+    float64 / float32 samples (the product and the sum each rounded, half to even, clamped to `bits` signed bits; NaN
+    gives 0), `interleave` input rows sample-interleaved into one output row (wfk_dac_rows_plan_create).
+    `.lo` / `.hi`: the rails; `.out_rows`, `.out_n`: the shape of the result.  ValueError before any device work:
+    no rows, lengths that differ, n < 0, bits outside [2, 16], shift outside [0, 16 - bits], an interleave other
+    than 1 or 2, a batch that is no multiple of it, a gain or offset that is not finite, a dtype other than float64 /
+    float32 (NotImplementedError for a complex one)."""
+    _destroy = 'wfk_dac_rows_plan_destroy'
+
+    def __init__(self, gain, offset, n: int, bits: int = 16, shift: int = 0, interleave: int = 1, dtype=np.float64):
+        (self.gain, self.offset, self.n, self.bits, self.shift, self.interleave,
+         self.dtype) = dac_rows_arguments(gain, offset, n, bits, shift, interleave, dtype)
+        self.batch = len(self.gain)
+        self.lo, self.hi = -2**(self.bits - 1), 2**(self.bits - 1) - 1
+        self.out_rows, self.out_n = self.batch // self.interleave, self.interleave * self.n
+        check(lib().wfk_dac_rows_plan_create(self.n, self.batch, _KIND_OF[self.dtype], self.gain.ctypes.data,
+                                             self.offset.ctypes.data, self.bits, self.shift, self.interleave,
+                                             C.byref(self._h)))
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, counts_ptr=None, stream=0):
+        """counts_ptr: None, or batch * 3 int64 on the device, overwritten with [below, above, nan] per input row"""
+        check(lib().wfk_dac_rows_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, counts_ptr, stream))
+
+    def kernel_name(self, counts: bool = False) -> str:
+        return lib().wfk_dac_rows_kernel_name(self._h, 1 if counts else 0).decode()
 
 
 class ExtractRowsPlan(_Handle):

@@ -9,12 +9,13 @@ _TORCH = {}
 
 
 def torch_dtype(dtype):
-    """the torch dtype of a plan's NumPy dtype: float64 / float32 rows, the demodulator's int16 codes and its
-    complex128 result"""
+    """the torch dtype of a plan's NumPy dtype: float64 / float32 rows, int16 codes (the demodulator's input, the DAC
+    stage's output), the DAC stage's int64 counts and the demodulator's complex128 result"""
     if not _TORCH:
         import torch
         _TORCH.update({np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32,
-                       np.dtype(np.int16): torch.int16, np.dtype(np.complex128): torch.complex128})
+                       np.dtype(np.int16): torch.int16, np.dtype(np.int64): torch.int64,
+                       np.dtype(np.complex128): torch.complex128})
     return _TORCH[np.dtype(dtype)]
 
 
@@ -30,12 +31,13 @@ def check_rows(t, rows, n, dtype, message, exact=False, device=True):
     return t.data_ptr(), max(t.stride(0), n)
 
 
-def check_state(z, shape, message, device=True):
-    """what goes with the rows -- zi / zf (rows, state_dim), levels (rows,): None, or a contiguous float64 device tensor
-    of that shape (ValueError(message) otherwise) -> None or its data_ptr"""
+def check_state(z, shape, message, device=True, dtype=np.float64):
+    """what goes with the rows -- zi / zf (rows, state_dim), levels (rows,), the DAC stage's int64 counts (rows, 3):
+    None, or a contiguous device tensor of that shape and of `dtype` (float64 unless given; ValueError(message)
+    otherwise) -> None or its data_ptr"""
     if z is None:
         return None
-    if ((device and not z.is_cuda) or z.dtype != torch_dtype(np.float64) or not z.is_contiguous()
+    if ((device and not z.is_cuda) or z.dtype != torch_dtype(dtype) or not z.is_contiguous()
             or tuple(z.shape) != tuple(shape)):
         raise ValueError(message)
     return z.data_ptr()

@@ -1183,6 +1183,111 @@ def shift_rows(sig, delays, dt):
         return y.download(sig2.shape, sig2.dtype)
 
 
+class DacStage:
+    """Device-resident volts -> DAC codes for `batch` rows of `n` samples (build once, apply many times): the last
+    step before an upload to an AWG.  Input row r has `gain[r]` (LSB per unit of the signal) and `offset[r]` (LSB);
+    in float64 (a float32 sample is widened first), product and sum each rounded (no fused multiply-add):
+        v = x[r, i] * gain[r] + offset[r];   q = rint(v), half to even;   lo = -2**(bits - 1), hi = 2**(bits - 1) - 1
+        c = 0 where v is NaN, lo where q < lo, hi where q > hi, q otherwise;   code = c * 2**shift as int16
+    (`shift` left-justifies a 12/14-bit converter in its 16-bit word).  `interleave=2` packs the rows [I, Q] of a pair
+    into one output row I0 Q0 I1 Q1 ...: `.out_rows = batch // interleave` rows of `.out_n = interleave * n` codes.
+    `gain` / `offset`: a scalar (every row; give `batch`) or one value per INPUT row.  An optional (batch, 3) int64
+    counts tensor is OVERWRITTEN by every apply with [below, above, nan] per input row: how many samples clipped.
+
+        st = DacStage.from_full_scale(1.0, n, batch=rows)       # +-1.0 -> +-32767
+        codes = st.apply_torch(z, counts=clipped)               # out of place, on torch's current stream
+    """
+
+    def __init__(self, gain, n: int, offset=0.0, bits: int = 16, shift: int = 0, interleave: int = 1,
+                 dtype=np.float64, batch=None):
+        if np.ndim(gain) == 0 and np.ndim(offset) == 0 and batch is None:
+            raise ValueError('DacStage: a scalar gain and offset need batch=')
+        if batch is None:
+            batch = np.size(gain) if np.ndim(gain) > 0 else np.size(offset)
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError('DacStage: no rows')
+        gains, offsets = (_per_row('DacStage', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v, batch)
+                          for what, v in (('gain', gain), ('offset', offset)))
+        self.plan = _engine.DacRowsPlan(gains, offsets, n, bits, shift, interleave, dtype)
+        p = self.plan
+        self.n, self.batch, self.dtype, self.gain, self.offset = p.n, p.batch, p.dtype, p.gain, p.offset
+        self.bits, self.shift, self.interleave = p.bits, p.shift, p.interleave
+        self.lo, self.hi, self.out_rows, self.out_n = p.lo, p.hi, p.out_rows, p.out_n
+
+    @classmethod
+    def from_full_scale(cls, full_scale_rows, n: int, **kw):
+        """the stage whose gain[r] = hi / full_scale_rows[r], so that +-full scale maps to +-hi (a scalar: every row;
+        give `batch`).  ValueError: a full scale that is not finite or not positive."""
+        bits = int(kw.get('bits', 16))
+        if not 2 <= bits <= 16:
+            raise ValueError('bits must lie in [2, 16]')
+        fs = np.asarray(full_scale_rows, dtype=np.float64)
+        if not np.all(np.isfinite(fs) & (fs > 0.0)):
+            raise ValueError('DacStage: every full scale must be finite and positive')
+        return cls((2**(bits - 1) - 1) / fs, n, **kw)
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, counts_ptr=None, stream=0):
+        self.plan.apply(in_ptr, in_stride, out_ptr, out_stride, counts_ptr, stream)
+
+    def kernel_name(self, counts: bool = False) -> str:
+        return self.plan.kernel_name(counts)
+
+    def apply_torch(self, x, out=None, counts=None):
+        """x: (batch, >= n) row-contiguous device tensor of the stage's dtype; out: (out_rows, >= out_n) int16 (rows
+        may be windows of a wider tensor; None: allocated); counts: None or a contiguous (batch, 3) int64 device
+        tensor, overwritten.  Out of place: `out` may share no memory with `x`, `counts` with neither (ValueError);
+        `x` is never written.  Asynchronous on torch's current stream.  -> out[:, :out_n]"""
+        import torch
+        x0, xs = _rows.check_rows(x, self.batch, self.n, _rows.torch_dtype(self.dtype),
+                                  'expected x: (batch, >=n) row-contiguous device tensor of the stage dtype')
+        if out is None:
+            out = torch.empty((self.out_rows, self.out_n), dtype=torch.int16, device=x.device)
+        y0, ys = _rows.check_rows(out, self.out_rows, self.out_n, torch.int16,
+                                  'expected out: (out_rows, >=out_n) row-contiguous int16 device tensor')
+        c0 = _rows.check_state(counts, (self.batch, 3), 'expected counts: contiguous (batch, 3) int64 device tensor',
+                               dtype=np.int64)
+        xr, yr = (x0, xs, self.batch, self.n, self.dtype.itemsize), (y0, ys, self.out_rows, self.out_n, 2)
+        if not _rows.rows_disjoint(xr, yr):
+            raise ValueError('dac stage is out of place: out overlaps x')
+        if c0 is not None and not (_rows.rows_disjoint((c0, 3, self.batch, 3, 8), xr)
+                                   and _rows.rows_disjoint((c0, 3, self.batch, 3, 8), yr)):
+            raise ValueError('dac stage: counts overlaps x / out')
+        self.apply(x0, xs, y0, ys, c0, torch.cuda.current_stream(x.device).cuda_stream)
+        return out[:, :self.out_n]
+
+    def close(self):
+        self.plan.close()
+
+
+def dac_codes_rows(sig, gain, offset=0.0, bits=16, shift=0, interleave=1, return_counts=False):
+    """The int16 DAC codes of every row of a 2-D real `sig` (see `DacStage` for the formula), all rows in one launch:
+    NumPy in, NumPy out, (rows // interleave, interleave * samples).  `gain` / `offset`: a scalar (every row) or one
+    value per row.  float32 rows stay float32 on the way in, anything else is read as float64.  `return_counts`:
+    -> (codes, counts), counts the (rows, 3) int64 [below, above, nan] per input row.  ValueError before any device
+    work: sig not 2-D, a number of gains or offsets that does not match, what `DacStage` refuses.
+    NotImplementedError: complex rows."""
+    src = np.asarray(sig)
+    if src.ndim == 2 and src.dtype == np.float32:
+        sig2 = np.ascontiguousarray(src)
+    else:
+        sig2 = _rows_signal('dac_codes_rows', sig)
+    batch, n = sig2.shape
+    gains = _per_row('dac_codes_rows', 'gain', gain, batch)
+    offsets = _per_row('dac_codes_rows', 'offset', offset, batch)
+    g, o, n, bits, shift, k, dtype = _engine.dac_rows_arguments(gains, offsets, n, bits, shift, interleave, sig2.dtype)
+    if n == 0:
+        codes, counts = np.zeros((batch // k, 0), dtype=np.int16), np.zeros((batch, 3), dtype=np.int64)
+        return (codes, counts) if return_counts else codes
+    with _engine.DacRowsPlan(g, o, n, bits, shift, k, dtype) as plan, _engine.DeviceBuffer(sig2.nbytes) as x, \
+            _engine.DeviceBuffer(batch * n * 2) as y, _engine.DeviceBuffer(batch * 24) as c:
+        x.upload(sig2)
+        plan.apply(x.ptr, n, y.ptr, k * n, c.ptr if return_counts else None)
+        _engine.sync()
+        codes = y.download((batch // k, k * n), np.int16)
+        return (codes, c.download((batch, 3), np.int64)) if return_counts else codes
+
+
 def _extract_taps(name, n, sample_rate, bw):
     """the smoothing taps of extractKernel for rows of n samples, by the reference's own expressions
     (distortion.py:45-47), or None where it does not smooth (bw is None or bw >= sample_rate / 2).  ValueError: a
