@@ -204,11 +204,17 @@ def test_parsed_tree_through_sample_and_chunks():
     # Waveform.sample() and the chunked iterator on a parsed tree (reference waveform.py:173-257)
     argv, text, twin, start, stop, rate, amp = cases.CLI_CASES['cli_awg']
     w = wave_eval(text)
-    w.start, w.stop, w.sample_rate = start, stop, rate
-    full = w.sample()
-    close(full, N4['cli.cli_awg'])
-    chunks = np.concatenate(list(w.sample(chunk_size=257)))
-    assert chunks.shape == full.shape and np.max(np.abs(chunks - full)) <= 1e-12
+    # (wave_eval is an lru_cache: the tree is shared with every later caller in the process, so what is set on it here
+    #  is put back -- tests/test_n4_oracle_cpu.py::test_cli_twin compares this tree's tolist() with a fresh twin's)
+    before = (w.start, w.stop, w.sample_rate)
+    try:
+        w.start, w.stop, w.sample_rate = start, stop, rate
+        full = w.sample()
+        close(full, N4['cli.cli_awg'])
+        chunks = np.concatenate(list(w.sample(chunk_size=257)))
+        assert chunks.shape == full.shape and np.max(np.abs(chunks - full)) <= 1e-12
+    finally:
+        w.start, w.stop, w.sample_rate = before
 
 
 @pytest.mark.parametrize('name', sorted(cases.out_nonfinite_cases()))

@@ -1,5 +1,8 @@
 """Sample indices beyond 2^31: one channel of 2^31 + 2^21 + 7 points (fp32, 8.6 GB).  Every index
-in the library is 64-bit; this is the test that says so.  The oracle cannot produce 2^31
+in the library is 64-bit; this file says so for LONG ROWS -- a sample index past 2^31 inside one row -- for the
+sampler, the FIR stage, the shared IIR plan and the two flat streaming stages (shift, DAC codes), and for a
+row * stride product past 2^31 with contiguous rows (512 x 1e7).  Rows that are FAR APART (a row stride past 2^32,
+every stage) are tests/test_gpu_far_rows.py.  The oracle cannot produce 2^31
 samples in seconds, so it evaluates windows of the same grid (first, middle, around 2^31, last)
 at the exact grid times; the FIR and IIR stages are checked on the tail the same way
 (size-independent properties: locality of the FIR, linearity / steady state of the IIR)."""
@@ -11,11 +14,14 @@ import waveforms_amd as wf
 from oracle import c_oracle
 from waveforms_amd import _engine, _flatten, workloads as wl
 from waveforms_amd._sampling import BatchSampler
-from waveforms_amd.distortion import FirStage
+from waveforms_amd.distortion import DacStage, FirStage, ShiftStage
+import dac_rows_ref
+import shift_rows_ref
 
 pytestmark = pytest.mark.gpu
 
 N = 2**31 + 2**21 + 7
+WINDOWS = [(0, 200000), (N // 2 - 60000, N // 2 + 60000), (2**31 - 70000, 2**31 + 70000), (N - 150000, N)]
 T0, T1 = 0.0, 4.0e-3                      # 4 ms at ~537 GS/s: step ~1.86e-12
 STEP = (T1 - T0) / N
 
@@ -45,9 +51,7 @@ def test_sampler_fir_iir_beyond_2_pow_31():
     bs.launch_torch(out)
     torch.cuda.synchronize()
     prog = _flatten.flatten([w])
-    windows = [(0, 200000), (N // 2 - 60000, N // 2 + 60000), (2**31 - 70000, 2**31 + 70000),
-               (N - 150000, N)]
-    for a, b in windows:
+    for a, b in WINDOWS:
         t = _grid_times(np.arange(a, b))
         ref = c_oracle.eval_tlist(prog, t)[0]
         got = out[0, a:b].cpu().numpy().astype(np.float64)
@@ -99,6 +103,50 @@ def test_sampler_fir_iir_beyond_2_pow_31():
     assert np.all(np.isfinite(zf.cpu().numpy()))
     iir.close()
     bs.close()
+
+
+def test_shift_and_dac_beyond_2_pow_31():
+    """The two flat streaming stages on one float32 row of N samples made on the device from a fixed seed: ShiftStage
+    with a fractional delay, out of place, then DacStage to int16 with counts.  On the host, the four windows of this
+    file: the shift against tests/shift_rows_ref.py at its float32 bound (a window's reference is the referee on the
+    window and the `lead` samples in front of it, which the delay reaches back into), the codes against
+    tests/dac_rows_ref.py for equality; the three counts against a recount in torch over the whole row."""
+    import torch
+    gen = torch.Generator(device='cuda').manual_seed(15)
+    x = torch.empty((1, N), dtype=torch.float32, device='cuda')
+    for lo in range(0, N, 2**28):                                   # samples in +-1.2 of full scale: both rails clip
+        x[0, lo:lo + 2**28].uniform_(-1.2, 1.2, generator=gen)
+    delay, lead = 2.25, 8
+    shift = ShiftStage([delay], N, 1.0, np.float32)
+    assert shift.kernel_name() == 'shift_rows<float>' and (shift.points[0], shift.deltas[0]) == (2, 0.25)
+    y = torch.full_like(x, 9.0)
+    shift.apply_torch(x, y)
+    gain, offset = 32767.0, 12.5
+    dac = DacStage([gain], N, offset=[offset], dtype=np.float32)
+    assert dac.kernel_name(counts=True) == 'dac_rows_count<float>'
+    counts = torch.full((1, 3), -77, dtype=torch.int64, device='cuda')
+    codes = dac.apply_torch(y, counts=counts)
+    torch.cuda.synchronize()
+    assert codes.shape == (1, N) and codes.dtype == torch.int16
+    for a, b in WINDOWS:
+        a0 = max(a - lead, 0)
+        xin = x[0, a0:b].cpu().numpy()
+        want, B = shift_rows_ref.shift_ref(xin, 2, 0.25)
+        got = y[0, a:b].cpu().numpy()
+        shift_rows_ref.check(got, want[a - a0:], B[a - a0:], f'shift window {a}..{b}', shift_rows_ref.EPS32)
+        want_codes, _ = dac_rows_ref.dac_ref(got[None], gain, offset)
+        assert np.array_equal(codes[0, a:b].cpu().numpy(), want_codes[0]), (a, b)
+    # the counts over the whole row, recounted on the device a slab at a time (float64, as the stage computes)
+    below = above = nan = 0
+    for lo in range(0, N, 2**27):
+        v = y[0, lo:lo + 2**27].double() * gain + offset
+        q = torch.round(v)
+        below += int((q < -32768).sum())
+        above += int((q > 32767).sum())
+        nan += int(torch.isnan(v).sum())
+    assert counts.cpu().numpy().tolist() == [[below, above, nan]] and below > 1e7 and above > 1e7 and nan == 0
+    shift.close()
+    dac.close()
 
 
 def test_c5_per_rank_shape_512_channels_1e7():

@@ -170,14 +170,33 @@ def test_shared_input_equals_replicated_input_bitwise_and_overlap_is_refused():
     plan.close()
 
 
-@pytest.mark.parametrize('pp,c', [(37, 18), (37, -10), (1, 0), (0, 5), (700, 3000), (2000, 999)])
-def test_raw_probe_plan_against_numpy(pp, c):
+def probe_input(pp, c, n=5000):
+    """-> (tlist: any ascending grid of n points, t: probe times inside, outside, on its ends and a NaN, gain)"""
     rng = np.random.default_rng(pp + 13 * c + 100)
-    n, rows, stride = 5000, 3, 5003
-    tlist = np.cumsum(rng.uniform(0.5, 1.5, n)) - 2500.0            # any ascending grid
+    tlist = np.cumsum(rng.uniform(0.5, 1.5, n)) - 2500.0
     t = np.concatenate([rng.uniform(tlist[0] - 50, tlist[-1] + 50, 300), tlist[[0, 1, n - 2, n - 1, 2500]],
                         np.nextafter(tlist[[0, n - 1]], 0.0), [np.nan]])
-    gain = 0.37
+    return rng, tlist, t, 0.37
+
+
+def probe_numpy(y, n, tlist, t, pp, c, gain):
+    """the probe in NumPy for rows y (rows, >= n): the box sum of pp samples ending c past each sample, from a cumulative
+    sum of y with zeros on both sides, interpolated at t -> (want (rows, len(t)), the bound of a row's finite results)"""
+    rows = y.shape[0]
+    pad = np.zeros((rows, 3 * n + 2 * abs(c) + pp))                  # y with zeros on both sides
+    off = n + abs(c) + pp
+    pad[:, off:off + n] = y[:, :n]
+    cs = np.concatenate([np.zeros((rows, 1)), np.cumsum(pad, axis=1)], axis=1)
+    i = np.arange(n)
+    conv = gain * (cs[:, off + i + c + 1] - cs[:, off + i + c - pp + 1])
+    tol = 1e-12 * gain * (pp + 1) * np.abs(y).max() + 1e-13 * np.abs(cs).max()
+    return np.stack([np.interp(t, tlist, conv[r]) for r in range(rows)]), tol
+
+
+@pytest.mark.parametrize('pp,c', [(37, 18), (37, -10), (1, 0), (0, 5), (700, 3000), (2000, 999)])
+def test_raw_probe_plan_against_numpy(pp, c):
+    n, rows, stride = 5000, 3, 5003
+    rng, tlist, t, gain = probe_input(pp, c, n)
     y = rng.standard_normal((rows, stride))
     plan = _engine.BoxProbePlan(tlist, t, pp, c, gain)
     assert plan.kernel_name() == 'boxprobe_wave'
@@ -188,16 +207,10 @@ def test_raw_probe_plan_against_numpy(pp, c):
     o = out.cpu().numpy()
     assert np.all(o[:, len(t):] == 5.0)
     got = o[:, :len(t)]
-    pad = np.zeros((rows, 3 * n + 2 * abs(c) + pp))                  # y with zeros on both sides
-    off = n + abs(c) + pp
-    pad[:, off:off + n] = y[:, :n]
-    cs = np.concatenate([np.zeros((rows, 1)), np.cumsum(pad, axis=1)], axis=1)
-    i = np.arange(n)
-    conv = gain * (cs[:, off + i + c + 1] - cs[:, off + i + c - pp + 1])
+    wants, tol = probe_numpy(y, n, tlist, t, pp, c, gain)
     for r in range(rows):
-        want = np.interp(t, tlist, conv[r])
+        want = wants[r]
         assert np.isnan(got[r, -1]) and np.isnan(want[-1])
-        tol = 1e-12 * gain * (pp + 1) * np.abs(y).max() + 1e-13 * np.abs(cs).max()
         assert np.max(np.abs(got[r, :-1] - want[:-1])) <= tol, (r, np.max(np.abs(got[r, :-1] - want[:-1])), tol)
     for bad in (lambda: plan.apply(yd.data_ptr(), rows, n - 1, out.data_ptr(), len(t)),
                 lambda: plan.apply(yd.data_ptr(), rows, stride, out.data_ptr(), len(t) - 1),
