@@ -12,7 +12,8 @@ The list: the sampler plans of tests/test_kernel_names.py with their environment
 lengths, far_from_origin_case, the fine-grid list and the malformed programs of tools/sanitize/run_sanitized.py
 and N random scripts, every one as a grid and as a jittered time list; a witness per request switch and per
 environment switch of the compiler's table; plans for every retry of the ladder; wfk_compile_geom at the two
-chain geometries; wfk_compile_blocks on 2, 3 and 4 threads; the three timing workloads."""
+chain geometries; wfk_compile_blocks on 2, 3 and 4 threads; plans that reach the branches of the piece loop which
+none of these takes (`reach.*`: found with the coverage build of tools/plan_image.sh); the three timing workloads."""
 import argparse
 import os
 import struct
@@ -308,6 +309,48 @@ def main():
         broken(k, e)
     w.add('malformed.grid_step', _flatten.flatten([wf.gaussian(0.5)]), grid=_flatten.wfk_grid(0.0, -1.0, 10, 0, 0.0))
     w.add('malformed.grid_i0', _flatten.flatten([wf.gaussian(0.5)]), grid=_flatten.wfk_grid(0.0, 1.0, 10, 0, 0.0, -1))
+
+    # ---- branches of the piece loop that none of the lists above takes ----
+    FINE_G = _flatten.grid_from_desc(tkn.FINE)
+    sq = wf.square(W) >> 60e-9
+    # direct-factor records: a Gaussian derivative next to a factor that does not fuse (the term stays generic) ...
+    for d in (1, 2):
+        w.both('reach.direct_dgauss.%d' % d, [(wf.gaussian(W, d=d) * wf.sinc(2e8)) >> 60e-9], tkn.FINE, rng)
+    # ... and a caller-evaluated factor: one table, its member piece cut into three device pieces by a second member
+    unit = _flatten.grid_linspace(-3.0, 3.0, 4001)
+    tanh = wf.function(np.tanh, start=-2, stop=2) * wf.cos(3.0)
+    w.add('reach.direct_sampled', _flatten.flatten([tanh], axis=unit), grid=unit)
+    stack = wf.WaveVStack([tanh, 0.5 * (wf.square(1.0) >> 0.25) * wf.sinc(2.0)])
+    w.add('reach.direct_sampled_shared', _flatten.flatten([stack], axis=unit), grid=unit)
+    # more generic terms than one LDS block holds: the piece is cut into several blocks
+    many = wf.zero()
+    for k in range(70):
+        many = many + 0.01 * wf.sinc(1e8 + 1e6 * k) * wf.cos(2 * np.pi * (2e7 + 3e6 * k))
+    w.both('reach.blocks_overflow', [sq * many], tkn.FINE, rng)
+    # a chirp multiplied by a carrier, in both orders, and by two
+    CH = ('linspace', 0.0, 500e-9, 50000, False)
+    chirp = wf.chirp(1e8, 2e8, 300e-9) >> 100e-9
+    w.both('reach.chirp_carrier', [chirp * wf.cos(2 * np.pi * 5e7, 0.3)], CH, rng)
+    w.both('reach.carrier_chirp', [wf.cos(2 * np.pi * 5e7, 0.3) * chirp + (wf.gaussian(20e-9) >> 50e-9)], CH, rng)
+    w.both('reach.chirp_two_carriers', [chirp * wf.cos(2 * np.pi * 5e7) * wf.cos(2 * np.pi * 3e7, 1.0)], CH, rng)
+    # an exponential of its own under a power of t (its rate weighed with the term's amplitude); rates that cancel to a constant
+    ramp = wf.poly([0.5, 1e7]) >> 60e-9
+    w.both('reach.exp_linear', [sq * (wf.exp(-3e7) >> 20e-9) * ramp, 40.0 * sq * (wf.exp(9e7) >> 20e-9) * ramp * ramp], tkn.FINE, rng)
+    w.both('reach.exp_cancels', [sq * (wf.exp(-3e7) >> 20e-9) * (wf.exp(3e7) >> 50e-9) * tones(2),
+                                 sq * (wf.cosh(2e7) >> 50e-9) * (wf.exp(2e7) >> 55e-9)], tkn.FINE, rng)
+    # a product of three DRAG pulses: more carriers than a term may expand into (it stays generic)
+    d3 = wf.drag(2e8, W, delta=1e6, block_freq=3e8) * wf.drag(1.5e8, W, phase=0.4) * wf.drag(1e8, W, delta=-2e6)
+    w.both('reach.carriers_overflow', [d3 >> 40e-9], tkn.FINE, rng)
+    # 36 tones under two Gaussians in turn: more per-lane state than a lean block has units
+    wide_state = wf.zero()
+    for k in range(36):
+        wide_state = wide_state + 0.03 * wf.gaussian(W + 2e-9 * (k % 2)) * wf.cos(2 * np.pi * (2e7 + 5e6 * k))
+    w.both('reach.state_units', [wide_state >> 60e-9], tkn.FINE, rng)
+    # refused: one generic term of more factors than the LDS parameter buffer takes
+    wide = sq
+    for k in range(50):
+        wide = wide * (wf.sinc(1e8 + 1e6 * k) >> (60e-9 + 1e-10 * k))
+    w.add('reach.term_too_wide', _flatten.flatten([wide]), grid=FINE_G)
 
     # ---- the timing workloads (plan_image --time) ----
     G1 = _flatten.grid_from_desc(wl.awg_grid(100000, 2e9))
