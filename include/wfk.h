@@ -472,6 +472,53 @@ int wfk_dac_rows_apply(wfk_dac_rows_plan* plan, const void* in_dev, int64_t in_s
 const char* wfk_dac_rows_kernel_name(const wfk_dac_rows_plan* plan, int with_counts);
 int wfk_dac_rows_plan_destroy(wfk_dac_rows_plan* plan);
 
+/* -- per-row gate markers: widened, as bytes or into one bit of the DAC codes -------------------- */
+/* `batch` real rows of n samples (kind: WFK_OUT_F64 or WFK_OUT_F32) drive batch / group marker rows: the marker
+ * line that opens a switch or blanks an amplifier around every pulse, derived from the IDEAL gate rows (exact zeros
+ * outside the pulses), not from predistorted ones.  group = k in {1, 2}, batch a multiple of k: marker row g is driven
+ * by the input rows g k .. g k + k - 1 (k = 2: the I and Q of a pair, as wfk_dac_rows pairs them).  Marker row g has
+ * threshold_host[g] (finite, >= 0) and lead_host[g], trail_host[g] (samples, in [0, WFK_MARKER_MAX_EDGE]).  Exact,
+ * in integers:
+ *   active[g, i] = any_j  fabs((double)x[g k + j, i]) > threshold[g]   (NaN is inactive, +-inf active, -0.0 and a
+ *                                                                       sample equal to the threshold inactive)
+ *   m[g, i]      = any    active[g, j]  for j in [i - trail[g], i + lead[g]], clipped to [0, n)
+ * so the marker rises `lead` samples before the first active sample of a burst and falls `trail` samples after the
+ * last, and gaps shorter than lead + trail + 1 close.  Two forms:
+ *   wfk_marker_rows_apply():        out[g, i] = m[g, i] as uint8 0 / 1, batch / k rows of n bytes;
+ *   wfk_marker_rows_apply_codes():  codes is batch / k rows of k n int16 in the layout wfk_dac_rows(interleave = k)
+ *     produces, and codes[g, p] = (codes[g, p] & ~(1 << bit)) | (m[g, p / k] << bit), 0 <= bit <= 15, IN PLACE: the
+ *     bit is overwritten, not OR-ed (a second apply gives the same codes), and no other bit of a code changes.
+ * n < 0, batch < 1, a group other than 1 or 2, a batch that is no multiple of it, a threshold that is negative or
+ * not finite, a lead or trail that is negative or exceeds WFK_MARKER_MAX_EDGE (the row is named: "row 3: lead exceeds
+ * 4096"), a kind other than F64 / F32, null pointers, more than 2^31 - 1 workgroups: WFK_EINVAL, before any device
+ * work; no device: WFK_EHIP.
+ * The applies allocate nothing and do not synchronise.  in_stride is in samples, >= n; out_stride in bytes, >= n,
+ * codes_stride in codes, >= k n, where there is more than one marker row.  counts_dev: NULL, or batch / k * 2 int64
+ * on the device, [high, pulses] per marker row -- the samples with m = 1, and those of them with i = 0 or
+ * m[g, i - 1] = 0; every apply OVERWRITES them (zeroed on the stream, then added to with integer atomics: bitwise
+ * reproducible); without them the kernel does no counting.  The input is never written; out / codes may share no
+ * memory with it, counts with neither; a bit outside [0, 15], rows not aligned to their element, a stride below
+ * the row: WFK_EINVAL.  n = 0: a no-op that still zeroes the counts.  The plan owns the small row table and nothing
+ * else, so it may serve several streams. */
+#define WFK_MARKER_MAX_EDGE 4096   /* 2 us at 2 GS/s */
+typedef struct wfk_marker_rows_plan wfk_marker_rows_plan;
+int wfk_marker_rows_plan_create(int64_t n, int32_t batch, int kind /* WFK_OUT_F64|F32 */, int group,
+                                const double* threshold_host, const int32_t* lead_host,
+                                const int32_t* trail_host /* batch / group of each */, wfk_marker_rows_plan** out);
+int wfk_marker_rows_apply(wfk_marker_rows_plan* plan, const void* in_dev, int64_t in_stride,
+                          uint8_t* out_dev, int64_t out_stride /* in bytes, >= n */,
+                          int64_t* counts_dev /* batch / group * 2, or NULL */, void* hip_stream);
+int wfk_marker_rows_apply_codes(wfk_marker_rows_plan* plan, const void* in_dev, int64_t in_stride,
+                                int16_t* codes_dev, int64_t codes_stride /* in codes, >= group * n */, int bit,
+                                int64_t* counts_dev /* batch / group * 2, or NULL */, void* hip_stream);
+/* the samples one workgroup covers: 16384 as bytes, 8192 / group into codes (0 for a null plan) */
+int64_t wfk_marker_rows_span(const wfk_marker_rows_plan* plan, int into_codes);
+/* "marker_rows<double>", "marker_rows_codes<double>", with counts "marker_rows_count<double>",
+ * "marker_rows_codes_count<double>", and the same four with <float> (the group is an argument of the kernel, not
+ * part of its name); a static string */
+const char* wfk_marker_rows_kernel_name(const wfk_marker_rows_plan* plan, int into_codes, int with_counts);
+int wfk_marker_rows_plan_destroy(wfk_marker_rows_plan* plan);
+
 /* -- per-row kernel extraction: the reference's extractKernel for every row ---------------------- */
 /* ker[r] = extractKernel(sig_in[r], sig_out[r], sample_rate, bw, skip) (waveforms/distortion.py:42-48) for `batch`
  * rows of n doubles: the kernel that maps sig_out back onto sig_in, the rows of an FIR plan's kernel matrix.  Per row

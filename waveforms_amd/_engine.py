@@ -144,6 +144,14 @@ def lib():
         l.wfk_dac_rows_kernel_name.argtypes = [VP, C.c_int]
         l.wfk_dac_rows_kernel_name.restype = C.c_char_p
         l.wfk_dac_rows_plan_destroy.argtypes = [VP]
+        l.wfk_marker_rows_plan_create.argtypes = [I64, I32, C.c_int, C.c_int, VP, VP, VP, P(VP)]
+        l.wfk_marker_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP]
+        l.wfk_marker_rows_apply_codes.argtypes = [VP, VP, I64, VP, I64, C.c_int, VP, VP]
+        l.wfk_marker_rows_span.argtypes = [VP, C.c_int]
+        l.wfk_marker_rows_span.restype = I64
+        l.wfk_marker_rows_kernel_name.argtypes = [VP, C.c_int, C.c_int]
+        l.wfk_marker_rows_kernel_name.restype = C.c_char_p
+        l.wfk_marker_rows_plan_destroy.argtypes = [VP]
         l.wfk_extract_rows_plan_create.argtypes = [I64, I32, I32, VP, I32, I64, P(VP)]
         l.wfk_extract_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, I64, VP]
         l.wfk_extract_rows_kernel_name.argtypes = [VP]
@@ -778,6 +786,83 @@ class DacRowsPlan(_Handle):
 
     def kernel_name(self, counts: bool = False) -> str:
         return lib().wfk_dac_rows_kernel_name(self._h, 1 if counts else 0).decode()
+
+
+MARKER_MAX_EDGE = 4096     # WFK_MARKER_MAX_EDGE
+
+
+def marker_rows_arguments(threshold, lead, trail, n, group=1, dtype=np.float64):
+    """the arguments of a MarkerRowsPlan, checked on the host -> (threshold: float64, lead, trail: int32 arrays of one
+    length, one entry per MARKER row, n, group, dtype).  ValueError / NotImplementedError as MarkerRowsPlan lists them."""
+    n, group, dtype = int(n), int(group), np.dtype(dtype)
+    if dtype.kind == 'c':
+        raise NotImplementedError('complex rows')
+    if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError('dtype must be float64 or float32')
+    threshold = np.ascontiguousarray(threshold, dtype=np.float64).reshape(-1)
+    edges = []
+    for name, v in (('lead', lead), ('trail', trail)):
+        a = np.asarray(v).reshape(-1)
+        if a.dtype.kind not in 'iu' and not (a.dtype.kind == 'f' and np.all(np.isfinite(a)) and np.all(a == np.rint(a))):
+            raise ValueError(f'{name} is a number of samples: integers, got {a.dtype}')
+        edges.append(np.array([int(e) for e in a], dtype=object))
+    if len(threshold) < 1 or len(edges[0]) != len(threshold) or len(edges[1]) != len(threshold):
+        raise ValueError(f'{len(threshold)} thresholds, {len(edges[0])} leads and {len(edges[1])} trails: one of each '
+                         f'per marker row, at least one row')
+    if n < 0:
+        raise ValueError('n >= 0')
+    if group not in (1, 2):
+        raise ValueError('group must be 1 or 2')
+    bad = np.flatnonzero(~np.isfinite(threshold))
+    if len(bad):
+        raise ValueError(f'row {int(bad[0])}: threshold is not finite')
+    bad = np.flatnonzero(threshold < 0.0)
+    if len(bad):
+        raise ValueError(f'row {int(bad[0])}: threshold is negative')
+    for name, a in zip(('lead', 'trail'), edges):
+        for r, e in enumerate(a):
+            if e < 0:
+                raise ValueError(f'row {r}: {name} is negative')
+            if e > MARKER_MAX_EDGE:
+                raise ValueError(f'row {r}: {name} exceeds {MARKER_MAX_EDGE}')
+    return threshold, edges[0].astype(np.int32), edges[1].astype(np.int32), n, group, dtype
+
+
+class MarkerRowsPlan(_Handle):
+    """m[g, i] = any |x[g k + j, i']| > threshold[g] over the k = `group` input rows of marker row g and i' in
+    [i - trail[g], i + lead[g]] (clipped to the row), for `batch` = group * len(threshold) rows of n float64 / float32
+    samples: as uint8 0 / 1 (`apply`), or written into bit `bit` of int16 codes in the layout
+    DacRowsPlan(interleave=group) produces (`apply_codes`) (wfk_marker_rows_plan_create).  `.out_rows`: the marker
+    rows.  ValueError before any device work: no rows, lengths that differ, n < 0, a group other than 1 or 2, a
+    threshold that is negative or not finite, a lead or trail that is no integer, negative or above MARKER_MAX_EDGE
+    (the row is named), a dtype other than float64 / float32 (NotImplementedError for a complex one)."""
+    _destroy = 'wfk_marker_rows_plan_destroy'
+
+    def __init__(self, threshold, lead, trail, n: int, group: int = 1, dtype=np.float64):
+        (self.threshold, self.lead, self.trail, self.n, self.group,
+         self.dtype) = marker_rows_arguments(threshold, lead, trail, n, group, dtype)
+        self.out_rows = len(self.threshold)
+        self.batch = self.out_rows * self.group
+        check(lib().wfk_marker_rows_plan_create(self.n, self.batch, _KIND_OF[self.dtype], self.group,
+                                                self.threshold.ctypes.data, self.lead.ctypes.data,
+                                                self.trail.ctypes.data, C.byref(self._h)))
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, counts_ptr=None, stream=0):
+        """counts_ptr: None, or out_rows * 2 int64 on the device, overwritten with [high, pulses] per marker row"""
+        check(lib().wfk_marker_rows_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, counts_ptr, stream))
+
+    def apply_codes(self, in_ptr, in_stride, codes_ptr, codes_stride, bit=0, counts_ptr=None, stream=0):
+        if not 0 <= int(bit) <= 15:
+            raise ValueError('bit must lie in [0, 15]')
+        check(lib().wfk_marker_rows_apply_codes(self._h, in_ptr, in_stride, codes_ptr, codes_stride, int(bit),
+                                                counts_ptr, stream))
+
+    def span(self, codes: bool = False) -> int:
+        """the samples one workgroup covers in that form"""
+        return int(lib().wfk_marker_rows_span(self._h, 1 if codes else 0))
+
+    def kernel_name(self, codes: bool = False, counts: bool = False) -> str:
+        return lib().wfk_marker_rows_kernel_name(self._h, 1 if codes else 0, 1 if counts else 0).decode()
 
 
 class ExtractRowsPlan(_Handle):

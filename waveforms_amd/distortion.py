@@ -1288,6 +1288,156 @@ def dac_codes_rows(sig, gain, offset=0.0, bits=16, shift=0, interleave=1, return
         return (codes, c.download((batch, 3), np.int64)) if return_counts else codes
 
 
+class MarkerStage:
+    """Device-resident gate markers for `batch` rows of `n` samples (build once, apply many times): the marker line
+    that opens a switch or blanks an amplifier around every pulse, from the IDEAL gate rows (exact zeros outside the
+    pulses, as the sampler writes them), into the bit `DacStage(shift=...)` left free.  `group` = k in {1, 2} input
+    rows drive one marker row (k = 2: the I and Q of a pair, as `DacStage(interleave=2)` pairs them);
+    `.out_rows = batch // group`.  Exact, in integers:
+        active[g, i] = any_j |x[g k + j, i]| > threshold[g]         (NaN inactive, +-inf active)
+        m[g, i]      = any active[g, j], j in [i - trail[g], i + lead[g]], clipped to the row
+    so a marker rises `lead` samples before a burst and falls `trail` samples after it, and gaps shorter than
+    lead + trail + 1 close.  `lead` / `trail` (samples, 0 .. 4096) / `threshold` (>= 0): a scalar (every marker row;
+    give `batch`, the number of INPUT rows) or one value per marker row.  An optional (out_rows, 2) int64 counts
+    tensor is OVERWRITTEN by every apply with [high, pulses] per marker row: the samples with m = 1 and its rising
+    edges (a marker high at i = 0 counts).
+
+        mk = MarkerStage(n, lead=20, trail=10, group=2, batch=rows)
+        mk.apply_codes_torch(gates, codes, bit=0)               # in place in the codes, on torch's current stream
+    """
+
+    _X_ROWS = 'expected x: (batch, >=n) row-contiguous device tensor of the stage dtype'
+
+    def __init__(self, n: int, lead=0, trail=0, threshold=0.0, group: int = 1, dtype=np.float64, batch=None):
+        group = int(group)
+        if group not in (1, 2):
+            raise ValueError('MarkerStage: group must be 1 or 2')
+        given = [np.size(v) for v in (lead, trail, threshold) if np.ndim(v) > 0]
+        if batch is None:
+            if not given:
+                raise ValueError('MarkerStage: scalar lead, trail and threshold need batch=')
+            batch = given[0] * group
+        batch = int(batch)
+        if batch < 1:
+            raise ValueError('MarkerStage: no rows')
+        if batch % group:
+            raise ValueError(f'MarkerStage: {batch} rows are no multiple of the group {group}')
+        leads, trails, thresholds = (
+            _per_row('MarkerStage', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v, batch // group)
+            for what, v in (('lead', lead), ('trail', trail), ('threshold', threshold)))
+        self.plan = _engine.MarkerRowsPlan(thresholds, leads, trails, n, group, dtype)
+        p = self.plan
+        self.n, self.batch, self.group, self.out_rows, self.dtype = p.n, p.batch, p.group, p.out_rows, p.dtype
+        self.lead, self.trail, self.threshold = p.lead, p.trail, p.threshold
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, counts_ptr=None, stream=0):
+        self.plan.apply(in_ptr, in_stride, out_ptr, out_stride, counts_ptr, stream)
+
+    def apply_codes(self, in_ptr, in_stride, codes_ptr, codes_stride, bit=0, counts_ptr=None, stream=0):
+        self.plan.apply_codes(in_ptr, in_stride, codes_ptr, codes_stride, bit, counts_ptr, stream)
+
+    def span(self, codes: bool = False) -> int:
+        """the samples one workgroup covers: as bytes, or (`codes`) into codes"""
+        return self.plan.span(codes)
+
+    def kernel_name(self, codes: bool = False, counts: bool = False) -> str:
+        return self.plan.kernel_name(codes, counts)
+
+    def _checked(self, x, out, out_n, out_dtype, what, counts):
+        """the row rule of both torch calls -> (x ptr, x stride, out ptr, out stride, counts ptr or None)"""
+        x0, xs = _rows.check_rows(x, self.batch, self.n, _rows.torch_dtype(self.dtype), self._X_ROWS)
+        y0, ys = _rows.check_rows(out, self.out_rows, out_n, _rows.torch_dtype(out_dtype),
+                                  f'expected {what}: (out_rows, >={"group * " if out_dtype == np.int16 else ""}n) '
+                                  f'row-contiguous {np.dtype(out_dtype).name} device tensor')
+        c0 = _rows.check_state(counts, (self.out_rows, 2),
+                               'expected counts: contiguous (out_rows, 2) int64 device tensor', dtype=np.int64)
+        xr = (x0, xs, self.batch, self.n, self.dtype.itemsize)
+        yr = (y0, ys, self.out_rows, out_n, np.dtype(out_dtype).itemsize)
+        if not _rows.rows_disjoint(xr, yr):
+            raise ValueError(f'marker stage: {what} overlaps x')
+        if c0 is not None and not (_rows.rows_disjoint((c0, 2, self.out_rows, 2, 8), xr)
+                                   and _rows.rows_disjoint((c0, 2, self.out_rows, 2, 8), yr)):
+            raise ValueError(f'marker stage: counts overlaps x / {what}')
+        return x0, xs, y0, ys, c0
+
+    def apply_torch(self, x, out=None, counts=None):
+        """x: (batch, >= n) row-contiguous device tensor of the stage's dtype; out: (out_rows, >= n) uint8 (rows may
+        be windows of a wider tensor; None: allocated); counts: None or a contiguous (out_rows, 2) int64 device
+        tensor, overwritten.  `out` may share no memory with `x`, `counts` with neither (ValueError); `x` is never
+        written.  Asynchronous on torch's current stream.  -> out[:, :n]"""
+        import torch
+        if out is None:
+            _rows.check_rows(x, self.batch, self.n, _rows.torch_dtype(self.dtype), self._X_ROWS)
+            out = torch.empty((self.out_rows, self.n), dtype=torch.uint8, device=x.device)
+        x0, xs, y0, ys, c0 = self._checked(x, out, self.n, np.uint8, 'out', counts)
+        self.apply(x0, xs, y0, ys, c0, torch.cuda.current_stream(x.device).cuda_stream)
+        return out[:, :self.n]
+
+    def apply_codes_torch(self, x, codes, bit: int = 0, counts=None):
+        """x as in `apply_torch`; codes: (out_rows, >= group * n) row-contiguous int16 device tensor in the layout
+        `DacStage(interleave=group)` writes, changed IN PLACE: bit `bit` (0 .. 15) of every code becomes the marker
+        of its sample -- overwritten, not OR-ed -- and no other bit changes.  -> codes[:, :group * n]"""
+        import torch
+        if not 0 <= int(bit) <= 15:
+            raise ValueError('bit must lie in [0, 15]')
+        x0, xs, y0, ys, c0 = self._checked(x, codes, self.group * self.n, np.int16, 'codes', counts)
+        self.apply_codes(x0, xs, y0, ys, int(bit), c0, torch.cuda.current_stream(x.device).cuda_stream)
+        return codes[:, :self.group * self.n]
+
+    def close(self):
+        self.plan.close()
+
+
+def marker_rows(sig, lead=0, trail=0, threshold=0.0, group=1, codes=None, bit=0, return_counts=False):
+    """The gate markers of a 2-D real `sig` (see `MarkerStage` for the formula), all rows in one launch: NumPy in,
+    NumPy out.  -> uint8 (rows // group, samples); with `codes` ((rows // group, group * samples) int16, the layout of
+    `dac_codes_rows(interleave=group)`): a COPY of them with bit `bit` of every code replaced by the marker of its
+    sample.  `lead` / `trail` / `threshold`: a scalar (every marker row) or one value per marker row.  float32 rows
+    stay float32 on the way in, anything else is read as float64.  `return_counts`: -> (result, counts), counts the
+    (rows // group, 2) int64 [high, pulses] per marker row.  ValueError before any device work: sig not 2-D, a number
+    of leads, trails or thresholds that does not match, codes of another shape or dtype, a bit outside 0 .. 15, what
+    `MarkerStage` refuses.  NotImplementedError: complex rows."""
+    src = np.asarray(sig)
+    if src.ndim == 2 and src.dtype == np.float32:
+        sig2 = np.ascontiguousarray(src)
+    else:
+        sig2 = _rows_signal('marker_rows', sig)
+    batch, n = sig2.shape
+    group = int(group)
+    if group not in (1, 2):
+        raise ValueError('marker_rows: group must be 1 or 2')
+    if batch < 1:
+        raise ValueError('marker_rows: no rows')
+    if batch % group:
+        raise ValueError(f'marker_rows: {batch} rows are no multiple of the group {group}')
+    rows = batch // group
+    leads, trails, thresholds = (_per_row('marker_rows', what, v, rows)
+                                 for what, v in (('lead', lead), ('trail', trail), ('threshold', threshold)))
+    th, le, tr, n, group, dtype = _engine.marker_rows_arguments(thresholds, leads, trails, n, group, sig2.dtype)
+    if not 0 <= int(bit) <= 15:
+        raise ValueError('marker_rows: bit must lie in [0, 15]')
+    if codes is not None:
+        codes = np.asarray(codes)
+        if codes.dtype != np.int16 or codes.shape != (rows, group * n):
+            raise ValueError(f'marker_rows: codes must be int16 of shape ({rows}, {group * n})')
+        codes = np.ascontiguousarray(codes)
+    if n == 0:
+        res = codes.copy() if codes is not None else np.zeros((rows, 0), dtype=np.uint8)
+        return (res, np.zeros((rows, 2), dtype=np.int64)) if return_counts else res
+    out_bytes = codes.nbytes if codes is not None else rows * n
+    with _engine.MarkerRowsPlan(th, le, tr, n, group, dtype) as plan, _engine.DeviceBuffer(sig2.nbytes) as x, \
+            _engine.DeviceBuffer(out_bytes) as y, _engine.DeviceBuffer(rows * 16) as c:
+        x.upload(sig2)
+        if codes is not None:
+            y.upload(codes)
+            plan.apply_codes(x.ptr, n, y.ptr, group * n, int(bit), c.ptr if return_counts else None)
+        else:
+            plan.apply(x.ptr, n, y.ptr, n, c.ptr if return_counts else None)
+        _engine.sync()
+        res = y.download((rows, group * n), np.int16) if codes is not None else y.download((rows, n), np.uint8)
+        return (res, c.download((rows, 2), np.int64)) if return_counts else res
+
+
 def _extract_taps(name, n, sample_rate, bw):
     """the smoothing taps of extractKernel for rows of n samples, by the reference's own expressions
     (distortion.py:45-47), or None where it does not smooth (bw is None or bw >= sample_rate / 2).  ValueError: a
