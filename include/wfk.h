@@ -519,6 +519,43 @@ int64_t wfk_marker_rows_span(const wfk_marker_rows_plan* plan, int into_codes);
 const char* wfk_marker_rows_kernel_name(const wfk_marker_rows_plan* plan, int into_codes, int with_counts);
 int wfk_marker_rows_plan_destroy(wfk_marker_rows_plan* plan);
 
+/* -- mixing across rows: a sparse matrix and an offset, per sample -------------------------------- */
+/* rows_in real rows of n samples (kind: WFK_OUT_F64 or WFK_OUT_F32) become rows_out rows of the same kind through a
+ * rows_out x rows_in matrix M and an offset per output row: flux crosstalk compensation (a band), IQ mixer correction
+ * (2 x 2 blocks and a DC offset).  M comes as CSR: row_ptr[rows_out + 1] from 0 and non-decreasing, col[nnz] strictly
+ * ascending inside a row, val[nnz] finite; offset: rows_out finite values, or NULL (all 0.0).  A TERM of output row o
+ * is a pair (c, M[o, c]) with M[o, c] != 0 -- a zero, stored or not, is no term.  Per sample, in double (a float
+ * sample is widened first) and without a fused multiply-add,
+ *   acc = 0.0;   for the terms of o in ascending c:  acc = fl(acc + fl(x[c, i] * M[o, c]));
+ *   y[o, i] = fl(acc + offset[o])          (a float result is rounded once, here)
+ * -- what the NumPy loop `acc = acc + x[c] * m` computes, bit for bit.  An input row on which o has no term is not
+ * read for o: its NaN and inf stay out of y[o] (a dense product would turn them into NaN).  A row without terms is
+ * fl(0.0 + offset[o]).  rows_out < 1, rows_in < 1, n < 0, a row_ptr that is not non-decreasing from 0, a column out of
+ * range ("row 3: column 9 is out of range"), columns that are not ascending, a coefficient or offset that is not
+ * finite (the row is named), a kind other than F64 / F32, null pointers, more than 2^31 - 1 workgroups: WFK_EINVAL,
+ * before any device work; no device: WFK_EHIP.
+ * One kernel (mix_rows<T>): a workgroup owns a column span of a tile of WFK_MIX_TILE_ROWS consecutive output rows and
+ * reads every input row the tile has a term on once.  wfk_mix_rows_reads(): the sum over tiles of the number of such
+ * input rows -- the kernel reads reads * n and writes rows_out * n samples (block-diagonal blocks that divide the
+ * tile: reads = rows_in; a band of half-width k: about (T + 2 k) / T * rows_in; dense: rows_in * tiles).
+ * wfk_mix_rows_apply() allocates nothing and does not synchronise; strides are in elements, >= n, and may differ.
+ * OUT OF PLACE only, and the input is never written: if [in, in + (rows_in - 1) * in_stride + n) meets
+ * [out, out + (rows_out - 1) * out_stride + n), WFK_EINVAL; so are rows not aligned to their element.  n = 0: a
+ * no-op that touches no pointer.  The plan owns its small tables and nothing else, so it may serve several streams. */
+#define WFK_MIX_TILE_ROWS 8
+typedef struct wfk_mix_rows_plan wfk_mix_rows_plan;
+/* CSR: row_ptr[rows_out + 1], col[nnz] ascending inside a row, val[nnz]; offset may be NULL (all 0.0) */
+int wfk_mix_rows_plan_create(int64_t n, int32_t rows_out, int32_t rows_in, int kind /* WFK_OUT_F64|F32 */,
+                             const int64_t* row_ptr, const int32_t* col, const double* val,
+                             const double* offset, wfk_mix_rows_plan** out);
+int wfk_mix_rows_apply(wfk_mix_rows_plan* plan, const void* in_dev, int64_t in_stride,
+                       void* out_dev, int64_t out_stride, void* hip_stream);
+/* sum over tiles of the size of the input union; 0 for NULL */
+int64_t wfk_mix_rows_reads(const wfk_mix_rows_plan* plan);
+/* "mix_rows<double>" / "mix_rows<float>"; "" for NULL; a static string */
+const char* wfk_mix_rows_kernel_name(const wfk_mix_rows_plan* plan);
+int wfk_mix_rows_plan_destroy(wfk_mix_rows_plan* plan);       /* NULL is fine */
+
 /* -- per-row kernel extraction: the reference's extractKernel for every row ---------------------- */
 /* ker[r] = extractKernel(sig_in[r], sig_out[r], sample_rate, bw, skip) (waveforms/distortion.py:42-48) for `batch`
  * rows of n doubles: the kernel that maps sig_out back onto sig_in, the rows of an FIR plan's kernel matrix.  Per row

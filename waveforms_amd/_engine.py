@@ -152,6 +152,13 @@ def lib():
         l.wfk_marker_rows_kernel_name.argtypes = [VP, C.c_int, C.c_int]
         l.wfk_marker_rows_kernel_name.restype = C.c_char_p
         l.wfk_marker_rows_plan_destroy.argtypes = [VP]
+        l.wfk_mix_rows_plan_create.argtypes = [I64, I32, I32, C.c_int, VP, VP, VP, VP, P(VP)]
+        l.wfk_mix_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP]
+        l.wfk_mix_rows_reads.argtypes = [VP]
+        l.wfk_mix_rows_reads.restype = I64
+        l.wfk_mix_rows_kernel_name.argtypes = [VP]
+        l.wfk_mix_rows_kernel_name.restype = C.c_char_p
+        l.wfk_mix_rows_plan_destroy.argtypes = [VP]
         l.wfk_extract_rows_plan_create.argtypes = [I64, I32, I32, VP, I32, I64, P(VP)]
         l.wfk_extract_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, I64, VP]
         l.wfk_extract_rows_kernel_name.argtypes = [VP]
@@ -863,6 +870,122 @@ class MarkerRowsPlan(_Handle):
 
     def kernel_name(self, codes: bool = False, counts: bool = False) -> str:
         return lib().wfk_marker_rows_kernel_name(self._h, 1 if codes else 0, 1 if counts else 0).decode()
+
+
+MIX_TILE_ROWS = 8          # WFK_MIX_TILE_ROWS
+
+
+def _mix_rows_csr(matrix):
+    """-> (rows_out, rows_in, row_ptr, col, val) of a 2-D array-like (its non-zero entries, row by row) or of an object
+    with `.tocsr()` (scipy.sparse: indptr / indices / data as they are stored); nothing is checked beyond the shape"""
+    if hasattr(matrix, 'tocsr'):
+        m = matrix.tocsr()
+        if len(m.shape) != 2:
+            raise ValueError('matrix must be 2-D')
+        return (int(m.shape[0]), int(m.shape[1]), np.asarray(m.indptr).astype(np.int64).reshape(-1),
+                np.asarray(m.indices).astype(np.int64).reshape(-1), np.asarray(m.data).reshape(-1))
+    a = np.asarray(matrix)
+    if a.ndim != 2:
+        raise ValueError('matrix must be 2-D')
+    if a.dtype.kind == 'c':
+        raise NotImplementedError('complex coefficients')
+    a = a.astype(np.float64)
+    rows, cols = np.nonzero(a)                         # row-major: ascending columns inside a row; NaN is non-zero
+    row_ptr = np.zeros(a.shape[0] + 1, dtype=np.int64)
+    np.cumsum(np.bincount(rows, minlength=a.shape[0]), out=row_ptr[1:])
+    return a.shape[0], a.shape[1], row_ptr, cols.astype(np.int64), a[rows, cols]
+
+
+def _mix_rows_checked(matrix, offset, n, dtype):
+    """mix_rows_arguments with the number of input rows in front"""
+    n, dtype = int(n), np.dtype(dtype)
+    if dtype.kind == 'c':
+        raise NotImplementedError('complex rows')
+    if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError('dtype must be float64 or float32')
+    rows_out, rows_in, row_ptr, col, val = _mix_rows_csr(matrix)
+    if np.iscomplexobj(val):
+        raise NotImplementedError('complex coefficients')
+    val = np.ascontiguousarray(val, dtype=np.float64)
+    if rows_out < 1:
+        raise ValueError('rows_out < 1')
+    if rows_in < 1:
+        raise ValueError('rows_in < 1')
+    if rows_out > 2**31 - 1 or rows_in > 2**31 - 1:
+        raise ValueError('more than 2**31 - 1 rows')
+    if n < 0:
+        raise ValueError('n < 0')
+    if (len(row_ptr) != rows_out + 1 or row_ptr[0] != 0 or np.any(np.diff(row_ptr) < 0)
+            or row_ptr[-1] != len(col) or len(val) != len(col)):
+        raise ValueError('row_ptr is not non-decreasing from 0')
+    if offset is None:
+        offset = np.zeros(rows_out, dtype=np.float64)
+    else:
+        offset = np.ascontiguousarray(offset, dtype=np.float64).reshape(-1)
+        if len(offset) != rows_out:
+            raise ValueError('offset: one per output row')
+    for r in range(rows_out):
+        c, v = col[row_ptr[r]:row_ptr[r + 1]], val[row_ptr[r]:row_ptr[r + 1]]
+        bad = np.flatnonzero((c < 0) | (c >= rows_in))
+        rising = np.flatnonzero(np.diff(c) <= 0)
+        if len(bad) and (not len(rising) or bad[0] <= rising[0] + 1):
+            raise ValueError(f'row {r}: column {int(c[bad[0]])} is out of range')
+        if len(rising):
+            raise ValueError(f'row {r}: columns are not ascending')
+        bad = np.flatnonzero(~np.isfinite(v))
+        if len(bad):
+            raise ValueError(f'row {r}: coefficient ({r}, {int(c[bad[0]])}) is not finite')
+        if not np.isfinite(offset[r]):
+            raise ValueError(f'row {r}: offset is not finite')
+    keep = val != 0.0                                  # a zero is no term, stored or not
+    kept = np.zeros(len(val) + 1, dtype=np.int64)
+    np.cumsum(keep, out=kept[1:])
+    return rows_in, np.ascontiguousarray(kept[row_ptr]), col[keep].astype(np.int32), val[keep], offset, n, dtype
+
+
+def mix_rows_arguments(matrix, offset, n, dtype=np.float64):
+    """the arguments of a MixRowsPlan, checked on the host -> (row_ptr int64, col int32, val float64: the CSR form of
+    the matrix's TERMS, its non-zero entries; offset float64, one per output row; n; dtype).  `matrix`: a 2-D
+    array-like, or an object with `.tocsr()` (scipy.sparse).  ValueError / NotImplementedError as MixRowsPlan lists
+    them.  Needs no device."""
+    return _mix_rows_checked(matrix, offset, n, dtype)[1:]
+
+
+def mix_rows_reads(row_ptr, col) -> int:
+    """the sum over tiles of MIX_TILE_ROWS consecutive output rows of the number of input rows the tile has a term on
+    (wfk_mix_rows_reads, computed on the host): the kernel reads that many rows of n samples"""
+    row_ptr, col = np.asarray(row_ptr), np.asarray(col)
+    return sum(len(np.unique(col[row_ptr[o]:row_ptr[min(o + MIX_TILE_ROWS, len(row_ptr) - 1)]]))
+               for o in range(0, len(row_ptr) - 1, MIX_TILE_ROWS))
+
+
+class MixRowsPlan(_Handle):
+    """y[o] = sum over the terms (c, M[o, c] != 0) of row o, in ascending c, of x[c] * M[o, c], plus offset[o], per
+    sample, for rows_in rows of n float64 / float32 samples -> rows_out rows of the same dtype (in float64, product and
+    sum each rounded, a float32 result rounded once; wfk_mix_rows_plan_create).  `.rows_out`, `.rows_in`, `.nnz` (the
+    terms), `.reads` (mix_rows_reads).  ValueError before any device work: `matrix must be 2-D`, `rows_out < 1`,
+    `rows_in < 1`, `n < 0`, `offset: one per output row`, `row r: column c is out of range`, `row r: columns are not
+    ascending`, `row r: coefficient (r, c) is not finite`, `row r: offset is not finite`, `row_ptr is not
+    non-decreasing from 0`, `dtype must be float64 or float32` (NotImplementedError for a complex one)."""
+    _destroy = 'wfk_mix_rows_plan_destroy'
+
+    def __init__(self, matrix, offset, n: int, dtype=np.float64):
+        (self.rows_in, self.row_ptr, self.col, self.val, self.offset, self.n,
+         self.dtype) = _mix_rows_checked(matrix, offset, n, dtype)
+        self.rows_out, self.nnz = len(self.row_ptr) - 1, len(self.col)
+        self.reads = mix_rows_reads(self.row_ptr, self.col)
+        check(lib().wfk_mix_rows_plan_create(self.n, self.rows_out, self.rows_in, _KIND_OF[self.dtype],
+                                             self.row_ptr.ctypes.data, self.col.ctypes.data, self.val.ctypes.data,
+                                             self.offset.ctypes.data, C.byref(self._h)))
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, stream=0):
+        check(lib().wfk_mix_rows_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, stream))
+
+    def library_reads(self) -> int:
+        return int(lib().wfk_mix_rows_reads(self._h))
+
+    def kernel_name(self) -> str:
+        return lib().wfk_mix_rows_kernel_name(self._h).decode()
 
 
 class ExtractRowsPlan(_Handle):

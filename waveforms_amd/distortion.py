@@ -1183,6 +1183,103 @@ def shift_rows(sig, delays, dt):
         return y.download(sig2.shape, sig2.dtype)
 
 
+class MixStage:
+    """Device-resident linear mixing ACROSS rows, per sample (build once, apply many times): `rows_in` rows of `n`
+    samples become `rows_out` rows through a sparse `matrix` (rows_out, rows_in) and an `offset` per output row -- flux
+    crosstalk compensation (the inverse of the measured crosstalk matrix, a band), IQ mixer correction (a 2 x 2 block per
+    pair and a DC offset against carrier leakage).  A TERM of output row o is an entry M[o, c] != 0; in float64 (a
+    float32 sample is widened first), product and sum each rounded (no fused multiply-add), terms in ascending c:
+        acc = 0.0;   acc = acc + x[c, i] * M[o, c]  for every term;   y[o, i] = acc + offset[o]
+    -- bit for bit what that NumPy loop gives; a float32 result is rounded once at the end.  A row of x on which o has
+    no term is not read for o: its NaN and inf stay out of y[o] (a dense product would make them NaN).
+    `matrix`: a 2-D array-like or a scipy.sparse matrix; `offset`: None (zeros) or one value per output row.
+    `.rows_out`, `.rows_in`, `.nnz` (the terms); `.reads`: the input rows the kernel reads, every tile of
+    `_engine.MIX_TILE_ROWS` consecutive output rows reading each row it has a term on once -- rows_in for blocks that
+    divide the tile, about (T + 2 k) / T * rows_in for a band of half-width k, rows_in * tiles for a dense matrix:
+    put coupled lines next to each other.
+
+        st = MixStage(np.linalg.inv(crosstalk), n)              # or MixStage.from_blocks([[[a, b], [c, d]], ...], n)
+        st.apply_torch(x, out=y)                                # out of place, on torch's current stream
+    """
+
+    def __init__(self, matrix, n: int, offset=None, dtype=np.float64):
+        self.plan = _engine.MixRowsPlan(matrix, offset, n, dtype)
+        p = self.plan
+        self.n, self.dtype, self.offset = p.n, p.dtype, p.offset
+        self.rows_out, self.rows_in, self.nnz, self.reads = p.rows_out, p.rows_in, p.nnz, p.reads
+
+    @staticmethod
+    def block_diagonal(blocks):
+        """the dense matrix with the 2-D `blocks` down its diagonal (they need not be square)"""
+        blocks = [np.asarray(b, dtype=np.float64) for b in blocks]
+        if not blocks or any(b.ndim != 2 for b in blocks):
+            raise ValueError('MixStage: blocks is a list of 2-D arrays, at least one')
+        m = np.zeros((sum(b.shape[0] for b in blocks), sum(b.shape[1] for b in blocks)))
+        r = c = 0
+        for b in blocks:
+            m[r:r + b.shape[0], c:c + b.shape[1]] = b
+            r, c = r + b.shape[0], c + b.shape[1]
+        return m
+
+    @classmethod
+    def from_blocks(cls, blocks, n: int, offset=None, dtype=np.float64):
+        """the stage of the block-diagonal matrix of a list of small 2-D arrays: [[a, b], [c, d]] per IQ pair gives
+        I' = a I + b Q, Q' = c I + d Q"""
+        return cls(cls.block_diagonal(blocks), n, offset, dtype)
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, stream=0):
+        self.plan.apply(in_ptr, in_stride, out_ptr, out_stride, stream)
+
+    def kernel_name(self) -> str:
+        return self.plan.kernel_name()
+
+    def apply_torch(self, x, out=None):
+        """x: (rows_in, >= n), out: (rows_out, >= n) row-contiguous device tensors of the stage's dtype (rows may be
+        windows of a wider tensor; out None: allocated); out of place: the rows of `out` may share no memory with the
+        rows of `x` (ValueError), and `x` is never written.  Asynchronous on torch's current stream.  -> out"""
+        import torch
+        tdt = _rows.torch_dtype(self.dtype)
+        x0, xs = _rows.check_rows(x, self.rows_in, self.n, tdt,
+                                  'expected x: (rows_in, >=n) row-contiguous device tensor of the stage dtype')
+        if out is None:
+            out = torch.empty((self.rows_out, self.n), dtype=tdt, device=x.device)
+        y0, ys = _rows.check_rows(out, self.rows_out, self.n, tdt,
+                                  'expected out: (rows_out, >=n) row-contiguous device tensor of the stage dtype')
+        es = self.dtype.itemsize
+        if not _rows.rows_disjoint((x0, xs, self.rows_in, self.n, es), (y0, ys, self.rows_out, self.n, es)):
+            raise ValueError('mix stage is out of place: out overlaps x')
+        self.apply(x0, xs, y0, ys, torch.cuda.current_stream(x.device).cuda_stream)
+        return out
+
+    def close(self):
+        self.plan.close()
+
+
+def mix_rows(sig, matrix, offset=None):
+    """`matrix` applied across the rows of a 2-D real `sig`, per sample, plus `offset` per output row (see `MixStage`
+    for the formula), in one launch: NumPy in, NumPy out, (rows of the matrix, samples).  float32 rows stay float32,
+    anything else is computed as float64.  ValueError before any device work: sig not 2-D, a matrix whose columns are
+    not the rows of sig, what `MixStage` refuses.  NotImplementedError: complex rows."""
+    src = np.asarray(sig)
+    if src.ndim == 2 and src.dtype == np.float32:
+        sig2 = np.ascontiguousarray(src)
+    else:
+        sig2 = _rows_signal('mix_rows', sig)
+    batch, n = sig2.shape
+    rows_in, row_ptr, col, val, off, n, dtype = _engine._mix_rows_checked(matrix, offset, n, sig2.dtype)
+    if rows_in != batch:
+        raise ValueError(f'mix_rows: a matrix of {rows_in} columns for {batch} rows')
+    rows_out = len(row_ptr) - 1
+    if n == 0:
+        return np.zeros((rows_out, 0), dtype=dtype)
+    with _engine.MixRowsPlan(matrix, offset, n, dtype) as plan, _engine.DeviceBuffer(sig2.nbytes) as x, \
+            _engine.DeviceBuffer(rows_out * n * dtype.itemsize) as y:
+        x.upload(sig2)
+        plan.apply(x.ptr, n, y.ptr, n)
+        _engine.sync()
+        return y.download((rows_out, n), dtype)
+
+
 class DacStage:
     """Device-resident volts -> DAC codes for `batch` rows of `n` samples (build once, apply many times): the last
     step before an upload to an AWG.  Input row r has `gain[r]` (LSB per unit of the signal) and `offset[r]` (LSB);
