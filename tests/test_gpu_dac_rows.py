@@ -262,6 +262,48 @@ def test_overlap_and_refused_tensors():
     empty.close()
 
 
+def test_library_refuses_a_bad_apply():
+    """the C side's own checks of an apply, through the raw pointers, one case per clause of the row rule: a null
+    side, rows not aligned to their element, a stride below the row, overlap, and the report's alignment and overlap
+    with either side: WFK_EINVAL, the stage named in the text, nothing launched (the acceptance table itself, the
+    lone output row among it: test_row_rule_cpu.py).  n = 0: a no-op that zeroes the report, whatever the row pointers"""
+    from waveforms_amd import _engine
+    rows, n = 4, 40
+    st = distortion.DacStage(1000.0, n, batch=rows)
+    x = torch.ones((rows, n), dtype=torch.float64, device=dev())
+    out = torch.full((rows, n), SENTINEL, dtype=torch.int16, device=dev())
+    counts = torch.full((rows, 3), 7, dtype=torch.int64, device=dev())
+    lib, h = _engine.lib(), st.plan._h
+    X, Y, C = x.data_ptr(), out.data_ptr(), counts.data_ptr()
+    for args, message in (((None, n, Y, n, None), b'null in / out'),
+                          ((X, n, None, n, None), b'null in / out'),
+                          ((X + 4, n, Y, n, None), b'not aligned to their element'),
+                          ((X, n, Y + 1, n, None), b'not aligned to their element'),
+                          ((X, n - 1, Y, n, None), b'in row stride smaller'),
+                          ((X, n, Y, n - 1, None), b'out row stride smaller'),
+                          ((X, n, X + 8, n, None), b'dac rows is out of place: out overlaps in'),
+                          ((Y + 2 * rows * n - 8, n, Y, n, None), b'overlaps'),
+                          ((X, n, Y, n, C + 4), b'counts are not aligned'),
+                          ((X, n, Y, n, X + 16), b'counts overlaps in'),
+                          ((X, n, Y, n, Y + 8), b'counts overlaps out')):
+        assert lib.wfk_dac_rows_apply(h, *args, None) == -1, args
+        text = lib.wfk_last_error()
+        assert text.startswith(b'dac rows') and message in text, (args, text)
+        with pytest.raises(_engine.EngineError, match=message.decode()):
+            st.apply(*args)
+    torch.cuda.synchronize()
+    assert np.all(out.cpu().numpy() == SENTINEL) and np.all(counts.cpu().numpy() == 7)
+    st.close()
+    empty = distortion.DacStage(1.0, 0, batch=rows)
+    assert lib.wfk_dac_rows_apply(empty.plan._h, None, 0, None, 0, C, None) == 0
+    torch.cuda.synchronize()
+    assert not counts.cpu().numpy().any()
+    assert lib.wfk_dac_rows_apply(empty.plan._h, None, 0, None, 0, None, None) == 0
+    assert lib.wfk_dac_rows_apply(empty.plan._h, None, 0, None, 0, C + 4, None) == -1
+    assert b'counts are not aligned' in lib.wfk_last_error()
+    empty.close()
+
+
 def test_numpy_round_trip():
     rows, n = 6, 3001
     x = rows_input(rows, n, 800)

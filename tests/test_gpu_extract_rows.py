@@ -235,6 +235,41 @@ def test_overlap_and_refused_tensors():
     empty.close()
 
 
+def test_library_refuses_a_bad_apply():
+    """the C side's own checks of an apply, through the raw pointers, one case per clause of the row rule with two
+    inputs against one result: a null side, rows not aligned to their element, a stride below the row on each side,
+    the result meeting either input: WFK_EINVAL, the stage named in the text, nothing launched"""
+    from waveforms_amd import _engine
+    rows, n, skip = 4, 40, 3
+    K = n - 2 * skip
+    ex = distortion.KernelExtractor(n, rows, FS, None, skip)
+    a = torch.ones((rows, n), dtype=torch.float64, device=dev())
+    b = torch.ones((rows, n), dtype=torch.float64, device=dev())
+    y = torch.full((rows, K), -7.0, dtype=torch.float64, device=dev())
+    lib, h = _engine.lib(), ex.plan._h
+    A, B, Y = a.data_ptr(), b.data_ptr(), y.data_ptr()
+    for args, message in (((None, n, B, n, Y, K), b'null'),
+                          ((A, n, None, n, Y, K), b'null'),
+                          ((A, n, B, n, None, K), b'null'),
+                          ((A + 4, n, B, n, Y, K), b'not aligned'),
+                          ((A, n, B + 4, n, Y, K), b'not aligned'),
+                          ((A, n, B, n, Y + 4, K), b'not aligned'),
+                          ((A, n - 1, B, n, Y, K), b'sig_in row stride smaller'),
+                          ((A, n, B, n - 1, Y, K), b'sig_out row stride smaller'),
+                          ((A, n, B, n, Y, K - 1), b'ker row stride smaller'),
+                          ((A, n, B, n, A + 8 * (rows * n - 1), K), b'ker overlaps sig_in'),
+                          ((A, n, B, n, B + 8, K), b'ker overlaps sig_out'),
+                          ((Y + 8 * (rows * K - 1), n, B, n, Y, K), b'ker overlaps sig_in')):
+        assert lib.wfk_extract_rows_apply(h, *args, None) == -1, args
+        text = lib.wfk_last_error()
+        assert text.startswith(b'extract rows') and message in text, (args, text)
+        with pytest.raises(_engine.EngineError, match=message.decode()):
+            ex.apply(*args)
+    torch.cuda.synchronize()
+    assert np.all(y.cpu().numpy() == -7.0)
+    ex.close()
+
+
 def test_many_workgroups_per_row():
     """64 x 100 003, M = 40: 49 workgroups per row in extract_smooth, 25 in extract_ratio.  The long-double transform
     of a row of this (prime) length takes 0.4 s on the host, so the 64 rows are 8 pairs of signals (seeds n + 1000 p),

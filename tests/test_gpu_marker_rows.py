@@ -411,6 +411,15 @@ def test_library_refuses_a_bad_apply():
     torch.cuda.synchronize()
     assert not out.cpu().numpy().any() and not codes.cpu().numpy().any()
     st.close()
+    empty = distortion.MarkerStage(0, 1, 1, batch=2)                               # n = 0: null rows, the report zeroed
+    for call in (lambda c: lib.wfk_marker_rows_apply(empty.plan._h, None, 0, None, 0, c, None),
+                 lambda c: lib.wfk_marker_rows_apply_codes(empty.plan._h, None, 0, None, 0, 3, c, None)):
+        counts.fill_(7)
+        assert call(counts.data_ptr()) == 0 and call(None) == 0
+        torch.cuda.synchronize()
+        assert not counts.cpu().numpy().any()
+        assert call(counts.data_ptr() + 4) == -1 and b'counts are not aligned' in lib.wfk_last_error()
+    empty.close()
 
 
 def test_numpy_round_trip():

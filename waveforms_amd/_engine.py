@@ -684,6 +684,15 @@ def spec_phase_step(tau: float, sample_rate: float, n: int):
     return hi.value, lo.value
 
 
+def _real_dtype(dtype, complex_is_pending=True):
+    """the np.dtype of a plan's rows is float64 or float32: ValueError otherwise, but NotImplementedError for a complex
+    one where `complex_is_pending`"""
+    if dtype.kind == 'c' and complex_is_pending:
+        raise NotImplementedError('complex rows')
+    if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError('dtype must be float64 or float32')
+
+
 class SpectralRowsPlan(_Handle):
     """out[r] = irfft(rfft(x[r]) * H_r): every row its own product of reflection / inverse-reflection / delay terms
     (`pack_spec_terms`), H formed on the device (wfk_spectral_rows_plan_create).  `batch` = len(terms_rows)."""
@@ -693,8 +702,7 @@ class SpectralRowsPlan(_Handle):
         terms, counts = pack_spec_terms(terms_rows)
         self.n, self.batch, self.dtype = int(n), len(counts), np.dtype(dtype)
         self.sample_rate = float(sample_rate)
-        if self.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
-            raise ValueError('dtype must be float64 or float32')
+        _real_dtype(self.dtype, complex_is_pending=False)
         if self.n < 1 or not (np.isfinite(self.sample_rate) and self.sample_rate > 0):
             raise ValueError('n >= 1 and a positive sample_rate')
         check(lib().wfk_spectral_rows_plan_create(self.n, self.batch, _KIND_OF[self.dtype], self.sample_rate,
@@ -714,10 +722,7 @@ class ShiftRowsPlan(_Handle):
 
     def __init__(self, points, deltas, n: int, dtype=np.float64):
         self.n, self.dtype = int(n), np.dtype(dtype)
-        if self.dtype.kind == 'c':
-            raise NotImplementedError('complex rows')
-        if self.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
-            raise ValueError('dtype must be float64 or float32')
+        _real_dtype(self.dtype)
         pts = [max(-2**62, min(2**62, int(p))) for p in np.asarray(points, dtype=object).reshape(-1)]
         self.points = np.array(pts, dtype=np.int64)
         self.deltas = np.ascontiguousarray(deltas, dtype=np.float64).reshape(-1)
@@ -742,10 +747,7 @@ def dac_rows_arguments(gain, offset, n, bits=16, shift=0, interleave=1, dtype=np
     """the arguments of a DacRowsPlan, checked on the host -> (gain, offset: float64 arrays of one length, n, bits,
     shift, interleave, dtype).  ValueError / NotImplementedError as DacRowsPlan lists them."""
     n, bits, shift, interleave, dtype = int(n), int(bits), int(shift), int(interleave), np.dtype(dtype)
-    if dtype.kind == 'c':
-        raise NotImplementedError('complex rows')
-    if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
-        raise ValueError('dtype must be float64 or float32')
+    _real_dtype(dtype)
     gain = np.ascontiguousarray(gain, dtype=np.float64).reshape(-1)
     offset = np.ascontiguousarray(offset, dtype=np.float64).reshape(-1)
     if len(gain) < 1 or len(offset) != len(gain):
@@ -802,10 +804,7 @@ def marker_rows_arguments(threshold, lead, trail, n, group=1, dtype=np.float64):
     """the arguments of a MarkerRowsPlan, checked on the host -> (threshold: float64, lead, trail: int32 arrays of one
     length, one entry per MARKER row, n, group, dtype).  ValueError / NotImplementedError as MarkerRowsPlan lists them."""
     n, group, dtype = int(n), int(group), np.dtype(dtype)
-    if dtype.kind == 'c':
-        raise NotImplementedError('complex rows')
-    if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
-        raise ValueError('dtype must be float64 or float32')
+    _real_dtype(dtype)
     threshold = np.ascontiguousarray(threshold, dtype=np.float64).reshape(-1)
     edges = []
     for name, v in (('lead', lead), ('trail', trail)):
@@ -899,10 +898,7 @@ def _mix_rows_csr(matrix):
 def _mix_rows_checked(matrix, offset, n, dtype):
     """mix_rows_arguments with the number of input rows in front"""
     n, dtype = int(n), np.dtype(dtype)
-    if dtype.kind == 'c':
-        raise NotImplementedError('complex rows')
-    if dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
-        raise ValueError('dtype must be float64 or float32')
+    _real_dtype(dtype)
     rows_out, rows_in, row_ptr, col, val = _mix_rows_csr(matrix)
     if np.iscomplexobj(val):
         raise NotImplementedError('complex coefficients')

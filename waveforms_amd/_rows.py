@@ -47,6 +47,12 @@ def check_state(z, shape, message, device=True, dtype=np.float64):
 def rows_disjoint(a, b) -> bool:
     """a, b: (ptr, row stride, batch, n, itemsize) of two row batches.  A batch occupies the bytes from the first
     sample of row 0 to the END of row batch - 1 (not batch * stride); two batches are disjoint when these half-open
-    ranges do not meet.  Rows of no samples occupy nothing.  (wfk_rows_bytes / wfk_ranges_overlap of wfk_host.h)"""
+    ranges do not meet.  Rows of no samples occupy nothing.  (RowSide::bytes / wfk_ranges_overlap of wfk_row_rule.h)"""
     (a0, a1), (b0, b1) = ((p, p + ((batch - 1) * stride + n) * es) for p, stride, batch, n, es in (a, b))
     return a[3] == 0 or b[3] == 0 or not (a0 < b1 and b0 < a1)
+
+
+def report_disjoint(ptr, rows, counters, *sides) -> bool:
+    """the contiguous int64 report of `rows` x `counters` at `ptr` (None: no report) meets none of `sides`, tuples as
+    rows_disjoint takes them  (RowReport of wfk_row_rule.h)"""
+    return ptr is None or all(rows_disjoint((ptr, counters, rows, counters, 8), s) for s in sides)

@@ -274,10 +274,7 @@ int wfk_dac_rows_plan_create(int64_t n, int32_t batch, int kind, const double* g
   p->blocks_per_row = bpr;
   DevTables tab;
   p->rows_off = tab.add(rows);
-  if (!(p->tables.alloc(tab.total()) && tab.upload(p->tables.get()))) {
-    (void)hipGetLastError();
-    return wfk_fail(WFK_EHIP, "dac rows plan: table upload failed");
-  }
+  if (const int rc = wfk_upload_tables("dac rows plan", tab, p->tables)) return rc;
   *out = p.release();
   return WFK_OK;
 } catch (const std::bad_alloc&) {
@@ -288,35 +285,15 @@ int wfk_dac_rows_apply(wfk_dac_rows_plan* p, const void* in_dev, int64_t in_stri
                        int64_t out_stride, int64_t* counts_dev, void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   hipStream_t s = (hipStream_t)hip_stream;
-  const size_t counts_bytes = (size_t)p->batch * 3 * sizeof(int64_t);
-  if (counts_dev && ((uintptr_t)counts_dev & 7)) return wfk_fail(WFK_EINVAL, "dac rows: counts are not aligned to int64");
-  if (p->n == 0) {   // nothing to quantise (the pointers of empty rows may be null); the report is still zeroed
-    if (counts_dev && hipMemsetAsync(counts_dev, 0, counts_bytes, s) != hipSuccess) {
-      (void)hipGetLastError();
-      return wfk_fail(WFK_EHIP, "dac rows: zeroing the counts failed");
-    }
-    return WFK_OK;
-  }
-  // the row rule with an element size per side (wfk_check_rows takes one)
-  const size_t es = wfk_elem_size(p->kind);
-  const int64_t out_rows = p->batch / p->k, out_n = p->k * p->n;
-  if (!in_dev || !out_dev) return wfk_fail(WFK_EINVAL, "dac rows: null in / out buffer");
-  if (((uintptr_t)in_dev & (es - 1)) || ((uintptr_t)out_dev & (sizeof(int16_t) - 1)))
-    return wfk_fail(WFK_EINVAL, "dac rows: rows are not aligned to their element");
-  if (in_stride < p->n) return wfk_fail(WFK_EINVAL, "dac rows: input row stride smaller than n");
-  if (out_rows > 1 && out_stride < out_n)
-    return wfk_fail(WFK_EINVAL, "dac rows: output row stride smaller than interleave * n");
-  const size_t in_bytes = wfk_rows_bytes(p->batch, in_stride, p->n, es);
-  const size_t out_bytes = wfk_rows_bytes(out_rows, out_stride, out_n, sizeof(int16_t));
-  if (wfk_ranges_overlap(in_dev, in_bytes, out_dev, out_bytes))
-    return wfk_fail(WFK_EINVAL, "dac rows is out of place: out overlaps in");
-  if (counts_dev && (wfk_ranges_overlap(counts_dev, counts_bytes, in_dev, in_bytes) ||
-                     wfk_ranges_overlap(counts_dev, counts_bytes, out_dev, out_bytes)))
-    return wfk_fail(WFK_EINVAL, "dac rows: counts overlaps in / out");
-  if (counts_dev && hipMemsetAsync(counts_dev, 0, counts_bytes, s) != hipSuccess) {
-    (void)hipGetLastError();
-    return wfk_fail(WFK_EHIP, "dac rows: zeroing the counts failed");
-  }
+  const RowReport report{counts_dev, p->batch, 3};
+  // nothing to quantise (the pointers of empty rows may be null); the report is still zeroed
+  if (p->n == 0) return wfk_zero_report("dac rows", report, s);
+  // a lone output row's stride is not read
+  if (const int rc = wfk_row_rule("dac rows", {{"in", in_dev, p->batch, in_stride, p->n, wfk_elem_size(p->kind)}},
+                                  {"out", out_dev, p->batch / p->k, out_stride, p->k * p->n, sizeof(int16_t), false},
+                                  kRowsAligned | kRowsDisjoint, wfk_fail, report))
+    return rc;
+  if (const int rc = wfk_zero_report("dac rows", report, s)) return rc;
   if (p->kind == WFK_OUT_F32)
     dac_launch<float>(p, in_dev, in_stride, out_dev, out_stride, counts_dev, s);
   else

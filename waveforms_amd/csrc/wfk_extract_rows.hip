@@ -219,15 +219,12 @@ int wfk_extract_rows_apply(wfk_extract_rows_plan* p, const double* sig_in_dev, i
                            void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->K == 0) return WFK_OK;   // nothing to write (the result's pointer may be null)
-  if (!sig_in_dev || !sig_out_dev || !ker_dev) return wfk_fail(WFK_EINVAL, "extract rows: null buffer");
-  if (((uintptr_t)sig_in_dev | (uintptr_t)sig_out_dev | (uintptr_t)ker_dev) & 7)
-    return wfk_fail(WFK_EINVAL, "extract rows: rows are not aligned to their element");
-  if (in_stride < p->n || out_sig_stride < p->n || ker_stride < p->K)
-    return wfk_fail(WFK_EINVAL, "extract rows: row stride smaller than the row");
-  const size_t ker_bytes = wfk_rows_bytes(p->batch, ker_stride, p->K, 8);
-  if (wfk_ranges_overlap(ker_dev, ker_bytes, sig_in_dev, wfk_rows_bytes(p->in_rows, in_stride, p->n, 8)) ||
-      wfk_ranges_overlap(ker_dev, ker_bytes, sig_out_dev, wfk_rows_bytes(p->batch, out_sig_stride, p->n, 8)))
-    return wfk_fail(WFK_EINVAL, "extract rows is out of place: the result overlaps an input");
+  if (const int rc = wfk_row_rule("extract rows",
+                                  {{"sig_in", sig_in_dev, p->in_rows, in_stride, p->n, 8},
+                                   {"sig_out", sig_out_dev, p->batch, out_sig_stride, p->n, 8}},
+                                  {"ker", ker_dev, p->batch, ker_stride, p->K, 8}, kRowsAligned | kRowsDisjoint,
+                                  wfk_fail))
+    return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   RocfftRows& f = p->fft;
   // both inputs go through the plan's own contiguous rows: they stay intact, any stride, any overlap between them

@@ -1,7 +1,8 @@
 // wfk_host.h -- what the host side of every stage shares: the error helper, the element kind and its size, the launch
-// arithmetic of the row-slot kernels, the row rule, the device probe, the owners of a plan's device memory (DevBuf,
-// MappedWord), the packer of several host tables into one device block (DevTables), next to the prototypes of the
-// functions one stage's file calls in another's (wfk_internal.h).  Host code only.
+// arithmetic of the row-slot kernels, the row rule of the one-size stages (the rule itself: wfk_row_rule.h), the
+// device probe, the owners of a plan's device memory (DevBuf, MappedWord), the packer of several host tables into one
+// device block (DevTables), next to the prototypes of the functions one stage's file calls in another's
+// (wfk_internal.h).  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +13,7 @@
 
 #include "wfk.h"
 #include "wfk_internal.h"
+#include "wfk_row_rule.h"
 
 namespace {
 
@@ -41,29 +43,24 @@ inline int wfk_row_blocks(const char* stage, int64_t n, int64_t per_block, int64
   return WFK_OK;
 }
 
-// The row rule of every apply (DESIGN.md "The row rule").  A batch of rows of n samples, `stride` samples apart,
-// occupies the bytes from the first sample of row 0 to the END of row batch - 1 -- not batch * stride.
-inline size_t wfk_rows_bytes(int64_t batch, int64_t stride, int64_t n, size_t es) {
-  return ((size_t)(batch - 1) * (size_t)stride + (size_t)n) * es;
-}
-
-// do the half-open byte ranges [a, a + bytes_a) and [b, b + bytes_b) meet
-inline bool wfk_ranges_overlap(const void* a, size_t bytes_a, const void* b, size_t bytes_b) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a0 < b0 + bytes_b && b0 < a0 + bytes_a;
-}
-
-// What an apply checks after its own `null plan` / `n == 0` handling: `in` (in_rows rows) and `out` (out_rows rows)
-// are there, no row stride is below n and -- `disjoint`, the out-of-place stages -- the two extents do not meet.
-// A stage whose rows all read ONE input row gives in_rows = 1; a launch without an input gives `out` twice.
+// The row rule (wfk_row_rule.h; DESIGN.md "The row rule") of the stages whose two sides have one row length and one
+// element size, alignment left to the caller:
+// `in` (in_rows rows) and `out` (out_rows rows) are there, no row stride is below n and -- `disjoint`, the
+// out-of-place stages -- the two extents do not meet.  A stage whose rows all read ONE input row gives in_rows = 1; a
+// launch without an input gives `out` twice.
 inline int wfk_check_rows(const char* stage, int64_t n, size_t es, const void* in, int64_t in_rows, int64_t in_stride,
                           const void* out, int64_t out_rows, int64_t out_stride, bool disjoint = false) {
-  if (!in || !out) return wfk_fail(WFK_EINVAL, std::string(stage) + ": null in / out buffer");
-  if (in_stride < n || out_stride < n) return wfk_fail(WFK_EINVAL, std::string(stage) + ": row stride smaller than n");
-  if (disjoint && wfk_ranges_overlap(in, wfk_rows_bytes(in_rows, in_stride, n, es), out,
-                                     wfk_rows_bytes(out_rows, out_stride, n, es)))
-    return wfk_fail(WFK_EINVAL, std::string(stage) + " is out of place: out overlaps in");
-  return WFK_OK;
+  return wfk_row_rule(stage, {{"in", in, in_rows, in_stride, n, es}}, {"out", out, out_rows, out_stride, n, es},
+                      disjoint ? kRowsDisjoint : 0u, wfk_fail);
+}
+
+// A counting stage's report, zeroed on the stream before the kernel adds to it: an apply overwrites its report.  The
+// n == 0 exit of such a stage is this alone, so it holds the report to its alignment itself.
+inline int wfk_zero_report(const char* stage, const RowReport& report, hipStream_t s) {
+  if (const int rc = wfk_report_rule(stage, report, wfk_fail)) return rc;
+  if (!report.ptr || hipMemsetAsync(const_cast<void*>(report.ptr), 0, report.bytes(), s) == hipSuccess) return WFK_OK;
+  (void)hipGetLastError();
+  return wfk_fail(WFK_EHIP, std::string(stage) + ": zeroing the counts failed");
 }
 
 inline bool wfk_have_device() {
@@ -146,5 +143,12 @@ class DevTables {
   template <typename T>
   static T* at(void* block, size_t offset) { return reinterpret_cast<T*>(static_cast<char*>(block) + offset); }
 };
+
+// a plan's tables: the block taken and the image sent to it; `plan` ("dac rows plan") names the failure
+inline int wfk_upload_tables(const char* plan, const DevTables& tab, DevBuf<char>& block) {
+  if (block.alloc(tab.total()) && tab.upload(block.get())) return WFK_OK;
+  (void)hipGetLastError();
+  return wfk_fail(WFK_EHIP, std::string(plan) + ": table upload failed");
+}
 
 }  // namespace

@@ -384,36 +384,16 @@ int marker_apply(wfk_marker_rows_plan* p, const void* in_dev, int64_t in_stride,
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (bit < 0 || bit > 15) return wfk_fail(WFK_EINVAL, "marker rows: bit must lie in [0, 15]");
   const int64_t rows = p->batch / p->k;
-  const size_t counts_bytes = (size_t)rows * 2 * sizeof(int64_t);
-  if (counts_dev && ((uintptr_t)counts_dev & 7))
-    return wfk_fail(WFK_EINVAL, "marker rows: counts are not aligned to int64");
-  if (p->n == 0) {   // nothing to mark (the pointers of empty rows may be null); the report is still zeroed
-    if (counts_dev && hipMemsetAsync(counts_dev, 0, counts_bytes, s) != hipSuccess) {
-      (void)hipGetLastError();
-      return wfk_fail(WFK_EHIP, "marker rows: zeroing the counts failed");
-    }
-    return WFK_OK;
-  }
-  const size_t es = wfk_elem_size(p->kind), out_es = into_codes ? sizeof(int16_t) : sizeof(uint8_t);
-  const int64_t out_n = into_codes ? p->k * p->n : p->n;
-  const char* what = into_codes ? "codes" : "out";
-  if (!in_dev || !out_dev) return wfk_fail(WFK_EINVAL, std::string("marker rows: null in / ") + what + " buffer");
-  if (((uintptr_t)in_dev & (es - 1)) || ((uintptr_t)out_dev & (out_es - 1)))
-    return wfk_fail(WFK_EINVAL, "marker rows: rows are not aligned to their element");
-  if (in_stride < p->n) return wfk_fail(WFK_EINVAL, "marker rows: input row stride smaller than n");
-  if (rows > 1 && out_stride < out_n)
-    return wfk_fail(WFK_EINVAL, std::string("marker rows: ") + what + " row stride smaller than the row");
-  const size_t in_bytes = wfk_rows_bytes(p->batch, in_stride, p->n, es);
-  const size_t out_bytes = wfk_rows_bytes(rows, out_stride, out_n, out_es);
-  if (wfk_ranges_overlap(in_dev, in_bytes, out_dev, out_bytes))
-    return wfk_fail(WFK_EINVAL, std::string("marker rows: ") + what + " overlaps in");
-  if (counts_dev && (wfk_ranges_overlap(counts_dev, counts_bytes, in_dev, in_bytes) ||
-                     wfk_ranges_overlap(counts_dev, counts_bytes, out_dev, out_bytes)))
-    return wfk_fail(WFK_EINVAL, std::string("marker rows: counts overlaps in / ") + what);
-  if (counts_dev && hipMemsetAsync(counts_dev, 0, counts_bytes, s) != hipSuccess) {
-    (void)hipGetLastError();
-    return wfk_fail(WFK_EHIP, "marker rows: zeroing the counts failed");
-  }
+  const RowReport report{counts_dev, rows, 2};
+  // nothing to mark (the pointers of empty rows may be null); the report is still zeroed
+  if (p->n == 0) return wfk_zero_report("marker rows", report, s);
+  // a lone output row's stride is not read
+  const RowSide out = into_codes ? RowSide{"codes", out_dev, rows, out_stride, p->k * p->n, sizeof(int16_t), false}
+                                 : RowSide{"out", out_dev, rows, out_stride, p->n, sizeof(uint8_t), false};
+  if (const int rc = wfk_row_rule("marker rows", {{"in", in_dev, p->batch, in_stride, p->n, wfk_elem_size(p->kind)}},
+                                  out, kRowsAligned | kRowsDisjoint, wfk_fail, report))
+    return rc;
+  if (const int rc = wfk_zero_report("marker rows", report, s)) return rc;
   if (p->kind == WFK_OUT_F32)
     marker_launch<float>(p, in_dev, in_stride, out_dev, out_stride, into_codes, bit, counts_dev, s);
   else
@@ -487,10 +467,7 @@ int wfk_marker_rows_plan_create(int64_t n, int32_t batch, int kind, int group, c
   p->blocks_per_row[0] = bpr[0]; p->blocks_per_row[1] = bpr[1];
   DevTables tab;
   p->rows_off = tab.add(tab_rows);
-  if (!(p->tables.alloc(tab.total()) && tab.upload(p->tables.get()))) {
-    (void)hipGetLastError();
-    return wfk_fail(WFK_EHIP, "marker rows plan: table upload failed");
-  }
+  if (const int rc = wfk_upload_tables("marker rows plan", tab, p->tables)) return rc;
   *out = p.release();
   return WFK_OK;
 } catch (const std::bad_alloc&) {

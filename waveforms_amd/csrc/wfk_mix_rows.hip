@@ -263,10 +263,7 @@ int wfk_mix_rows_plan_create(int64_t n, int32_t rows_out, int32_t rows_in, int k
   p->entries_off = tab.add(entries);
   p->coef_off = tab.add(coef);
   p->offset_off = tab.add(offs);
-  if (!(p->tables.alloc(tab.total()) && tab.upload(p->tables.get()))) {
-    (void)hipGetLastError();
-    return wfk_fail(WFK_EHIP, "mix rows plan: table upload failed");
-  }
+  if (const int rc = wfk_upload_tables("mix rows plan", tab, p->tables)) return rc;
   *out = p.release();
   return WFK_OK;
 } catch (const std::bad_alloc&) {
@@ -277,15 +274,11 @@ int wfk_mix_rows_apply(wfk_mix_rows_plan* p, const void* in_dev, int64_t in_stri
                        int64_t out_stride, void* hip_stream) {
   if (!p) return wfk_fail(WFK_EINVAL, "null plan");
   if (p->n == 0) return WFK_OK;   // nothing to mix (the pointers of empty rows may be null)
-  // the row rule with a number of rows per side (wfk_check_rows takes one stride test for both)
   const size_t es = wfk_elem_size(p->kind);
-  if (!in_dev || !out_dev) return wfk_fail(WFK_EINVAL, "mix rows: null in / out buffer");
-  if (((uintptr_t)in_dev & (es - 1)) || ((uintptr_t)out_dev & (es - 1)))
-    return wfk_fail(WFK_EINVAL, "mix rows: rows are not aligned to their element");
-  if (in_stride < p->n || out_stride < p->n) return wfk_fail(WFK_EINVAL, "mix rows: row stride smaller than n");
-  if (wfk_ranges_overlap(in_dev, wfk_rows_bytes(p->rows_in, in_stride, p->n, es), out_dev,
-                         wfk_rows_bytes(p->rows_out, out_stride, p->n, es)))
-    return wfk_fail(WFK_EINVAL, "mix rows is out of place: out overlaps in");
+  if (const int rc = wfk_row_rule("mix rows", {{"in", in_dev, p->rows_in, in_stride, p->n, es}},
+                                  {"out", out_dev, p->rows_out, out_stride, p->n, es}, kRowsAligned | kRowsDisjoint,
+                                  wfk_fail))
+    return rc;
   hipStream_t s = (hipStream_t)hip_stream;
   if (p->kind == WFK_OUT_F32)
     mix_launch<float>(p, in_dev, in_stride, out_dev, out_stride, s);

@@ -1,0 +1,88 @@
+// wfk_row_rule.h -- the row rule of every apply (DESIGN.md "The row rule") as integer arithmetic on addresses: no
+// HIP, no device, no state, so a plain C++ program holds it to its table (tests/c_abi/row_rule_host.cpp).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <initializer_list>
+#include <string>
+
+#include "wfk.h"
+
+namespace {
+
+// do the half-open byte ranges [a, a + bytes_a) and [b, b + bytes_b) meet
+inline bool wfk_ranges_overlap(const void* a, size_t bytes_a, const void* b, size_t bytes_b) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + bytes_b && b0 < a0 + bytes_a;
+}
+
+// One side of an apply: `rows` rows of `n` elements of `es` bytes, `stride` elements apart.  The sides of one apply
+// may differ in all of these.
+struct RowSide {
+  const char* what;   // its name in a refusal: "in", "out", "codes", ...
+  const void* ptr;
+  int64_t rows, stride, n;
+  size_t es;
+  bool lone_stride = true;   // is the stride of a single row held to n (no kernel reads it: dac and marker let it pass)
+  // the bytes from the first element of row 0 to the END of row rows - 1 -- not rows * stride
+  size_t bytes() const { return ((size_t)(rows - 1) * (size_t)stride + (size_t)n) * es; }
+  bool meets(const void* p, size_t b) const { return wfk_ranges_overlap(ptr, bytes(), p, b); }
+};
+
+// What a counting stage writes next to its output: rows x counters contiguous int64 (ptr null: it does not count)
+struct RowReport {
+  const void* ptr = nullptr;
+  int64_t rows = 0, counters = 0;
+  size_t bytes() const { return (size_t)rows * (size_t)counters * sizeof(int64_t); }
+};
+
+// the clauses a stage may leave out: every side starts at a multiple of its element size; `out` meets no input
+enum : unsigned { kRowsAligned = 1, kRowsDisjoint = 2 };
+
+// Every refusal is WFK_EINVAL with a text that names the stage first, handed to `fail` (code, text) -> code: wfk_fail
+// of wfk_host.h in the library.
+
+// what remains of the rule for rows of no elements: a report that is there starts at a multiple of 8
+template <typename Fail>
+int wfk_report_rule(const char* stage, const RowReport& report, Fail&& fail) {
+  if (!((uintptr_t)report.ptr & 7)) return WFK_OK;
+  return fail(WFK_EINVAL, std::string(stage) + ": counts are not aligned to int64");
+}
+
+// The rule, after the apply's own `null plan` / `n == 0` exits, clause by clause in this order: the report's alignment;
+// no null side; (kRowsAligned) every side aligned to its element; every stride >= that side's own n, but for a single
+// row with lone_stride off; (kRowsDisjoint) `out` meets no side of `in`; the report meets no side.  An apply without
+// an input gives `out` as its input.
+template <typename Fail>
+int wfk_row_rule(const char* stage, std::initializer_list<RowSide> in, const RowSide& out, unsigned clauses,
+                 Fail&& fail, const RowReport& report = RowReport()) {
+  if (const int rc = wfk_report_rule(stage, report, fail)) return rc;
+  const auto refuse = [&](const std::string& text) { return fail(WFK_EINVAL, stage + text); };
+  const auto sides = [&](auto&& f) {   // the inputs, then `out`
+    for (const RowSide& s : in) f(s);
+    f(out);
+  };
+  bool null = false, misaligned = false;
+  const RowSide *narrow = nullptr, *counted = nullptr;   // the first side with a stride below its n / under the report
+  std::string names;
+  sides([&](const RowSide& s) {
+    null = null || !s.ptr;
+    misaligned = misaligned || ((uintptr_t)s.ptr & (s.es - 1));
+    if (!narrow && s.stride < s.n && (s.rows > 1 || s.lone_stride)) narrow = &s;
+    if (!counted && report.ptr && s.meets(report.ptr, report.bytes())) counted = &s;
+    names += std::string(names.empty() ? "" : " / ") + s.what;
+  });
+  if (null) return refuse(": null " + names + " buffer");
+  if ((clauses & kRowsAligned) && misaligned) return refuse(": rows are not aligned to their element");
+  if (narrow)
+    return refuse(std::string(": ") + narrow->what + " row stride smaller than n (" + std::to_string(narrow->stride) +
+                  " < " + std::to_string(narrow->n) + ")");
+  for (const RowSide& s : in) {
+    if ((clauses & kRowsDisjoint) && s.meets(out.ptr, out.bytes()))
+      return refuse(std::string(" is out of place: ") + out.what + " overlaps " + s.what);
+  }
+  if (counted) return refuse(std::string(": counts overlaps ") + counted->what);
+  return WFK_OK;
+}
+
+}  // namespace

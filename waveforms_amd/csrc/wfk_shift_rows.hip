@@ -165,10 +165,7 @@ int wfk_shift_rows_plan_create(int64_t n, int32_t batch, int kind, const int64_t
   p->blocks_per_row = bpr;
   DevTables tab;
   p->rows_off = tab.add(rows);
-  if (!(p->tables.alloc(tab.total()) && tab.upload(p->tables.get()))) {
-    (void)hipGetLastError();
-    return wfk_fail(WFK_EHIP, "shift rows plan: table upload failed");
-  }
+  if (const int rc = wfk_upload_tables("shift rows plan", tab, p->tables)) return rc;
   *out = p.release();
   return WFK_OK;
 } catch (const std::bad_alloc&) {

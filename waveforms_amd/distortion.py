@@ -1028,6 +1028,14 @@ def _rows_signal(name, sig):
     return np.ascontiguousarray(sig, dtype=np.float64)
 
 
+def _rows_signal_f32(name, sig):
+    """_rows_signal, but float32 rows stay float32"""
+    src = np.asarray(sig)
+    if src.ndim == 2 and src.dtype == np.float32:
+        return np.ascontiguousarray(src)
+    return _rows_signal(name, sig)
+
+
 def _spectral_rows_host(sig2, terms_rows, sample_rate):
     """NumPy in, NumPy out: upload, one SpectralRowsPlan apply in place, download"""
     batch, n = sig2.shape
@@ -1166,11 +1174,7 @@ def shift_rows(sig, delays, dt):
     fewer than 3 samples or with inf in them differ from the reference.  float32 rows stay float32, anything else
     is computed as float64.  ValueError before any device work: sig not 2-D, a number of delays that does not match,
     a delay that is not finite.  NotImplementedError: complex rows."""
-    src = np.asarray(sig)
-    if src.ndim == 2 and src.dtype == np.float32:
-        sig2 = np.ascontiguousarray(src)
-    else:
-        sig2 = _rows_signal('shift_rows', sig)
+    sig2 = _rows_signal_f32('shift_rows', sig)
     batch, n = sig2.shape
     points, deltas = _shift_split('shift_rows', _per_row('shift_rows', 'delay', delays, batch), dt)
     if n == 0 or batch == 0:
@@ -1260,11 +1264,7 @@ def mix_rows(sig, matrix, offset=None):
     for the formula), in one launch: NumPy in, NumPy out, (rows of the matrix, samples).  float32 rows stay float32,
     anything else is computed as float64.  ValueError before any device work: sig not 2-D, a matrix whose columns are
     not the rows of sig, what `MixStage` refuses.  NotImplementedError: complex rows."""
-    src = np.asarray(sig)
-    if src.ndim == 2 and src.dtype == np.float32:
-        sig2 = np.ascontiguousarray(src)
-    else:
-        sig2 = _rows_signal('mix_rows', sig)
+    sig2 = _rows_signal_f32('mix_rows', sig)
     batch, n = sig2.shape
     rows_in, row_ptr, col, val, off, n, dtype = _engine._mix_rows_checked(matrix, offset, n, sig2.dtype)
     if rows_in != batch:
@@ -1347,8 +1347,7 @@ class DacStage:
         xr, yr = (x0, xs, self.batch, self.n, self.dtype.itemsize), (y0, ys, self.out_rows, self.out_n, 2)
         if not _rows.rows_disjoint(xr, yr):
             raise ValueError('dac stage is out of place: out overlaps x')
-        if c0 is not None and not (_rows.rows_disjoint((c0, 3, self.batch, 3, 8), xr)
-                                   and _rows.rows_disjoint((c0, 3, self.batch, 3, 8), yr)):
+        if not _rows.report_disjoint(c0, self.batch, 3, xr, yr):
             raise ValueError('dac stage: counts overlaps x / out')
         self.apply(x0, xs, y0, ys, c0, torch.cuda.current_stream(x.device).cuda_stream)
         return out[:, :self.out_n]
@@ -1364,11 +1363,7 @@ def dac_codes_rows(sig, gain, offset=0.0, bits=16, shift=0, interleave=1, return
     -> (codes, counts), counts the (rows, 3) int64 [below, above, nan] per input row.  ValueError before any device
     work: sig not 2-D, a number of gains or offsets that does not match, what `DacStage` refuses.
     NotImplementedError: complex rows."""
-    src = np.asarray(sig)
-    if src.ndim == 2 and src.dtype == np.float32:
-        sig2 = np.ascontiguousarray(src)
-    else:
-        sig2 = _rows_signal('dac_codes_rows', sig)
+    sig2 = _rows_signal_f32('dac_codes_rows', sig)
     batch, n = sig2.shape
     gains = _per_row('dac_codes_rows', 'gain', gain, batch)
     offsets = _per_row('dac_codes_rows', 'offset', offset, batch)
@@ -1452,8 +1447,7 @@ class MarkerStage:
         yr = (y0, ys, self.out_rows, out_n, np.dtype(out_dtype).itemsize)
         if not _rows.rows_disjoint(xr, yr):
             raise ValueError(f'marker stage: {what} overlaps x')
-        if c0 is not None and not (_rows.rows_disjoint((c0, 2, self.out_rows, 2, 8), xr)
-                                   and _rows.rows_disjoint((c0, 2, self.out_rows, 2, 8), yr)):
+        if not _rows.report_disjoint(c0, self.out_rows, 2, xr, yr):
             raise ValueError(f'marker stage: counts overlaps x / {what}')
         return x0, xs, y0, ys, c0
 
@@ -1494,11 +1488,7 @@ def marker_rows(sig, lead=0, trail=0, threshold=0.0, group=1, codes=None, bit=0,
     (rows // group, 2) int64 [high, pulses] per marker row.  ValueError before any device work: sig not 2-D, a number
     of leads, trails or thresholds that does not match, codes of another shape or dtype, a bit outside 0 .. 15, what
     `MarkerStage` refuses.  NotImplementedError: complex rows."""
-    src = np.asarray(sig)
-    if src.ndim == 2 and src.dtype == np.float32:
-        sig2 = np.ascontiguousarray(src)
-    else:
-        sig2 = _rows_signal('marker_rows', sig)
+    sig2 = _rows_signal_f32('marker_rows', sig)
     batch, n = sig2.shape
     group = int(group)
     if group not in (1, 2):
