@@ -15,7 +15,25 @@
  * returns 0 on success or a negative WFK_E* code; wfk_last_error() returns a
  * thread-local message.  The caller owns every host buffer and every opaque
  * handle (explicit *_destroy); the library owns device tables inside a plan.
- * wfk_plan_launch() and wfk_fir_apply() do no allocation and no host sync.
+ * wfk_plan_launch() and wfk_fir_apply() allocate nothing and do not synchronise.
+ *
+ * Graph capture.  Every entry whose comment says that it "allocates nothing and does not synchronise" -- in these
+ * words -- enqueues kernels, memsets and device-to-device copies on `hip_stream` and does nothing else to the device,
+ * so it may be called while that stream is being captured (hipStreamBeginCapture, torch.cuda.graph) and the graph
+ * replayed once per shot: wfk_plan_launch, wfk_fir_apply, wfk_chain_launch, wfk_iir_apply, wfk_iir_rows_apply,
+ * wfk_chain_iir_launch, wfk_chain_iir_rows_launch, wfk_spectral_apply, wfk_spectral_rows_apply, wfk_shift_rows_apply,
+ * wfk_dac_rows_apply, wfk_marker_rows_apply, wfk_marker_rows_apply_codes, wfk_mix_rows_apply, wfk_extract_rows_apply,
+ * wfk_demod_apply and wfk_boxprobe_apply.  Creation, destruction, *_run_host, wfk_iir_status and wfk_chain_iir_status
+ * allocate or synchronise and must stay outside a capture.
+ * A capture freezes what the call was given and what it decided: every pointer and stride (feed a replay by copying
+ * into the captured buffers), the scalar `initial` of the IIR entries, `bit` of wfk_marker_rows_apply_codes, `flags`
+ * and `out_kind`, and the environment switches an entry reads when it launches (WFK_IIR_SPIN, WFK_IIR_OP_DEPTH).
+ * Device arrays -- zi, the per-row initial_dev, an accumulate base -- are read anew by every replay; zf, counts and
+ * every other output are written anew, never accumulated across replays.  No launch depends on how many went before.
+ * A look-back time-out of the single-pass IIR during a REPLAY is reported by wfk_iir_status / wfk_chain_iir_status
+ * alone (the replay calls no entry that could return WFK_ETIMEOUT); the graph keeps launching the single-pass form, so
+ * capture again after it.  "One plan per concurrent stream" also means: a plan that owns scratch is not in two graphs
+ * that replay at the same time, nor in a graph replaying while the plan is applied eagerly on another stream.
  */
 #ifndef WFK_H
 #define WFK_H
@@ -258,7 +276,9 @@ int wfk_chain_plan_destroy(wfk_chain_plan* plan);
  * four first-order sections, one section of order 3 or 4) run as ONE kernel that reads x once (chained scan with decoupled
  * look-back); other shapes as a block scan in three launches; cascades of mixed orders or beyond
  * those sizes as consecutive passes.  A plan owns scratch state for its launches: use one plan per
- * concurrent stream.  In place (out_dev == in_dev) is allowed in every form.           */
+ * concurrent stream.  In place (out_dev == in_dev) is allowed in every form.
+ * wfk_iir_apply() allocates nothing and does not synchronise: the single pass clears its tickets and chunk flags with
+ * a small kernel in front of its own, a cut cascade repacks zi / zf with device-to-device copies.                  */
 typedef struct wfk_iir_plan wfk_iir_plan;
 int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double* b,
                         const double* a, int64_t n, int32_t batch,
@@ -378,7 +398,8 @@ int wfk_chain_iir_rows_plan_destroy(wfk_chain_iir_rows_plan* plan);
 typedef struct wfk_spectral_plan wfk_spectral_plan;
 int wfk_spectral_plan_create(int64_t n, int32_t batch, int kind, wfk_spectral_plan** out);
 /* The one H serves all `batch` rows.  In place (out_dev == in_dev) is allowed: the input is copied to a
- * staging buffer of the plan before anything is written.  Asynchronous on `hip_stream`.              */
+ * staging buffer of the plan before anything is written.  Asynchronous on `hip_stream`:
+ * wfk_spectral_apply() allocates nothing and does not synchronise (the plan owns rocFFT's work buffer).  */
 int wfk_spectral_apply(wfk_spectral_plan* plan, const void* in_dev, void* out_dev,
                        const void* H_dev, void* hip_stream);
 int wfk_spectral_plan_destroy(wfk_spectral_plan* plan);
@@ -492,7 +513,8 @@ int wfk_dac_rows_plan_destroy(wfk_dac_rows_plan* plan);
  * not finite, a lead or trail that is negative or exceeds WFK_MARKER_MAX_EDGE (the row is named: "row 3: lead exceeds
  * 4096"), a kind other than F64 / F32, null pointers, more than 2^31 - 1 workgroups: WFK_EINVAL, before any device
  * work; no device: WFK_EHIP.
- * The applies allocate nothing and do not synchronise.  in_stride is in samples, >= n; out_stride in bytes, >= n,
+ * wfk_marker_rows_apply() and wfk_marker_rows_apply_codes() allocate nothing and do not synchronise.
+ * in_stride is in samples, >= n; out_stride in bytes, >= n,
  * codes_stride in codes, >= k n, where there is more than one marker row.  counts_dev: NULL, or batch / k * 2 int64
  * on the device, [high, pulses] per marker row -- the samples with m = 1, and those of them with i = 0 or
  * m[g, i - 1] = 0; every apply OVERWRITES them (zeroed on the stream, then added to with integer atomics: bitwise

@@ -174,10 +174,30 @@ static int plan_upload(wfk_plan* p, const double* tlist) {
   return WFK_OK;
 }
 
+// `words` 32-bit words from p on set to zero (grid-stride)
+__global__ void wfk_zero_words(uint32_t* __restrict__ p, size_t words) {
+  const size_t step = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += step) p[i] = 0u;
+}
+
 extern "C" {
 
 // shared with the other stages (wfk_internal.h; not part of the public header)
 void wfk_internal_set_error(const char* msg) { g_err = msg ? msg : ""; }
+
+// Zero `bytes` of device memory in stream order, by a KERNEL: what an apply clears in front of its own kernel (counts,
+// tickets, chunk flags).  A hipMemsetAsync does the same when it runs eagerly, but captured into a graph it replayed with
+// another fill value from the second replay on (tests/test_gpu_graph_replay.py found counts of 0x789a... + the count);
+// a kernel node replays as it was captured.  The range is whole 32-bit words.
+int wfk_internal_zero_async(void* dev, size_t bytes, void* hip_stream) {
+  if (bytes == 0) return WFK_OK;
+  if (!dev || (bytes & 3) || ((uintptr_t)dev & 3)) return wfk_fail(WFK_EINVAL, "zeroing: not a range of 32-bit words");
+  const size_t words = bytes / 4;
+  const unsigned blocks = (unsigned)std::min<size_t>((words + 255) / 256, 1024);
+  hipLaunchKernelGGL(wfk_zero_words, dim3(blocks), dim3(256), 0, (hipStream_t)hip_stream, (uint32_t*)dev, words);
+  if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "zeroing kernel launch failed");
+  return WFK_OK;
+}
 
 int wfk_abi_version(void) { return WFK_ABI_VERSION; }
 

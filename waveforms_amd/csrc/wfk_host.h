@@ -58,8 +58,7 @@ inline int wfk_check_rows(const char* stage, int64_t n, size_t es, const void* i
 // n == 0 exit of such a stage is this alone, so it holds the report to its alignment itself.
 inline int wfk_zero_report(const char* stage, const RowReport& report, hipStream_t s) {
   if (const int rc = wfk_report_rule(stage, report, wfk_fail)) return rc;
-  if (!report.ptr || hipMemsetAsync(const_cast<void*>(report.ptr), 0, report.bytes(), s) == hipSuccess) return WFK_OK;
-  (void)hipGetLastError();
+  if (!report.ptr || wfk_internal_zero_async(const_cast<void*>(report.ptr), report.bytes(), s) == WFK_OK) return WFK_OK;
   return wfk_fail(WFK_EHIP, std::string(stage) + ": zeroing the counts failed");
 }
 

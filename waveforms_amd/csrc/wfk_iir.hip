@@ -372,7 +372,7 @@ __device__ __forceinline__ void op_publish(double* buf, unsigned* status, int64_
 // sin_ = S_in; returns `poisoned` (wave-uniform): the look-back ran out of polls, the chunk's outputs must be NaN.
 template <int DD>
 __device__ __forceinline__ bool op_chunk_start(const double (&z)[IIR_MAXD], int lane, int row, int64_t chunk,
-                                               int64_t nchunks, unsigned epoch, unsigned* status,
+                                               int64_t nchunks, unsigned* status,
                                                double* aggbuf, double* prefbuf,
                                                const double* lanepU, const double* zi,
                                                unsigned* fault, int spin_limit, double (&vprev)[DD],
@@ -385,7 +385,9 @@ __device__ __forceinline__ bool op_chunk_start(const double (&z)[IIR_MAXD], int 
     agg[i] = __shfl(z[i], 63);
   }
   const int64_t slot = ((int64_t)row * nchunks + chunk);
-  const unsigned F_AGG = epoch * 4u + 1u, F_PRE = epoch * 4u + 2u;
+  // every launch starts from cleared flags (the host clears them with the tickets, in stream order): nothing in a
+  // launch depends on how many went before it, so a captured launch replays as it ran
+  constexpr unsigned F_AGG = 1u, F_PRE = 2u;
   if (chunk > 0 && lane == 0) op_publish<DD>(aggbuf, status, slot, F_AGG, agg);
 
   // ---- state at the chunk's start
@@ -511,7 +513,7 @@ __global__ void __launch_bounds__(64, OP_WAVES) iir_onepass(const IirCoef c, con
                                                   const double* __restrict__ pw1, const double* __restrict__ lanep1,
                                                   const double* __restrict__ lanepU, const double* __restrict__ zi,
                                                   double* __restrict__ zf, int64_t n, int64_t nchunks, int rows,
-                                                  unsigned epoch, double pre_sub, double post_add, int persist,
+                                                  double pre_sub, double post_add, int persist,
                                                   unsigned* __restrict__ fault, int spin_limit) {
   constexpr int DD = NSEC * ORD;       // state dimension (<= 4)
   __shared__ T tile[64][OP_LB + 1];
@@ -575,7 +577,7 @@ __global__ void __launch_bounds__(64, OP_WAVES) iir_onepass(const IirCoef c, con
   else wave_scan<DD>(z, pw1, DD, lane);                      // z = v_l (inclusive)
   // ---- state at the chunk's start (aggregate, look-back, prefix), then sweep 2 from the true block states v_{l-1} + T1^l * S_in
   double vprev[DD], sin_[IIR_MAXD];
-  const bool poisoned = op_chunk_start<DD>(z, lane, row, chunk, nchunks, epoch, status, aggbuf, prefbuf, lanepU, zi, fault,
+  const bool poisoned = op_chunk_start<DD>(z, lane, row, chunk, nchunks, status, aggbuf, prefbuf, lanepU, zi, fault,
                                            spin_limit, vprev, sin_);
   op_lane_start<DD, PLAIN>(z, vprev, lanep1, sin_, lane);
   const double bad = poisoned ? __builtin_nan("") : 0.0;
@@ -775,7 +777,7 @@ __global__ void __launch_bounds__(64, OPS_WAVES) iir_sampled(const IirCoef c, co
                                                   const double* __restrict__ pwL, const double* __restrict__ lanepL,
                                                   const double* __restrict__ lanepU, const double* __restrict__ wdot,
                                                   const double* __restrict__ zi, double* __restrict__ zf, int64_t n,
-                                                  int64_t nchunks, int rows, unsigned epoch, double pre_sub,
+                                                  int64_t nchunks, int rows, double pre_sub,
                                                   double post_add, int persist, unsigned* __restrict__ fault,
                                                   int spin_limit) {
   constexpr int DD = NSEC * ORD;       // state dimension (<= 4)
@@ -880,7 +882,7 @@ __global__ void __launch_bounds__(64, OPS_WAVES) iir_sampled(const IirCoef c, co
   // ---- state at the chunk's start (aggregate, look-back, prefix), then pass 2: the run again from its true state
   // v_(l-1) + TL^l S_in: evaluate, sweep, store
   double vprev[DD], sin_[IIR_MAXD];
-  const bool poisoned = op_chunk_start<DD>(z, lane, row, chunk, nchunks, epoch, status, aggbuf, prefbuf, lanepU, zi, fault,
+  const bool poisoned = op_chunk_start<DD>(z, lane, row, chunk, nchunks, status, aggbuf, prefbuf, lanepU, zi, fault,
                                            spin_limit, vprev, sin_);
   op_lane_start<DD, PLAIN>(z, vprev, lanepL, sin_, lane);
   const double bad = poisoned ? __builtin_nan("") : 0.0;
@@ -977,9 +979,12 @@ struct wfk_iir_plan {
   // and one table set per kernel (T1: the transition over OP_LB samples)
   bool onepass = false;
   int64_t op_chunks = 0;
-  unsigned epoch = 0;
-  DevBuf<unsigned> op_status;
-  DevBuf<unsigned> op_ticket;
+  // one allocation, cleared in stream order by ONE launch of the zeroing kernel in front of every launch: a ticket
+  // counter per row (64 B apart), then a status word per chunk of every row
+  DevBuf<unsigned> op_sync;
+  size_t op_sync_bytes = 0;
+  unsigned* op_ticket() const { return op_sync.get(); }
+  unsigned* op_status() const { return op_sync.get() + (size_t)batch * 16; }
   DevBuf<double> op_agg;
   DevBuf<double> op_pref;
   OpTables op1;                      // iir_onepass: lane blocks of OP_LB samples, B = T1
@@ -1150,8 +1155,8 @@ int wfk_iir_plan_create(int32_t n_sections, const int32_t* orders, const double*
       if (!tL.plain) tL = table_set(OPS_RUN_SWEEP, false, true);
       p->op_chunks = (n + OP_CHUNK - 1) / OP_CHUNK;
       const size_t slots = (size_t)batch * (size_t)p->op_chunks;
-      if (!p->op_status.alloc(slots * 4) || hipMemset(p->op_status.get(), 0, slots * 4) != hipSuccess ||
-          !p->op_ticket.alloc((size_t)batch * 64) || !p->op_agg.alloc(slots * D * 8) ||
+      p->op_sync_bytes = ((size_t)batch * 16 + slots) * 4;
+      if (!p->op_sync.alloc(p->op_sync_bytes) || !p->op_agg.alloc(slots * D * 8) ||
           !p->op_pref.alloc(slots * D * 8) || !p->op1.upload(t1) || !p->opL.upload(tL) || !p->op_fault.alloc())
         return wfk_fail(WFK_ENOMEM, "IIR single-pass buffer allocation failed");
       // ONE section of order 3 / 4 whose transition powers grow past 1e3 (clustered poles: butter(4, 0.022) as a single
@@ -1218,7 +1223,6 @@ struct OpCall {
   double initial, post;
   unsigned total;              // workgroups
   int64_t nchunks;
-  unsigned epoch;
   int persist, spin_limit;
   hipStream_t s;
 };
@@ -1231,14 +1235,14 @@ static void op_launch(wfk_iir_plan* p, const OpCall& k) {
     constexpr bool PLAIN = decltype(plain)::value;
     if (k.src)
       hipLaunchKernelGGL((iir_sampled<T, NSEC, ORD, PLAIN>), dim3(k.total), dim3(64), 0, k.s, p->c, *k.src, (T*)k.out,
-                         k.out_stride, p->op_status.get(), p->op_agg.get(), p->op_pref.get(), p->op_ticket.get(),
+                         k.out_stride, p->op_status(), p->op_agg.get(), p->op_pref.get(), p->op_ticket(),
                          t.pw.get(), t.lanep.get(), t.lanepU.get(), t.wdot.get(), k.zi, k.zf, p->n, k.nchunks,
-                         (int)p->batch, k.epoch, k.initial, k.post, k.persist, p->op_fault.dev(), k.spin_limit);
+                         (int)p->batch, k.initial, k.post, k.persist, p->op_fault.dev(), k.spin_limit);
     else
       hipLaunchKernelGGL((iir_onepass<T, NSEC, ORD, PLAIN>), dim3(k.total), dim3(64), 0, k.s, p->c, (const T*)k.in,
-                         k.in_stride, (T*)k.out, k.out_stride, p->op_status.get(), p->op_agg.get(), p->op_pref.get(),
-                         p->op_ticket.get(), t.pw.get(), t.lanep.get(), t.lanepU.get(), k.zi, k.zf, p->n, k.nchunks,
-                         (int)p->batch, k.epoch, k.initial, k.post, k.persist, p->op_fault.dev(), k.spin_limit);
+                         k.in_stride, (T*)k.out, k.out_stride, p->op_status(), p->op_agg.get(), p->op_pref.get(),
+                         p->op_ticket(), t.pw.get(), t.lanep.get(), t.lanepU.get(), k.zi, k.zf, p->n, k.nchunks,
+                         (int)p->batch, k.initial, k.post, k.persist, p->op_fault.dev(), k.spin_limit);
   };
   if (t.plain) go(std::true_type{}); else go(std::false_type{});
 }
@@ -1369,12 +1373,12 @@ static int iir_apply_impl(wfk_iir_plan* p, const void* in_dev, int64_t in_stride
   if (p->onepass) {
     int spin_limit = OP_SPIN;
     if (const char* e = getenv("WFK_IIR_SPIN")) spin_limit = atoi(e);   // (tests: force the timeout)
-    // tickets restart at 0; the flags of earlier launches are told apart by the epoch
-    if (hipMemsetAsync(p->op_ticket.get(), 0, (size_t)p->batch * 64, s) != hipSuccess)
-      return wfk_fail(WFK_EHIP, "IIR ticket reset failed");
-    const unsigned epoch = ++p->epoch;
+    // tickets restart at 0 and no chunk has published anything: the launch reads no host counter, so a captured
+    // launch (two kernel nodes) replays as it ran
+    if (wfk_internal_zero_async(p->op_sync.get(), p->op_sync_bytes, s) != WFK_OK)
+      return wfk_fail(WFK_EHIP, "IIR ticket and flag reset failed");
     const OpShape sh = iir_op_shape(p, src != nullptr);
-    const OpCall call{src, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial, post, sh.total, sh.nchunks, epoch,
+    const OpCall call{src, in_dev, in_stride, out_dev, out_stride, zi_dev, zf_dev, initial, post, sh.total, sh.nchunks,
                       sh.persist, spin_limit, s};
 #ifdef OPS_ONLY_22     /* A/B builds (tools/iirchain_ablate.sh): one shape, a third of the compile time */
     op_launch<double, 2, 2>(p, call);

@@ -362,6 +362,8 @@ int wfk_launch_short(const SArgs& a, const SamplerPick& k, void* stream, std::st
 // functions one stage's file calls in another's, exported but not part of include/wfk.h
 extern "C" {
 void wfk_internal_set_error(const char* msg);   // wfk_api.cpp: this thread's text behind wfk_last_error
+// wfk_api.cpp: zero whole 32-bit words of device memory in stream order with a kernel (not a memset: see there)
+int wfk_internal_zero_async(void* dev, size_t bytes, void* hip_stream);
 // wfk_api.cpp: the compiled plan and its parameter table on the device; launch of a mixed short plan's general-kernel part
 void wfk_internal_plan_tables(const wfk_plan* p, const HostPlan** h, const double** d_params);
 // wfk_api.cpp: wfk_plan_create_grid (tlist == NULL) / wfk_plan_create_tlist (grid == NULL) with a request to the compiler
