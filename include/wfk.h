@@ -578,6 +578,50 @@ int64_t wfk_mix_rows_reads(const wfk_mix_rows_plan* plan);
 const char* wfk_mix_rows_kernel_name(const wfk_mix_rows_plan* plan);
 int wfk_mix_rows_plan_destroy(wfk_mix_rows_plan* plan);       /* NULL is fine */
 
+/* -- per-row calibration curve: piecewise-linear lookup over sample VALUES ------------------------ */
+/* `batch` real rows of n samples (kind: WFK_OUT_F64 or WFK_OUT_F32) go through a curve of their own: a flux pulse
+ * programmed in its physical unit to volts through a measured monotone curve, an amplifier's compression table, a
+ * DAC's INL table.  The curves come CSR-like: knot_ptr[batch + 1] from 0 and non-decreasing; row r has the
+ * K = knot_ptr[r + 1] - knot_ptr[r] knots xp[knot_ptr[r] ..) -- finite, strictly increasing,
+ * 2 <= K <= WFK_CURVE_MAX_KNOTS -- and the values fp[knot_ptr[r] ..), finite; rows may differ in K.  left / right:
+ * batch doubles each, ANY double (NaN too), what a sample below xp[0] / above xp[K - 1] becomes; NULL: fp[0] / fp[K - 1]
+ * of the row.  The host computes slope[j] = fl(fl(fp[j + 1] - fp[j]) / fl(xp[j + 1] - xp[j])) once, at creation.  Per
+ * sample, in double (a float sample is widened first, the result rounded once) and without a fused multiply-add,
+ *   x is NaN        -> y = x                                      (counted as nan)
+ *   x < xp[0]       -> y = left                                   (below; -inf too)
+ *   x > xp[K - 1]   -> y = right                                  (above; +inf too)
+ *   j = the largest index with xp[j] <= x;   y = fp[j] if x == xp[j] (j = K - 1 is this case),
+ *   y = fl(fl(slope[j] * fl(x - xp[j])) + fp[j]) otherwise
+ * -- np.interp(x, xp, fp, left, right), bit for bit.  Departures from np.interp, on purpose: K = 1, knots that are
+ * not finite or not strictly increasing and values that are not finite are refused.  n < 0, batch < 1, a knot_ptr
+ * that is not non-decreasing from 0, a row with fewer than 2 or more than WFK_CURVE_MAX_KNOTS knots, such knots or
+ * values (the row is named: "row 3: knots are not strictly increasing at 17"), a kind other than F64 / F32, null
+ * pointers, more than 2^31 - 1 workgroups: WFK_EINVAL, before any device work; no device: WFK_EHIP.
+ * wfk_curve_rows_apply() enqueues at most one memset (of the counts) and one kernel on `hip_stream`, and that is all
+ * it does to the device.  Strides are in elements, >= n.  IN PLACE (out_dev == in_dev and out_stride == in_stride) or
+ * out of place with extents that do not meet: [in, in + (batch - 1) * in_stride + n) meeting the same range of out in
+ * any other way, rows not aligned to their element, null buffers: WFK_EINVAL.  counts_dev: NULL, or batch * 3 int64 on
+ * the device, [below, above, nan] per row; every apply OVERWRITES them (zeroed on the stream, then added to with
+ * integer atomics: bitwise reproducible); without them the kernel does no counting; counts that meet either side or
+ * do not start at a multiple of 8: WFK_EINVAL.  n = 0: a no-op that still zeroes the counts.
+ * One kernel (curve_rows<T>, with counts curve_rows_counts<T>): a workgroup copies its row's knots and a bucket table
+ * over them into LDS and walks wfk_curve_rows_spans() consecutive spans of 2048 (F64) / 4096 (F32) samples of the row.
+ * The plan owns its tables and nothing else, so it may serve several streams. */
+#define WFK_CURVE_MAX_KNOTS 1024
+typedef struct wfk_curve_rows_plan wfk_curve_rows_plan;
+int wfk_curve_rows_plan_create(int64_t n, int32_t batch, int kind /* WFK_OUT_F64|F32 */,
+                               const int64_t* knot_ptr /* batch + 1, from 0 */, const double* xp, const double* fp,
+                               const double* left /* batch, or NULL */, const double* right /* batch, or NULL */,
+                               wfk_curve_rows_plan** out);
+int wfk_curve_rows_apply(wfk_curve_rows_plan* plan, const void* in_dev, int64_t in_stride, void* out_dev,
+                         int64_t out_stride, int64_t* counts_dev /* batch * 3, or NULL */, void* hip_stream);
+/* the spans one workgroup walks, chosen at creation from the size of the tables and of the grid; 0 for NULL */
+int wfk_curve_rows_spans(const wfk_curve_rows_plan* plan);
+/* "curve_rows<double>" / "curve_rows<float>", or with counts "curve_rows_counts<double>" /
+ * "curve_rows_counts<float>"; "" for NULL; a static string */
+const char* wfk_curve_rows_kernel_name(const wfk_curve_rows_plan* plan, int counts);
+int wfk_curve_rows_plan_destroy(wfk_curve_rows_plan* plan);   /* NULL is fine */
+
 /* -- per-row kernel extraction: the reference's extractKernel for every row ---------------------- */
 /* ker[r] = extractKernel(sig_in[r], sig_out[r], sample_rate, bw, skip) (waveforms/distortion.py:42-48) for `batch`
  * rows of n doubles: the kernel that maps sig_out back onto sig_in, the rows of an FIR plan's kernel matrix.  Per row

@@ -159,6 +159,12 @@ def lib():
         l.wfk_mix_rows_kernel_name.argtypes = [VP]
         l.wfk_mix_rows_kernel_name.restype = C.c_char_p
         l.wfk_mix_rows_plan_destroy.argtypes = [VP]
+        l.wfk_curve_rows_plan_create.argtypes = [I64, I32, C.c_int, VP, VP, VP, VP, VP, P(VP)]
+        l.wfk_curve_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP]
+        l.wfk_curve_rows_spans.argtypes = [VP]
+        l.wfk_curve_rows_kernel_name.argtypes = [VP, C.c_int]
+        l.wfk_curve_rows_kernel_name.restype = C.c_char_p
+        l.wfk_curve_rows_plan_destroy.argtypes = [VP]
         l.wfk_extract_rows_plan_create.argtypes = [I64, I32, I32, VP, I32, I64, P(VP)]
         l.wfk_extract_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, I64, VP]
         l.wfk_extract_rows_kernel_name.argtypes = [VP]
@@ -982,6 +988,116 @@ class MixRowsPlan(_Handle):
 
     def kernel_name(self) -> str:
         return lib().wfk_mix_rows_kernel_name(self._h).decode()
+
+
+CURVE_MAX_KNOTS = 1024     # WFK_CURVE_MAX_KNOTS
+
+
+def _curve_rows_list(name, rows):
+    """`rows` -- a list of 1-D array-likes (ragged), a 2-D array, or ONE 1-D array-like -- as a list of float64 1-D
+    arrays; ValueError for anything else, NotImplementedError for complex values"""
+    if isinstance(rows, np.ndarray) and rows.dtype != object:
+        if rows.ndim not in (1, 2):
+            raise ValueError(f'{name}: a list of 1-D arrays, a 2-D array or one 1-D array')
+        rows = [rows] if rows.ndim == 1 else list(rows)
+    else:
+        rows = list(rows)
+        if rows and all(np.ndim(r) == 0 for r in rows):
+            rows = [rows]
+    out = []
+    for r, a in enumerate(rows):
+        a = np.asarray(a)
+        if a.ndim != 1:
+            raise ValueError(f'row {r}: {name} is not 1-D')
+        if a.dtype.kind == 'c':
+            raise NotImplementedError('complex curves')
+        out.append(np.ascontiguousarray(a, dtype=np.float64))
+    return out
+
+
+def _curve_ends(name, value, default, batch):
+    """left / right: None (the row's own end value), a scalar (every row) or one value per row; any double"""
+    if value is None:
+        return np.array(default, dtype=np.float64)
+    v = np.asarray(value, dtype=np.float64)
+    if v.ndim == 0:
+        return np.full(batch, float(v))
+    v = np.ascontiguousarray(v).reshape(-1)
+    if len(v) != batch:
+        raise ValueError(f'{len(v)} values of {name} for {batch} rows')
+    return v
+
+
+def curve_rows_arguments(xp_rows, fp_rows, left=None, right=None, batch=None, n=0, dtype=np.float64):
+    """the arguments of a CurveRowsPlan, checked on the host -> (knot_ptr int64 [batch + 1], xp, fp float64 [knot_ptr[-1]]:
+    the rows' knots and values back to back; left, right float64 [batch]; n; dtype).  `xp_rows` / `fp_rows`: a list of
+    1-D arrays (rows may differ in length), a 2-D array, or one 1-D pair that every one of `batch` rows shares.
+    ValueError / NotImplementedError as CurveRowsPlan lists them.  Needs no device."""
+    n, dtype = int(n), np.dtype(dtype)
+    _real_dtype(dtype)
+    xs, fs = _curve_rows_list('xp', xp_rows), _curve_rows_list('fp', fp_rows)
+    if len(xs) != len(fs):
+        raise ValueError(f'{len(xs)} rows of xp and {len(fs)} rows of fp')
+    if batch is None:
+        batch = len(xs)
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError('no rows')
+    if len(xs) == 1 and batch > 1:
+        xs, fs = xs * batch, fs * batch
+    if len(xs) != batch:
+        raise ValueError(f'{len(xs)} curves for {batch} rows')
+    if n < 0:
+        raise ValueError('n >= 0')
+    for r, (x, f) in enumerate(zip(xs, fs)):
+        if len(x) != len(f):
+            raise ValueError(f'row {r}: {len(x)} knots and {len(f)} values')
+        if len(x) < 2:
+            raise ValueError(f'row {r}: fewer than 2 knots')
+        if len(x) > CURVE_MAX_KNOTS:
+            raise ValueError(f'row {r}: more than {CURVE_MAX_KNOTS} knots')
+        bad = np.flatnonzero(~np.isfinite(x))
+        rising = np.flatnonzero(~(x[1:] > x[:-1])) + 1            # (a NaN knot fails the comparison on both sides)
+        if len(bad) and (not len(rising) or bad[0] <= rising[0]):
+            raise ValueError(f'row {r}: knot {int(bad[0])} is not finite')
+        if len(rising):
+            raise ValueError(f'row {r}: knots are not strictly increasing at {int(rising[0])}')
+        bad = np.flatnonzero(~np.isfinite(f))
+        if len(bad):
+            raise ValueError(f'row {r}: value {int(bad[0])} is not finite')
+    knot_ptr = np.zeros(batch + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in xs], out=knot_ptr[1:])
+    left = _curve_ends('left', left, [f[0] for f in fs], batch)
+    right = _curve_ends('right', right, [f[-1] for f in fs], batch)
+    return knot_ptr, np.concatenate(xs), np.concatenate(fs), left, right, n, dtype
+
+
+class CurveRowsPlan(_Handle):
+    """y[r] = np.interp(x[r], xp[r], fp[r], left[r], right[r]), bit for bit, for `batch` rows of n float64 / float32
+    samples, every row its own curve of 2 .. CURVE_MAX_KNOTS knots (in float64: a rounded difference, product and sum,
+    no fused multiply-add; a float32 result rounded once; a NaN sample stays that NaN; wfk_curve_rows_plan_create).
+    `.knots`: the knots per row; `.spans`: the spans a workgroup walks.  ValueError before any device work: `no rows`,
+    `N curves for B rows`, `n >= 0`, `row r: K knots and M values`, `row r: fewer than 2 knots`, `row r: more than 1024
+    knots`, `row r: knot j is not finite`, `row r: knots are not strictly increasing at j`, `row r: value j is not
+    finite`, `dtype must be float64 or float32` (NotImplementedError for a complex one)."""
+    _destroy = 'wfk_curve_rows_plan_destroy'
+
+    def __init__(self, xp_rows, fp_rows, n: int, batch=None, left=None, right=None, dtype=np.float64):
+        (self.knot_ptr, self.xp, self.fp, self.left, self.right, self.n,
+         self.dtype) = curve_rows_arguments(xp_rows, fp_rows, left, right, batch, n, dtype)
+        self.batch = len(self.knot_ptr) - 1
+        self.knots = np.diff(self.knot_ptr)
+        check(lib().wfk_curve_rows_plan_create(self.n, self.batch, _KIND_OF[self.dtype], self.knot_ptr.ctypes.data,
+                                               self.xp.ctypes.data, self.fp.ctypes.data, self.left.ctypes.data,
+                                               self.right.ctypes.data, C.byref(self._h)))
+        self.spans = int(lib().wfk_curve_rows_spans(self._h))
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, counts_ptr=None, stream=0):
+        """counts_ptr: None, or batch * 3 int64 on the device, overwritten with [below, above, nan] per row"""
+        check(lib().wfk_curve_rows_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, counts_ptr, stream))
+
+    def kernel_name(self, counts: bool = False) -> str:
+        return lib().wfk_curve_rows_kernel_name(self._h, 1 if counts else 0).decode()
 
 
 class ExtractRowsPlan(_Handle):

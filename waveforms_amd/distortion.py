@@ -1380,6 +1380,111 @@ def dac_codes_rows(sig, gain, offset=0.0, bits=16, shift=0, interleave=1, return
         return (codes, c.download((batch, 3), np.int64)) if return_counts else codes
 
 
+class CurveStage:
+    """Device-resident calibration curve over sample VALUES for `batch` rows of `n` samples (build once, apply many
+    times): a flux pulse programmed in its physical unit (detuning, flux) to volts through the line's measured
+    monotone curve, an amplifier's compression table, a DAC's INL table.  Row r has knots `xp_rows[r]` (finite,
+    strictly increasing, 2 .. `_engine.CURVE_MAX_KNOTS` of them; rows may differ in number) and values `fp_rows[r]`
+    (finite); a sample below the first / above the last knot becomes `left[r]` / `right[r]` (any float, NaN too;
+    default: the row's first / last value), a NaN sample stays that NaN.  In float64 (a float32 sample is widened
+    first, the result rounded once), difference, product and sum each rounded (no fused multiply-add):
+        y[r, i] = np.interp(x[r, i], xp_rows[r], fp_rows[r], left[r], right[r])           -- bit for bit.
+    `xp_rows` / `fp_rows`: a list of 1-D arrays, a 2-D array, or one 1-D pair shared by `batch` rows; `left` /
+    `right`: None, a scalar (every row) or one value per row.  `.batch`, `.n`, `.knots` (the knots per row).  An
+    optional (batch, 3) int64 counts tensor is OVERWRITTEN by every apply with [below, above, nan] per row: how many
+    samples left the measured range.
+
+        st = CurveStage.inverse(volts, detuning, n)             # measured f(V), wanted V(f): one curve per line
+        st.apply_torch(x, out=x)                                # in place (or out of place), on torch's current stream
+    """
+
+    def __init__(self, xp_rows, fp_rows, n: int, batch=None, left=None, right=None, dtype=np.float64):
+        self.plan = _engine.CurveRowsPlan(xp_rows, fp_rows, n, batch, left, right, dtype)
+        p = self.plan
+        self.n, self.batch, self.dtype, self.knots = p.n, p.batch, p.dtype, p.knots
+        self.left, self.right = p.left, p.right
+
+    @staticmethod
+    def inverse_rows(xp_rows, fp_rows):
+        """the curves with the roles swapped -- knots `fp`, values `xp` -- rows whose `fp` descends reversed, so that
+        the new knots ascend; ValueError names a row whose `fp` is not strictly monotone.  -> (xp_rows, fp_rows), lists"""
+        xs, fs = _engine._curve_rows_list('xp', xp_rows), _engine._curve_rows_list('fp', fp_rows)
+        if len(xs) != len(fs):
+            raise ValueError(f'{len(xs)} rows of xp and {len(fs)} rows of fp')
+        new_x, new_f = [], []
+        for r, (x, f) in enumerate(zip(xs, fs)):
+            if len(x) != len(f):
+                raise ValueError(f'row {r}: {len(x)} knots and {len(f)} values')
+            up, down = np.all(f[1:] > f[:-1]), np.all(f[1:] < f[:-1])
+            if len(f) < 2 or not (up or down):
+                raise ValueError(f'row {r}: values are not strictly monotone')
+            new_x.append(f.copy() if up else f[::-1].copy())
+            new_f.append(x.copy() if up else x[::-1].copy())
+        return new_x, new_f
+
+    @classmethod
+    def inverse(cls, xp_rows, fp_rows, n: int, **kw):
+        """the stage of the INVERSE curves: f(V) was measured at the points `xp_rows` with the results `fp_rows`, and
+        V(f) is what the line needs.  Rows whose `fp_rows` descend are reversed; a row that is not strictly monotone is
+        refused (ValueError, the row named).  Host work only, then the constructor's."""
+        new_x, new_f = cls.inverse_rows(xp_rows, fp_rows)
+        return cls(new_x, new_f, n, **kw)
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, counts_ptr=None, stream=0):
+        self.plan.apply(in_ptr, in_stride, out_ptr, out_stride, counts_ptr, stream)
+
+    def kernel_name(self, counts: bool = False) -> str:
+        return self.plan.kernel_name(counts)
+
+    def apply_torch(self, x, out=None, counts=None):
+        """x, out: (batch, >= n) row-contiguous device tensors of the stage's dtype (rows may be windows of a wider
+        tensor; out None: allocated; `out is x`, or the same rows: in place); counts: None or a contiguous (batch, 3)
+        int64 device tensor, overwritten.  Out of place the rows of `out` may share no memory with the rows of `x`,
+        `counts` with neither (ValueError).  Asynchronous on torch's current stream.  -> out[:, :n]"""
+        import torch
+        tdt = _rows.torch_dtype(self.dtype)
+        x0, xs = _rows.check_rows(x, self.batch, self.n, tdt,
+                                  'expected x: (batch, >=n) row-contiguous device tensor of the stage dtype')
+        if out is None:
+            out = torch.empty((self.batch, self.n), dtype=tdt, device=x.device)
+        y0, ys = _rows.check_rows(out, self.batch, self.n, tdt,
+                                  'expected out: (batch, >=n) row-contiguous device tensor of the stage dtype')
+        c0 = _rows.check_state(counts, (self.batch, 3), 'expected counts: contiguous (batch, 3) int64 device tensor',
+                               dtype=np.int64)
+        es = self.dtype.itemsize
+        xr, yr = (x0, xs, self.batch, self.n, es), (y0, ys, self.batch, self.n, es)
+        if not (x0 == y0 and xs == ys) and not _rows.rows_disjoint(xr, yr):
+            raise ValueError('curve stage: out overlaps x without being x')
+        if not _rows.report_disjoint(c0, self.batch, 3, xr, yr):
+            raise ValueError('curve stage: counts overlaps x / out')
+        self.apply(x0, xs, y0, ys, c0, torch.cuda.current_stream(x.device).cuda_stream)
+        return out[:, :self.n]
+
+    def close(self):
+        self.plan.close()
+
+
+def interp_rows(sig, xp_rows, fp_rows, left=None, right=None, return_counts=False):
+    """np.interp(sig[r], xp_rows[r], fp_rows[r], left[r], right[r]) for every row of a 2-D real `sig`, all rows in one
+    launch (see `CurveStage`): NumPy in, NumPy out.  float32 rows stay float32, anything else (integers too) is read as
+    float64.  `xp_rows` / `fp_rows`: one curve per row, or one 1-D pair for every row.  `return_counts`: -> (y, counts),
+    counts the (rows, 3) int64 [below, above, nan] per row.  ValueError before any device work: sig not 2-D, what
+    `CurveStage` refuses.  NotImplementedError: complex rows.  A `sig` without samples is answered without a device."""
+    sig2 = _rows_signal_f32('interp_rows', sig)
+    batch, n = sig2.shape
+    _engine.curve_rows_arguments(xp_rows, fp_rows, left, right, batch, n, sig2.dtype)   # every refusal comes first
+    if n == 0:
+        y, counts = np.zeros((batch, 0), dtype=sig2.dtype), np.zeros((batch, 3), dtype=np.int64)
+        return (y, counts) if return_counts else y
+    with _engine.CurveRowsPlan(xp_rows, fp_rows, n, batch, left, right, sig2.dtype) as plan, \
+            _engine.DeviceBuffer(sig2.nbytes) as x, _engine.DeviceBuffer(batch * 24) as c:
+        x.upload(sig2)
+        plan.apply(x.ptr, n, x.ptr, n, c.ptr if return_counts else None)          # in place
+        _engine.sync()
+        y = x.download(sig2.shape, sig2.dtype)
+        return (y, c.download((batch, 3), np.int64)) if return_counts else y
+
+
 class MarkerStage:
     """Device-resident gate markers for `batch` rows of `n` samples (build once, apply many times): the marker line
     that opens a switch or blanks an amplifier around every pulse, from the IDEAL gate rows (exact zeros outside the
