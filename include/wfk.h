@@ -672,6 +672,41 @@ int wfk_demod_apply(wfk_demod_plan* p, const void* traces_dev, int64_t n_shots, 
 const char* wfk_demod_kernel_name(const wfk_demod_plan* p, int64_t n_shots);
 int wfk_demod_plan_destroy(wfk_demod_plan* p);
 
+/* -- per-step shot sums of readout traces: the reduction over shots ------------------------------ */
+/* A block of n_shots traces (rows of >= n_points samples of in_kind, row stride trace_stride elements) taken while a
+ * sequence cycled through `steps` steps, `first` shots of the run before it: shot s of the block belongs to step
+ * (first + s) mod steps; a block may start and end anywhere in a cycle, n_shots < steps and n_shots = 0 are fine.
+ * Per step g and column c, over the block's shots of that step:  sum[g, c] = SUM x[s, c],  sumsq[g, c] = SUM x[s, c]^2
+ * -- int64 for WFK_IN_I16 codes (exact), fp64 for WFK_IN_F32 / WFK_IN_F64 (a float32 sample is widened first, so its
+ * square is exact).  sum and sumsq (NULL: none) are the caller's, `steps` rows of n_points 8-byte elements, row
+ * strides in elements.  accumulate = 0 OVERWRITES every element of both (a step without a shot in the block gets 0);
+ * accumulate != 0 ADDS the block's sums to what is there -- the block's sum is formed first, then added with one add
+ * per element -- and leaves a step without a shot in the block bit for bit as it was: the way to carry sums across
+ * the blocks a digitiser delivers.  No atomics: the order of the float additions is a fixed function of (n_shots,
+ * steps, n_points, first mod steps, in_kind), so two applies of one call agree to the bit; a NaN or Inf in a sample
+ * reaches its own (step, column) only.
+ * wfk_avg_apply() enqueues one kernel (avg_tile) or two (avg_tile into the plan's workspace, then avg_reduce: a block
+ * whose column tiles and steps alone do not fill the chip splits the shots of a step over wfk_avg_splits() workgroups)
+ * on `hip_stream`, and that is all it does to the device (as wfk_curve_rows_apply: it may be called while the stream
+ * is being captured, and every replay reads an accumulate base anew).  The plan owns that workspace, taken at
+ * creation (8 to 34 MB by in_kind): one plan per concurrent stream.
+ * WFK_EINVAL: n_points < 1, steps < 1, a stride < n_points, n_shots < 0, first < 0, null or misaligned rows, sum or
+ * sumsq overlapping the traces or each other.  No device: WFK_EHIP. */
+typedef struct wfk_avg_plan wfk_avg_plan;
+int wfk_avg_plan_create(int64_t n_points, int64_t steps, int in_kind /* WFK_IN_F64|F32|I16 */, wfk_avg_plan** out);
+int wfk_avg_apply(wfk_avg_plan* plan, const void* traces_dev, int64_t n_shots, int64_t trace_stride, int64_t first,
+                  void* sum_dev, int64_t sum_stride, void* sumsq_dev /* NULL: none */, int64_t sumsq_stride,
+                  int accumulate, void* hip_stream);
+/* the workgroups that share the shots of one step for a block of n_shots (1: avg_tile writes the outputs itself): with
+ * T = ceil(n_points / (256 * 16 / sizeof(sample))) column tiles, min(1024 / T / steps, ceil(n_shots / steps) / 32),
+ * at least 1; the environment's WFK_AVG_SPLITS = k, read at creation, asks for k in place of the second term (an
+ * experiment's switch).  0 for NULL */
+int64_t wfk_avg_splits(const wfk_avg_plan* plan, int64_t n_shots, int64_t first);
+/* "avg_tile<short|float|double>" or "avg_tile<...,sumsq>", with " + avg_reduce" when a block of n_shots splits; the
+ * string lives until the next call on this plan; "" for NULL */
+const char* wfk_avg_kernel_name(const wfk_avg_plan* plan, int64_t n_shots, int with_sumsq);
+int wfk_avg_plan_destroy(wfk_avg_plan* plan);   /* NULL is fine */
+
 /* -- boxcar integral read off at probe times (reference distortion.py:349-366: the tail of phase_curve) ----- */
 /* out[r, q] = np.interp(t_q, tlist, conv[r]) with conv[r, i] = gain * sum_{m < pp} y[r, i + c - m] (y zero outside
  * [0, n)) -- np.convolve(s, [ones(pp), zeros(sp)], 'same') for c = (pp + sp - 1) / 2 -- for every row of y

@@ -175,6 +175,13 @@ def lib():
         l.wfk_demod_kernel_name.argtypes = [VP, I64]
         l.wfk_demod_kernel_name.restype = C.c_char_p
         l.wfk_demod_plan_destroy.argtypes = [VP]
+        l.wfk_avg_plan_create.argtypes = [I64, I64, C.c_int, P(VP)]
+        l.wfk_avg_apply.argtypes = [VP, VP, I64, I64, I64, VP, I64, VP, I64, C.c_int, VP]
+        l.wfk_avg_splits.argtypes = [VP, I64, I64]
+        l.wfk_avg_splits.restype = I64
+        l.wfk_avg_kernel_name.argtypes = [VP, I64, C.c_int]
+        l.wfk_avg_kernel_name.restype = C.c_char_p
+        l.wfk_avg_plan_destroy.argtypes = [VP]
         l.wfk_boxprobe_brackets.argtypes = [VP, I64, VP, I64, VP, VP, VP]
         l.wfk_boxprobe_plan_create.argtypes = [VP, I64, VP, I32, I64, I64, C.c_double, P(VP)]
         l.wfk_boxprobe_apply.argtypes = [VP, VP, I64, I64, VP, I64, VP]
@@ -1164,6 +1171,42 @@ class DemodPlan(_Handle):
 
     def kernel_name(self, n_shots: int) -> str:
         return lib().wfk_demod_kernel_name(self._h, n_shots).decode()
+
+
+def avg_arguments(n_points, steps, dtype):
+    """the arguments of an AvgPlan, checked on the host -> (n_points, steps, dtype).  ValueError: `n_points >= 1`,
+    `steps >= 1`, a trace dtype that is not float64, float32 or int16.  Needs no device."""
+    n_points, steps, dtype = int(n_points), int(steps), np.dtype(dtype)
+    if n_points < 1:
+        raise ValueError('trace averager: n_points >= 1, got %d' % n_points)
+    if steps < 1:
+        raise ValueError('trace averager: steps >= 1, got %d' % steps)
+    if dtype not in DEMOD_IN_KIND:
+        raise ValueError('trace dtype must be float64, float32 or int16, got %s' % dtype)
+    return n_points, steps, dtype
+
+
+class AvgPlan(_Handle):
+    """sum[g, c] = the sum over the block's shots s with (first + s) mod steps == g of x[s, c], and the same of the
+    squares: real traces (shots, >= n_points) of float64 / float32 / int16 into (steps, n_points) int64 (int16 codes,
+    exact) or float64 sums on the device (wfk_avg_plan_create); the plan owns the workspace of a split launch."""
+    _destroy = 'wfk_avg_plan_destroy'
+
+    def __init__(self, n_points: int, steps: int = 1, dtype=np.int16):
+        self.n, self.steps, self.dtype = avg_arguments(n_points, steps, dtype)
+        self.sum_dtype = np.dtype(np.int64 if self.dtype == np.dtype(np.int16) else np.float64)
+        check(lib().wfk_avg_plan_create(self.n, self.steps, DEMOD_IN_KIND[self.dtype], C.byref(self._h)))
+
+    def apply(self, x_ptr, n_shots, x_stride, first, sum_ptr, sum_stride, sumsq_ptr=None, sumsq_stride=0,
+              accumulate=False, stream=0):
+        check(lib().wfk_avg_apply(self._h, x_ptr, n_shots, x_stride, first, sum_ptr, sum_stride, sumsq_ptr,
+                                  sumsq_stride, 1 if accumulate else 0, stream))
+
+    def splits(self, n_shots: int, first: int = 0) -> int:
+        return int(lib().wfk_avg_splits(self._h, n_shots, first))
+
+    def kernel_name(self, n_shots: int, sumsq: bool = True) -> str:
+        return lib().wfk_avg_kernel_name(self._h, n_shots, 1 if sumsq else 0).decode()
 
 
 def probe_brackets(tlist, t):

@@ -24,7 +24,7 @@ import scipy.sparse as sp
 
 from .distortion import shift
 
-__all__ = ['freeze', 'getFTMatrix', 'shift', 'Demodulator']
+__all__ = ['freeze', 'getFTMatrix', 'shift', 'Demodulator', 'TraceAverager', 'average_traces']
 
 
 def freeze(x):
@@ -159,3 +159,157 @@ class Demodulator:
     def close(self):
         if self.plan is not None:
             self.plan.close()
+
+
+class TraceAverager:
+    """Per-step sums of digitiser traces on the device (csrc/wfk_avg.hip): the reduction over SHOTS that goes with the
+    demodulator's reduction over time.  The shots of a run cycle through `steps` steps (a delay sweep, the points of a
+    Rabi scan); shot s of a block that `first` shots precede belongs to step (first + s) mod steps.  An apply forms,
+    per step and sample, the sum of the block's traces and -- `sumsq` -- of their squares: int64 for int16 codes
+    (exact), float64 for float32 / float64 traces (fixed order of additions: two applies agree to the bit).
+
+        av = TraceAverager(N, steps=10, dtype=np.int16)
+        for k, block in enumerate(blocks):                       # blocks of any length, cut anywhere in a cycle
+            av.apply_torch(block, total, total_sq, first=shots_so_far, accumulate=k > 0)
+        mean, var = av.finish_torch(total, total_sq, av.counts(shots_so_far))
+
+    Building one needs no GPU (the device plan is made by the first apply); ValueError: numOfPoints < 1, steps < 1,
+    a dtype that is not float64, float32 or int16."""
+
+    def __init__(self, numOfPoints, steps=1, dtype=np.int16, sumsq=True):
+        from . import _engine
+        self.n, self.steps, self.dtype = _engine.avg_arguments(numOfPoints, steps, dtype)
+        self.sum_dtype = np.dtype(np.int64 if self.dtype == np.dtype(np.int16) else np.float64)
+        self.sumsq = bool(sumsq)
+        self._plan = None
+
+    @property
+    def plan(self):
+        if self._plan is None:
+            from . import _engine
+            self._plan = _engine.AvgPlan(self.n, self.steps, self.dtype)
+        return self._plan
+
+    def kernel_name(self, shots: int, sumsq=None) -> str:
+        """Device kernel(s) an apply on `shots` traces runs (a split launch adds the reduce)."""
+        return self.plan.kernel_name(int(shots), self.sumsq if sumsq is None else bool(sumsq))
+
+    def splits(self, shots: int, first: int = 0) -> int:
+        """The workgroups that share the shots of one step for a block of `shots` (1: no workspace, no reduce)."""
+        return self.plan.splits(int(shots), int(first) % self.steps)
+
+    def counts(self, shots: int, first: int = 0) -> np.ndarray:
+        """(steps,) int64: how many of `shots` consecutive shots, `first` before them, belong to each step.  Host
+        arithmetic, no device; with first = 0 and the run's total it is what `finish_torch` divides by."""
+        shots, first = int(shots), int(first)
+        if shots < 0 or first < 0:
+            raise ValueError('shots and first must not be negative')
+        whole, rest = divmod(shots, self.steps)
+        c = np.full(self.steps, whole, dtype=np.int64)
+        c[(first % self.steps + np.arange(min(rest, self.steps))) % self.steps] += 1
+        return c
+
+    def check(self, traces, sum, sumsq=None, first=0, device=True):
+        """What `apply_torch` holds its tensors to, on their metadata alone (`device=False` leaves the "is a device
+        tensor" clause out) -> ((ptr, stride) of traces, of sum, of sumsq or (None, 0)).  ValueError: traces that are
+        not (shots, >= N) rows of the plan dtype with a row stride >= N; sum / sumsq that are not (steps, N) rows of
+        int64 (int16 traces) or float64 with a row stride >= N on the traces' device; a negative first; sum or sumsq
+        overlapping the traces or each other."""
+        from . import _rows
+        if int(first) < 0:
+            raise ValueError('first must not be negative, got %d' % first)
+        if traces.is_complex():
+            raise ValueError('complex traces are not supported')
+        x = _rows.check_rows(
+            traces, None, self.n, _rows.torch_dtype(self.dtype),
+            'traces must be a (shots, >= %d) row-contiguous device tensor of %s' % (self.n, self.dtype), device=device)
+        shots = traces.shape[0]
+        sides = [('traces', x + (shots, self.n, self.dtype.itemsize))] if shots else []
+        out = []
+        for name, t in (('sum', sum), ('sumsq', sumsq)):
+            if t is None:
+                out.append((None, 0))
+                continue
+            message = '%s must be a (%d, %d) row-contiguous %s tensor on the traces\' device' % (
+                name, self.steps, self.n, self.sum_dtype)
+            side = _rows.check_rows(t, self.steps, self.n, _rows.torch_dtype(self.sum_dtype), message, exact=True,
+                                    device=device)
+            if t.device != traces.device:
+                raise ValueError(message)
+            for other, rows in sides:
+                if not _rows.rows_disjoint(side + (self.steps, self.n, 8), rows):
+                    raise ValueError('trace averager is out of place: %s overlaps %s' % (name, other))
+            sides.append((name, side + (self.steps, self.n, 8)))
+            out.append(side)
+        return x, out[0], out[1]
+
+    def apply_torch(self, traces, sum=None, sumsq=None, first=0, accumulate=False):
+        """traces: (shots, >= N) row-contiguous device tensor of the plan dtype (windows x[:, w0:w0 + N] work without
+        a copy; shots = 0 and shots < steps are fine).  sum / sumsq: (steps, N) int64 (int16 traces) or float64, any row
+        stride >= N; allocated when None (sumsq only if the averager was built with sumsq=True), which needs
+        accumulate=False.  accumulate=False overwrites them (a step without a shot in the block gets 0);
+        accumulate=True adds the block's sums to them and leaves a step without a shot bit for bit as it was.
+        Asynchronous on torch's current stream.  -> sum, or (sum, sumsq)."""
+        import torch
+        from . import _rows
+        if accumulate and (sum is None or (sumsq is None and self.sumsq)):
+            raise ValueError('accumulate=True needs the tensors to add to')
+        out_dtype = _rows.torch_dtype(self.sum_dtype)
+        if sum is None:
+            sum = torch.empty((self.steps, self.n), dtype=out_dtype, device=traces.device)
+        if sumsq is None and self.sumsq:
+            sumsq = torch.empty((self.steps, self.n), dtype=out_dtype, device=traces.device)
+        (x_ptr, x_stride), (s_ptr, s_stride), (q_ptr, q_stride) = self.check(traces, sum, sumsq, first)
+        stream = torch.cuda.current_stream(traces.device).cuda_stream
+        self.plan.apply(x_ptr, traces.shape[0], x_stride, int(first) % self.steps, s_ptr, s_stride, q_ptr, q_stride,
+                        accumulate, stream)
+        return sum if sumsq is None else (sum, sumsq)
+
+    def finish_torch(self, sum, sumsq, counts):
+        """(mean, var) float64 (steps, N) from the sums and the shots per step (`counts(total)`): mean = sum / count,
+        var = sumsq / count - mean^2 (the population variance; None without sumsq), NaN where a step has no shot.
+        Plain torch ops on steps x N elements."""
+        import torch
+        cnt = torch.as_tensor(np.asarray(counts, dtype=np.float64), device=sum.device).reshape(self.steps, 1)
+        mean = sum.to(torch.float64) / cnt
+        var = None if sumsq is None else sumsq.to(torch.float64) / cnt - mean * mean
+        return mean, var
+
+    def close(self):
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+
+
+def average_traces(signal, steps=1, return_var=False):
+    """NumPy in, NumPy out: the mean trace per step of a real (shots, N) signal whose shots cycle through `steps`
+    steps from step 0 -> (steps, N) float64 mean [, var with return_var].  int16 stays int16 on the device (exact
+    sums), float32 stays float32, narrower integers are read as int16 and anything else that fits as float64.  A step
+    without a shot is NaN; no shots or no samples are answered without a device."""
+    import torch
+    signal = np.asarray(signal)
+    if np.iscomplexobj(signal):
+        raise ValueError('complex traces are not supported')
+    if signal.ndim != 2:
+        raise ValueError('signal must have shape (shots, N), got %s' % (signal.shape,))
+    if int(steps) < 1:
+        raise ValueError('steps >= 1, got %d' % steps)
+    steps = int(steps)
+    shots, n = signal.shape
+    if shots == 0 or n == 0:
+        nan = np.full((steps, n), np.nan)
+        return (nan, nan.copy()) if return_var else nan
+    dtype = next((d for d in (np.int16, np.float32, np.float64)
+                  if signal.dtype == d or (d != np.float32 and np.can_cast(signal.dtype, d, 'safe'))), None)
+    if dtype is None:
+        raise ValueError('a %s signal fits neither int16 nor float64' % signal.dtype)
+    av = TraceAverager(n, steps, dtype, sumsq=return_var)
+    try:
+        dev = torch.device('cuda', torch.cuda.current_device())
+        x = torch.from_numpy(np.ascontiguousarray(signal, dtype=dtype)).to(dev)
+        res = av.apply_torch(x)
+        total, total_sq = res if return_var else (res, None)
+        mean, var = av.finish_torch(total, total_sq, av.counts(shots))
+        return (mean.cpu().numpy(), var.cpu().numpy()) if return_var else mean.cpu().numpy()
+    finally:
+        av.close()
