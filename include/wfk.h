@@ -707,6 +707,55 @@ int64_t wfk_avg_splits(const wfk_avg_plan* plan, int64_t n_shots, int64_t first)
 const char* wfk_avg_kernel_name(const wfk_avg_plan* plan, int64_t n_shots, int with_sumsq);
 int wfk_avg_plan_destroy(wfk_avg_plan* plan);   /* NULL is fine */
 
+/* -- IQ points to qubit states and per-step counts: the link behind the demodulator -------------- */
+/* points: n_shots rows of n_tones complex128 IQ points (the demodulator's output as it is; row stride points_stride
+ * complex elements, 16-byte aligned); centres: n_tones x n_states complex128 on the host, 2 <= n_states <= 8,
+ * 1 <= n_tones <= 1024; a tone with fewer states pads its row with NaN centres.  Per shot s, tone j, state k, in
+ * double, every operation rounded on its own (two subtractions, two products, one addition, no fused multiply-add --
+ * the bits of NumPy's dr * dr + di * di):
+ *   dr = re(p) - re(c),  di = im(p) - im(c),  d2 = dr * dr + di * di
+ * and walking k = 0 .. n_states - 1 from best = +inf, k wins when d2 < best (strict): ties go to the lowest k, a NaN
+ * or infinite d2 (a NaN centre, a NaN or Inf point, a distance that overflows) never wins, a point no centre wins
+ * gets label 255 ("invalid"), -0.0 behaves as 0.0.  With b = 1 for n_states = 2, 2 for <= 4, 3 for <= 8 bits per tone,
+ * the outputs -- all the caller's, NULL for each one not wanted, at least one -- are
+ *   labels  n_shots rows of n_tones uint8, row stride labels_stride
+ *   words   n_shots int64: tone j in bits [j b, (j + 1) b); -1 when a tone of the shot is invalid; n_tones * b <= 62
+ *   counts  steps x n_tones x (n_states + 1) int64, contiguous: counts[g, j, k] = the block's shots of step g whose
+ *           tone j got state k, column n_states the invalid ones
+ *   joint   steps x (2^(n_tones b) + 1) int64, contiguous: bin w = the shots of step g whose word is w, the last bin
+ *           those with word -1; codes no state produces stay 0; n_tones * b <= 16
+ * Shot s of the block belongs to step (first + s) mod steps, `first` shots of the run before it (any int64 >= 0): a
+ * block may start and end anywhere in a cycle, n_shots < steps and n_shots = 0 are fine.  accumulate = 0 OVERWRITES
+ * every element of counts and joint (a step without a shot gets 0; they are zeroed by a kernel on the stream, then
+ * added to); accumulate != 0 ADDS the block's counts to what is there: the way to carry counts across the blocks a
+ * digitiser delivers.  All sums are integers (64-bit atomic adds): the tables do not depend on the order of arrival;
+ * labels and words are a pure function of the inputs.
+ * wfk_states_apply() enqueues at most two zeroing kernels and one kernel (states_block) on `hip_stream`, and that is
+ * all it does to the device (as wfk_curve_rows_apply: it may be called while the stream is being captured, and every
+ * replay reads an accumulate base anew).  The plan owns its table of centres and nothing else, so it may serve several
+ * streams.
+ * WFK_EINVAL, before any device work: n_tones outside [1, 1024], n_states outside [2, 8], steps < 1, steps * n_tones *
+ * (n_states + 1) above 2^31 - 1, a tone without a finite centre (the tone is named); n_shots < 0, first < 0, no output
+ * at all, words with n_tones * b > 62, joint with n_tones * b > 16 or more than 2^31 - 1 entries, a stride below
+ * n_tones, null or misaligned rows, an output that overlaps the points or another output.  No device: WFK_EHIP. */
+#define WFK_STATES_MAX_TONES 1024
+#define WFK_STATES_MAX_STATES 8
+typedef struct wfk_states_plan wfk_states_plan;
+int wfk_states_plan_create(const double* centres_host /* n_tones * n_states complex128, interleaved */,
+                           int32_t n_tones, int32_t n_states, int64_t steps, wfk_states_plan** out);
+int wfk_states_apply(wfk_states_plan* plan, const void* points_dev, int64_t n_shots, int64_t points_stride,
+                     int64_t first, uint8_t* labels_dev /* or NULL */, int64_t labels_stride,
+                     int64_t* words_dev /* or NULL */, int64_t* counts_dev /* or NULL */,
+                     int64_t* joint_dev /* or NULL */, int accumulate, void* hip_stream);
+/* "states_block<KT> tile=T counts:lds|global joint:lds|global|none": KT = n_states rounded up to 2, 4 or 8; T the
+ * points of a workgroup's block for n_shots (4096, halved down to 1024 while the launch has fewer than 1024
+ * workgroups); where each table is counted -- in a per-workgroup LDS histogram when it has at most 4096 entries, by
+ * global atomic adds otherwise, a function of the plan's shape alone; the environment's WFK_STATES_COUNTERS = global,
+ * read at creation, takes every table to global memory (= lds asks for the rule; an experiment's and the tests'
+ * switch).  The string lives until the next call on this plan; "" for NULL */
+const char* wfk_states_kernel_name(const wfk_states_plan* plan, int64_t n_shots);
+int wfk_states_plan_destroy(wfk_states_plan* plan);   /* NULL is fine */
+
 /* -- boxcar integral read off at probe times (reference distortion.py:349-366: the tail of phase_curve) ----- */
 /* out[r, q] = np.interp(t_q, tlist, conv[r]) with conv[r, i] = gain * sum_{m < pp} y[r, i + c - m] (y zero outside
  * [0, n)) -- np.convolve(s, [ones(pp), zeros(sp)], 'same') for c = (pp + sp - 1) / 2 -- for every row of y

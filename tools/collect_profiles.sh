@@ -16,13 +16,14 @@ OUT=gpurun_out/prof_${TAG}_${WL}
 mkdir -p "$OUT" gpurun_out/profiles
 export TMPDIR=/tmp
 ARGS="bench.py --workload $WL --steps 5 --warmup 1 --no-cpu-baseline --no-also"   # (--no-also: the c2 / c3 / c4 legs of the default line run the same kernel symbols; each is profiled by its own workload)
-# stage benches outside bench.py (their own scripts): iir, readout, multitone, demod, avg, dac, marker
+# stage benches outside bench.py (their own scripts): iir, readout, multitone, demod, avg, states, dac, marker
 case "$WL" in
   iir) ARGS="tools/iir_bench.py" ;;
   readout) ARGS="tools/readout_bench.py" ;;
   multitone) ARGS="tools/multitone_bench.py 10" ;;
   demod) ARGS="tools/demod_bench.py --no-baseline --reps 5" ;;
   avg) ARGS="tools/avg_bench.py --cases A1,A2 --no-baseline --reps 5" ;;
+  states) ARGS="tools/states_bench.py --cases S1,S2 --no-baseline --reps 5" ;;
   dac) ARGS="tools/dac_rows_bench.py --cases D2 --reps 5" ;;
   marker) ARGS="tools/marker_rows_bench.py --cases M1 --dtypes f64 --reps 5 --chain-reps 1" ;;
   awg_f32) ARGS="bench.py --workload awg --dtype f32 --steps 5 --warmup 1 --no-cpu-baseline --no-also" ;;

@@ -182,6 +182,11 @@ def lib():
         l.wfk_avg_kernel_name.argtypes = [VP, I64, C.c_int]
         l.wfk_avg_kernel_name.restype = C.c_char_p
         l.wfk_avg_plan_destroy.argtypes = [VP]
+        l.wfk_states_plan_create.argtypes = [VP, I32, I32, I64, P(VP)]
+        l.wfk_states_apply.argtypes = [VP, VP, I64, I64, I64, VP, I64, VP, VP, VP, C.c_int, VP]
+        l.wfk_states_kernel_name.argtypes = [VP, I64]
+        l.wfk_states_kernel_name.restype = C.c_char_p
+        l.wfk_states_plan_destroy.argtypes = [VP]
         l.wfk_boxprobe_brackets.argtypes = [VP, I64, VP, I64, VP, VP, VP]
         l.wfk_boxprobe_plan_create.argtypes = [VP, I64, VP, I32, I64, I64, C.c_double, P(VP)]
         l.wfk_boxprobe_apply.argtypes = [VP, VP, I64, I64, VP, I64, VP]
@@ -1207,6 +1212,62 @@ class AvgPlan(_Handle):
 
     def kernel_name(self, n_shots: int, sumsq: bool = True) -> str:
         return lib().wfk_avg_kernel_name(self._h, n_shots, 1 if sumsq else 0).decode()
+
+
+STATES_MAX_TONES, STATES_MAX_STATES = 1024, 8      # WFK_STATES_MAX_TONES / WFK_STATES_MAX_STATES
+
+
+def states_bits(n_states: int) -> int:
+    """bits a tone takes in a shot's word: 1 for two states, 2 up to four, 3 up to eight"""
+    return 1 if n_states <= 2 else 2 if n_states <= 4 else 3
+
+
+def states_arguments(centres, steps=1):
+    """the arguments of a StatesPlan, checked on the host -> (centres: a C-contiguous (n_tones, n_states) complex128
+    array, steps).  ValueError: centres that are not 2-D, n_states outside [2, 8], n_tones outside [1, 1024],
+    `steps >= 1`, steps * n_tones * (n_states + 1) above 2^31 - 1, a tone without a finite centre (NaN centres pad a
+    tone with fewer states; the tone is named).  Needs no device."""
+    centres = np.asarray(centres)
+    if centres.ndim != 2:
+        raise ValueError('state discriminator: centres must be (n_tones, n_states), got shape %s' % (centres.shape,))
+    centres = np.ascontiguousarray(centres, dtype=np.complex128)
+    nf, k = centres.shape
+    steps = int(steps)
+    if not 2 <= k <= STATES_MAX_STATES:
+        raise ValueError('state discriminator: n_states must lie in [2, %d], got %d' % (STATES_MAX_STATES, k))
+    if not 1 <= nf <= STATES_MAX_TONES:
+        raise ValueError('state discriminator: n_tones must lie in [1, %d], got %d' % (STATES_MAX_TONES, nf))
+    if steps < 1:
+        raise ValueError('state discriminator: steps >= 1, got %d' % steps)
+    if steps * nf * (k + 1) > 2**31 - 1:
+        raise ValueError('state discriminator: steps * n_tones * (n_states + 1) exceeds 2^31 - 1')
+    bad = np.flatnonzero(~(np.isfinite(centres.real) & np.isfinite(centres.imag)).any(axis=1))
+    if len(bad):
+        raise ValueError('tone %d: no finite centre' % int(bad[0]))
+    return centres, steps
+
+
+class StatesPlan(_Handle):
+    """label[s, j] = the nearest of tone j's centres to the IQ point x[s, j] (complex128 rows, squared distance in
+    double without a fused multiply-add, ties to the lowest state, 255 where no centre wins), and from the labels the
+    packed words, the per-step counts (steps, n_tones, n_states + 1) and the joint histogram (steps, 2^(n_tones bits)
+    + 1), all int64 (wfk_states_plan_create); the plan owns the table of centres."""
+    _destroy = 'wfk_states_plan_destroy'
+
+    def __init__(self, centres, steps: int = 1):
+        self.centres, self.steps = states_arguments(centres, steps)
+        self.nf, self.k = self.centres.shape
+        self.bits = states_bits(self.k)
+        check(lib().wfk_states_plan_create(self.centres.ctypes.data, self.nf, self.k, self.steps, C.byref(self._h)))
+
+    def apply(self, x_ptr, n_shots, x_stride, first, labels_ptr=None, labels_stride=0, words_ptr=None,
+              counts_ptr=None, joint_ptr=None, accumulate=False, stream=0):
+        check(lib().wfk_states_apply(self._h, x_ptr, n_shots, x_stride, first, labels_ptr, labels_stride, words_ptr,
+                                     counts_ptr, joint_ptr, 1 if accumulate else 0, stream))
+
+    def kernel_name(self, n_shots: int) -> str:
+        """'states_block<KT> tile=T counts:lds|global joint:lds|global|none'"""
+        return lib().wfk_states_kernel_name(self._h, n_shots).decode()
 
 
 def probe_brackets(tlist, t):

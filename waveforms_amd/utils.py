@@ -24,7 +24,8 @@ import scipy.sparse as sp
 
 from .distortion import shift
 
-__all__ = ['freeze', 'getFTMatrix', 'shift', 'Demodulator', 'TraceAverager', 'average_traces']
+__all__ = ['freeze', 'getFTMatrix', 'shift', 'Demodulator', 'StateDiscriminator', 'classify_points', 'TraceAverager',
+           'average_traces']
 
 
 def freeze(x):
@@ -313,3 +314,198 @@ def average_traces(signal, steps=1, return_var=False):
         return (mean.cpu().numpy(), var.cpu().numpy()) if return_var else mean.cpu().numpy()
     finally:
         av.close()
+
+
+class StateDiscriminator:
+    """IQ points to qubit states and per-step counts on the device (csrc/wfk_states.hip): the link behind the
+    demodulator.  `centres` is (nf, K) complex, 2 <= K <= 8, 1 <= nf <= 1024; a tone with fewer states pads its row
+    with NaN.  A point takes the state of the nearest centre of its tone -- squared distance in double, every operation
+    rounded on its own, so NumPy's `dr * dr + di * di` gives the same bits; ties go to the lowest state; a NaN or
+    infinite distance never wins and a point no centre wins is labelled 255.  The shots of a run cycle through `steps`
+    steps: shot s of a block that `first` shots precede belongs to step (first + s) mod steps.
+
+        sd = StateDiscriminator.from_calibration(cal_iq, n_states=2, steps=10)
+        counts = torch.zeros((10, sd.nf, sd.n_states + 1), dtype=torch.int64, device='cuda')
+        for k, iq in enumerate(blocks):                          # blocks of any length, cut anywhere in a cycle
+            sd.apply_torch(iq, counts=counts, first=shots_so_far, accumulate=k > 0)
+        p = sd.probabilities(counts, sd.counts_of(shots_so_far))  # (steps, nf, K): p[:, j, 1] is P(1) of tone j
+
+    Building one needs no GPU (the device plan is made by the first apply); ValueError: centres that are not 2-D,
+    K < 2, K > 8, nf > 1024, steps < 1, a tone whose centres are all NaN."""
+
+    INVALID = 255
+
+    def __init__(self, centres, steps=1):
+        from . import _engine
+        self.centres, self.steps = _engine.states_arguments(centres, steps)
+        self.nf, self.n_states = self.centres.shape
+        self.bits = _engine.states_bits(self.n_states)
+        self.word_bits = self.nf * self.bits
+        self.joint_bins = 2 ** self.word_bits + 1 if self.word_bits <= 16 else None
+        self._plan = None
+
+    @classmethod
+    def from_calibration(cls, points, n_states, first=0, steps=1) -> 'StateDiscriminator':
+        """Centres from a calibration run whose shots cycle through the `n_states` prepared states: shot s (`first`
+        shots before it) was prepared in state (first + s) mod n_states, and centre[j, k] is the mean of tone j over
+        the shots of state k.  points: (shots, nf) complex, a tensor on any device or an array.  Plain torch ops on a
+        small problem.  `steps`: of the discriminator that is returned."""
+        import torch
+        n_states, first = int(n_states), int(first)
+        if n_states < 2:
+            raise ValueError('state discriminator: n_states must lie in [2, 8], got %d' % n_states)
+        if first < 0:
+            raise ValueError('first must not be negative, got %d' % first)
+        pts = torch.as_tensor(points)
+        if pts.dim() != 2 or not pts.is_complex():
+            raise ValueError('points must be (shots, nf) complex, got shape %s of %s' % (tuple(pts.shape), pts.dtype))
+        pts = pts.to(torch.complex128)
+        # the shots of state k are every n_states-th one from (k - first) mod n_states; a state without a shot gives NaN
+        means = [pts[(k - first) % n_states::n_states].mean(dim=0) for k in range(n_states)]
+        return cls(torch.stack(means, dim=1).cpu().numpy(), steps)
+
+    @property
+    def plan(self):
+        if self._plan is None:
+            from . import _engine
+            self._plan = _engine.StatesPlan(self.centres, self.steps)
+        return self._plan
+
+    def kernel_name(self, shots: int) -> str:
+        """The device kernel an apply on `shots` points runs, its block and where each table is counted."""
+        return self.plan.kernel_name(int(shots))
+
+    def counts_of(self, shots: int, first: int = 0) -> np.ndarray:
+        """(steps,) int64: how many of `shots` consecutive shots, `first` before them, belong to each step.  Host
+        arithmetic, no device; with first = 0 and the run's total it is what `probabilities` divides by."""
+        shots, first = int(shots), int(first)
+        if shots < 0 or first < 0:
+            raise ValueError('shots and first must not be negative')
+        whole, rest = divmod(shots, self.steps)
+        c = np.full(self.steps, whole, dtype=np.int64)
+        c[(first % self.steps + np.arange(min(rest, self.steps))) % self.steps] += 1
+        return c
+
+    def check(self, points, labels=None, words=None, counts=None, joint=None, first=0, device=True):
+        """What `apply_torch` holds its tensors to, on their metadata alone (`device=False` leaves the "is a device
+        tensor" clause out) -> ((ptr, stride) of points, (ptr, stride) of labels or (None, 0), the pointers of words,
+        counts and joint or None).  ValueError: points that are not (shots, >= nf) rows of complex128 with a row stride
+        >= nf; labels that are not (shots, nf) uint8 rows with a row stride >= nf; words that are not (shots,) int64
+        with unit stride, or asked for with nf * bits > 62; counts that are not a contiguous (steps, nf, K + 1) int64
+        tensor; joint that is not a contiguous (steps, 2^(nf bits) + 1) int64 tensor, or asked for with nf * bits >
+        16; an output on another device than the points; a negative first; no output at all; an output overlapping
+        the points or another output."""
+        import torch
+        from . import _rows
+        stage = 'state discriminator'
+        if int(first) < 0:
+            raise ValueError('first must not be negative, got %d' % first)
+        if labels is None and words is None and counts is None and joint is None:
+            raise ValueError('%s: no output' % stage)
+        x = _rows.check_rows(points, None, self.nf, torch.complex128,
+                             'points must be a (shots, >= %d) row-contiguous device tensor of complex128' % self.nf,
+                             device=device)
+        shots = points.shape[0]
+        sides = [('points', x + (shots, self.nf, 16))] if shots else []
+
+        def place(name, side, t, message, report=False):
+            if t.device != points.device:
+                raise ValueError(message)
+            for other, rows in sides:
+                if not (_rows.report_disjoint(side[0], side[2], side[1], rows) if report
+                        else _rows.rows_disjoint(side, rows)):
+                    raise ValueError('%s is out of place: %s overlaps %s' % (stage, name, other))
+            sides.append((name, side))
+
+        lab = (None, 0)
+        if labels is not None:
+            message = 'labels must be a (shots, %d) row-contiguous uint8 tensor on the points\' device' % self.nf
+            lab = _rows.check_rows(labels, shots, self.nf, torch.uint8, message, exact=True, device=device)
+            if shots:
+                place('labels', lab + (shots, self.nf, 1), labels, message)
+        w_ptr = None
+        if words is not None:
+            if self.word_bits > 62:
+                raise ValueError('%s: words need nf * bits <= 62, got %d' % (stage, self.word_bits))
+            message = 'words must be a (shots,) int64 tensor of unit stride on the points\' device'
+            if ((device and not words.is_cuda) or words.dtype != torch.int64 or words.dim() != 1
+                    or words.shape[0] != shots or (shots > 1 and words.stride(0) != 1)):
+                raise ValueError(message)
+            w_ptr = words.data_ptr()
+            if shots:
+                place('words', (w_ptr, shots, 1, shots, 8), words, message)
+        c_ptr = j_ptr = None
+        if counts is not None:
+            shape = (self.steps, self.nf, self.n_states + 1)
+            message = 'counts must be a contiguous %s int64 tensor on the points\' device' % (shape,)
+            c_ptr = _rows.check_state(counts, shape, message, device=device, dtype=np.int64)
+            place('counts', (c_ptr, shape[1] * shape[2], self.steps, shape[1] * shape[2], 8), counts, message, True)
+        if joint is not None:
+            if self.joint_bins is None:
+                raise ValueError('%s: joint needs nf * bits <= 16, got %d' % (stage, self.word_bits))
+            shape = (self.steps, self.joint_bins)
+            message = 'joint must be a contiguous %s int64 tensor on the points\' device' % (shape,)
+            j_ptr = _rows.check_state(joint, shape, message, device=device, dtype=np.int64)
+            place('joint', (j_ptr, self.joint_bins, self.steps, self.joint_bins, 8), joint, message, True)
+        return x, lab, w_ptr, c_ptr, j_ptr
+
+    def apply_torch(self, points, labels=None, words=None, counts=None, joint=None, first=0, accumulate=False):
+        """points: (shots, >= nf) row-contiguous complex128 device tensor (the demodulator's output as it is, or a
+        window x[:, w0:w0 + nf] of a wider one, without a copy; shots = 0 and shots < steps are fine).  The outputs are
+        the caller's: labels (shots, nf) uint8, any row stride >= nf; words (shots,) int64; counts (steps, nf, K + 1)
+        and joint (steps, 2^(nf bits) + 1) int64, contiguous.  With none of the four, labels are allocated.
+        accumulate=False overwrites counts and joint (a step without a shot gets 0); accumulate=True adds the block's
+        counts to them, which needs the tensors to add to.  Asynchronous on torch's current stream.  -> what it wrote:
+        one tensor, or a tuple in the order (labels, words, counts, joint)."""
+        import torch
+        if accumulate and counts is None and joint is None:
+            raise ValueError('accumulate=True needs the tensors to add to')
+        if labels is None and words is None and counts is None and joint is None:
+            if not points.is_cuda or points.dim() != 2:
+                raise ValueError('points must be a (shots, >= %d) row-contiguous device tensor of complex128' % self.nf)
+            labels = torch.empty((points.shape[0], self.nf), dtype=torch.uint8, device=points.device)
+        (x_ptr, x_stride), (l_ptr, l_stride), w_ptr, c_ptr, j_ptr = self.check(points, labels, words, counts, joint, first)
+        stream = torch.cuda.current_stream(points.device).cuda_stream
+        self.plan.apply(x_ptr, points.shape[0], x_stride, int(first), l_ptr, l_stride, w_ptr, c_ptr, j_ptr,
+                        accumulate, stream)
+        wrote = tuple(t for t in (labels, words, counts, joint) if t is not None)
+        return wrote[0] if len(wrote) == 1 else wrote
+
+    def probabilities(self, counts, shots_per_step):
+        """(steps, nf, K) float64: counts[g, j, k] / shots_per_step[g] (`counts_of(total)`) -- the invalid column is
+        left out, so a row sums to less than 1 by the invalid fraction; NaN where a step has no shot.  Plain torch ops
+        on the small table."""
+        import torch
+        shots = torch.as_tensor(np.asarray(shots_per_step, dtype=np.float64), device=counts.device).reshape(self.steps, 1, 1)
+        return counts[:, :, :self.n_states].to(torch.float64) / shots
+
+    def close(self):
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
+
+
+def classify_points(points, centres, steps=1, return_counts=False):
+    """NumPy in, NumPy out: the state of every IQ point of a complex (..., nf) array against (nf, K) centres -> labels
+    (..., nf) uint8 (255: invalid) [, counts (steps, nf, K + 1) int64 with return_counts: the shots, in C order of the
+    leading axes, cycle through `steps` steps from step 0].  No shots are answered without a device."""
+    import torch
+    sd = StateDiscriminator(centres, steps)
+    points = np.asarray(points)
+    if points.ndim < 1 or points.shape[-1] != sd.nf:
+        raise ValueError('points must have shape (..., %d), got %s' % (sd.nf, points.shape))
+    lead = points.shape[:-1]
+    x = np.ascontiguousarray(points.reshape(-1, sd.nf), dtype=np.complex128)
+    if x.shape[0] == 0:
+        labels = np.zeros(lead + (sd.nf,), dtype=np.uint8)
+        return (labels, np.zeros((sd.steps, sd.nf, sd.n_states + 1), dtype=np.int64)) if return_counts else labels
+    try:
+        dev = torch.device('cuda', torch.cuda.current_device())
+        xt = torch.from_numpy(x).to(dev)
+        labels = torch.empty((x.shape[0], sd.nf), dtype=torch.uint8, device=dev)
+        counts = torch.empty((sd.steps, sd.nf, sd.n_states + 1), dtype=torch.int64, device=dev) if return_counts else None
+        sd.apply_torch(xt, labels, counts=counts)
+        labels = labels.cpu().numpy().reshape(lead + (sd.nf,))
+        return (labels, counts.cpu().numpy()) if return_counts else labels
+    finally:
+        sd.close()
