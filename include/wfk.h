@@ -672,6 +672,41 @@ int wfk_demod_apply(wfk_demod_plan* p, const void* traces_dev, int64_t n_shots, 
 const char* wfk_demod_kernel_name(const wfk_demod_plan* p, int64_t n_shots);
 int wfk_demod_plan_destroy(wfk_demod_plan* p);
 
+/* -- readout demodulation per time bin: the IQ trajectory of every shot --------------------------- */
+/* out[s, w, j] = sum over the samples k of bin w of x[s, k] * e[k, j], bin w = [start + w * bin, start + (w + 1) * bin),
+ * w = 0 .. bins - 1, with start >= 0, bin >= 1, bins >= 1 and start + bins * bin <= n_points: traces and e as
+ * wfk_demod_plan_create takes them (e keeps the global time axis, so the phases run on from bin to bin), fp64
+ * arithmetic throughout.  out is n_shots x bins x n_freq complex128, dense within a shot, shots out_stride >= bins *
+ * n_freq complex elements apart, 16-byte aligned: out[:, w] is a points matrix as wfk_states_apply takes it (row stride
+ * out_stride).  Samples before `start` and behind the last bin are not read; a sample outside a bin is left out of
+ * the sum, not multiplied by zero, so a NaN or Inf in sample k of shot s reaches out[s, bin of k, :] and nothing else.
+ * The rows [start, start + bins * bin) of e must be finite (a zero-filled position of the kernel multiplies them);
+ * the first entry that is not is named in the refusal.  The plan uploads these rows once (zero-padded column blocks).
+ * A bin is summed by one wave in a fixed order: no float atomics, no workspace, no second kernel, and two applies of one
+ * call agree to the bit.  wfk_bdemod_apply() enqueues one kernel (bdemod_tile) on `hip_stream`, and that is all it does
+ * to the device (as wfk_avg_apply: it may be called while the stream is being captured); n_shots = 0 enqueues nothing.
+ * The plan owns no scratch: it may serve several streams at once.
+ * WFK_EINVAL, before any device work: n_points < 1, n_freq < 1, bin < 1, bins < 1, start < 0, start + bins * bin >
+ * n_points (tested without a product), bins * n_freq above 2^31 - 1, a bad in_kind, a used entry of e that is not
+ * finite; n_shots < 0, trace_stride < n_points with more than one shot, out_stride < bins * n_freq, a null or
+ * misaligned side, out overlapping the traces.  No device: WFK_EHIP, after these. */
+typedef struct wfk_bdemod_plan wfk_bdemod_plan;
+int wfk_bdemod_plan_create(const double* e_host, int64_t n_points, int32_t n_freq, int in_kind,
+                           int64_t start, int64_t bin, int64_t bins, wfk_bdemod_plan** out);
+int wfk_bdemod_apply(wfk_bdemod_plan* p, const void* traces_dev, int64_t n_shots, int64_t trace_stride,
+                     void* out_dev, int64_t out_stride /* complex elements per shot */, void* hip_stream);
+/* workgroups along the bin axis for a block of n_shots: a function of the shape alone, no plan, no device.  A workgroup
+ * owns 64 shots, one block of NB = 4 / 8 / 16 / 32 tones (the least that holds n_freq, 32 above) and one group of
+ * consecutive bins.  With blocks = ceil(n_shots / 64) * ceil(n_freq / NB): g = max(1, 1024 / blocks) groups bring the
+ * launch to about 1024 workgroups, at most max(1, bins / 4) of them so that a group keeps four bins (one per wave) where
+ * bins allows, both divisions rounding down; a group then holds per = ceil(bins / g) bins and the answer is
+ * ceil(bins / per).  0 for n_shots < 1, n_freq < 1 or bins < 1 */
+int64_t wfk_bdemod_bin_groups(int64_t n_shots, int32_t n_freq, int64_t bins);
+/* "bdemod_tile<T,NB> groups=G", G = wfk_bdemod_bin_groups(n_shots, ...); the string lives until the next call on this
+ * plan; "" for NULL */
+const char* wfk_bdemod_kernel_name(const wfk_bdemod_plan* p, int64_t n_shots);
+int wfk_bdemod_plan_destroy(wfk_bdemod_plan* p);   /* NULL is fine */
+
 /* -- per-step shot sums of readout traces: the reduction over shots ------------------------------ */
 /* A block of n_shots traces (rows of >= n_points samples of in_kind, row stride trace_stride elements) taken while a
  * sequence cycled through `steps` steps, `first` shots of the run before it: shot s of the block belongs to step

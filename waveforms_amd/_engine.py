@@ -175,6 +175,13 @@ def lib():
         l.wfk_demod_kernel_name.argtypes = [VP, I64]
         l.wfk_demod_kernel_name.restype = C.c_char_p
         l.wfk_demod_plan_destroy.argtypes = [VP]
+        l.wfk_bdemod_plan_create.argtypes = [VP, I64, I32, C.c_int, I64, I64, I64, P(VP)]
+        l.wfk_bdemod_apply.argtypes = [VP, VP, I64, I64, VP, I64, VP]
+        l.wfk_bdemod_bin_groups.argtypes = [I64, I32, I64]
+        l.wfk_bdemod_bin_groups.restype = I64
+        l.wfk_bdemod_kernel_name.argtypes = [VP, I64]
+        l.wfk_bdemod_kernel_name.restype = C.c_char_p
+        l.wfk_bdemod_plan_destroy.argtypes = [VP]
         l.wfk_avg_plan_create.argtypes = [I64, I64, C.c_int, P(VP)]
         l.wfk_avg_apply.argtypes = [VP, VP, I64, I64, I64, VP, I64, VP, I64, C.c_int, VP]
         l.wfk_avg_splits.argtypes = [VP, I64, I64]
@@ -1176,6 +1183,64 @@ class DemodPlan(_Handle):
 
     def kernel_name(self, n_shots: int) -> str:
         return lib().wfk_demod_kernel_name(self._h, n_shots).decode()
+
+
+def bdemod_arguments(e, bin, start=0, bins=None, dtype=np.float64):
+    """the arguments of a BinnedDemodPlan, checked on the host -> (e: a C-contiguous (N, nf) complex128 array, start,
+    bin, bins, dtype); `bins=None` means all that fit, (N - start) // bin.  ValueError: a matrix that is not a non-empty
+    (N, nf), a trace dtype that is not float64, float32 or int16, `bin >= 1`, `start >= 0`, `bins >= 1`, start + bins *
+    bin > N, bins * nf above 2^31 - 1, an entry of the rows [start, start + bins * bin) of e that is not finite (its
+    index is named).  Needs no device."""
+    e = np.asarray(e)
+    if e.ndim != 2 or e.shape[0] < 1 or e.shape[1] < 1:
+        raise ValueError('the matrix must be (N, nf) with N >= 1 and nf >= 1, got shape %s' % (e.shape,))
+    dtype = np.dtype(dtype)
+    if dtype not in DEMOD_IN_KIND:
+        raise ValueError('trace dtype must be float64, float32 or int16, got %s' % dtype)
+    e = np.ascontiguousarray(e, dtype=np.complex128)
+    n, nf = e.shape
+    bin, start = int(bin), int(start)
+    if bin < 1:
+        raise ValueError('binned demodulator: bin >= 1, got %d' % bin)
+    if start < 0:
+        raise ValueError('binned demodulator: start >= 0, got %d' % start)
+    bins = max(n - start, 0) // bin if bins is None else int(bins)
+    if bins < 1:
+        raise ValueError('binned demodulator: bins >= 1, got %d (N = %d, start = %d, bin = %d)' % (bins, n, start, bin))
+    if start + bins * bin > n:
+        raise ValueError('binned demodulator: start + bins * bin = %d exceeds N = %d' % (start + bins * bin, n))
+    if bins * nf > 2**31 - 1:
+        raise ValueError('binned demodulator: bins * nf exceeds 2^31 - 1')
+    used = e[start:start + bins * bin]
+    bad = np.argwhere(~(np.isfinite(used.real) & np.isfinite(used.imag)))
+    if len(bad):
+        raise ValueError('binned demodulator: e[%d, %d] is not finite' % (start + int(bad[0][0]), int(bad[0][1])))
+    return e, start, bin, bins, dtype
+
+
+def bdemod_bin_groups(n_shots: int, n_freq: int, bins: int) -> int:
+    """workgroups along the bin axis for a block of n_shots (wfk_bdemod_bin_groups): the shape alone, no device"""
+    return int(lib().wfk_bdemod_bin_groups(n_shots, n_freq, bins))
+
+
+class BinnedDemodPlan(_Handle):
+    """out[s, w, j] = the sum over bin w = [start + w bin, start + (w + 1) bin) of x[s, k] * e[k, j]: real traces
+    (shots, >= N) of float64 / float32 / int16 times a complex (N, nf) matrix, per time bin, fp64 on the device
+    (wfk_bdemod_plan_create); the used rows of `e` are uploaded once."""
+    _destroy = 'wfk_bdemod_plan_destroy'
+
+    def __init__(self, e, bin, start=0, bins=None, dtype=np.float64):
+        e, self.start, self.bin, self.bins, self.dtype = bdemod_arguments(e, bin, start, bins, dtype)
+        self.n, self.nf = int(e.shape[0]), int(e.shape[1])
+        check(lib().wfk_bdemod_plan_create(e.ctypes.data, self.n, self.nf, DEMOD_IN_KIND[self.dtype], self.start,
+                                           self.bin, self.bins, C.byref(self._h)))
+
+    def apply(self, x_ptr, n_shots, x_stride, out_ptr, out_stride, stream=0):
+        check(lib().wfk_bdemod_apply(self._h, x_ptr, n_shots, x_stride, out_ptr, out_stride, stream))
+
+    def kernel_name(self, n_shots: int) -> str:
+        """'bdemod_tile<T,NB> groups=G'"""
+        return lib().wfk_bdemod_kernel_name(self._h, n_shots).decode()
 
 
 def avg_arguments(n_points, steps, dtype):

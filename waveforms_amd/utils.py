@@ -11,6 +11,9 @@ int16 traces, in fp64.
     iq = dm.apply_torch(traces)          # (shots, >= N) device tensor -> (shots, nf) complex128
     iq = dm(signal)                      # NumPy in, NumPy out: signal @ e
 
+`BinnedDemodulator` ends the same product per time bin (csrc/wfk_bdemod.hip): (shots, bins, nf), the IQ trajectory of
+every shot.
+
 Importing this module needs no GPU; creating a `Demodulator` does.
 """
 from __future__ import annotations
@@ -24,7 +27,7 @@ import scipy.sparse as sp
 
 from .distortion import shift
 
-__all__ = ['freeze', 'getFTMatrix', 'shift', 'Demodulator', 'StateDiscriminator', 'classify_points', 'TraceAverager',
+__all__ = ['freeze', 'getFTMatrix', 'shift', 'Demodulator', 'BinnedDemodulator', 'StateDiscriminator', 'classify_points', 'TraceAverager',
            'average_traces']
 
 
@@ -160,6 +163,103 @@ class Demodulator:
     def close(self):
         if self.plan is not None:
             self.plan.close()
+
+
+class BinnedDemodulator:
+    """The IQ trajectory of every shot on the device (csrc/wfk_bdemod.hip): `Demodulator`'s product ended per time bin,
+    out[s, w, j] = sum over the samples k of bin w of traces[s, k] * e[k, j], bin w = [start + w * bin, start + (w + 1)
+    * bin), w = 0 .. bins - 1 (`bins=None`: all that fit, (N - start) // bin).  e = getFTMatrix(fList, N, ...) keeps the
+    global time axis, so the phases run on from bin to bin; samples before `start` and behind the last bin are not
+    read, and a NaN in a sample reaches its own bin only.  fp64 throughout, a fixed order of additions.
+
+        bd = BinnedDemodulator([f1, f2], 4096, bin=128, dtype=np.int16)
+        traj = bd.apply_torch(traces)                  # (shots, >= N) device tensor -> (shots, 32, nf) complex128
+        labels = disc.apply_torch(traj[:, w])          # a bin's points as StateDiscriminator takes them
+
+    `weight=None` means np.full(N, 2 / bin) -- not getFTMatrix's 2 / N: a steady tone of amplitude A and phase phi at
+    f_j then reads about A * exp(1j * phi) in EVERY bin (up to the leakage of a bin that holds no whole number of
+    periods), and with start = 0 and bins * bin = N, `out.sum(1) * bin / N` is `Demodulator`'s result.  An explicit
+    weight, and the matrix of `from_matrix`, are used as given.  Building one needs no GPU (the device plan is made by
+    the first apply); ValueError: bin < 1, start < 0, bins < 1, start + bins * bin > N, a dtype that is not float64,
+    float32 or int16, an entry of the used rows of e that is not finite."""
+
+    def __init__(self, fList, numOfPoints, bin, start=0, bins=None, phaseList=None, weight=None, sampleRate=1e9,
+                 dtype=np.float64):
+        if (weight is None or len(weight) == 0) and int(bin) >= 1:
+            weight = np.full(numOfPoints, 2 / int(bin))
+        self._setup(getFTMatrix(fList, numOfPoints, phaseList, weight, sampleRate), bin, start, bins, dtype)
+
+    @classmethod
+    def from_matrix(cls, e, bin, start=0, bins=None, dtype=np.float64) -> 'BinnedDemodulator':
+        """A binned demodulator for any (N, nf) complex matrix (matched-filter weights, ...), used as given."""
+        self = cls.__new__(cls)
+        self._setup(e, bin, start, bins, dtype)
+        return self
+
+    def _setup(self, e, bin, start, bins, dtype):
+        from . import _engine
+        self._plan = None
+        self.e, self.start, self.bin, self.bins, self.dtype = _engine.bdemod_arguments(e, bin, start, bins, dtype)
+        self.n, self.nf = self.e.shape
+
+    @property
+    def plan(self):
+        if self._plan is None:
+            from . import _engine
+            self._plan = _engine.BinnedDemodPlan(self.e, self.bin, self.start, self.bins, self.dtype)
+        return self._plan
+
+    def kernel_name(self, shots: int) -> str:
+        """'bdemod_tile<T,NB> groups=G': the kernel an apply on `shots` traces runs and its workgroups along the bins."""
+        return self.plan.kernel_name(int(shots))
+
+    def apply_torch(self, traces, out=None):
+        """traces: (shots, >= N) row-contiguous device tensor of the plan dtype (windows x[:, w0:w0 + N] work without a
+        copy).  Writes `out` (shots, bins, nf) complex128 (allocated when None; dense within a shot, any shot stride
+        >= bins * nf) on torch's current stream, asynchronously, and returns it."""
+        import torch
+        from . import _rows
+        if traces.is_complex():
+            raise ValueError('complex traces are not supported')
+        x_ptr, x_stride = _rows.check_rows(
+            traces, None, self.n, _rows.torch_dtype(self.dtype),
+            'traces must be a (shots, >= %d) row-contiguous device tensor of %s' % (self.n, self.dtype))
+        shots, row = traces.shape[0], self.bins * self.nf
+        if out is None:
+            out = torch.empty((shots, self.bins, self.nf), dtype=torch.complex128, device=traces.device)
+        message = ('out must be a (shots, %d, %d) complex128 tensor on the traces\' device, dense within a shot'
+                   % (self.bins, self.nf))
+        if (out.dim() != 3 or tuple(out.shape) != (shots, self.bins, self.nf) or out.device != traces.device
+                or (self.bins > 1 and out.stride(1) != self.nf) or (self.nf > 1 and out.stride(2) != 1)):
+            raise ValueError(message)
+        flat = out.as_strided((shots, row), (out.stride(0), 1))              # a shot's bins and tones as one row
+        out_ptr, out_stride = _rows.check_rows(flat, shots, row, torch.complex128, message, exact=True)
+        if shots:
+            stream = torch.cuda.current_stream(traces.device).cuda_stream
+            self.plan.apply(x_ptr, shots, x_stride, out_ptr, out_stride, stream)
+        return out
+
+    def __call__(self, signal):
+        """NumPy in, NumPy out: a real signal of shape (..., N) -> (..., bins, nf); a 1-D signal gives (bins, nf)."""
+        import torch
+        signal = np.asarray(signal)
+        if np.iscomplexobj(signal):
+            raise ValueError('complex traces are not supported')
+        if signal.ndim < 1 or signal.shape[-1] != self.n:
+            raise ValueError('signal must have shape (..., %d), got %s' % (self.n, signal.shape))
+        if not np.can_cast(signal.dtype, self.dtype, 'safe'):
+            raise ValueError('a %s signal does not fit a %s demodulator' % (signal.dtype, self.dtype))
+        lead = signal.shape[:-1]
+        x = np.ascontiguousarray(signal.reshape(-1, self.n), dtype=self.dtype)
+        dev = torch.device('cuda', torch.cuda.current_device())
+        xt = torch.from_numpy(x).to(dev)
+        out = self.apply_torch(xt)
+        return out.cpu().numpy().reshape(lead + (self.bins, self.nf))
+
+    def close(self):
+        if self._plan is not None:
+            self._plan.close()
+            self._plan = None
 
 
 class TraceAverager:
