@@ -493,6 +493,36 @@ int wfk_dac_rows_apply(wfk_dac_rows_plan* plan, const void* in_dev, int64_t in_s
 const char* wfk_dac_rows_kernel_name(const wfk_dac_rows_plan* plan, int with_counts);
 int wfk_dac_rows_plan_destroy(wfk_dac_rows_plan* plan);
 
+/* -- sampler -> DAC codes: the AWG-rate sampler writes the int16 codes itself ---------------------- */
+/* codes = wfk_dac_rows(wfk_plan_launch(prog on grid, WFK_OUT_F64)) for the channels of `prog`, bit for bit -- codes and
+ * counts -- without the float64 rows: gain_host / offset_host hold one value per channel, bits / shift / interleave
+ * and the formula are those of wfk_dac_rows_plan_create, whose argument checks run first, before any device work;
+ * complex channels: WFK_EINVAL.  Fused -- the sampler plan is a pure short-tier plan (no time list, not mixed, no
+ * second launch of the general kernel) and interleave == 1 -- ONE kernel, "wfk_sample_short_dac<16,FAM,COUNT>": the
+ * short tier's unit pipeline with the scaling, rounding and saturation behind each sample, 2 B per sample stored.
+ * Everything else -- WFK_CHAIN_UNFUSED=1, n == 0, no short plan, a mixed plan, interleave == 2 -- runs the sampler
+ * into scratch_dev (n_channels float64 rows, scratch_stride >= n samples apart) and dac_rows on it; the name is
+ * then the kernels joined with " + " and the reason is never empty.  The decision is taken once, at creation.
+ * wfk_chain_dac_launch() enqueues its kernels (the zeroing of the counts among them) on `hip_stream`, and that is all
+ * it does to the device (as wfk_avg_apply: it may be called while the stream is being captured).  out_dev:
+ * n_channels / interleave rows of interleave * n codes, out_stride codes apart (a lone row's stride is not read),
+ * aligned to 2 bytes, anywhere in a wider buffer; counts_dev: NULL, or n_channels * 3 int64 [below, above, nan],
+ * OVERWRITTEN by every launch, meeting neither the codes nor the scratch; scratch_dev: NULL for a fused plan (not
+ * touched), WFK_EINVAL for an unfused one.  n == 0 launches no sampler and still zeroes the counts.  The strings live
+ * as long as the plan; one plan per concurrent stream. */
+typedef struct wfk_chain_dac_plan wfk_chain_dac_plan;
+int wfk_chain_dac_plan_create(const wfk_program* prog, const wfk_grid* grid, const double* gain_host,
+                              const double* offset_host, int bits, int shift, int interleave,
+                              wfk_chain_dac_plan** out);
+int wfk_chain_dac_is_fused(const wfk_chain_dac_plan* plan);
+const char* wfk_chain_dac_unfused_reason(const wfk_chain_dac_plan* plan);
+const char* wfk_chain_dac_kernel_name(const wfk_chain_dac_plan* plan, int with_counts);
+int64_t wfk_chain_dac_table_bytes(const wfk_chain_dac_plan* plan);
+int wfk_chain_dac_launch(wfk_chain_dac_plan* plan, int16_t* out_dev, int64_t out_stride,
+                         int64_t* counts_dev /* n_channels * 3, or NULL */, void* scratch_dev /* or NULL */,
+                         int64_t scratch_stride, void* hip_stream);
+int wfk_chain_dac_plan_destroy(wfk_chain_dac_plan* plan);
+
 /* -- per-row gate markers: widened, as bytes or into one bit of the DAC codes -------------------- */
 /* `batch` real rows of n samples (kind: WFK_OUT_F64 or WFK_OUT_F32) drive batch / group marker rows: the marker
  * line that opens a switch or blanks an amplifier around every pulse, derived from the IDEAL gate rows (exact zeros

@@ -144,6 +144,16 @@ def lib():
         l.wfk_dac_rows_kernel_name.argtypes = [VP, C.c_int]
         l.wfk_dac_rows_kernel_name.restype = C.c_char_p
         l.wfk_dac_rows_plan_destroy.argtypes = [VP]
+        l.wfk_chain_dac_plan_create.argtypes = [P(wfk_program), P(wfk_grid), VP, VP, C.c_int, C.c_int, C.c_int, P(VP)]
+        l.wfk_chain_dac_is_fused.argtypes = [VP]
+        l.wfk_chain_dac_unfused_reason.argtypes = [VP]
+        l.wfk_chain_dac_unfused_reason.restype = C.c_char_p
+        l.wfk_chain_dac_kernel_name.argtypes = [VP, C.c_int]
+        l.wfk_chain_dac_kernel_name.restype = C.c_char_p
+        l.wfk_chain_dac_table_bytes.argtypes = [VP]
+        l.wfk_chain_dac_table_bytes.restype = I64
+        l.wfk_chain_dac_launch.argtypes = [VP, VP, I64, VP, VP, I64, VP]
+        l.wfk_chain_dac_plan_destroy.argtypes = [VP]
         l.wfk_marker_rows_plan_create.argtypes = [I64, I32, C.c_int, C.c_int, VP, VP, VP, P(VP)]
         l.wfk_marker_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP]
         l.wfk_marker_rows_apply_codes.argtypes = [VP, VP, I64, VP, I64, C.c_int, VP, VP]
@@ -820,6 +830,42 @@ class DacRowsPlan(_Handle):
 
     def kernel_name(self, counts: bool = False) -> str:
         return lib().wfk_dac_rows_kernel_name(self._h, 1 if counts else 0).decode()
+
+
+class ChainDacPlan(_Handle):
+    """sampler -> DAC codes for every channel of `prog` on `grid` (wfk_chain_dac_*): DacRowsPlan's arithmetic and
+    arguments (one gain and offset per channel, float64 samples) on what Plan(prog, grid) samples.  Fused -- a pure
+    short-tier plan, interleave 1 -- the sampler's own kernel stores the int16 codes
+    ('wfk_sample_short_dac<16,FAM,COUNT>') and the float64 rows never exist; everything else (`why_not`) runs the
+    sampler into a float64 scratch the caller lends, then dac_rows.  Codes and counts are those of the two launches
+    bit for bit either way."""
+    _destroy = 'wfk_chain_dac_plan_destroy'
+
+    def __init__(self, prog: Program, grid: wfk_grid, gain, offset, bits: int = 16, shift: int = 0, interleave: int = 1):
+        (self.gain, self.offset, self.n, self.bits, self.shift, self.interleave,
+         _) = dac_rows_arguments(gain, offset, int(grid.n), bits, shift, interleave)
+        if len(self.gain) != prog.n_channels:
+            raise ValueError(f'{len(self.gain)} gains for {prog.n_channels} rows')
+        self.prog, self.grid, self.n_channels = prog, grid, prog.n_channels
+        self.lo, self.hi = -2**(self.bits - 1), 2**(self.bits - 1) - 1
+        self.out_rows, self.out_n = self.n_channels // self.interleave, self.interleave * self.n
+        check(lib().wfk_chain_dac_plan_create(C.byref(prog.struct), C.byref(grid), self.gain.ctypes.data,
+                                              self.offset.ctypes.data, self.bits, self.shift, self.interleave,
+                                              C.byref(self._h)))
+        self.fused = bool(lib().wfk_chain_dac_is_fused(self._h))
+        self.why_not = lib().wfk_chain_dac_unfused_reason(self._h).decode()
+
+    def launch(self, out_ptr, out_stride, counts_ptr=None, scratch_ptr=None, scratch_stride=0, stream=0):
+        """counts_ptr: None, or n_channels * 3 int64 on the device, overwritten; scratch_ptr: n_channels float64 rows
+        `scratch_stride` apart, which an unfused plan needs and a fused one does not touch"""
+        check(lib().wfk_chain_dac_launch(self._h, out_ptr, out_stride, counts_ptr, scratch_ptr, scratch_stride, stream))
+
+    def kernel_name(self, counts: bool = False) -> str:
+        """'wfk_sample_short_dac<16,FAM,COUNT>', or the sampler's kernels and dac_rows' joined with ' + '"""
+        return lib().wfk_chain_dac_kernel_name(self._h, 1 if counts else 0).decode()
+
+    def table_bytes(self) -> int:
+        return int(lib().wfk_chain_dac_table_bytes(self._h))
 
 
 MARKER_MAX_EDGE = 4096     # WFK_MARKER_MAX_EDGE

@@ -400,6 +400,29 @@ static KArgs sampler_args(const wfk_plan* p, const SamplerPick& k, void* out_dev
   return a;
 }
 
+// the arguments of a whole launch of a short plan's wfk_sample_short, but for where it writes (out, ch_stride, accumulate)
+static SArgs short_args(const wfk_plan* p, bool packed) {
+  SArgs sa{};
+  sa.channels = p->d_channels; sa.units = p->d_units; sa.slots = p->d_slots; sa.recs = p->d_params; sa.pool = p->d_pool;
+  sa.n_units = (int64_t)p->h.s_units.size();
+  sa.units_per_chunk = p->h.s_units_per_chunk;
+  sa.n_chunks = (sa.n_units + sa.units_per_chunk - 1) / sa.units_per_chunk;
+  sa.lds_samples = p->h.s_lds_samples; sa.fam = p->h.short_fam; sa.pk = packed ? 1 : 0;
+  sa.t0 = p->h.t0; sa.last = p->h.last; sa.step = p->h.step; sa.di0 = (double)p->h.i0;
+  sa.dlast = p->h.has_last ? (double)(p->h.i0 + p->h.n - 1) : -1.0;
+  return sa;
+}
+
+int wfk_internal_plan_short_args(const wfk_plan* p, SArgs* out) {
+  if (!p || !p->on_device || !p->h.shortp) return 0;
+  *out = short_args(p, false);
+  return 1;
+}
+
+void wfk_internal_plan_note_async(wfk_plan* p) {
+  if (p) p->async_launch = true;
+}
+
 // Launch the plan, or part `part` of `nparts` of it (single-channel plans only: the part's chunks are
 // a contiguous sample range, returned in *s_lo / *s_hi).  nparts == 1: everything.
 static int plan_launch_part(wfk_plan* p, void* out_dev, int64_t ch_stride, int out_kind, uint32_t flags,
@@ -422,15 +445,9 @@ static int plan_launch_part(wfk_plan* p, void* out_dev, int64_t ch_stride, int o
   for (int i = 0; i < picks.n && !rc; ++i) {
     const SamplerPick& k = picks.pick[i];
     if (k.tier == SamplerTier::Short) {
-      SArgs sa{};
-      sa.channels = p->d_channels; sa.units = p->d_units; sa.slots = p->d_slots; sa.recs = p->d_params; sa.pool = p->d_pool;
+      SArgs sa = short_args(p, packed);
       sa.out = out_dev; sa.ch_stride = ch_stride; sa.accumulate = (flags & WFK_ACCUMULATE) ? 1 : 0;
-      sa.n_units = (int64_t)p->h.s_units.size();
-      sa.units_per_chunk = p->h.s_units_per_chunk;
-      sub((sa.n_units + sa.units_per_chunk - 1) / sa.units_per_chunk, sa.chunk_base, sa.n_chunks);
-      sa.lds_samples = p->h.s_lds_samples; sa.fam = p->h.short_fam; sa.pk = packed ? 1 : 0;
-      sa.t0 = p->h.t0; sa.last = p->h.last; sa.step = p->h.step; sa.di0 = (double)p->h.i0;
-      sa.dlast = p->h.has_last ? (double)(p->h.i0 + p->h.n - 1) : -1.0;
+      sub(sa.n_chunks, sa.chunk_base, sa.n_chunks);
       if (s_lo && nparts > 1) {
         const int64_t u0 = sa.chunk_base * sa.units_per_chunk, u1 = (sa.chunk_base + sa.n_chunks) * sa.units_per_chunk;
         *s_lo = u0 < sa.n_units ? p->h.s_units[(size_t)u0].j0 : p->h.n;

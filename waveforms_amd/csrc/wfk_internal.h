@@ -224,6 +224,13 @@ struct SArgs {                // short-tier launch (wfk_short.hip)
                                  // in the caller's full grid (-1: none), the slice offset i0 -- as doubles
 };
 
+struct DacKArgs {             // what the short tier's DAC build takes next to SArgs (wfk_sample_short_dac, wfk_short.hip):
+  const double* rows;         // [n_channels] (gain, offset) pairs, read by scalar loads; SArgs::out / ch_stride are the
+  unsigned long long* counts; // int16 codes and their row stride; [n_channels][3] below / above / nan (the counting build)
+  double lo, hi;              // the rails, -2^(bits - 1) and 2^(bits - 1) - 1
+  int32_t shift, pad;
+};
+
 struct KArgs {
   const DevChannel* channels;
   const DevPiece* pieces;
@@ -358,6 +365,8 @@ void wfk_internal_grid_times(const wfk_grid* g, double* out);         // out[g->
 struct SamplerPick;
 int wfk_launch_sampler(const KArgs& a, const SamplerPick& k, int32_t n_channels, void* stream, std::string& err);
 int wfk_launch_short(const SArgs& a, const SamplerPick& k, void* stream, std::string& err);
+// the DAC build of the short tier for op family `fam` (0 / 1 / 2 / 4 / 6): int16 codes to a.out, d.counts or null
+int wfk_launch_short_dac(const SArgs& a, const DacKArgs& d, int fam, void* stream, std::string& err);
 
 // functions one stage's file calls in another's, exported but not part of include/wfk.h
 extern "C" {
@@ -370,6 +379,11 @@ void wfk_internal_plan_tables(const wfk_plan* p, const HostPlan** h, const doubl
 int wfk_internal_plan_create(const wfk_program* prog, const wfk_grid* grid, const double* tlist, int64_t n,
                              const CompileRequest& req, wfk_plan** out);
 int wfk_internal_plan_launch_foreign(wfk_plan* p, void* out_dev, int64_t ch_stride, int out_kind, void* hip_stream);
+// wfk_api.cpp: the arguments of a whole launch of a short plan's wfk_sample_short (out / ch_stride / accumulate left
+// zero); 0 where the plan is no short plan on the device.  A launch on a caller's stream is noted in the plan as
+// wfk_plan_launch notes its own (wfk_internal_plan_note_async).
+int wfk_internal_plan_short_args(const wfk_plan* p, SArgs* out);
+void wfk_internal_plan_note_async(wfk_plan* p);
 // wfk_fir.hip: kernel spectrum and twiddles of a plan that runs as ONE pass of the on-chip transform; its row stride
 void wfk_internal_fir_tables(const wfk_fir_plan* p, const void** kspec, const void** tw, int* fused, int* nseg,
                              int* K, int* lead);

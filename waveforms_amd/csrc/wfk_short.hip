@@ -122,6 +122,30 @@ __device__ __forceinline__ void add_old(E& v, const E& old) {
   if constexpr (CPLX) { v.x += old.x; v.y += old.y; } else { v += old; }
 }
 
+// ---- the DAC build (wfk_sample_short_dac): what it has beside the sampler's own body --------------------------------
+__device__ __forceinline__ void buf_store16(int16_t v, __amdgpu_buffer_rsrc_t r, int byte_off) {
+  __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(unsigned short, v), r, byte_off, 0, WFK_SH_STORE_AUX);
+}
+// one sample to its code, statement by statement what dac_block (wfk_dac_rows.hip) does: a rounded product and a
+// rounded sum, rint, the rails compared in double, NaN -> 0; `rails`: below | above << 16, `isnan`: 0 / 1 (a unit has
+// <= 1008 samples: a wave's sums of these stay inside their 16 bits)
+__device__ __forceinline__ int16_t dac_code(double v, double gain, double offset, double lo, double hi, int shift,
+                                            unsigned& rails, unsigned& isnan) {
+#pragma clang fp contract(off)
+  const double w = v * gain + offset;
+  const double q = rint(w);
+  const bool nan = w != w, below = q < lo, above = q > hi;
+  const double c = nan ? 0.0 : below ? lo : above ? hi : q;
+  rails = (unsigned)below | ((unsigned)above << 16);
+  isnan = (unsigned)nan;
+  return (int16_t)((int)c * (1 << shift));
+}
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {     // every lane gets the sum over the wave
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += (unsigned)__shfl_xor((int)v, m, 64);
+  return v;
+}
+
 // elements of the staging array: the longest unit (WFK_SH_LCAP samples + 15 of row alignment = 16 rows
 // of 64) in the 17-per-16 swizzle, plus the overrun of a last partial row
 constexpr int kStage = 68 * 16 + 16;
@@ -148,267 +172,40 @@ constexpr int kStage = 68 * 16 + 16;
 #ifndef WFK_SH_WAVES6
 #define WFK_SH_WAVES6 2       // family 6 (corrected carriers): 219 registers and no spill at two waves per SIMD against 168 + 46 spilled
 #endif                        // at three -- rows 1 ms from t = 0, same box: 1.06 -> 0.835 ms
+// DAC / COUNT: off in the sampler (wfk_sample_short); the DAC build without / with the clip report
+// (wfk_sample_short_dac: T = double, real, no accumulate).  Same unit walk, same op evaluation, same pipeline; what differs is what a sample
+// becomes once it is final.  The sample v = acc[k] + offset goes through dac_code with the row's gain and offset (a
+// second scalar load, issued for the NEXT unit as the descriptors are) and is staged as an int16 code at head + i,
+// head = the unit's first code's position in its 16-byte group of 8 -- the groups are laid out from the 16-byte
+// boundary at or before the output row's first code, whatever 2-byte offset the row starts at.  The unit (<= 7 + 1008
+// codes: <= 127 groups) leaves in THREE masked store instructions: two of 16 bytes per lane for the groups that lie
+// whole inside the unit, one of 2 bytes per lane (lanes 0-7: group 0, lanes 8-15: the last group) for the codes of a
+// first and a last partial group -- those 16 bytes are shared with the neighbouring unit, which another wave owns (or
+// with whatever lies in front of and behind the row), and are never read or written as a whole.  A pure-fill unit
+// stores the code of the channel's constant the same way.  Counting (COUNT): every lane counts its own run's samples
+// below / above the rails and NaN, the wave sums them (two packed words through the cross-lane network), the samples
+// of the unit no run covers count as the constant does, and lanes 0-2 add the three sums to the row's int64 counters,
+// one atomic each where the sum is not zero.  Integer sums: the report does not depend on the order of arrival.
+// The body is ONE text, wfk_short_body.inc, included into both kernels -- not a function the two call: handed the
+// kernel's arguments by reference, the compiler first copied them out of the kernel-argument segment, and 42 of the
+// sampler's 44 instantiations came out with other instruction words and registers (tools/kernel_cmp.py).  The body
+// reads T, CPLX, ACC, R, FAM, DAC, COUNT, `a` and `dk` from where it is included; DAC and COUNT depend on a template
+// parameter in both kernels, so that the other build's statements are discarded, never instantiated.
 template <typename T, bool CPLX, bool ACC, int R, int FAM>
 __global__ void __launch_bounds__(64, CPLX ? 2 : (FAM == 6 ? WFK_SH_WAVES6 : WFK_SH_WAVES)) wfk_sample_short(const SArgs a) {
-  using E = typename std::conditional<CPLX, typename ShOut<T>::Cplx, T>::type;
-  // float launches of the plain pulse train (family 3 = family 0 in packed fp32 arithmetic, wfk_short_dev.h: short_op_pk)
-  constexpr bool PK = FAM == 3;
-  // what a family holds beside the carrier-envelope ops: F1 closing ops of flat tops / multi-tone pieces and linear chirps,
-  // F2 table / mollifier envelopes, F4 exponential / hyperbolic chirp multipliers (libm log behind a call: a family of
-  // its own, so that the table envelopes keep their register allocation)
-  constexpr bool F1 = FAM == 1 || FAM == 2 || FAM == 4, F2 = FAM == 2 || FAM == 4, F4 = FAM == 4;
-  // family 6 = family 0 + carriers with the grid-rounding correction (pulse trains milliseconds from t = 0: short_op_corr)
-  constexpr bool F6 = FAM == 6;
-  static_assert(!PK || (std::is_same<T, float>::value && !CPLX), "packed arithmetic: real float launches only");
-  __shared__ __attribute__((aligned(16))) E s_out[kStage];
-  const int lane = threadIdx.x;
-  // XCD-aware chunk map (workgroup b runs on XCD b % 8): XCD x walks the x-th contiguous eighth
-  const int64_t b = blockIdx.x;
-  const int64_t per = (a.n_chunks + 7) >> 3;
-  const int64_t lchunk = (b & 7) * per + (b >> 3);
-  if (lchunk >= a.n_chunks) return;
-  const int64_t chunk = a.chunk_base + lchunk;
-  const int64_t u0 = chunk * a.units_per_chunk;
-  const int64_t u1 = u0 + a.units_per_chunk < a.n_units ? u0 + a.units_per_chunk : a.n_units;
-  const int64_t ulast = a.n_units - 1;
+  constexpr bool DAC = sizeof(T) == 0, COUNT = DAC;
+  [[maybe_unused]] const DacKArgs dk{};
+#include "wfk_short_body.inc"
+}
 
-  auto slot_of = [&](const UnitDesc& d) -> uint32_t {     // lanes >= nslots read 0: no segment
-    return buf_load<uint32_t>(make_rsrc(a.slots + d.slot0, (unsigned)d.nslots * 4u), lane * 4);
-  };
-  // (len, o, first sample's index, record) of this lane's segment
-  struct Seg { int len, o, j; const double* rec; };
-  auto decode = [&](uint32_t slot, const UnitDesc& d) -> Seg {
-    Seg g;
-    g.len = (slot >> 31) ? (int)((slot >> 26) & 15) + 1 : 0;
-    g.o = (int)((slot >> 16) & 0x3ff);
-    g.j = (int)(uint32_t)d.j0 + g.o;
-    g.rec = a.recs + 2 * (d.rec0 + (int64_t)(slot & 0xffff));
-    return g;
-  };
-
-  // The pipeline fills INSIDE the loop: iteration u0 - 1 works on an empty unit (no slots, zero samples:
-  // the range check drops its stores).  With a separate prologue the compiler merges two histories at the
-  // loop header and waits for the record as if only the prologue's single load followed it (vmcnt(1):
-  // every store of the previous unit), instead of leaving the 16 stores and the slot load in flight.
-  UnitDesc cur{};
-  UnitDesc nxt = load_unit(a.units + u0);
-  Seg seg{0, 0, 0, a.recs};
-  OpRec first{};
-
-  for (int64_t ui = u0 - 1; ui < u1; ++ui) {
-    // two units ahead: descriptor; one ahead: slot words (none past the end of the chunk)
-    const UnitDesc nn = load_unit(a.units + (ui + 2 <= ulast ? ui + 2 : ulast));
-    if (ui + 1 >= u1) { nxt.nslots = 0; nxt.ns = 0; }
-    const uint32_t nslot = slot_of(nxt);
-    E* const orow = uniptr(reinterpret_cast<E*>(a.out) + (int64_t)cur.ch * a.ch_stride + cur.j0);
-    const int head = (int)(cur.j0 & 15);     // rows start on 16-sample boundaries (whole 128-B lines for fp64)
-    const int ns = cur.ns;
-    E fillv;
-    if constexpr (CPLX) { fillv.x = (T)cur.offset; fillv.y = (T)0; } else { fillv = (T)cur.offset; }
-    const int l0 = lane - head;                 // this lane's sample in row 0 (negative: before the unit)
-    // Staging layout, chosen per unit by the host for the unit's own segment offsets: plain (sample i at
-    // element i: conflict-free when the runs start an odd number of samples apart, e.g. 15), or padded by
-    // one element per 16 (i + (i >> 4): runs of 16 then start 17 apart).  Either way row r, lane x sits at
-    // rs * r + f(x), one per-lane base and a uniform row stride.
-    const bool sw = (cur.gaps & 2) != 0;
-    const int rs = sw ? 68 : 64;
-    const int s0 = sw ? l0 + (l0 >> 4) : l0;    // (arithmetic shift: exact for the negative l0 of row 0 too)
-
-    double acc[PK ? 1 : R], acci[CPLX ? R : 1];
-    f32x2 accp[PK ? R / 2 : 1];
-    SH_EACH(PK ? 1 : R, k) acc[k] = 0.0; SH_END
-    SH_EACH(CPLX ? R : 1, k) acci[k] = 0.0; SH_END
-    SH_EACH(PK ? R / 2 : 1, k) accp[k] = 0.0f; SH_END
-
-    if (cur.nslots != 0) {
-      const double kf = (double)(seg.j - op_ref(first));   // samples from the record's reference sample
-      const double* op = seg.rec;
-      OpRec rec = first;
-      bool live = seg.len > 0;
-      // The first op is evaluated in straight-line code, further ops (multi-tone pieces) in a loop:
-      // a loop whose body reads registers loaded before it gets a vmcnt(0) in its preheader from the
-      // compiler (SIInsertWaitcnts' preheader flush), which here would wait for the slot load just
-      // issued and for every store of the previous unit.
-      auto eval = [&](const OpRec& rc, const double* opp, bool lv) -> bool {   // -> another op follows
-        // (the unused halves of the record stay "live" up to here: registers that die at the load are
-        //  handed out again as temporaries while the load is still in flight, and writing them means
-        //  waiting for it -- a vmcnt(3) right behind the prefetch)
-        asm volatile("" : : "v"(rc.a.x));
-        const int w = op_word(rc);
-        const bool closing = ((w >> 4) & 3) == 3;       // closing multiplier (erf edge, table, mollifier)
-        const bool mine = lv && !closing && (CPLX || !(w & 8));   // op of the imaginary part: a real launch keeps .real
-        const bool chirp = F1 && (w & 512) != 0;  // quadratic phase (16-double record, polynomials of degree <= 1)
-        const bool cubic = __any(mine && !chirp && (w & 3) > 1 && !(F6 && (w & 4096)));
-        if constexpr (PK) {
-          if (mine) {
-            if (cubic) short_op_pk<R, true>(rc, opp, w, kf, a.step, accp);
-            else short_op_pk<R, false>(rc, opp, w, kf, a.step, accp);
-          }
-          return lv && !(w & WFK_SH_LAST);
-        } else {
-        if constexpr (F1) {
-          if (__any(mine && chirp)) {
-            if (mine && chirp) short_chirp<R, CPLX>(rc, opp, w, kf, a.step, acc, acci);
-          }
-        }
-        // bare carriers (degree 0, no envelope): the tones of a multi-tone piece, plateaus -- half the instructions per sample
-        const bool bare = F1 && !chirp && (w & 0x33) == 0 && (w & 4) != 0;
-        if constexpr (F1) {
-          if (__any(mine && bare)) {
-            if (mine && bare) short_op_bare<R, CPLX>(rc, w, kf, acc, acci);
-          }
-        }
-        bool corr = false;
-        if constexpr (F6) {
-          corr = (w & 4096) != 0;
-          if (__any(mine && corr)) {
-            if (mine && corr) {
-              ShortCorr cc;
-              cc.dj0 = a.di0 + (double)seg.j;
-              cc.step = a.step; cc.t0 = a.t0; cc.last = a.last; cc.dlast = a.dlast;
-              short_op_corr<R, CPLX>(rc, opp, w, kf, cc, acc, acci);
-            }
-          }
-        }
-        if (mine && !chirp && !bare && !corr) {
-#ifndef WFK_SH_SKIP0
-#define WFK_SH_SKIP0 0
-#endif
-          if (cubic) short_op<R, true, CPLX, (F1 || WFK_SH_SKIP0)>(rc, opp, w, kf, a.step, acc, acci);
-          else short_op<R, false, CPLX, (F1 || WFK_SH_SKIP0)>(rc, opp, w, kf, a.step, acc, acci);
-        }
-        if constexpr (F1)
-        if (__any(lv && closing)) {
-          const bool own = F2 && (w & 128) != 0;      // envelope x carrier in one op: adds its own term
-          if constexpr (F2) {
-            if (__any(lv && closing && own)) {
-              if (lv && closing && own && (CPLX || !(w & 8))) short_cmul<R, CPLX>(rc, a.pool, w, kf, acc, acci);
-            }
-          }
-          const bool xch = F4 && (w & 1024) != 0;    // chirp multiplier (exponential / hyperbolic)
-          if constexpr (F4) {
-            if (__any(lv && closing && xch)) {
-              if (lv && closing && xch) short_xchirpmul<R, CPLX>(rc, w, kf, acc, acci);
-            }
-          }
-          const int kind = (own || xch) ? -1 : (w & 3);      // 0: erf edge; 1: shared Gaussian; 2: INTERP table, 3: mollifier (stateless multipliers)
-          if constexpr (F1) {
-            if (__any(lv && closing && kind == 1)) {
-              if (lv && closing && kind == 1) short_envmul<R, CPLX>(rc, kf, acc, acci);
-            }
-          }
-          if (__any(lv && closing && kind == 0)) {
-            if (lv && closing && kind == 0) short_erfmul_run<R, CPLX>(rc, kf, seg.len, acc, acci);
-          }
-          if constexpr (F2) {
-            if (__any(lv && closing && kind == 2)) {
-              if (lv && closing && kind == 2) short_tabmul<R, CPLX>(rc, a.pool, kf, acc, acci);
-            }
-            if (__any(lv && closing && kind == 3)) {
-              if (lv && closing && kind == 3) short_mollmul<R, CPLX>(rc, kf, acc, acci);
-            }
-          }
-        }
-        return lv && !(w & WFK_SH_LAST);
-        }
-      };
-      live = eval(rec, op, live);
-      while (__any(live)) {
-        op += (op_word(rec) & 3) > 1 ? WFK_SH_OP3 : WFK_SH_OP1;
-        if (live) rec = load_op(op);
-        live = eval(rec, op, live);
-      }
-    }
-
-    // the next unit's segment and first op record: in flight while this unit is staged and stored
-    const Seg nseg = decode(nslot, nxt);
-    first = load_op(nseg.rec);
-
-    if (cur.nslots != 0) {
-      __syncthreads();            // the previous unit's store phase is done with the staging array
-      if (cur.gaps & 1) {
-        const int f0 = sw ? swz(lane) : lane;
-        SH_EACH(16, r)
-          if (64 * r < ns) s_out[f0 + rs * r] = fillv;
-        SH_END
-        __syncthreads();
-      }
-      // clip (evaluated pieces only: every slot is one), + offset
-      if (cur.do_clip) {
-        if constexpr (CPLX) {
-          // np.clip of complex values: lexicographic against the real bounds (see clip_np_cplx in wfk_kernels.hip)
-          SH_EACH(R, k)
-            if (acc[k] < cur.clip_lo || (acc[k] == cur.clip_lo && acci[k] < 0.0)) { acc[k] = cur.clip_lo; acci[k] = 0.0; }
-            if (acc[k] > cur.clip_hi || (acc[k] == cur.clip_hi && acci[k] > 0.0)) { acc[k] = cur.clip_hi; acci[k] = 0.0; }
-          SH_END
-        } else if constexpr (PK) {
-          // (the double path clips the fp64 sum and rounds once; here the float sum is clipped against the bounds --
-          //  np.clip semantics, NaN propagates)
-          SH_EACH(R, k)
-            float v = accp[k / 2][k % 2];
-            v = v < (float)cur.clip_lo ? (float)cur.clip_lo : v;
-            v = v > (float)cur.clip_hi ? (float)cur.clip_hi : v;
-            accp[k / 2][k % 2] = v;
-          SH_END
-        } else {
-          SH_EACH(R, k) acc[k] = clip_np(acc[k], cur.clip_lo, cur.clip_hi); SH_END
-        }
-      }
-      {
-        // padded layout: element o + k lands at swz(o) + k + [k >= 16 - (o & 15)]: two bases, immediate offsets
-        const int o = seg.o, len = seg.len;
-        const int t = sw ? 16 - (o & 15) : 99;
-        E* const b0 = s_out + (sw ? swz(o) : o);
-        SH_EACH(R, k)
-          if (k < len) {                      // (a masked LDS write needs no wait: the branch is cheap)
-            E* const at = (k >= t ? b0 + 1 : b0) + k;
-            double v;
-            if constexpr (PK) v = (double)(accp[k / 2][k % 2] + (float)cur.offset);
-            else v = acc[k] + cur.offset;
-            if constexpr (CPLX) {
-              E e;
-              e.x = (T)v;
-              e.y = (T)acci[k];
-              *at = e;
-            } else {
-              *at = (T)v;
-            }
-          }
-        SH_END
-      }
-      __syncthreads();
-    }
-
-    // store the unit's range: 64 consecutive samples per instruction, 16 masked rows in two batches of
-    // eight.  The LDS reads are unconditional (row 0's index clamped: lanes before the unit read element
-    // 0 and never store it); a pure-fill unit (a zero stretch: skipped _zero pieces, no clip,
-    // waveforms/_waveform.pyx:160-163) stores `offset`.
-    const __amdgpu_buffer_rsrc_t ores = make_rsrc(orow, (unsigned)ns * (unsigned)sizeof(E));
-    const int b0off = l0 * (int)sizeof(E);                  // row 0: "negative" for the lanes before the unit
-    const int b1off = (64 + l0) * (int)sizeof(E);           // rows >= 1: never negative
-    SH_EACH(2, hb)
-      E v[8];
-      SH_EACH(8, rr)
-        constexpr int r = hb * 8 + rr;
-        v[rr] = fillv;
-        if (cur.nslots != 0) v[rr] = s_out[r == 0 ? max(s0, 0) : s0 + rs * r];
-      SH_END
-      if constexpr (ACC) {
-        SH_EACH(8, rr)
-          constexpr int r = hb * 8 + rr;
-          add_old<E, CPLX>(v[rr], buf_load<E>(ores, r == 0 ? b0off : b1off + 64 * (r - 1) * (int)sizeof(E)));
-        SH_END
-      }
-      SH_EACH(8, rr)
-        constexpr int r = hb * 8 + rr;
-        buf_store<E>(v[rr], ores, r == 0 ? b0off : b1off + 64 * (r - 1) * (int)sizeof(E));
-      SH_END
-    SH_END
-
-    cur = nxt;
-    nxt = nn;
-    seg = nseg;
-  }
+// the DAC build: int16 codes to a.out, rows a.ch_stride codes apart; real double arithmetic, no accumulate
+// (family 4, and the counting builds of families 1 and 2, spill 2 to 13 VGPRs to scratch at three waves per SIMD: two)
+template <int R, int FAM, bool COUNTED>
+__global__ void __launch_bounds__(64, FAM == 6 || FAM == 4 || (COUNTED && FAM != 0) ? WFK_SH_WAVES6 : WFK_SH_WAVES) wfk_sample_short_dac(const SArgs a, const DacKArgs dk) {
+  using T = double;
+  constexpr bool DAC = FAM >= 0, COUNT = COUNTED, CPLX = !DAC, ACC = !DAC;
+  static_assert(FAM != 3, "family 3 is packed fp32: no DAC build");
+#include "wfk_short_body.inc"
 }
 
 // one build of the kernel, the pick's: 0 / 1 / 2 / 4 / 6, and 3 = family 0 in packed fp32 (real float outputs only)
@@ -427,7 +224,34 @@ bool launch_short(const SArgs& a, int build, unsigned blocks, hipStream_t s) {
   return false;
 }
 
+template <bool COUNT>
+bool launch_short_dac(const SArgs& a, const DacKArgs& d, int fam, unsigned blocks, hipStream_t s) {
+#define SH_LAUNCH(FAMV) hipLaunchKernelGGL((wfk_sample_short_dac<WFK_SH_R, FAMV, COUNT>), dim3(blocks), dim3(64), 0, s, a, d)
+  switch (fam) {
+    case 0: SH_LAUNCH(0); return true;
+    case 1: SH_LAUNCH(1); return true;
+    case 2: SH_LAUNCH(2); return true;
+    case 4: SH_LAUNCH(4); return true;
+    case 6: SH_LAUNCH(6); return true;
+  }
+#undef SH_LAUNCH
+  return false;
+}
+
 }  // namespace
+
+int wfk_launch_short_dac(const SArgs& a, const DacKArgs& d, int fam, void* stream, std::string& err) {
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t blocks = ((a.n_chunks + 7) >> 3) << 3;
+  if (blocks == 0) return WFK_OK;
+  if (blocks > 0x7fffffffLL) { err = "grid too large"; return WFK_EINVAL; }
+  if (a.lds_samples > WFK_SH_LCAP) { err = "short plan: unit longer than the staging array"; return WFK_EINVAL; }
+  const bool built = d.counts ? launch_short_dac<true>(a, d, fam, (unsigned)blocks, s)
+                              : launch_short_dac<false>(a, d, fam, (unsigned)blocks, s);
+  if (!built) { err = "short plan: no DAC build for op family " + std::to_string(fam); return WFK_EINVAL; }
+  if (hipGetLastError() != hipSuccess) { err = std::string("short DAC kernel launch failed: ") + hipGetErrorString(hipGetLastError()); return WFK_EHIP; }
+  return WFK_OK;
+}
 
 int wfk_launch_short(const SArgs& a, const SamplerPick& k, void* stream, std::string& err) {
   hipStream_t s = (hipStream_t)stream;

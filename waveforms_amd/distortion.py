@@ -1380,6 +1380,103 @@ def dac_codes_rows(sig, gain, offset=0.0, bits=16, shift=0, interleave=1, return
         return (codes, c.download((batch, 3), np.int64)) if return_counts else codes
 
 
+class SampledDac:
+    """`BatchSampler(channels, grid).launch_torch(z)` (float64) followed by `DacStage(gain, n, offset, ...)
+    .apply_torch(z)`, device-resident and bit for bit -- codes and counts -- with the float64 rows left out: a
+    microwave drive line has no predistortion between its waveform and its converter, so at AWG sample rates the
+    sampler's own kernel scales, rounds, saturates and stores the int16 codes (`fused`; `kernel_name()` is
+    'wfk_sample_short_dac<16,FAM,COUNT>'): 2 B per sample of HBM traffic instead of 8 written, 8 read and 2 written.
+    Plans the fused kernel does not take (`why_not`: long pieces, mixed plans, `interleave=2`, WFK_CHAIN_UNFUSED=1)
+    run the two launches through a float64 scratch taken once, here.  `gain` / `offset`: a scalar or one value per
+    channel; `bits`, `shift`, `interleave` and the optional (n_channels, 3) int64 counts as `DacStage` has them.
+    Build once, launch many times.
+
+        sd = SampledDac.from_full_scale(channels, wl.awg_grid(n, 2e9), 1.0)      # +-1.0 -> +-32767
+        sd.launch_torch(codes, counts=clipped)       # (n_channels, >= n) int16 device tensor, torch's current stream
+    """
+
+    def __init__(self, channels, grid, gain, offset=0.0, bits: int = 16, shift: int = 0, interleave: int = 1,
+                 function_lib=None, tile=1):
+        """`tile` > 1 repeats the channel list that many times (synthetic batches, as BatchSampler's)"""
+        from . import _flatten
+        channels = list(channels)
+        rows = len(channels) * max(int(tile), 1)
+        if rows < 1:
+            raise ValueError('SampledDac: no rows')
+        gains, offsets = (_per_row('SampledDac', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v, rows)
+                          for what, v in (('gain', gain), ('offset', offset)))
+        if not isinstance(grid, _flatten.wfk_grid):
+            grid = _flatten.grid_from_desc(grid)
+        # argument errors before any device work
+        _engine.dac_rows_arguments(gains, offsets, int(grid.n), bits, shift, interleave)
+        self.prog = _flatten.tile_program(_flatten.flatten(channels, grid, function_lib), tile)
+        if self.prog.n_channels != rows:
+            raise ValueError(f'SampledDac: {rows} gains for {self.prog.n_channels} rows')
+        if self.prog.complex_amp or self.prog.host_complex:
+            raise NotImplementedError('complex rows')
+        self.plan = _engine.ChainDacPlan(self.prog, grid, gains, offsets, bits, shift, interleave)
+        p = self.plan
+        self.n, self.n_channels, self.gain, self.offset = p.n, p.n_channels, p.gain, p.offset
+        self.bits, self.shift, self.interleave = p.bits, p.shift, p.interleave
+        self.lo, self.hi, self.out_rows, self.out_n = p.lo, p.hi, p.out_rows, p.out_n
+        self.fused, self.why_not = p.fused, p.why_not
+        # the unfused path's float64 rows: taken once, here
+        self._scratch = None if self.fused else _engine.DeviceBuffer(max(self.n_channels * self.n, 1) * 8)
+
+    @classmethod
+    def from_full_scale(cls, channels, grid, full_scale, **kw):
+        """the plan whose gain[r] = hi / full_scale[r], so that +-full scale maps to +-hi (a scalar: every row).
+        ValueError: a full scale that is not finite or not positive."""
+        bits = int(kw.get('bits', 16))
+        if not 2 <= bits <= 16:
+            raise ValueError('bits must lie in [2, 16]')
+        fs = np.asarray(full_scale, dtype=np.float64)
+        if not np.all(np.isfinite(fs) & (fs > 0.0)):
+            raise ValueError('SampledDac: every full scale must be finite and positive')
+        return cls(channels, grid, (2**(bits - 1) - 1) / fs, **kw)
+
+    def kernel_name(self, counts: bool = False) -> str:
+        """'wfk_sample_short_dac<16,FAM,COUNT>' | '<sampler kernels> + dac_rows<double>' (dac_rows_count with counts)"""
+        return self.plan.kernel_name(counts)
+
+    def launch(self, out_ptr, out_stride=None, counts_ptr=None, stream=0):
+        """raw pointers; out_stride in codes (None: out_n)"""
+        s = self._scratch
+        self.plan.launch(out_ptr, self.out_n if out_stride is None else out_stride, counts_ptr,
+                         None if s is None else s.ptr, self.n, stream)
+
+    def launch_torch(self, codes, counts=None):
+        """codes: (n_channels // interleave, >= interleave * n) row-contiguous int16 device tensor (rows may be a window
+        of a wider tensor); counts: None or a contiguous (n_channels, 3) int64 device tensor, overwritten with [below,
+        above, nan] per channel; it may share no memory with `codes` (ValueError).  Asynchronous on torch's current
+        stream.  -> codes[:, :out_n]"""
+        import torch
+        y0, ys = _rows.check_rows(codes, self.out_rows, self.out_n, torch.int16,
+                                  'expected codes: (out_rows, >=out_n) row-contiguous int16 device tensor')
+        c0 = _rows.check_state(counts, (self.n_channels, 3),
+                               'expected counts: contiguous (n_channels, 3) int64 device tensor', dtype=np.int64)
+        if not _rows.report_disjoint(c0, self.n_channels, 3, (y0, ys, self.out_rows, self.out_n, 2)):
+            raise ValueError('sampled dac: counts overlaps codes')
+        self.launch(y0, ys, c0, torch.cuda.current_stream(codes.device).cuda_stream)
+        return codes[:, :self.out_n]
+
+    def to_host(self, return_counts=False):
+        """NumPy codes (out_rows, out_n) [, counts (n_channels, 3)]"""
+        with contextlib.ExitStack() as stack:
+            y = _dev(stack, self.out_rows * self.out_n * 2)
+            c = _dev(stack, self.n_channels * 24) if return_counts else None
+            self.launch(y.ptr, None, None if c is None else c.ptr)
+            _engine.sync()
+            codes = y.download((self.out_rows, self.out_n), np.int16)
+            return (codes, c.download((self.n_channels, 3), np.int64)) if return_counts else codes
+
+    def close(self):
+        self.plan.close()
+        if self._scratch is not None:
+            self._scratch.close()
+            self._scratch = None
+
+
 class CurveStage:
     """Device-resident calibration curve over sample VALUES for `batch` rows of `n` samples (build once, apply many
     times): a flux pulse programmed in its physical unit (detuning, flux) to volts through the line's measured
