@@ -608,6 +608,44 @@ int64_t wfk_mix_rows_reads(const wfk_mix_rows_plan* plan);
 const char* wfk_mix_rows_kernel_name(const wfk_mix_rows_plan* plan);
 int wfk_mix_rows_plan_destroy(wfk_mix_rows_plan* plan);       /* NULL is fine */
 
+/* -- mixing across rows straight to DAC codes: wfk_mix_rows and wfk_dac_rows in one kernel --------- */
+/* codes = wfk_dac_rows(wfk_mix_rows(in)) bit for bit -- codes and counts -- without the float rows between the two:
+ * the matrix (CSR), mix_offset (rows_out values or NULL) and kind are those of wfk_mix_rows_plan_create; gain,
+ * dac_offset (rows_out values each), bits, shift and interleave those of wfk_dac_rows_plan_create for batch =
+ * rows_out.  Per sample, in double, without a fused multiply-add,
+ *   acc = 0.0;   for the terms of o in ascending c:  acc = fl(acc + fl(x[c, i] * M[o, c]));   y = fl(acc + mix_offset[o])
+ *   y = (double)(float)y     (kind F32 only: the two stages round the mixed row to float once)
+ *   v = fl(fl(y * gain[o]) + dac_offset[o]),   q = rint(v),   c = 0 if v is NaN, lo if q < lo, hi if q > hi, else q
+ *   out[g, i k + j] = ((int)c << shift as int16) of mix row o = g k + j   (k = interleave)
+ * Every refusal of the two creators applies with its text, the mix's first, before any device work; no device:
+ * WFK_EHIP.  One kernel, "mix_dac_rows<T,K,COUNT>": a workgroup owns a column span of a tile of
+ * WFK_MIX_DAC_TILE_ROWS consecutive mix output rows (tile / k code rows) and reads every input row the tile has a term
+ * on once; wfk_mix_dac_reads() is the sum over tiles of the number of such rows, so the kernel reads reads * n samples
+ * and writes rows_out * n codes.  wfk_mix_dac_span(): the codes of one row a workgroup covers (4096 k).
+ * wfk_mix_dac_apply() enqueues at most the zeroing of the counts and that kernel on `hip_stream`, and that is all it
+ * does to the device (as wfk_chain_dac_launch: it may be called while the stream is being captured).  in_stride is in samples, >= n; out_stride in codes, >= k n where there is more than one code row;
+ * counts_dev: NULL (the kernel then does no counting), or rows_out * 3 int64 [below, above, nan] per mix output row,
+ * OVERWRITTEN by every apply.  OUT OF PLACE only, and the input is never written: out that meets in, or counts that
+ * meet either, rows not aligned to their element, a stride below the row: WFK_EINVAL.  Nothing outside [0, n) of an
+ * input row or [0, k n) of a code row is read or written.  n = 0: the kernel is not launched; the counts are still
+ * zeroed.  The plan owns its small tables and nothing else, so it may serve several streams. */
+#define WFK_MIX_DAC_TILE_ROWS 4
+typedef struct wfk_mix_dac_plan wfk_mix_dac_plan;
+int wfk_mix_dac_plan_create(int64_t n, int32_t rows_out, int32_t rows_in, int kind /* WFK_OUT_F64|F32 */,
+                            const int64_t* row_ptr, const int32_t* col, const double* val,
+                            const double* mix_offset /* or NULL */, const double* gain, const double* dac_offset,
+                            int bits, int shift, int interleave, wfk_mix_dac_plan** out);
+int wfk_mix_dac_apply(wfk_mix_dac_plan* plan, const void* in_dev, int64_t in_stride,
+                      int16_t* out_dev, int64_t out_stride /* in codes, >= interleave * n */,
+                      int64_t* counts_dev /* rows_out * 3, or NULL */, void* hip_stream);
+/* sum over tiles of the size of the input union; 0 for NULL */
+int64_t wfk_mix_dac_reads(const wfk_mix_dac_plan* plan);
+/* the codes of one row a workgroup covers; 0 for NULL */
+int64_t wfk_mix_dac_span(const wfk_mix_dac_plan* plan);
+/* "mix_dac_rows<double,2,true>": T in {double, float}, K = interleave, COUNT = with_counts; "" for NULL; static */
+const char* wfk_mix_dac_kernel_name(const wfk_mix_dac_plan* plan, int with_counts);
+int wfk_mix_dac_plan_destroy(wfk_mix_dac_plan* plan);         /* NULL is fine */
+
 /* -- per-row calibration curve: piecewise-linear lookup over sample VALUES ------------------------ */
 /* `batch` real rows of n samples (kind: WFK_OUT_F64 or WFK_OUT_F32) go through a curve of their own: a flux pulse
  * programmed in its physical unit to volts through a measured monotone curve, an amplifier's compression table, a

@@ -169,6 +169,16 @@ def lib():
         l.wfk_mix_rows_kernel_name.argtypes = [VP]
         l.wfk_mix_rows_kernel_name.restype = C.c_char_p
         l.wfk_mix_rows_plan_destroy.argtypes = [VP]
+        l.wfk_mix_dac_plan_create.argtypes = [I64, I32, I32, C.c_int, VP, VP, VP, VP, VP, VP, C.c_int, C.c_int, C.c_int,
+                                              P(VP)]
+        l.wfk_mix_dac_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP]
+        l.wfk_mix_dac_reads.argtypes = [VP]
+        l.wfk_mix_dac_reads.restype = I64
+        l.wfk_mix_dac_span.argtypes = [VP]
+        l.wfk_mix_dac_span.restype = I64
+        l.wfk_mix_dac_kernel_name.argtypes = [VP, C.c_int]
+        l.wfk_mix_dac_kernel_name.restype = C.c_char_p
+        l.wfk_mix_dac_plan_destroy.argtypes = [VP]
         l.wfk_curve_rows_plan_create.argtypes = [I64, I32, C.c_int, VP, VP, VP, VP, VP, P(VP)]
         l.wfk_curve_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP]
         l.wfk_curve_rows_spans.argtypes = [VP]
@@ -1053,6 +1063,67 @@ class MixRowsPlan(_Handle):
 
     def kernel_name(self) -> str:
         return lib().wfk_mix_rows_kernel_name(self._h).decode()
+
+
+MIX_DAC_TILE_ROWS = 4      # WFK_MIX_DAC_TILE_ROWS
+
+
+def mix_dac_arguments(matrix, mix_offset, gain, dac_offset, n, bits=16, shift=0, interleave=1, dtype=np.float64):
+    """the arguments of a MixDacPlan, checked on the host: mix_rows_arguments(matrix, mix_offset, n, dtype), then
+    dac_rows_arguments(gain, dac_offset, n, bits, shift, interleave, dtype) for one gain and offset per OUTPUT row of
+    the matrix -> (rows_in, row_ptr, col, val, mix_offset, gain, dac_offset, n, bits, shift, interleave, dtype).
+    ValueError / NotImplementedError as the two list them, the mix's first.  Needs no device."""
+    rows_in, row_ptr, col, val, mix_offset, n, dtype = _mix_rows_checked(matrix, mix_offset, n, dtype)
+    gain, dac_offset, n, bits, shift, interleave, dtype = dac_rows_arguments(gain, dac_offset, n, bits, shift,
+                                                                             interleave, dtype)
+    if len(gain) != len(row_ptr) - 1:
+        raise ValueError(f'{len(gain)} gains for {len(row_ptr) - 1} output rows')
+    return rows_in, row_ptr, col, val, mix_offset, gain, dac_offset, n, bits, shift, interleave, dtype
+
+
+def mix_dac_reads(row_ptr, col) -> int:
+    """mix_rows_reads at the fused kernel's tile height, MIX_DAC_TILE_ROWS (wfk_mix_dac_reads, computed on the host)"""
+    row_ptr, col = np.asarray(row_ptr), np.asarray(col)
+    return sum(len(np.unique(col[row_ptr[o]:row_ptr[min(o + MIX_DAC_TILE_ROWS, len(row_ptr) - 1)]]))
+               for o in range(0, len(row_ptr) - 1, MIX_DAC_TILE_ROWS))
+
+
+class MixDacPlan(_Handle):
+    """DacRowsPlan(gain, dac_offset, ...) on what MixRowsPlan(matrix, mix_offset, ...) gives, in ONE kernel and bit for
+    bit -- codes and counts -- without the float rows between them (wfk_mix_dac_plan_create): rows_in rows of n float64 /
+    float32 samples -> `.out_rows` = rows_out // interleave rows of `.out_n` = interleave * n int16 codes.  `.rows_out`,
+    `.rows_in`, `.nnz`, `.reads` (mix_dac_reads), `.lo` / `.hi`.  ValueError before any device work: what MixRowsPlan
+    and DacRowsPlan list, and a number of gains other than rows_out."""
+    _destroy = 'wfk_mix_dac_plan_destroy'
+
+    def __init__(self, matrix, mix_offset, gain, dac_offset, n: int, bits: int = 16, shift: int = 0,
+                 interleave: int = 1, dtype=np.float64):
+        (self.rows_in, self.row_ptr, self.col, self.val, self.mix_offset, self.gain, self.dac_offset, self.n, self.bits,
+         self.shift, self.interleave, self.dtype) = mix_dac_arguments(matrix, mix_offset, gain, dac_offset, n, bits,
+                                                                      shift, interleave, dtype)
+        self.rows_out, self.nnz = len(self.row_ptr) - 1, len(self.col)
+        self.reads = mix_dac_reads(self.row_ptr, self.col)
+        self.lo, self.hi = -2**(self.bits - 1), 2**(self.bits - 1) - 1
+        self.out_rows, self.out_n = self.rows_out // self.interleave, self.interleave * self.n
+        check(lib().wfk_mix_dac_plan_create(self.n, self.rows_out, self.rows_in, _KIND_OF[self.dtype],
+                                            self.row_ptr.ctypes.data, self.col.ctypes.data, self.val.ctypes.data,
+                                            self.mix_offset.ctypes.data, self.gain.ctypes.data,
+                                            self.dac_offset.ctypes.data, self.bits, self.shift, self.interleave,
+                                            C.byref(self._h)))
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, counts_ptr=None, stream=0):
+        """counts_ptr: None, or rows_out * 3 int64 on the device, overwritten with [below, above, nan] per mix row"""
+        check(lib().wfk_mix_dac_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, counts_ptr, stream))
+
+    def library_reads(self) -> int:
+        return int(lib().wfk_mix_dac_reads(self._h))
+
+    def span(self) -> int:
+        """the codes of one row a workgroup covers"""
+        return int(lib().wfk_mix_dac_span(self._h))
+
+    def kernel_name(self, counts: bool = False) -> str:
+        return lib().wfk_mix_dac_kernel_name(self._h, 1 if counts else 0).decode()
 
 
 CURVE_MAX_KNOTS = 1024     # WFK_CURVE_MAX_KNOTS

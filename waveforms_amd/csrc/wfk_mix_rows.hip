@@ -28,6 +28,7 @@
 
 #include "wfk.h"
 #include "wfk_host.h"
+#include "wfk_mix_tables.h"
 #include "wfk_rows_dev.h"
 
 #pragma clang fp contract(off)   // a rounded product and a rounded sum, as the host formula
@@ -37,12 +38,6 @@ namespace {
 constexpr int kTile = WFK_MIX_TILE_ROWS;   // output rows per tile
 constexpr int kChunk = 8;                  // input rows whose loads are in flight together
 static_assert(kTile <= 32, "the term mask of a union entry is one 32-bit word");
-
-// one entry of a tile's input list: the input row, and bit j set where row j of the tile has a term on it
-struct MixEntry {
-  int32_t col;
-  uint32_t mask;
-};
 
 // the V elements of the slot that starts at element i0 of the row x[0 .. n); `vec`: the row's slot addresses are
 // 16-byte aligned.  Elements outside [0, n) are not read (and come out 0).
@@ -201,67 +196,23 @@ int wfk_mix_rows_plan_create(int64_t n, int32_t rows_out, int32_t rows_in, int k
                              wfk_mix_rows_plan** out) try {
   if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
-  if (!row_ptr) return wfk_fail(WFK_EINVAL, "mix rows plan: null row_ptr");
-  if (rows_out < 1) return wfk_fail(WFK_EINVAL, "mix rows plan: rows_out < 1");
-  if (rows_in < 1) return wfk_fail(WFK_EINVAL, "mix rows plan: rows_in < 1");
-  if (n < 0) return wfk_fail(WFK_EINVAL, "mix rows plan: n < 0");
-  if (const int rc = wfk_check_kind(kind)) return rc;
-  bool rising = row_ptr[0] == 0;
-  for (int32_t r = 0; r < rows_out && rising; ++r) rising = row_ptr[r + 1] >= row_ptr[r];
-  if (!rising) return wfk_fail(WFK_EINVAL, "mix rows plan: row_ptr is not non-decreasing from 0");
-  if (row_ptr[rows_out] > 0 && (!col || !val)) return wfk_fail(WFK_EINVAL, "mix rows plan: null col / val");
-  for (int32_t r = 0; r < rows_out; ++r) {
-    const std::string row = "row " + std::to_string(r) + ": ";
-    for (int64_t k = row_ptr[r]; k < row_ptr[r + 1]; ++k) {
-      if (col[k] < 0 || col[k] >= rows_in)
-        return wfk_fail(WFK_EINVAL, row + "column " + std::to_string(col[k]) + " is out of range");
-      if (k > row_ptr[r] && col[k] <= col[k - 1]) return wfk_fail(WFK_EINVAL, row + "columns are not ascending");
-      if (!std::isfinite(val[k]))
-        return wfk_fail(WFK_EINVAL, row + "coefficient (" + std::to_string(r) + ", " + std::to_string(col[k]) +
-                                        ") is not finite");
-    }
-    if (offset && !std::isfinite(offset[r])) return wfk_fail(WFK_EINVAL, row + "offset is not finite");
-  }
+  if (const int rc = wfk_mix_check(n, rows_out, rows_in, kind, row_ptr, col, val, offset)) return rc;
   const int64_t tiles = ((int64_t)rows_out + kTile - 1) / kTile;
   const int V = 16 / (int)wfk_elem_size(kind);
   uint32_t bpr = 0;
   if (const int rc = wfk_row_blocks("mix rows plan", n, (int64_t)kSlots * kThreads * V, V - 1, tiles, &bpr)) return rc;
-  // per tile: the sorted union of the columns its rows have terms on (zeros in val are not terms), and per (union
-  // entry, tile row) the coefficient
-  std::vector<int64_t> tile_ptr((size_t)tiles + 1, 0);
-  std::vector<MixEntry> entries;
-  std::vector<double> coef, offs((size_t)tiles * kTile, 0.0);
-  std::vector<int32_t> cols;
-  for (int64_t t = 0; t < tiles; ++t) {
-    const int64_t o0 = t * kTile, o1 = std::min<int64_t>(o0 + kTile, rows_out);
-    cols.clear();
-    for (int64_t k = row_ptr[o0]; k < row_ptr[o1]; ++k)
-      if (val[k] != 0.0) cols.push_back(col[k]);
-    std::sort(cols.begin(), cols.end());
-    cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-    const size_t u0 = entries.size();
-    for (const int32_t c : cols) entries.push_back(MixEntry{c, 0u});
-    coef.resize(entries.size() * kTile, 0.0);
-    for (int64_t o = o0; o < o1; ++o) {
-      for (int64_t k = row_ptr[o]; k < row_ptr[o + 1]; ++k) {
-        if (val[k] == 0.0) continue;
-        const size_t u = u0 + (size_t)(std::lower_bound(cols.begin(), cols.end(), col[k]) - cols.begin());
-        entries[u].mask |= 1u << (o - o0);
-        coef[u * kTile + (size_t)(o - o0)] = val[k];
-      }
-      if (offset) offs[(size_t)o] = offset[o];
-    }
-    tile_ptr[(size_t)t + 1] = (int64_t)entries.size();
-  }
+  const MixTiles tiled = wfk_mix_tiles(kTile, rows_out, row_ptr, col, val);
+  std::vector<double> offs((size_t)tiles * kTile, 0.0);
+  if (offset) std::copy(offset, offset + rows_out, offs.begin());
   if (!wfk_have_device()) return wfk_fail(WFK_EHIP, "no HIP device visible");
   std::unique_ptr<wfk_mix_rows_plan> p(new wfk_mix_rows_plan());
   p->n = n; p->rows_out = rows_out; p->rows_in = rows_in; p->kind = kind;
-  p->reads = (int64_t)entries.size();
+  p->reads = (int64_t)tiled.entries.size();
   p->tiles = (uint32_t)tiles; p->blocks_per_row = bpr;
   DevTables tab;
-  p->ptr_off = tab.add(tile_ptr);
-  p->entries_off = tab.add(entries);
-  p->coef_off = tab.add(coef);
+  p->ptr_off = tab.add(tiled.tile_ptr);
+  p->entries_off = tab.add(tiled.entries);
+  p->coef_off = tab.add(tiled.coef);
   p->offset_off = tab.add(offs);
   if (const int rc = wfk_upload_tables("mix rows plan", tab, p->tables)) return rc;
   *out = p.release();

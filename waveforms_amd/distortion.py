@@ -1380,6 +1380,116 @@ def dac_codes_rows(sig, gain, offset=0.0, bits=16, shift=0, interleave=1, return
         return (codes, c.download((batch, 3), np.int64)) if return_counts else codes
 
 
+class MixDacStage:
+    """`MixStage(matrix, n, mix_offset, dtype).apply_torch(x)` followed by `DacStage(gain, n, dac_offset, bits, shift,
+    interleave, dtype, batch=rows_out).apply_torch(., counts=)`, device-resident and bit for bit -- codes and counts --
+    in ONE kernel ('mix_dac_rows<T,K,COUNT>') without the float rows between the two: the inverse crosstalk matrix of
+    the flux lines, or the 2 x 2 mixer correction and DC offset of every IQ pair, ending in the int16 codes of the
+    converter.  In float64, product and sum each rounded, terms in ascending column (see `MixStage`, `DacStage`):
+        y = sum of x[c, i] * M[o, c] + mix_offset[o]       (a float32 plan rounds y to float32 once, as the two stages)
+        code[o, i] = saturate(rint(y * gain[o] + dac_offset[o])) * 2**shift;   out[g, i * k + j] = code[g * k + j, i]
+    `gain` / `dac_offset`: a scalar (every row) or one value per OUTPUT row of the matrix; `interleave=2` packs the mixed
+    rows [I, Q] of a pair into one code row I0 Q0 I1 Q1 ...  An optional (rows_out, 3) int64 counts tensor is OVERWRITTEN
+    by every apply with [below, above, nan] per mixed row.  `.rows_out`, `.rows_in`, `.nnz`; `.reads`: the input rows
+    the kernel reads at its tile height `_engine.MIX_DAC_TILE_ROWS`; `.span`: the codes of one row a workgroup covers;
+    `.out_rows`, `.out_n`, `.lo`, `.hi`, `.gain`, `.offset` (the DAC's; `.mix_offset`: the mix's).
+
+        st = MixDacStage.from_blocks([[[a, b], [c, d]], ...], n, gain, mix_offset=leak, interleave=2)
+        codes = st.apply_torch(x, counts=clipped)               # out of place, on torch's current stream
+    """
+
+    def __init__(self, matrix, n: int, gain, mix_offset=None, dac_offset=0.0, bits: int = 16, shift: int = 0,
+                 interleave: int = 1, dtype=np.float64):
+        rows_out = _engine._mix_rows_csr(matrix)[0]
+        gains, offsets = (_per_row('MixDacStage', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v,
+                                   rows_out) if rows_out >= 1 else [0.0]
+                          for what, v in (('gain', gain), ('offset', dac_offset)))
+        self.plan = _engine.MixDacPlan(matrix, mix_offset, gains, offsets, n, bits, shift, interleave, dtype)
+        p = self.plan
+        self.n, self.dtype, self.mix_offset, self.gain, self.offset = p.n, p.dtype, p.mix_offset, p.gain, p.dac_offset
+        self.rows_out, self.rows_in, self.nnz, self.reads = p.rows_out, p.rows_in, p.nnz, p.reads
+        self.bits, self.shift, self.interleave = p.bits, p.shift, p.interleave
+        self.lo, self.hi, self.out_rows, self.out_n = p.lo, p.hi, p.out_rows, p.out_n
+        self.span = p.span()
+
+    @classmethod
+    def from_blocks(cls, blocks, n: int, gain, **kw):
+        """the stage of the block-diagonal matrix of a list of small 2-D arrays (`MixStage.from_blocks`)"""
+        return cls(MixStage.block_diagonal(blocks), n, gain, **kw)
+
+    @classmethod
+    def from_full_scale(cls, matrix, n: int, full_scale, **kw):
+        """the stage whose gain[o] = hi / full_scale[o], so that a mixed +-full scale maps to +-hi (a scalar: every
+        row).  ValueError: a full scale that is not finite or not positive."""
+        bits = int(kw.get('bits', 16))
+        if not 2 <= bits <= 16:
+            raise ValueError('bits must lie in [2, 16]')
+        fs = np.asarray(full_scale, dtype=np.float64)
+        if not np.all(np.isfinite(fs) & (fs > 0.0)):
+            raise ValueError('MixDacStage: every full scale must be finite and positive')
+        return cls(matrix, n, (2**(bits - 1) - 1) / fs, **kw)
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, counts_ptr=None, stream=0):
+        self.plan.apply(in_ptr, in_stride, out_ptr, out_stride, counts_ptr, stream)
+
+    def kernel_name(self, counts: bool = False) -> str:
+        return self.plan.kernel_name(counts)
+
+    def apply_torch(self, x, out=None, counts=None):
+        """x: (rows_in, >= n) row-contiguous device tensor of the stage's dtype; out: (out_rows, >= out_n) int16 (rows
+        may be windows of a wider tensor; None: allocated); counts: None or a contiguous (rows_out, 3) int64 device
+        tensor, overwritten.  Out of place: `out` may share no memory with `x`, `counts` with neither (ValueError);
+        `x` is never written.  Asynchronous on torch's current stream.  -> out[:, :out_n]"""
+        import torch
+        x0, xs = _rows.check_rows(x, self.rows_in, self.n, _rows.torch_dtype(self.dtype),
+                                  'expected x: (rows_in, >=n) row-contiguous device tensor of the stage dtype')
+        if out is None:
+            out = torch.empty((self.out_rows, self.out_n), dtype=torch.int16, device=x.device)
+        y0, ys = _rows.check_rows(out, self.out_rows, self.out_n, torch.int16,
+                                  'expected out: (out_rows, >=out_n) row-contiguous int16 device tensor')
+        c0 = _rows.check_state(counts, (self.rows_out, 3),
+                               'expected counts: contiguous (rows_out, 3) int64 device tensor', dtype=np.int64)
+        xr, yr = (x0, xs, self.rows_in, self.n, self.dtype.itemsize), (y0, ys, self.out_rows, self.out_n, 2)
+        if not _rows.rows_disjoint(xr, yr):
+            raise ValueError('mix dac stage is out of place: out overlaps x')
+        if not _rows.report_disjoint(c0, self.rows_out, 3, xr, yr):
+            raise ValueError('mix dac stage: counts overlaps x / out')
+        self.apply(x0, xs, y0, ys, c0, torch.cuda.current_stream(x.device).cuda_stream)
+        return out[:, :self.out_n]
+
+    def close(self):
+        self.plan.close()
+
+
+def mix_dac_rows(sig, matrix, gain, mix_offset=None, dac_offset=0.0, bits=16, shift=0, interleave=1,
+                 return_counts=False):
+    """`dac_codes_rows(mix_rows(sig, matrix, mix_offset), gain, dac_offset, bits, shift, interleave)` in one launch
+    (see `MixDacStage`): NumPy in, NumPy out, (rows of the matrix // interleave, interleave * samples) int16.  float32
+    rows stay float32 on the way in, anything else is read as float64.  `return_counts`: -> (codes, counts), counts the
+    (rows of the matrix, 3) int64 [below, above, nan].  ValueError before any device work: sig not 2-D, a matrix whose
+    columns are not the rows of sig, what `MixDacStage` refuses.  NotImplementedError: complex rows."""
+    sig2 = _rows_signal_f32('mix_dac_rows', sig)
+    batch, n = sig2.shape
+    rows_out = _engine._mix_rows_csr(matrix)[0]
+    gains = _per_row('mix_dac_rows', 'gain', gain, max(rows_out, 1))
+    offsets = _per_row('mix_dac_rows', 'offset', dac_offset, max(rows_out, 1))
+    rows_in = _engine.mix_dac_arguments(matrix, mix_offset, gains, offsets, n, bits, shift, interleave, sig2.dtype)[0]
+    if rows_in != batch:
+        raise ValueError(f'mix_dac_rows: a matrix of {rows_in} columns for {batch} rows')
+    k = int(interleave)
+    if n == 0:
+        codes, counts = np.zeros((rows_out // k, 0), dtype=np.int16), np.zeros((rows_out, 3), dtype=np.int64)
+        return (codes, counts) if return_counts else codes
+    with _engine.MixDacPlan(matrix, mix_offset, gains, offsets, n, bits, shift, k, sig2.dtype) as plan, \
+            _engine.DeviceBuffer(sig2.nbytes) as x, _engine.DeviceBuffer(rows_out * n * 2) as y, \
+            _engine.DeviceBuffer(rows_out * 24) as c:
+        x.upload(sig2)
+        plan.apply(x.ptr, n, y.ptr, k * n, c.ptr if return_counts else None)
+        _engine.sync()
+        codes = y.download((rows_out // k, k * n), np.int16)
+        return (codes, c.download((rows_out, 3), np.int64)) if return_counts else codes
+
+
 class SampledDac:
     """`BatchSampler(channels, grid).launch_torch(z)` (float64) followed by `DacStage(gain, n, offset, ...)
     .apply_torch(z)`, device-resident and bit for bit -- codes and counts -- with the float64 rows left out: a
