@@ -229,9 +229,23 @@ int wfk_fir_plan_create_rows(const double* kers_host, int32_t K, int64_t n,
 /* Row r: n elements at in_dev + r * in_stride -> out_dev + r * out_stride (strides in elements, >= n).
  * OUT OF PLACE: workgroups read input that belongs to the blocks of others, and a long kernel reads `in` in
  * several passes.  WFK_EINVAL if [in, in + (batch-1)*in_stride + n) and [out, out + (batch-1)*out_stride + n)
- * share a byte.                                                                                            */
+ * share a byte.
+ * Non-finite input: a NaN or Inf in sample p of row r reaches every output of row r that was computed in one
+ * transform with it, and no other row.  That is at least out[r][p - K/2 .. p - K/2 + K) (the outputs whose sum has a
+ * term on sample p; none of them is ever finite) and at most the output blocks of the windows that read sample p: on
+ * the on-chip transform blocks of M = 4097 - Kseg samples (Kseg = K up to 1537 taps, else ceil(K / nseg) with nseg =
+ * ceil(K / 1537) passes, pass j reading j * Kseg samples earlier), window b reading in[b M - lead, b M - lead + 4096),
+ * lead = Kseg - 1 - K/2 + j Kseg, and taking the block of its pair partner b ^ 1 with it (two windows share one
+ * complex transform): 6146 samples for K = 1024; on the rocFFT pipeline blocks of M = L - K + 1 samples, no partner.
+ * Every output outside that span is bit for bit what it is without the bad sample.  (scipy's fftconvolve, one
+ * transform per signal, loses the whole row.)                                                               */
 int wfk_fir_apply(wfk_fir_plan* plan, const void* in_dev, int64_t in_stride,
                   void* out_dev, int64_t out_stride, void* hip_stream);
+/* The form wfk_fir_apply runs: "fir_fused<T>" (" x N" behind it for a kernel cut into N accumulated passes,
+ * " per-row spectra" for wfk_fir_plan_create_rows) or "fir_gather<T> + rocfft<L=..,rows=..> + fir_multiply<T> +
+ * fir_scatter<T>" (transform length, rows per chunk); "" for n == 0.  The string belongs to the calling thread and
+ * lasts until its next call.                                                                                */
+const char* wfk_fir_kernel_name(const wfk_fir_plan* plan);
 int wfk_fir_plan_destroy(wfk_fir_plan* plan);
 
 /* -- sampler -> FIR chain (BASELINE configs[3]) --------------------------------- */
@@ -244,6 +258,10 @@ int wfk_fir_plan_destroy(wfk_fir_plan* plan);
  * windows are sampled the short tier's way (fir_short); pieces without a short form travel through a
  * sparsely written workspace.  Otherwise the plan owns a workspace and runs
  * sampler -> workspace -> FIR (wfk_chain_is_fused() == 0, wfk_chain_unfused_reason() says why).
+ * Non-finite samples: a NaN or Inf that channel r's program evaluates to at sample p (a table envelope with a bad
+ * knot) reaches row r as it does through wfk_fir_apply, and no other row -- fused, the windows hop 3072 samples (K <=
+ * 1025) or 2560, window b reads samples [b hop - lead, b hop - lead + 4096), lead = K - 1 - K/2, and takes the block
+ * of its pair partner with it; unfused, the geometry is that of wfk_fir_apply.
  * wfk_chain_launch() allocates nothing and does not synchronise.                              */
 typedef struct wfk_chain_plan wfk_chain_plan;
 int wfk_chain_plan_create(const wfk_program* prog, const wfk_grid* grid, const double* ker_host,
@@ -277,6 +295,17 @@ int wfk_chain_plan_destroy(wfk_chain_plan* plan);
  * look-back); other shapes as a block scan in three launches; cascades of mixed orders or beyond
  * those sizes as consecutive passes.  A plan owns scratch state for its launches: use one plan per
  * concurrent stream.  In place (out_dev == in_dev) is allowed in every form.
+ * Non-finite input: a NaN or Inf in sample p of row r reaches out[r][p .. n) and all of zf[r], and no other row, in
+ * every form: nothing from p on is ever finite again, however far behind the sample lies (a transition power that
+ * has underflowed to zero times a non-finite state is NaN, not 0), everything before p and every other row are what
+ * they are without it.  That is bit for bit in the three-launch form.  The single pass is reproducible to rounding
+ * only, with or without a bad sample: a chunk's start state is a sum that closes on whichever earlier chunk of the
+ * row has published its prefix when the wave looks, every choice the same sum in another association, so two applies
+ * of one plan on one input may differ in the last bit (measured: one sample one ulp off in 18 of 150 applies).  A
+ * look-back in double-double rounded once removes that and costs 7-8 % of the kernel (256 x 1e7 fp64, same box: 9.48
+ * -> 10.21 ms two biquads, 10.84 -> 11.59 ms four first-order sections): not built in.
+ * Such a NaN is data: wfk_iir_status stays WFK_OK and the plan keeps its form.
+ * (+-Inf comes out as NaN in most places, as from scipy.signal.lfilter: non-finite is the promise, not the value.)
  * wfk_iir_apply() allocates nothing and does not synchronise: the single pass clears its tickets and chunk flags with
  * a small kernel in front of its own, a cut cascade repacks zi / zf with device-to-device copies.                  */
 typedef struct wfk_iir_plan wfk_iir_plan;
@@ -313,7 +342,10 @@ int wfk_iir_plan_destroy(wfk_iir_plan* plan);
  * written once; no workgroup waits for another, so there is no status call and no timeout, and results are
  * bitwise reproducible and independent of a row's position in the batch.  The plan holds one table of block
  * transition matrices per row (built in quad precision at creation, ~18 KB per row at state dimension 4) and no
- * scratch: a plan may serve several streams at once.  wfk_iir_rows_apply() allocates nothing and does not
+ * scratch: a plan may serve several streams at once.  Non-finite input: a NaN or Inf in sample p of row r reaches
+ * out[r][p .. n) and all of zf[r] (the entries of its own sections; padding entries stay zero), none of which is ever
+ * finite, and no other row; out[r][0 .. p) and the other rows are bit for bit what they are without it.
+ * wfk_iir_rows_apply() allocates nothing and does not
  * synchronise; in place (out_dev == in_dev) is allowed; strides are in elements.                              */
 typedef struct wfk_iir_rows_plan wfk_iir_rows_plan;
 int wfk_iir_rows_plan_create(int32_t n_sections, const int32_t* orders, const double* b_rows,
@@ -344,6 +376,9 @@ int wfk_iir_rows_plan_destroy(wfk_iir_rows_plan* plan);
  * the wave that owns a chunk of the scan (8192 or 16384 samples) EVALUATES its input instead of loading it (iir_sampled): the
  * unfiltered samples never touch HBM and the pass moves the 8 (4) B/sample of its output only.  Otherwise
  * sampler -> (in place) IIR.  The FIR stage reads the filtered rows from a workspace the plan owns.
+ * Non-finite samples: a NaN or Inf that channel r's program evaluates to at sample p reaches out[r][p .. n) and zf[r]
+ * as through wfk_iir_apply (with a FIR behind the cascade: from p - K/2 on, back to the start of the first window that
+ * reads sample p at most), and no other row; it is data, not a time-out: the status stays WFK_OK.
  * wfk_chain_iir_launch() allocates nothing and does not synchronise; status / timeout semantics as wfk_iir_status
  * (after a timeout the plan runs unfused in the three-launch form).                                            */
 typedef struct wfk_chain_iir_plan wfk_chain_iir_plan;
@@ -376,6 +411,8 @@ int wfk_chain_iir_plan_destroy(wfk_chain_iir_plan* plan);
  * fine grid, table / mollifier envelopes and corrected carriers at AWG rates, mixed plans, WFK_CHAIN_UNFUSED=1 --
  * runs the sampler into `out` and iir_rows_tile in place on it; the name is then the two kernels joined with " + "
  * and the reason is never empty.  The decision is taken once, at creation.
+ * Non-finite samples: a NaN or Inf that channel c's program evaluates to at sample p reaches out[c][p .. n) and
+ * zf[c], as through wfk_iir_rows_apply, and no other row.
  * wfk_chain_iir_rows_launch() allocates nothing and does not synchronise; n == 0 launches nothing.  The strings
  * live as long as the plan.                                                                                      */
 typedef struct wfk_chain_iir_rows_plan wfk_chain_iir_rows_plan;
@@ -398,7 +435,9 @@ int wfk_chain_iir_rows_plan_destroy(wfk_chain_iir_rows_plan* plan);
 typedef struct wfk_spectral_plan wfk_spectral_plan;
 int wfk_spectral_plan_create(int64_t n, int32_t batch, int kind, wfk_spectral_plan** out);
 /* The one H serves all `batch` rows.  In place (out_dev == in_dev) is allowed: the input is copied to a
- * staging buffer of the plan before anything is written.  Asynchronous on `hip_stream`:
+ * staging buffer of the plan before anything is written.  Non-finite input: a NaN or Inf anywhere in row r reaches
+ * all of out[r] (one transform per row: no element of it is finite) and no other row -- the batched transform never
+ * mixes rows; the other rows are bit for bit what they are without it.  Asynchronous on `hip_stream`:
  * wfk_spectral_apply() allocates nothing and does not synchronise (the plan owns rocFFT's work buffer).  */
 int wfk_spectral_apply(wfk_spectral_plan* plan, const void* in_dev, void* out_dev,
                        const void* H_dev, void* hip_stream);
@@ -419,7 +458,9 @@ int wfk_spectral_plan_destroy(wfk_spectral_plan* plan);
  * The plan owns the batched rocFFT pair, its work / spectrum / staging buffers and the term table.
  * wfk_spectral_rows_apply() allocates nothing and does not synchronise; strides are in elements, >= n, otherwise
  * arbitrary; in place (out_dev == in_dev) and any other overlap are allowed (the input is staged before anything
- * is written).  A row's result does not depend on its position in the batch.  One plan per concurrent stream. */
+ * is written).  A row's result does not depend on its position in the batch.  One plan per concurrent stream.
+ * Non-finite input: a NaN or Inf anywhere in row r reaches all of out[r] (one transform per row: no element of it is
+ * finite) and no other row; the other rows are bit for bit what they are without it.                            */
 #define WFK_SPEC_ROWS_MAX_TERMS 8
 enum { WFK_SPEC_REFLECT = 0, WFK_SPEC_CORRECT = 1, WFK_SPEC_DELAY = 2 };
 typedef struct wfk_spec_term {

@@ -117,8 +117,8 @@ def test_grid_slices_are_the_same_samples():
 
 
 def _poison_worker(rank, world, port, q):
-    """rank 1 of 3 fails in its own pass: ranks 1 AND 2 must raise (rank 2 receives a NaN-poisoned state instead
-    of waiting in recv for ever), rank 0 completes"""
+    """rank 1 of 3 fails in its own pass: ranks 1 AND 2 must raise (rank 2 receives a message whose status column is
+    set instead of waiting in recv for ever), rank 0 completes"""
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
     dist.init_process_group('gloo', rank=rank, world_size=world)
@@ -148,6 +148,84 @@ def _poison_worker(rank, world, port, q):
         q.put((rank, repr(e)))
     finally:
         dist.destroy_process_group()
+
+
+NAN_STATE = [[1.5, float('nan')], [float('inf'), -2.0], [0.25, -0.0]]      # what rank 0 hands on in case 'nan_state'
+
+
+def _hand_off_worker(rank, world, port, q, case):
+    """two ranks, `apply_local` a host function on CPU tensors.
+    'nan_state': rank 0's final state holds a NaN and an Inf -- data: rank 1's apply_local must see it bit for bit.
+    'value_error': rank 0's apply_local raises ValueError -- rank 1 must raise, not wait in recv."""
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port))
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    try:
+        from waveforms_amd._dist import TimeShardedIir
+        seen = {}
+
+        class _Sampler:
+            n_channels = 3
+
+        class _Stage(TimeShardedIir):
+            def __init__(self):
+                self.sampler, self.D = _Sampler(), 2
+                self.sampler.rank, self.sampler.world = rank, world
+
+            def apply_local(self, x, y, state, initial=0.0):
+                assert state.shape == (3, 2) and state.is_contiguous() and state.dtype == torch.float64
+                seen['state'] = state.clone()
+                if rank == 0:
+                    if case == 'value_error':
+                        raise ValueError('bad argument on rank 0')
+                    return torch.tensor(NAN_STATE, dtype=torch.float64)
+                return state * 2.0
+
+        x = torch.zeros((3, 8), dtype=torch.float64)
+        try:
+            zf = _Stage().apply_torch(x, x)
+            if rank == 1:       # bit for bit: NaN, Inf and -0.0 as they were sent; and its own final state comes back
+                want = torch.tensor(NAN_STATE, dtype=torch.float64)
+                same = torch.equal(seen['state'].view(torch.int64), want.view(torch.int64))
+                back = zf is not None and torch.equal(zf.view(torch.int64), (want * 2.0).view(torch.int64))
+                q.put((rank, 'state handed on' if same and back else 'state changed: %r -> %r' % (seen['state'], zf)))
+            else:
+                q.put((rank, 'done' if zf is None else 'state'))
+        except Exception as e:
+            q.put((rank, 'raised %s: %s' % (type(e).__name__, str(e)[:120])))
+    except Exception as e:  # pragma: no cover
+        q.put((rank, repr(e)))
+    finally:
+        dist.destroy_process_group()
+
+
+def _run_hand_off(case, port0):
+    ctx = mp.get_context('spawn')
+    q = ctx.Queue()
+    port = port0 + os.getpid() % 2000
+    procs = [ctx.Process(target=_hand_off_worker, args=(r, 2, port, q, case)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = dict(q.get(timeout=180) for _ in procs)       # (a rank left in recv would run into this limit)
+    for p in procs:
+        p.join(timeout=60)
+    return res
+
+
+def test_a_nan_state_is_data_and_flows_through_the_hand_off():
+    """the failure travels in a status column of the message, not in the state: a NaN / Inf state -- a non-finite
+    sample, an unstable cascade -- reaches the next rank's apply_local unchanged and nobody raises, as in the unsharded
+    stage and in scipy"""
+    res = _run_hand_off('nan_state', 33500)
+    assert res == {0: 'done', 1: 'state handed on'}, res
+
+
+def test_any_exception_on_a_rank_reaches_the_ranks_behind_it():
+    """a ValueError (not only the RuntimeError of a time-out) in rank 0's pass: rank 0 raises it, rank 1 raises the
+    'earlier rank failed' error instead of waiting in recv"""
+    res = _run_hand_off('value_error', 35500)
+    assert res[0].startswith('raised ValueError: bad argument on rank 0'), res
+    assert res[1].startswith('raised RuntimeError: IIR stage: rank 1 received a poisoned') and 'earlier rank failed' in res[1], res
 
 
 def test_a_failing_rank_poisons_the_iir_hand_off_instead_of_hanging_it():

@@ -10,8 +10,8 @@ Two ways to cut a job, both without a data-path collective:
   grid).  A FIR stage needs K - 1 neighbouring samples: the sampler is pure, so each rank RECOMPUTES that
   halo itself instead of exchanging it (reference analogue: chunked sampling, waveforms/waveform.py:209-257;
   FIR crop distortion.py:329-337).  An IIR stage is a recurrence: the state zf of rank r - 1 is rank r's zi
-  (the reference carries `zi` from chunk to chunk the same way, waveform.py:244-251) -- a (rows, D) message
-  per rank boundary, handed on in rank order.
+  (the reference carries `zi` from chunk to chunk the same way, waveform.py:244-251) -- a (rows, D + 1) message
+  per rank boundary (the state and a status column), handed on in rank order.
 
 Collectives (torch.distributed: RCCL over xGMI with backend "nccl", gloo on CPU) exist only for optional
 RESULT PLACEMENT (`gather_rows`, `gather_rows_to_host`) and for timing reductions.
@@ -203,9 +203,10 @@ class TimeShardedFir:
 class TimeShardedIir:
     """sample(filters=(sos, initial)) / predistort(filters=) cut along time.  A recurrence cannot be split without
     its state: rank r filters its own samples starting from the final state of rank r - 1 (`zi`), received as a
-    (rows, D) message, and passes its own final state on -- the sampling itself runs on all ranks at once, the
+    (rows, D + 1) message, and passes its own final state on -- the sampling itself runs on all ranks at once, the
     filter passes follow one another in rank order (reference: zi carried from chunk to chunk,
-    waveforms/waveform.py:244-251)."""
+    waveforms/waveform.py:244-251).  The message's last column is a status: a rank that fails sets it, so that the
+    ranks behind it raise too; a NaN or Inf in the state itself is data and is handed on like any other value."""
 
     def __init__(self, sections, sampler: TimeShardedSampler, dtype=np.float64):
         from . import _engine
@@ -237,34 +238,42 @@ class TimeShardedIir:
         import torch.distributed as dist
         rank, world = self.sampler.rank, self.sampler.world
         rows, D = self.sampler.n_channels, self.D
-        state = torch.zeros((rows, max(D, 1)), dtype=torch.float64, device=x.device)
+        # The message between two ranks is (rows, W + 1): the state in the first W columns, a STATUS in the last
+        # (0.0: the state is good, anything else: an earlier rank failed).  The failure travels out of band: a NaN
+        # or Inf IN the state is data -- a non-finite sample, an unstable cascade -- and flows through, as it does
+        # in the unsharded stage and in scipy's lfilter.
+        W = max(D, 1)
+        msg = torch.zeros((rows, W + 1), dtype=torch.float64, device=x.device)
         if rank == 0:
             if zi is not None:
                 z = np.broadcast_to(np.asarray(zi, dtype=np.float64), (rows, D)).copy()
-                state[:, :D] = torch.as_tensor(z, device=x.device)
+                msg[:, :D] = torch.as_tensor(z, device=x.device)
         elif world > 1:
             if dist.get_backend(group) == 'gloo':      # (rehearsals: CPU transport)
-                h = torch.empty(state.shape, dtype=state.dtype)
+                h = torch.empty(msg.shape, dtype=msg.dtype)
                 dist.recv(h, src=rank - 1, group=group)
-                state.copy_(h)
+                msg.copy_(h)
             else:
-                dist.recv(state, src=rank - 1, group=group)
-        # A rank that cannot produce its state still hands a message on -- a NaN-poisoned one -- so that the ranks
-        # behind it raise as well instead of waiting in recv for ever.
+                dist.recv(msg, src=rank - 1, group=group)
+        # A rank that cannot produce its state still hands a message on -- with the status set -- so that the ranks
+        # behind it raise as well instead of waiting in recv for ever.  Whatever apply_local raises is caught for
+        # that (a ValueError or a ctypes error leaves the next rank in recv just as a time-out would).
         err = None
-        if rank > 0 and bool(torch.isnan(state).any()):
-            err = RuntimeError('IIR stage: rank %d received a poisoned state (an earlier rank failed)' % rank)
-            zf = state
+        if rank > 0 and bool((msg[:, W] != 0).any()):
+            err = RuntimeError('IIR stage: rank %d received a poisoned hand-off (an earlier rank failed)' % rank)
         else:
             try:
-                zf = self.apply_local(x, y, state, initial)
-            except RuntimeError as exc:
+                zf = self.apply_local(x, y, msg[:, :W].contiguous(), initial)
+                msg[:, :W] = zf
+            except Exception as exc:
                 err = exc
-                zf = torch.full_like(state, float('nan'))
+        if err is not None:
+            msg[:, W] = 1.0
         if rank + 1 < world:
-            dist.send(zf.cpu() if dist.get_backend(group) == 'gloo' else zf, dst=rank + 1, group=group)
+            dist.send(msg.cpu() if dist.get_backend(group) == 'gloo' else msg, dst=rank + 1, group=group)
         if err is not None:
             raise err
+        zf = msg[:, :W]
         if rank + 1 < world:
             return None
         return zf[:, :D]

@@ -80,6 +80,8 @@ def lib():
         l.wfk_chain_plan_create_rows.argtypes = [P(wfk_program), P(wfk_grid), VP, I32, C.c_int, P(VP)]
         l.wfk_fir_apply.argtypes = [VP, VP, I64, VP, I64, VP]
         l.wfk_fir_plan_destroy.argtypes = [VP]
+        l.wfk_fir_kernel_name.argtypes = [VP]
+        l.wfk_fir_kernel_name.restype = C.c_char_p
         l.wfk_chain_plan_create.argtypes = [P(wfk_program), P(wfk_grid), VP, I32, C.c_int, P(VP)]
         l.wfk_chain_is_fused.argtypes = [VP]
         l.wfk_chain_unfused_reason.argtypes = [VP]
@@ -416,6 +418,11 @@ class FirPlan(_Handle):
               stream: int = 0):
         check(lib().wfk_fir_apply(self._h, in_ptr, in_stride, out_ptr, out_stride,
                                   stream))
+
+    def kernel_name(self) -> str:
+        """'fir_fused<T>' (+ ' x N' accumulated passes, + ' per-row spectra') or
+        'fir_gather<T> + rocfft<L=..,rows=..> + fir_multiply<T> + fir_scatter<T>'"""
+        return lib().wfk_fir_kernel_name(self._h).decode()
 
 
 class ChainPlan(_Handle):

@@ -159,6 +159,20 @@ extern "C" int64_t wfk_internal_fir_krow(const wfk_fir_plan* p) { return p->krow
 
 extern "C" {
 
+// the form wfk_fir_apply runs, read from the fields it branches on
+const char* wfk_fir_kernel_name(const wfk_fir_plan* p) {
+  if (!p || p->n == 0) return "";
+  static thread_local std::string name;
+  const std::string T = p->kind == WFK_OUT_F32 ? "float" : "double";
+  if (p->fused)
+    name = "fir_fused<" + T + ">" + (p->nseg > 1 ? " x " + std::to_string(p->nseg) : std::string()) +
+           (p->krow ? " per-row spectra" : "");
+  else
+    name = "fir_gather<" + T + "> + rocfft<L=" + std::to_string(p->L) + ",rows=" + std::to_string(p->chunk) + "> + fir_multiply<" +
+           T + "> + fir_scatter<" + T + ">";
+  return name.c_str();
+}
+
 int wfk_fir_plan_destroy(wfk_fir_plan* p) {
   delete p;
   return WFK_OK;

@@ -32,6 +32,10 @@ class FirStage:
     def apply(self, in_ptr, in_stride, out_ptr, out_stride, stream=0):
         self.plan.apply(in_ptr, in_stride, out_ptr, out_stride, stream)
 
+    def kernel_name(self) -> str:
+        """the form the stage runs (`_engine.FirPlan.kernel_name`)"""
+        return self.plan.kernel_name()
+
     def apply_torch(self, x, y):
         import torch
         (x0, xs), (y0, ys) = (_rows.check_rows(
