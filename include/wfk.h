@@ -687,6 +687,72 @@ int64_t wfk_mix_dac_span(const wfk_mix_dac_plan* plan);
 const char* wfk_mix_dac_kernel_name(const wfk_mix_dac_plan* plan, int with_counts);
 int wfk_mix_dac_plan_destroy(wfk_mix_dac_plan* plan);         /* NULL is fine */
 
+/* -- per-row IIR straight to DAC codes: wfk_iir_rows and wfk_dac_rows in one kernel --------------- */
+/* codes = wfk_dac_rows(wfk_iir_rows(in)) bit for bit -- codes, counts and zf -- without the float rows between the
+ * two: a flux line without a crosstalk matrix, whose last float stage is its own exp-decay correction.  The sections,
+ * n, batch and kind are those of wfk_iir_rows_plan_create (one cascade per row, equal-order sections, state dimension
+ * <= 4); gain, offset (batch values each), bits and shift those of wfk_dac_rows_plan_create with interleave 1.  Per
+ * sample
+ *   y = the result of wfk_iir_rows_apply (kind F32: rounded to float once, as the two stages), widened to double
+ *   v = fl(fl(y * gain[r]) + offset[r]),   q = rint(v),   c = 0 if v is NaN, lo if q < lo, hi if q > hi, else q
+ *   out[r, i] = (int)c << shift as int16
+ * Every refusal of the two creators applies with its text, the converter's first, before any device work; no device:
+ * WFK_EHIP.  One kernel, "iir_rows_dac<T,NSEC,ORD>" (T: f64 / f32): a workgroup owns a row, walks it in tiles of 4096
+ * samples through LDS as iir_rows_tile does and stores the tile as codes: in_elem + 2 bytes per sample.
+ * wfk_iir_rows_dac_apply() enqueues that kernel on `hip_stream`, and that is all it does to the device (as
+ * wfk_chain_dac_launch: it may be called while the stream is being captured).  in_stride is in samples, >= n; out_stride in
+ * codes, >= n where there is more than one row; zi_dev / zf_dev / initial_dev as wfk_iir_rows_apply takes them;
+ * counts_dev: NULL (the kernel then does no counting), or batch * 3 int64 [below, above, nan] per row, OVERWRITTEN by
+ * every apply (the row's workgroup stores its totals: no zeroing in front).  OUT OF PLACE only, and the input is never
+ * written: out that meets in, or counts that meet either, rows not aligned to their element, a stride below the row:
+ * WFK_EINVAL.  Nothing outside [0, n) of a row is read or written; code rows may start at any 2-byte boundary
+ * (16-byte stores where a row's slots are aligned, code by code elsewhere).  _apply_shared_in: every row reads the
+ * SAME n samples at in_dev.  n = 0: the kernel is not launched; the counts are zeroed.  The plan owns its tables and
+ * nothing else, so it may serve several streams. */
+typedef struct wfk_iir_rows_dac_plan wfk_iir_rows_dac_plan;
+int wfk_iir_rows_dac_plan_create(int32_t n_sections, const int32_t* orders, const double* b_rows,
+                                 const double* a_rows, int64_t n, int32_t batch,
+                                 int kind /* WFK_OUT_F64|F32 */, const double* gain, const double* offset,
+                                 int bits, int shift, wfk_iir_rows_dac_plan** out);
+int wfk_iir_rows_dac_apply(wfk_iir_rows_dac_plan* plan, const void* in_dev, int64_t in_stride,
+                           int16_t* out_dev, int64_t out_stride /* in codes */,
+                           int64_t* counts_dev /* batch * 3, or NULL */, const double* zi_dev, double* zf_dev,
+                           const double* initial_dev, void* hip_stream);
+int wfk_iir_rows_dac_apply_shared_in(wfk_iir_rows_dac_plan* plan, const void* in_dev, int16_t* out_dev,
+                                     int64_t out_stride, int64_t* counts_dev, const double* zi_dev,
+                                     double* zf_dev, const double* initial_dev, void* hip_stream);
+int wfk_iir_rows_dac_state_dim(const wfk_iir_rows_dac_plan* plan);
+/* "iir_rows_dac<f64,1,3>"; "" for NULL; owned by the plan */
+const char* wfk_iir_rows_dac_kernel_name(const wfk_iir_rows_dac_plan* plan);
+int wfk_iir_rows_dac_plan_destroy(wfk_iir_rows_dac_plan* plan);   /* NULL is fine */
+
+/* -- sampler -> per-row IIR -> DAC codes: a whole flux line in one kernel ------------------------- */
+/* wfk_chain_iir_rows_launch (WFK_OUT_F64) followed by wfk_dac_rows_apply, bit for bit -- codes, counts and zf. The
+ * program, grid and sections are those of wfk_chain_iir_rows_plan_create; gain, offset (one per channel), bits and shift
+ * those of wfk_dac_rows_plan_create with interleave 1; every refusal of the two with its text, the converter's first.
+ * Where the chain plan fuses (wfk_chain_iir_rows_is_fused), the same fill runs in front of the codes store:
+ * "iir_rows_sampled_dac<f64,NSEC,ORD>" on fine grids, "iir_rows_short_dac<f64,NSEC,ORD>" at AWG rates, 2 B per sample of
+ * HBM traffic.  Otherwise (_unfused_reason) the sampler writes float64 rows into scratch_dev (n_channels rows,
+ * scratch_stride >= n doubles apart, lent by the caller for the launch; it may meet neither the codes nor the counts)
+ * and "iir_rows_dac<f64,NSEC,ORD>" reads them; a fused plan does not touch scratch_dev (NULL is fine).  zi_dev / zf_dev /
+ * initial_dev as wfk_iir_rows_apply takes them; counts_dev as wfk_iir_rows_dac_apply.  A launch enqueues its one or two
+ * kernels on `hip_stream`, and that is all it does to the device (it may be called while the stream is being captured).  n = 0: nothing is launched; the counts are zeroed. */
+typedef struct wfk_chain_iir_rows_dac_plan wfk_chain_iir_rows_dac_plan;
+int wfk_chain_iir_rows_dac_plan_create(const wfk_program* prog, const wfk_grid* grid, int32_t n_sections,
+                                       const int32_t* orders, const double* b_rows, const double* a_rows,
+                                       const double* gain, const double* offset, int bits, int shift,
+                                       wfk_chain_iir_rows_dac_plan** out);
+int wfk_chain_iir_rows_dac_launch(wfk_chain_iir_rows_dac_plan* plan, int16_t* out_dev, int64_t out_stride,
+                                  int64_t* counts_dev /* n_channels * 3, or NULL */, void* scratch_dev,
+                                  int64_t scratch_stride, const double* zi_dev, double* zf_dev,
+                                  const double* initial_dev, void* hip_stream);
+int wfk_chain_iir_rows_dac_is_fused(const wfk_chain_iir_rows_dac_plan* plan);
+const char* wfk_chain_iir_rows_dac_unfused_reason(const wfk_chain_iir_rows_dac_plan* plan);   /* "" when fused */
+const char* wfk_chain_iir_rows_dac_kernel_name(const wfk_chain_iir_rows_dac_plan* plan);
+int64_t wfk_chain_iir_rows_dac_table_bytes(const wfk_chain_iir_rows_dac_plan* plan);
+int wfk_chain_iir_rows_dac_state_dim(const wfk_chain_iir_rows_dac_plan* plan);
+int wfk_chain_iir_rows_dac_plan_destroy(wfk_chain_iir_rows_dac_plan* plan);   /* NULL is fine */
+
 /* -- per-row calibration curve: piecewise-linear lookup over sample VALUES ------------------------ */
 /* `batch` real rows of n samples (kind: WFK_OUT_F64 or WFK_OUT_F32) go through a curve of their own: a flux pulse
  * programmed in its physical unit to volts through a measured monotone curve, an amplifier's compression table, a

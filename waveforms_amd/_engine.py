@@ -146,6 +146,25 @@ def lib():
         l.wfk_dac_rows_kernel_name.argtypes = [VP, C.c_int]
         l.wfk_dac_rows_kernel_name.restype = C.c_char_p
         l.wfk_dac_rows_plan_destroy.argtypes = [VP]
+        l.wfk_iir_rows_dac_plan_create.argtypes = [I32, VP, VP, VP, I64, I32, C.c_int, VP, VP, C.c_int, C.c_int, P(VP)]
+        l.wfk_iir_rows_dac_state_dim.argtypes = [VP]
+        l.wfk_iir_rows_dac_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP, VP, VP, VP]
+        l.wfk_iir_rows_dac_apply_shared_in.argtypes = [VP, VP, VP, I64, VP, VP, VP, VP, VP]
+        l.wfk_iir_rows_dac_kernel_name.argtypes = [VP]
+        l.wfk_iir_rows_dac_kernel_name.restype = C.c_char_p
+        l.wfk_iir_rows_dac_plan_destroy.argtypes = [VP]
+        l.wfk_chain_iir_rows_dac_plan_create.argtypes = [P(wfk_program), P(wfk_grid), I32, VP, VP, VP, VP, VP, C.c_int,
+                                                         C.c_int, P(VP)]
+        l.wfk_chain_iir_rows_dac_is_fused.argtypes = [VP]
+        l.wfk_chain_iir_rows_dac_unfused_reason.argtypes = [VP]
+        l.wfk_chain_iir_rows_dac_unfused_reason.restype = C.c_char_p
+        l.wfk_chain_iir_rows_dac_kernel_name.argtypes = [VP]
+        l.wfk_chain_iir_rows_dac_kernel_name.restype = C.c_char_p
+        l.wfk_chain_iir_rows_dac_table_bytes.argtypes = [VP]
+        l.wfk_chain_iir_rows_dac_table_bytes.restype = I64
+        l.wfk_chain_iir_rows_dac_state_dim.argtypes = [VP]
+        l.wfk_chain_iir_rows_dac_launch.argtypes = [VP, VP, I64, VP, VP, I64, VP, VP, VP, VP]
+        l.wfk_chain_iir_rows_dac_plan_destroy.argtypes = [VP]
         l.wfk_chain_dac_plan_create.argtypes = [P(wfk_program), P(wfk_grid), VP, VP, C.c_int, C.c_int, C.c_int, P(VP)]
         l.wfk_chain_dac_is_fused.argtypes = [VP]
         l.wfk_chain_dac_unfused_reason.argtypes = [VP]
@@ -847,6 +866,90 @@ class DacRowsPlan(_Handle):
 
     def kernel_name(self, counts: bool = False) -> str:
         return lib().wfk_dac_rows_kernel_name(self._h, 1 if counts else 0).decode()
+
+
+class IirRowsDacPlan(_Handle):
+    """IirRowsPlan(sections_per_row, n, dtype) followed by DacRowsPlan(gain, offset, n, bits, shift, 1, dtype), bit for
+    bit -- codes, counts and final states -- in one kernel, 'iir_rows_dac<T,NSEC,ORD>', without the float rows between
+    the two (wfk_iir_rows_dac_plan_create).  One cascade and one gain and offset per row; the errors of both parents,
+    the converter's first, before any device work.  `state_dim`, `own_orders`, `orders` as IirRowsPlan; `.lo` / `.hi`:
+    the rails."""
+    _destroy = 'wfk_iir_rows_dac_plan_destroy'
+
+    def __init__(self, sections_per_row, gain, offset, n: int, bits: int = 16, shift: int = 0, dtype=np.float64,
+                 packed=None):
+        (self.gain, self.offset, self.n, self.bits, self.shift, _,
+         self.dtype) = dac_rows_arguments(gain, offset, n, bits, shift, 1, dtype)
+        orders, bm, am, self.own_orders = packed if packed is not None else pack_sections_rows(sections_per_row)
+        self.batch, self.orders = int(bm.shape[0]), orders
+        if len(self.gain) != self.batch:
+            raise ValueError(f'{len(self.gain)} gains for {self.batch} rows')
+        self.lo, self.hi = -2**(self.bits - 1), 2**(self.bits - 1) - 1
+        bm, am = np.ascontiguousarray(bm), np.ascontiguousarray(am)
+        check(lib().wfk_iir_rows_dac_plan_create(len(orders), orders.ctypes.data, bm.ctypes.data, am.ctypes.data,
+                                                 self.n, self.batch, _KIND_OF[self.dtype], self.gain.ctypes.data,
+                                                 self.offset.ctypes.data, self.bits, self.shift, C.byref(self._h)))
+        self.state_dim = int(orders.sum())
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, counts_ptr=None, zi_ptr=None, zf_ptr=None,
+              initial_ptr=None, stream=0):
+        """counts_ptr: None, or batch * 3 int64 on the device, overwritten with [below, above, nan] per row;
+        initial_ptr: device array of `batch` doubles (one level per row) or None"""
+        check(lib().wfk_iir_rows_dac_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, counts_ptr, zi_ptr, zf_ptr,
+                                           initial_ptr, stream))
+
+    def apply_shared_in(self, in_ptr, out_ptr, out_stride, counts_ptr=None, zi_ptr=None, zf_ptr=None,
+                        initial_ptr=None, stream=0):
+        """every row reads the SAME n input samples at `in_ptr`"""
+        check(lib().wfk_iir_rows_dac_apply_shared_in(self._h, in_ptr, out_ptr, out_stride, counts_ptr, zi_ptr, zf_ptr,
+                                                     initial_ptr, stream))
+
+    def kernel_name(self) -> str:
+        return lib().wfk_iir_rows_dac_kernel_name(self._h).decode()
+
+
+class ChainIirRowsDacPlan(_Handle):
+    """sampler -> per-row IIR -> DAC codes for every channel of `prog` on `grid` (wfk_chain_iir_rows_dac_*):
+    ChainIirRowsPlan (float64) followed by DacRowsPlan, bit for bit.  Where ChainIirRowsPlan fuses, the same fill runs
+    in front of the codes store ('iir_rows_sampled_dac<f64,NSEC,ORD>' on fine grids, 'iir_rows_short_dac<...>' at AWG
+    rates: 2 B per sample of HBM traffic); everything else (`why_not`) runs the sampler into a float64 scratch the
+    caller lends, then 'iir_rows_dac<f64,NSEC,ORD>'."""
+    _destroy = 'wfk_chain_iir_rows_dac_plan_destroy'
+
+    def __init__(self, prog: Program, grid: wfk_grid, sections_per_row, gain, offset, bits: int = 16, shift: int = 0,
+                 packed=None):
+        (self.gain, self.offset, self.n, self.bits, self.shift, _,
+         _) = dac_rows_arguments(gain, offset, int(grid.n), bits, shift, 1)
+        orders, bm, am, self.own_orders = pack_sections_rows(sections_per_row) if packed is None else packed
+        if bm.shape[0] != prog.n_channels:
+            raise ValueError(f'{bm.shape[0]} cascades for {prog.n_channels} rows')
+        if len(self.gain) != prog.n_channels:
+            raise ValueError(f'{len(self.gain)} gains for {prog.n_channels} rows')
+        self.prog, self.grid, self.n_channels, self.orders = prog, grid, prog.n_channels, orders
+        self.lo, self.hi = -2**(self.bits - 1), 2**(self.bits - 1) - 1
+        bm, am = np.ascontiguousarray(bm), np.ascontiguousarray(am)
+        check(lib().wfk_chain_iir_rows_dac_plan_create(C.byref(prog.struct), C.byref(grid), len(orders),
+                                                       orders.ctypes.data, bm.ctypes.data, am.ctypes.data,
+                                                       self.gain.ctypes.data, self.offset.ctypes.data, self.bits,
+                                                       self.shift, C.byref(self._h)))
+        self.state_dim = int(orders.sum())
+        self.fused = bool(lib().wfk_chain_iir_rows_dac_is_fused(self._h))
+        self.why_not = lib().wfk_chain_iir_rows_dac_unfused_reason(self._h).decode()
+
+    def launch(self, out_ptr, out_stride, counts_ptr=None, scratch_ptr=None, scratch_stride=0, zi_ptr=None, zf_ptr=None,
+               initial_ptr=None, stream=0):
+        """counts_ptr: None, or n_channels * 3 int64 on the device, overwritten; scratch_ptr: n_channels float64 rows
+        `scratch_stride` apart, which an unfused plan needs and a fused one does not touch"""
+        check(lib().wfk_chain_iir_rows_dac_launch(self._h, out_ptr, out_stride, counts_ptr, scratch_ptr, scratch_stride,
+                                                  zi_ptr, zf_ptr, initial_ptr, stream))
+
+    def kernel_name(self) -> str:
+        """'iir_rows_sampled_dac<f64,NSEC,ORD>', 'iir_rows_short_dac<f64,NSEC,ORD>', or the sampler's kernels and
+        'iir_rows_dac<f64,NSEC,ORD>' joined with ' + '"""
+        return lib().wfk_chain_iir_rows_dac_kernel_name(self._h).decode()
+
+    def table_bytes(self) -> int:
+        return int(lib().wfk_chain_iir_rows_dac_table_bytes(self._h))
 
 
 class ChainDacPlan(_Handle):

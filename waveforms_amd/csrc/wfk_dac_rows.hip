@@ -244,12 +244,9 @@ const char* wfk_dac_rows_kernel_name(const wfk_dac_rows_plan* p, int with_counts
   return p->kind == WFK_OUT_F32 ? "dac_rows<float>" : "dac_rows<double>";
 }
 
-int wfk_dac_rows_plan_create(int64_t n, int32_t batch, int kind, const double* gain_host, const double* offset_host,
-                             int bits, int shift, int interleave, wfk_dac_rows_plan** out) try {
-  if (!out) return wfk_fail(WFK_EINVAL, "null out");
-  *out = nullptr;
-  if (n < 0 || batch < 1 || !gain_host || !offset_host) return wfk_fail(WFK_EINVAL, "bad dac rows plan arguments");
-  if (const int rc = wfk_check_kind(kind)) return rc;
+// the converter side of a plan's arguments: the format, the interleave, one finite gain and offset per row
+int wfk_internal_dac_check(int32_t batch, const double* gain_host, const double* offset_host, int bits, int shift,
+                           int interleave) {
   if (bits < 2 || bits > 16) return wfk_fail(WFK_EINVAL, "dac rows plan: bits must lie in [2, 16]");
   if (shift < 0 || shift > 16 - bits) return wfk_fail(WFK_EINVAL, "dac rows plan: shift must lie in [0, 16 - bits]");
   if (interleave != 1 && interleave != 2) return wfk_fail(WFK_EINVAL, "dac rows plan: interleave must be 1 or 2");
@@ -260,6 +257,16 @@ int wfk_dac_rows_plan_create(int64_t n, int32_t batch, int kind, const double* g
     if (!std::isfinite(offset_host[r]))
       return wfk_fail(WFK_EINVAL, "row " + std::to_string(r) + ": offset is not finite");
   }
+  return WFK_OK;
+}
+
+int wfk_dac_rows_plan_create(int64_t n, int32_t batch, int kind, const double* gain_host, const double* offset_host,
+                             int bits, int shift, int interleave, wfk_dac_rows_plan** out) try {
+  if (!out) return wfk_fail(WFK_EINVAL, "null out");
+  *out = nullptr;
+  if (n < 0 || batch < 1 || !gain_host || !offset_host) return wfk_fail(WFK_EINVAL, "bad dac rows plan arguments");
+  if (const int rc = wfk_check_kind(kind)) return rc;
+  if (const int rc = wfk_internal_dac_check(batch, gain_host, offset_host, bits, shift, interleave)) return rc;
   if (n > INT64_MAX / interleave) return wfk_fail(WFK_EINVAL, "dac rows plan: batch * n too large for one launch");
   uint32_t bpr = 0;
   if (const int rc = wfk_row_blocks("dac rows plan", interleave * n, (int64_t)kCodes * kThreads * kSlots, kCodes - 1,

@@ -40,6 +40,7 @@
 #include "wfk_iir_rows_dev.h"
 
 #define IRW_LOADS_INPUT          // for wfk_iir_rows_head.inc: this file's kernel loads its tiles (it holds T^lane, has x)
+#define IRW_STORE_INC "wfk_iir_rows_store.inc"   // for wfk_iir_rows_body.inc: the tile is stored as T, whole lines
 
 namespace {
 

@@ -1,7 +1,9 @@
 // wfk_iir_rows_body.inc -- the tile body of the per-row IIR kernels, written once and included as TEXT inside the tile loop
 // of iir_rows_tile (wfk_iir_rows.hip) and of iir_rows_sampled / iir_rows_short (wfk_iir_rows_sampled.hip): everything
-// after the fill of the tile -- sweep from zero state, double-double wave scan, carry chain, replay from LDS, whole-line
-// stores (DESIGN.md §3.8.1, steps 2-4).  Text, not a function: behind a call boundary (a __forceinline__ function, even
+// after the fill of the tile -- sweep from zero state, double-double wave scan, carry chain, replay from LDS, and the
+// store section the kernel names in IRW_STORE_INC: whole-line stores of T (wfk_iir_rows_store.inc: these three kernels) or
+// int16 DAC codes (wfk_iir_rows_store_dac.inc: iir_rows_dac and the _dac builds of the other two) (DESIGN.md §3.8.1,
+// steps 2-4; §3.23).  Text, not a function: behind a call boundary (a __forceinline__ function, even
 // an always-inline lambda inside the kernel) the compiler schedules iir_rows_tile differently and takes 16 more VGPRs in
 // every instantiation, which costs the state-dimension-4 shapes a wave per SIMD (DESIGN.md §3.8.2 has the figures);
 // included, iir_rows_tile keeps its instruction words (tools/kernel_cmp.py).
@@ -79,18 +81,6 @@
 #pragma unroll
       for (int i = 0; i < D; ++i) zf[row * D + i] = z[i];
     }
-    __syncthreads();
-    if (left >= IRW_TILE) {
-#pragma unroll
-      for (int i = 0; i < IRW_RUN; ++i) {
-        const int j = i * IRW_THREADS + tid;
-        y[base + j] = tile[(j / IRW_RUN) * IRW_PITCH + (j % IRW_RUN)];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < IRW_RUN; ++i) {
-        const int j = i * IRW_THREADS + tid;
-        if (j < left) y[base + j] = tile[(j / IRW_RUN) * IRW_PITCH + (j % IRW_RUN)];
-      }
-    }
-    __syncthreads();
+    // ---- the store section (from the barrier after sweep 2 to the barrier that frees the tile): IRW_STORE_INC, the text
+    // each kernel names -- wfk_iir_rows_store.inc writes the tile as T, wfk_iir_rows_store_dac.inc as int16 DAC codes
+#include IRW_STORE_INC

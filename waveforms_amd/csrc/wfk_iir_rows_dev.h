@@ -12,6 +12,7 @@
 //   pw, W = pw + 6 * MM, L[MM]                      the row's T^(2^k) tables, T^64, T^lane as (hi, lo) pairs
 //   pre, zf, row, y                                 the row's level, the final states (or null), its index, its output
 //   t, base = t * IRW_TILE, left = n - base         the tile
+// and IRW_STORE_INC names the text of the body's store section (wfk_iir_rows_store.inc | wfk_iir_rows_store_dac.inc).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +25,11 @@
 #define IRW_PITCH (IRW_RUN + 1)           // elements between the runs of neighbouring lanes
 #define IRW_MAXD 4                        // state dimension limit
 #define IRW_NPW 7                         // T^(2^k), k = 0 .. 6 (k = 6: one wave)
+
+// the converter side of the kernels that store int16 DAC codes (iir_rows_dac, iir_rows_sampled_dac, iir_rows_short_dac;
+// DESIGN.md §3.23): gd [batch][2] = (gain, offset) per row; counts [batch][3] = [below, above, nan] or null; the rails
+#define IRW_DAC_PARAMS \
+  const double* __restrict__ gd, unsigned long long* __restrict__ counts, double lo, double hi, int shift
 
 namespace {
 

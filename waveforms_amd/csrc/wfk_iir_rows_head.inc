@@ -6,6 +6,10 @@
 // IRW_LOADS_INPUT (defined by wfk_iir_rows.hip): the kernel loads its tiles from `in` -- it holds L = T^lane for the whole
 // row and has the row's input x; the evaluating kernels read L after their fill.  (The statements keep the order
 // iir_rows_tile had them in: moved, they change its schedule and registers -- tools/kernel_cmp.py.)
+// IRW_OUT_T: the element of `out` -- T, unless the kernel has said otherwise (wfk_iir_rows_dac.hip: int16_t codes).
+#ifndef IRW_OUT_T
+#define IRW_OUT_T T
+#endif
   constexpr int D = NSEC * ORD, NC = NSEC * (ORD + 1), MM = D * D * 2;
   __shared__ T tile[IRW_THREADS * IRW_PITCH];
   __shared__ double s_tot[IRW_WAVES][D];
@@ -31,6 +35,6 @@
 #ifdef IRW_LOADS_INPUT
   const T* x = in + row * in_stride;
 #endif
-  T* y = out + row * out_stride;
+  IRW_OUT_T* y = out + row * out_stride;
   const int64_t ntile = (n + IRW_TILE - 1) / IRW_TILE;
   T* const my = tile + tid * IRW_PITCH;

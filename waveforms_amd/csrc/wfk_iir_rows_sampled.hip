@@ -17,6 +17,8 @@
 // Tile t is evaluated right before its sweeps: there is no next-tile prefetch (nothing to load), and the row's T^lane
 // table -- 64 VGPRs that iir_rows_tile holds across the row -- is read where it is applied, after the fill (64 dwords
 // per lane and 4096 samples), so that the fill phases have the registers they want.
+// Both kernels are built a second time with the tile leaving LDS as int16 DAC codes (iir_rows_sampled_dac,
+// iir_rows_short_dac; the plan behind them is at the end of this file).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +35,8 @@
 #include "wfk_short_dev.h"
 #include "wfk_chain_dev.h"
 #include "wfk_iir_rows_dev.h"
+
+#define IRW_STORE_INC "wfk_iir_rows_store.inc"   // for wfk_iir_rows_body.inc: the tile is stored as T, whole lines
 
 #define IRS_PAR 2048            // doubles of LDS the lean fill stages a piece's parameter block in (its own area: the
                                 // tile array is not free while a tile is filled)
@@ -58,169 +62,23 @@ struct IrsShortArgs {
   double step;
 };
 
-// ---- the lean fill: stride-256 chains (the sampling phase of fir_sampled, CL = 16, no carried op state) -----------
-template <typename T, int NSEC, int ORD>
-__global__ void __launch_bounds__(IRW_THREADS) iir_rows_sampled(const IrsLeanArgs a, T* out, int64_t out_stride,
-                                                                const double* __restrict__ tab,
-                                                                const double* __restrict__ zi, double* __restrict__ zf,
-                                                                const double* __restrict__ initial, int64_t n) {
-  constexpr int CL = IRW_RUN;
-#include "wfk_iir_rows_head.inc"
-  __shared__ __attribute__((aligned(16))) double s_par[IRS_PAR + 2 * (CL + 1)];
-  double2* const unit_tab = reinterpret_cast<double2*>(s_par + IRS_PAR);
-  const DevChannel C = a.channels[row];
-  if (tid <= CL) unit_tab[tid] = make_double2(1.0, 0.0);       // phasor table of ops without a carrier
-  for (int64_t t = 0; t < ntile; ++t) {
-    const int64_t s1 = t * IRW_TILE, range_end = s1 + IRW_TILE; // per-thread sample index: s1 + tid + 256 k
-    T acc[CL];
-    CH_EACH(CL, k) acc[k] = (T)0; CH_END
-    double x;
-    {
-      // t[j] = fl(fl(j*step) + t0) (NumPy's linspace / arange element formula), as fir_sampled's chain_time.  As there,
-      // the time is taken for the chain's FIRST sample only: an endpoint grid's overridden last sample gets `last` where
-      // it starts a chain (k = 0); further down a chain its time is the stride-256 continuation, one ulp of t away
-#pragma clang fp contract(off)
-      const int64_t j = s1 + tid;
-      const double m = (double)(j + a.i0) * a.step;
-      x = m + a.t0;
-      if (a.has_last && j == n - 1) x = a.last;
-    }
-    if (C.tshift != 0.0) x = x - C.tshift;
-    int q = cuni(a.tile_first[row * ntile + t]);
-    for (; q < C.piece_end; q = cuni(q + 1)) {
-      const DevPiece P = a.pieces[q];
-      if (P.start >= range_end) break;
-      if (P.n_blk == 0 || P.stop <= s1) continue;               // zero piece / entirely before the tile
-      __syncthreads();                                           // every wave is done with the previous block
-      for (int i = tid; i < P.first_len; i += IRW_THREADS) s_par[i] = a.params[P.par_off + i];
-      __syncthreads();
-      const int nops = cuni((int)s_par[1]);
-      const bool full = P.start <= s1 && P.stop >= range_end;   // wave-uniform: the whole tile is inside
-      int klo = 0, khi = CL;
-      if (!full) {
-        // samples k of this thread inside the piece: P.start <= s1 + tid + 256 k < P.stop (scalar parts clamped to
-        // what matters for k in [0, CL): the per-thread part is 32-bit)
-        const int64_t lim = 256 * (int64_t)(CL + 2);
-        const int64_t los = P.start - s1, his = P.stop - s1;
-        const int lo = (int)(los < -lim ? -lim : (los > lim ? lim : los)) - tid;
-        const int hi = (int)(his < -lim ? -lim : (his > lim ? lim : his)) - tid;
-        klo = lo <= 0 ? 0 : (lo + 255) >> 8;
-        khi = hi <= 0 ? 0 : (hi + 255) >> 8;
-        klo = klo > CL ? CL : klo;
-        khi = khi > CL ? CL : khi;
-      }
-      for (int op = 0; op < nops; ++op) {
-        const double* rec = s_par + WFK_BLK_HDR + op * WFK_FCE_REC;
-        const int fl = cuni(WFK_FCE_WORD(rec));
-        const int env = (fl >> 4) & 3, carrier = (fl >> 2) & 1;
-        ChSeeds nx;
-        const ChSeeds sd = chain_make_seeds(rec, x, fl);         // exact
-        if (env == 3) {
-          chain_envmul<T, CL, -1>(rec, sd, acc, klo, khi, nx);
-        } else {
-          const double2* ptab = carrier ? reinterpret_cast<const double2*>(s_par + WFK_FCE_TABOFF(fl)) : unit_tab;
-          const double qq = env ? rec[WFK_FCE_Q] : 1.0;
-          const double u0 = x - rec[WFK_FCE_SLIN];
-          if (full && (fl & 3) <= 1) chain_loop<T, CL, -1, false, true>(ptab, rec, sd, u0, qq, acc, 0, CL, nx);
-          else if (full) chain_loop<T, CL, -1, false, false>(ptab, rec, sd, u0, qq, acc, 0, CL, nx);
-          else chain_loop<T, CL, -1, true, false>(ptab, rec, sd, u0, qq, acc, klo, khi, nx);
-        }
-      }
-    }
-    // channel offset inside [0, n), zeros behind the row; into the tile by the scatter of iir_rows_tile's loads
-    // (the previous tile's body ended with a barrier: the array is free)
-    const T off = (T)C.offset;
-    const int64_t left = n - s1;
-    CH_EACH(CL, k)
-      const int j = k * IRW_THREADS + tid;
-      tile[irw_at(j)] = j < left ? acc[k] + off : (T)0;
-    CH_END
-    __syncthreads();
-    {
-      const int64_t base = s1;
-      double L[MM];                                              // T^lane, read here: after the fill
-#pragma unroll
-      for (int e = 0; e < MM; ++e) L[e] = pw[(IRW_NPW + lane) * MM + e];
-#include "wfk_iir_rows_body.inc"
-    }
-  }
-}
+// the two kernels (wfk_iir_rows_sampled_kernels.inc: the text this file had here), storing their rows as T ...
+#define IRS_K(name) name
+#define IRS_OUT_PARAMS T* out, int64_t out_stride,
+#include "wfk_iir_rows_sampled_kernels.inc"
+#undef IRS_K
+#undef IRS_OUT_PARAMS
+#undef IRW_OUT_T
+#undef IRW_STORE_INC
 
-// ---- the short fill: runs of one piece (the entry evaluation of fir_short) -----------------------------------------
-template <typename T, int NSEC, int ORD>
-__global__ void __launch_bounds__(IRW_THREADS) iir_rows_short(const IrsShortArgs a, T* out, int64_t out_stride,
-                                                              const double* __restrict__ tab,
-                                                              const double* __restrict__ zi, double* __restrict__ zf,
-                                                              const double* __restrict__ initial, int64_t n) {
-  constexpr int R = WFK_SH_R;
-  static_assert(R == IRW_RUN, "an entry is at most one run of the tile");
-#include "wfk_iir_rows_head.inc"
-  const DevChannel C = a.channels[row];
-  const double coff = C.offset;
-  const ShortWin* const wp = a.wins + row * 2 * a.npairs;
-  for (int64_t t = 0; t < ntile; ++t) {
-    const int64_t h0 = t * IRW_TILE, left = n - h0;
-    const int64_t rec0 = cuni64(wp[t].rec0), e0 = cuni64(wp[t].e0);   // (block-uniform: SGPRs)
-    const int cnt = cuni(wp[t].cnt);
-    // zeros behind the row, the channel offset inside (skipped zero pieces, gaps between entries); the previous tile's
-    // body ended with a barrier: the array is free.  Always the padded layout: it is the tile's
-    CH_EACH(IRW_RUN, k)
-      const int j = k * IRW_THREADS + tid;
-      tile[irw_at(j)] = j < left ? (T)coff : (T)0;
-    CH_END
-    __syncthreads();
-    for (int eb = 0; eb < cnt; eb += IRW_THREADS) {             // block-uniform trip count
-      const int idx = eb + tid;
-      bool live = idx < cnt;
-      const uint32_t word = live ? a.entries[e0 + idx] : 0u;
-      const int len = live ? (int)(word >> 28) + 1 : 0;
-      const int o = (int)((word >> 16) & 0xfff);
-      const double* op = a.recs + 2 * (rec0 + (int64_t)(word & 0xffff));
-      shdev::OpRec rec = shdev::load_op(op);
-      const double kf = (double)((int)(uint32_t)(h0 + o) - shdev::op_ref(rec));   // samples from the record's reference sample
-      double acc[R], acci[1];
-      CH_EACH(R, k) acc[k] = 0.0; CH_END
-      acci[0] = 0.0;
-      auto eval = [&](const shdev::OpRec& rc, const double* opp, bool lv) -> bool {   // -> another op follows
-        const int w = shdev::op_word(rc);
-        const bool closing = ((w >> 4) & 3) == 3;               // erf edge multiplier
-        const bool mine = lv && !closing && !(w & 8);           // (real channels only: no op of an imaginary part)
-        const bool cubic = __any(mine && (w & 3) > 1);
-        if (mine) {
-          if (cubic) shdev::short_op<R, true, false>(rc, opp, w, kf, a.step, acc, acci);
-          else shdev::short_op<R, false, false>(rc, opp, w, kf, a.step, acc, acci);
-        }
-        if (__any(lv && closing)) {
-          if (lv && closing) shdev::short_erfmul<R, false>(rc, kf, acc, acci);
-        }
-        return lv && !(w & WFK_SH_LAST);
-      };
-      live = eval(rec, op, live);
-      while (__any(live)) {
-        op += (shdev::op_word(rec) & 3) > 1 ? WFK_SH_OP3 : WFK_SH_OP1;
-        if (live) rec = shdev::load_op(op);
-        live = eval(rec, op, live);
-      }
-      if (C.do_clip) {
-        CH_EACH(R, k) acc[k] = shdev::clip_np(acc[k], C.clip_lo, C.clip_hi); CH_END
-      }
-      // element o + k of the tile sits at (o + k) + ((o + k) >> 4) = irw_at(o) + k + [k >= 16 - (o & 15)]
-      T* const b0 = tile + o + (o >> 4);
-      const int tk = 16 - (o & 15);
-      CH_EACH(R, k)
-        if (k < len) *((k >= tk ? b0 + 1 : b0) + k) = (T)(acc[k] + coff);
-      CH_END
-    }
-    __syncthreads();
-    {
-      const int64_t base = h0;
-      double L[MM];                                              // T^lane, read here: after the fill
-#pragma unroll
-      for (int e = 0; e < MM; ++e) L[e] = pw[(IRW_NPW + lane) * MM + e];
-#include "wfk_iir_rows_body.inc"
-    }
-  }
-}
+// ... and once more ending in int16 DAC codes: iir_rows_sampled_dac, iir_rows_short_dac
+#define IRW_DAC
+#define IRW_OUT_T int16_t
+#define IRW_STORE_INC "wfk_iir_rows_store_dac.inc"
+#define IRS_K(name) name##_dac
+#define IRS_OUT_PARAMS int16_t* out, int64_t out_stride, IRW_DAC_PARAMS,
+#include "wfk_iir_rows_sampled_kernels.inc"
+#undef IRW_DAC
 
 // the eight cascade shapes iir_rows_tile has: f(NSEC, ORD as integral constants); false: none of them
 template <typename F>
@@ -428,3 +286,121 @@ extern "C" int wfk_chain_iir_rows_launch(wfk_chain_iir_rows_plan* p, void* out_d
   if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "fused sampler -> per-row IIR kernel launch failed");
   return WFK_OK;
 }
+
+// ---- the same chain ending in int16 DAC codes: SampledIirRows -> DacStage in one kernel -----------------
+// The plan is a float64 chain plan -- its fill decision, its tables, its sampler, its rows' IIR tables -- and the rows'
+// (gain, offset) pairs.  Where the chain plan fuses, the same fill runs in front of the codes store
+// (iir_rows_sampled_dac / iir_rows_short_dac); where it does not, the sampler writes float64 rows into a scratch the
+// caller lends and iir_rows_dac (wfk_iir_rows_dac.hip) reads them: two launches instead of three.
+struct wfk_chain_iir_rows_dac_plan {
+  wfk_chain_iir_rows_plan* chain = nullptr;
+  DevBuf<double> gd;                // [n_channels][2]: gain, offset
+  int bits = 0, shift = 0;
+  std::string why, name;
+  ~wfk_chain_iir_rows_dac_plan() {  // (the pairs go after this body: nothing on the device reads them any more)
+    if (gd) (void)hipDeviceSynchronize();
+    wfk_chain_iir_rows_plan_destroy(chain);
+  }
+};
+
+extern "C" {
+
+int wfk_chain_iir_rows_dac_plan_destroy(wfk_chain_iir_rows_dac_plan* p) {
+  delete p;
+  return WFK_OK;
+}
+
+int wfk_chain_iir_rows_dac_plan_create(const wfk_program* prog, const wfk_grid* grid, int32_t n_sections,
+                                       const int32_t* orders, const double* b_rows, const double* a_rows,
+                                       const double* gain, const double* offset, int bits, int shift,
+                                       wfk_chain_iir_rows_dac_plan** out) try {
+  if (!out) return wfk_fail(WFK_EINVAL, "null out");
+  *out = nullptr;
+  if (!prog || !grid) return wfk_fail(WFK_EINVAL, "null argument");
+  if (prog->n_channels < 1) return wfk_fail(WFK_EINVAL, "per-row IIR chain: a program without channels");
+  if (!gain || !offset) return wfk_fail(WFK_EINVAL, "bad dac rows plan arguments");
+  // the converter's refusals, then the chain's: both before any device work
+  if (const int rc = wfk_internal_dac_check(prog->n_channels, gain, offset, bits, shift, 1)) return rc;
+  std::unique_ptr<wfk_chain_iir_rows_dac_plan> p(new wfk_chain_iir_rows_dac_plan());
+  if (const int rc = wfk_chain_iir_rows_plan_create(prog, grid, n_sections, orders, b_rows, a_rows, WFK_OUT_F64, &p->chain))
+    return rc;
+  const wfk_chain_iir_rows_plan* c = p->chain;
+  p->bits = bits; p->shift = shift;
+  std::vector<double> gd((size_t)c->n_channels * 2);
+  for (int32_t r = 0; r < c->n_channels; ++r) { gd[2 * (size_t)r] = gain[r]; gd[2 * (size_t)r + 1] = offset[r]; }
+  if (!p->gd.upload(gd)) {
+    (void)hipGetLastError();
+    return wfk_fail(WFK_ENOMEM, "per-row IIR dac chain: device allocation / upload failed");
+  }
+  const std::string shape = "f64," + std::to_string(c->nsec) + "," + std::to_string(c->ord) + ">";
+  if (c->fill == IrsFill::Lean) p->name = "iir_rows_sampled_dac<" + shape;
+  else if (c->fill == IrsFill::Short) p->name = "iir_rows_short_dac<" + shape;
+  else {
+    p->why = c->why + ": the sampler writes float64 rows into the plan's scratch, iir_rows_dac reads them";
+    p->name = std::string(wfk_plan_kernel_name(c->sampler, WFK_OUT_F64)) + " + iir_rows_dac<" + shape;
+  }
+  *out = p.release();
+  return WFK_OK;
+} catch (const std::bad_alloc&) {
+  return wfk_fail(WFK_ENOMEM, "out of host memory while building the chain plan");
+}
+
+int wfk_chain_iir_rows_dac_is_fused(const wfk_chain_iir_rows_dac_plan* p) { return p ? wfk_chain_iir_rows_is_fused(p->chain) : 0; }
+
+const char* wfk_chain_iir_rows_dac_unfused_reason(const wfk_chain_iir_rows_dac_plan* p) { return p ? p->why.c_str() : ""; }
+
+const char* wfk_chain_iir_rows_dac_kernel_name(const wfk_chain_iir_rows_dac_plan* p) { return p ? p->name.c_str() : ""; }
+
+int64_t wfk_chain_iir_rows_dac_table_bytes(const wfk_chain_iir_rows_dac_plan* p) {
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
+  return wfk_chain_iir_rows_table_bytes(p->chain) + (int64_t)p->chain->n_channels * 16;
+}
+
+int wfk_chain_iir_rows_dac_state_dim(const wfk_chain_iir_rows_dac_plan* p) {
+  return p ? wfk_chain_iir_rows_state_dim(p->chain) : WFK_EINVAL;
+}
+
+int wfk_chain_iir_rows_dac_launch(wfk_chain_iir_rows_dac_plan* p, int16_t* out_dev, int64_t out_stride,
+                                  int64_t* counts_dev, void* scratch_dev, int64_t scratch_stride, const double* zi_dev,
+                                  double* zf_dev, const double* initial_dev, void* hip_stream) {
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
+  const wfk_chain_iir_rows_plan* c = p->chain;
+  hipStream_t s = (hipStream_t)hip_stream;
+  const RowReport report{counts_dev, c->n_channels, 3};
+  // nothing to sample (the pointers of empty rows may be null); the report is still zeroed
+  if (c->n == 0) return wfk_zero_report("per-row IIR dac chain", report, s);
+  // a lone code row's stride is not read
+  const RowSide codes{"out", out_dev, c->n_channels, out_stride, c->n, sizeof(int16_t), false};
+  const double* tab = wfk_internal_iir_rows_table(c->iir);
+  if (c->fill == IrsFill::None) {
+    if (!scratch_dev) return wfk_fail(WFK_EINVAL, "per-row IIR dac chain: an unfused launch needs scratch (" + c->why + ")");
+    if (const int rc = wfk_row_rule("per-row IIR dac chain",
+                                    {{"scratch", scratch_dev, c->n_channels, scratch_stride, c->n, sizeof(double)}}, codes,
+                                    kRowsAligned | kRowsDisjoint, wfk_fail, report))
+      return rc;
+    if (const int rc = wfk_plan_launch(c->sampler, scratch_dev, scratch_stride, WFK_OUT_F64, 0, hip_stream)) return rc;
+    if (const int rc = wfk_internal_iir_rows_dac_run(tab, c->nsec, c->ord, WFK_OUT_F64, c->n_channels, c->n, scratch_dev,
+                                                     scratch_stride, out_dev, out_stride, p->gd.get(), counts_dev, zi_dev,
+                                                     zf_dev, initial_dev, p->bits, p->shift, hip_stream))
+      return rc;
+  } else {
+    // (no input side: the rule takes `out` in its place; scratch is not touched)
+    if (const int rc = wfk_row_rule("per-row IIR dac chain", {codes}, codes, kRowsAligned, wfk_fail, report)) return rc;
+    const double lo = -(double)(1 << (p->bits - 1)), hi = (double)((1 << (p->bits - 1)) - 1);
+    const dim3 grid((unsigned)c->n_channels), block(IRW_THREADS);
+    unsigned long long* counts = (unsigned long long*)counts_dev;
+    (void)irs_shape(c->nsec, c->ord, [&](auto ns, auto od) {
+      constexpr int NS = decltype(ns)::value, OD = decltype(od)::value;
+      if (c->fill == IrsFill::Lean)
+        hipLaunchKernelGGL((iir_rows_sampled_dac<double, NS, OD>), grid, block, 0, s, c->la, out_dev, out_stride,
+                           p->gd.get(), counts, lo, hi, p->shift, tab, zi_dev, zf_dev, initial_dev, c->n);
+      else
+        hipLaunchKernelGGL((iir_rows_short_dac<double, NS, OD>), grid, block, 0, s, c->sa, out_dev, out_stride,
+                           p->gd.get(), counts, lo, hi, p->shift, tab, zi_dev, zf_dev, initial_dev, c->n);
+    });
+  }
+  if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "sampler -> per-row IIR -> codes kernel launch failed");
+  return WFK_OK;
+}
+
+}  // extern "C"

@@ -395,5 +395,15 @@ int wfk_internal_fir_fused_launch(int kind, const void* in, int64_t in_stride, v
 int wfk_internal_fir_fused_len(void);
 // wfk_iir_rows.hip: the rows' tables on the device ([batch][irw_row_doubles], wfk_iir_rows_dev.h)
 const double* wfk_internal_iir_rows_table(const wfk_iir_rows_plan* p);
+// wfk_iir_rows_dac.hip: the launch of iir_rows_dac<kind, nsec, ord> on `batch` rows of n samples; tab: the rows' IIR
+// tables, gd: [batch][2] = (gain, offset), both on the device; in_stride = 0: every row reads the one input row
+int wfk_internal_iir_rows_dac_run(const double* tab, int nsec, int ord, int kind, int32_t batch, int64_t n,
+                                  const void* in, int64_t in_stride, int16_t* out, int64_t out_stride, const double* gd,
+                                  int64_t* counts, const double* zi, double* zf, const double* initial, int bits,
+                                  int shift, void* hip_stream);
+// wfk_dac_rows.hip: what wfk_dac_rows_plan_create asks of bits, shift, interleave and the batch gains and offsets
+// (neither null), with its texts: every plan that ends in the converter holds its arguments to it
+int wfk_internal_dac_check(int32_t batch, const double* gain_host, const double* offset_host, int bits, int shift,
+                           int interleave);
 }
 #endif

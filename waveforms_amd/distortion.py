@@ -1494,6 +1494,151 @@ def mix_dac_rows(sig, matrix, gain, mix_offset=None, dac_offset=0.0, bits=16, sh
         return (codes, c.download((rows_out, 3), np.int64)) if return_counts else codes
 
 
+class IirDacStage:
+    """`IirStage(sections_rows, n, batch, dtype).apply_torch(x, out=z, initial=, zi=, zf=)` followed by `DacStage(gain, n,
+    offset, bits, shift, dtype=dtype).apply_torch(z, counts=)`, device-resident and bit for bit -- codes, counts and
+    zf -- in ONE kernel ('iir_rows_dac<T,NSEC,ORD>') without the float rows between the two: a flux line without a
+    crosstalk matrix, whose last float stage is its own exp-decay correction, ending in the int16 codes of the
+    converter.  Row r, with `IirStage`'s per-row rules (cascades padded to a common shape: sections of equal order,
+    total state dimension <= 4) and `DacStage`'s formula:
+        y = F_r(x[r] - initial[r]) + initial[r]            (a float32 plan rounds y to float32 once, as the two stages)
+        code[r, i] = saturate(rint(y[i] * gain[r] + offset[r])) * 2**shift
+    `sections_rows`: one cascade [(b, a), ...] per row; ONE cascade -- [(b, a), ...] or an SOS matrix -- is given to
+    every row (`batch=`, or the number of gains).  `gain` / `offset`: a scalar (every row) or one value per row.  An
+    optional (batch, 3) int64 counts tensor is OVERWRITTEN by every apply with [below, above, nan] per row.
+    `interleave` is not part of this stage (NotImplementedError: a pair is `IirStage` + `DacStage(interleave=2)`).
+
+        st = IirDacStage.from_full_scale([[exp_decay_filter(A, tau, 2e9)] for A, tau in lines], n, 1.0)
+        codes = st.apply_torch(x, counts=clipped, initial=levels, zf=zf)     # out of place, torch's current stream
+    """
+
+    def __init__(self, sections_rows, n: int, gain, offset=0.0, bits: int = 16, shift: int = 0, dtype=np.float64,
+                 interleave: int = 1, batch=None):
+        if interleave != 1:
+            raise NotImplementedError('IirDacStage has no interleave: a workgroup owns one row; run IirStage and then '
+                                      'DacStage(interleave=2) for a pair')
+        depth = _nesting(sections_rows)
+        if depth == 2:                                             # an SOS matrix
+            sec = np.asarray(sections_rows, dtype=np.float64)
+            if sec.ndim != 2 or sec.shape[1] != 6:
+                raise ValueError('IirDacStage: an SOS matrix has shape (n_sections, 6)')
+            sections_rows, depth = _engine.sos_sections(sec), 3
+        if depth not in (3, 4):
+            raise ValueError('IirDacStage: sections is one [(b, a), ...] per row, one [(b, a), ...], or an SOS matrix')
+        if depth == 3:                                             # one cascade: every row gets it
+            if batch is None:
+                batch = max(np.size(gain) if np.ndim(gain) > 0 else 1, np.size(offset) if np.ndim(offset) > 0 else 1)
+            sections_rows = [list(sections_rows)] * int(batch)
+        sections_rows = list(sections_rows)
+        rows = len(sections_rows)
+        if rows < 1 or (batch is not None and int(batch) != rows):
+            raise ValueError(f'IirDacStage: {rows} cascades for {batch} rows')
+        gains, offsets = (_per_row('IirDacStage', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v, rows)
+                          for what, v in (('gain', gain), ('offset', offset)))
+        self.plan = _engine.IirRowsDacPlan(sections_rows, gains, offsets, n, bits, shift, dtype)
+        p = self.plan
+        self.n, self.batch, self.dtype, self.gain, self.offset = p.n, p.batch, p.dtype, p.gain, p.offset
+        self.bits, self.shift, self.lo, self.hi = p.bits, p.shift, p.lo, p.hi
+        self.state_dim, self.own_orders, self.section_order = p.state_dim, p.own_orders, int(p.orders[0])
+        self._initial_cache = None
+
+    @classmethod
+    def from_full_scale(cls, sections_rows, n: int, full_scale, **kw):
+        """the stage whose gain[r] = hi / full_scale[r], so that a filtered +-full scale maps to +-hi (a scalar: every
+        row).  ValueError: a full scale that is not finite or not positive."""
+        bits = int(kw.get('bits', 16))
+        if not 2 <= bits <= 16:
+            raise ValueError('bits must lie in [2, 16]')
+        fs = np.asarray(full_scale, dtype=np.float64)
+        if not np.all(np.isfinite(fs) & (fs > 0.0)):
+            raise ValueError('IirDacStage: every full scale must be finite and positive')
+        return cls(sections_rows, n, (2**(bits - 1) - 1) / fs, **kw)
+
+    def kernel_name(self) -> str:
+        """'iir_rows_dac<T,NSEC,ORD>'"""
+        return self.plan.kernel_name()
+
+    def row_state(self, z, r: int):
+        """row r's own state (scipy layout, its sections back to back) out of a (batch, state_dim) host array"""
+        return _row_state(z, r, self.own_orders, self.section_order)
+
+    def apply_torch(self, x, codes=None, counts=None, initial=0.0, zi=None, zf=None):
+        """x: (batch, >= n) row-contiguous device tensor of the stage's dtype -- or ONE row, (1, >= n) or 1-D, that
+        every row reads (the shared-input form); codes: (batch, >= n) int16 (rows may be windows of a wider tensor;
+        None: allocated); counts: None or a contiguous (batch, 3) int64 device tensor, overwritten; `initial`: a
+        scalar, one value per row, or a (batch,) float64 device tensor; zi / zf: optional (batch, state_dim) float64
+        device tensors.  Out of place: `codes` may share no memory with `x`, `counts` with neither (ValueError); `x`
+        is never written.  Asynchronous on torch's current stream.  -> codes[:, :n]"""
+        import torch
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        shared = self.batch > 1 and x.shape[0] == 1
+        in_rows = 1 if shared else self.batch
+        x0, xs = _rows.check_rows(x, in_rows, self.n, _rows.torch_dtype(self.dtype),
+                                  'expected x: (batch, >=n) row-contiguous device tensor of the stage dtype, or one row')
+        if codes is None:
+            codes = torch.empty((self.batch, self.n), dtype=torch.int16, device=x.device)
+        y0, ys = _rows.check_rows(codes, self.batch, self.n, torch.int16,
+                                  'expected codes: (batch, >=n) row-contiguous int16 device tensor')
+        c0 = _rows.check_state(counts, (self.batch, 3), 'expected counts: contiguous (batch, 3) int64 device tensor',
+                               dtype=np.int64)
+        zip_, zfp = (_rows.check_state(z, (self.batch, self.state_dim),
+                                       'zi / zf must be contiguous (batch, state_dim) float64 device tensors')
+                     for z in (zi, zf))
+        xr, yr = (x0, xs, in_rows, self.n, self.dtype.itemsize), (y0, ys, self.batch, self.n, 2)
+        if not _rows.rows_disjoint(xr, yr):
+            raise ValueError('iir dac stage is out of place: codes overlaps x')
+        if not _rows.report_disjoint(c0, self.batch, 3, xr, yr):
+            raise ValueError('iir dac stage: counts overlaps x / codes')
+        ini = _initial_rows(self, self.batch, initial, x.device)
+        inip = None if ini is None else ini.data_ptr()
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        if shared:
+            self.plan.apply_shared_in(x0, y0, ys, c0, zip_, zfp, inip, stream)
+        else:
+            self.plan.apply(x0, xs, y0, ys, c0, zip_, zfp, inip, stream)
+        return codes[:, :self.n]
+
+    def close(self):
+        self.plan.close()
+
+
+def iir_dac_rows(sig, filters_rows, gain, offset=0.0, bits=16, shift=0, initial=0.0, return_counts=False):
+    """`dac_codes_rows(<IirStage of one cascade per row>(sig, initial=initial), gain, offset, bits, shift)` in one
+    launch (see `IirDacStage`): NumPy in, NumPy out, (rows, samples) int16.  `filters_rows`: one list of (b, a)
+    sections per row (run as a cascade, in `IirStage`'s per-row shapes); `initial`: a scalar or one level per row.
+    float32 rows stay float32 on the way in, anything else is read as float64.  `return_counts`: -> (codes, counts),
+    counts the (rows, 3) int64 [below, above, nan].  ValueError before any device work: sig not 2-D, a number of
+    cascades, gains, offsets or levels that does not match, what `IirDacStage` refuses.  NotImplementedError: complex
+    rows or coefficients."""
+    sig2 = _rows_signal_f32('iir_dac_rows', sig)
+    batch, n = sig2.shape
+    filters_rows = [list(f) for f in filters_rows]
+    if len(filters_rows) != batch:
+        raise ValueError(f'iir_dac_rows: {len(filters_rows)} filter lists for {batch} rows')
+    gains = _per_row('iir_dac_rows', 'gain', gain, batch)
+    offsets = _per_row('iir_dac_rows', 'offset', offset, batch)
+    g, o, n, bits, shift, _, dtype = _engine.dac_rows_arguments(gains, offsets, n, bits, shift, 1, sig2.dtype)
+    packed = _engine.pack_sections_rows(filters_rows)
+    ini = np.asarray(initial, dtype=np.float64)
+    if ini.ndim == 0:
+        ini = np.full(batch, float(ini))
+    if ini.shape != (batch, ):
+        raise ValueError('iir_dac_rows: initial is a scalar or one value per row')
+    if n == 0:
+        codes, counts = np.zeros((batch, 0), dtype=np.int16), np.zeros((batch, 3), dtype=np.int64)
+        return (codes, counts) if return_counts else codes
+    with _engine.IirRowsDacPlan(filters_rows, g, o, n, bits, shift, dtype, packed=packed) as plan, \
+            _engine.DeviceBuffer(sig2.nbytes) as x, _engine.DeviceBuffer(batch * n * 2) as y, \
+            _engine.DeviceBuffer(batch * 24) as c, _engine.DeviceBuffer(batch * 8) as lv:
+        x.upload(sig2)
+        lv.upload(np.ascontiguousarray(ini))
+        plan.apply(x.ptr, n, y.ptr, n, c.ptr if return_counts else None, None, None, lv.ptr if ini.any() else None)
+        _engine.sync()
+        codes = y.download((batch, n), np.int16)
+        return (codes, c.download((batch, 3), np.int64)) if return_counts else codes
+
+
 class SampledDac:
     """`BatchSampler(channels, grid).launch_torch(z)` (float64) followed by `DacStage(gain, n, offset, ...)
     .apply_torch(z)`, device-resident and bit for bit -- codes and counts -- with the float64 rows left out: a
@@ -1583,6 +1728,135 @@ class SampledDac:
             _engine.sync()
             codes = y.download((self.out_rows, self.out_n), np.int16)
             return (codes, c.download((self.n_channels, 3), np.int64)) if return_counts else codes
+
+    def close(self):
+        self.plan.close()
+        if self._scratch is not None:
+            self._scratch.close()
+            self._scratch = None
+
+
+class SampledIirDac:
+    """`SampledIirRows(channels, grid, filters_rows).launch_torch(z, initial=, zi=, zf=)` (float64) followed by
+    `DacStage(gain, n, offset, bits, shift).apply_torch(z, counts=)`, device-resident and bit for bit -- codes, counts
+    and zf -- with the float64 rows left out: a whole flux line, waveform, exp-decay correction and converter, in ONE
+    kernel with 2 B per sample of HBM traffic.  Where `SampledIirRows` fuses (`fused`), the same fill runs in front of
+    the codes store: `kernel_name()` is 'iir_rows_sampled_dac<f64,NSEC,ORD>' on fine grids,
+    'iir_rows_short_dac<f64,NSEC,ORD>' at AWG sample rates.  Plans it does not take (`why_not`: clip on a fine grid,
+    generic terms, WFK_CHAIN_UNFUSED=1) run the sampler into a float64 scratch taken once, here, and then
+    'iir_rows_dac<f64,NSEC,ORD>': two launches instead of three.  `filters_rows`: one cascade [(b, a), ...] per row with
+    `IirStage`'s per-row rules; `gain` / `offset`: a scalar or one value per channel; `bits`, `shift` and the optional
+    (n_channels, 3) int64 counts as `DacStage` has them.  Build once, launch many times.
+
+        sd = SampledIirDac.from_full_scale(channels, wl.awg_grid(n, 2e9), filters_rows, 1.0)     # +-1.0 -> +-32767
+        sd.launch_torch(codes, counts=clipped, initial=levels, zf=zf)    # (n_channels, >= n) int16, the current stream
+    """
+
+    def __init__(self, channels, grid, filters_rows, gain, offset=0.0, bits: int = 16, shift: int = 0,
+                 function_lib=None, tile=1):
+        """`tile` > 1 repeats the channel list that many times (synthetic batches, as BatchSampler's)"""
+        from . import _flatten
+        channels, filters_rows = list(channels), list(filters_rows)
+        rows = len(channels) * max(int(tile), 1)
+        if rows < 1:
+            raise ValueError('SampledIirDac: no rows')
+        if len(filters_rows) != rows:
+            raise ValueError(f'SampledIirDac: {len(filters_rows)} cascades for {rows} rows')
+        gains, offsets = (_per_row('SampledIirDac', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v, rows)
+                          for what, v in (('gain', gain), ('offset', offset)))
+        if not isinstance(grid, _flatten.wfk_grid):
+            grid = _flatten.grid_from_desc(grid)
+        # argument errors before any device work
+        _engine.dac_rows_arguments(gains, offsets, int(grid.n), bits, shift, 1)
+        packed = _engine.pack_sections_rows(filters_rows)
+        self.prog = _flatten.tile_program(_flatten.flatten(channels, grid, function_lib), tile)
+        if self.prog.n_channels != rows:
+            raise ValueError(f'SampledIirDac: {rows} cascades for {self.prog.n_channels} rows')
+        if self.prog.complex_amp or self.prog.host_complex:
+            raise NotImplementedError('complex rows')
+        self.plan = _engine.ChainIirRowsDacPlan(self.prog, grid, filters_rows, gains, offsets, bits, shift, packed=packed)
+        p = self.plan
+        self.n, self.n_channels, self.gain, self.offset = p.n, p.n_channels, p.gain, p.offset
+        self.bits, self.shift, self.lo, self.hi = p.bits, p.shift, p.lo, p.hi
+        self.state_dim, self.own_orders, self.section_order = p.state_dim, packed[3], int(packed[0][0])
+        self.fused, self.why_not = p.fused, p.why_not
+        self._initial_cache = None
+        # the unfused path's float64 rows: taken once, here
+        self._scratch = None if self.fused else _engine.DeviceBuffer(max(self.n_channels * self.n, 1) * 8)
+
+    @classmethod
+    def from_full_scale(cls, channels, grid, filters_rows, full_scale, **kw):
+        """the plan whose gain[r] = hi / full_scale[r], so that a filtered +-full scale maps to +-hi (a scalar: every
+        row).  ValueError: a full scale that is not finite or not positive."""
+        bits = int(kw.get('bits', 16))
+        if not 2 <= bits <= 16:
+            raise ValueError('bits must lie in [2, 16]')
+        fs = np.asarray(full_scale, dtype=np.float64)
+        if not np.all(np.isfinite(fs) & (fs > 0.0)):
+            raise ValueError('SampledIirDac: every full scale must be finite and positive')
+        return cls(channels, grid, filters_rows, (2**(bits - 1) - 1) / fs, **kw)
+
+    def row_state(self, z, r: int):
+        """row r's own state (scipy layout, its sections back to back) out of a (n_channels, state_dim) host array"""
+        return _row_state(z, r, self.own_orders, self.section_order)
+
+    def kernel_name(self) -> str:
+        """'iir_rows_sampled_dac<f64,NSEC,ORD>' | 'iir_rows_short_dac<f64,NSEC,ORD>' | '<sampler kernels> +
+        iir_rows_dac<f64,NSEC,ORD>'"""
+        return self.plan.kernel_name()
+
+    def launch(self, out_ptr, out_stride=None, counts_ptr=None, zi_ptr=None, zf_ptr=None, initial_ptr=None, stream=0):
+        """raw pointers; out_stride in codes (None: n); initial_ptr: device array of n_channels doubles or None"""
+        s = self._scratch
+        self.plan.launch(out_ptr, self.n if out_stride is None else out_stride, counts_ptr,
+                         None if s is None else s.ptr, self.n, zi_ptr, zf_ptr, initial_ptr, stream)
+
+    def launch_torch(self, codes, counts=None, initial=0.0, zi=None, zf=None):
+        """codes: (n_channels, >= n) row-contiguous int16 device tensor (rows may be a window of a wider tensor);
+        counts: None or a contiguous (n_channels, 3) int64 device tensor, overwritten with [below, above, nan] per
+        channel; it may share no memory with `codes` (ValueError); `initial`: a scalar, one value per row, or a
+        (n_channels,) float64 device tensor; zi / zf: optional (n_channels, state_dim) float64 device tensors.
+        Asynchronous on torch's current stream.  -> codes[:, :n]"""
+        import torch
+        y0, ys = _rows.check_rows(codes, self.n_channels, self.n, torch.int16,
+                                  'expected codes: (n_channels, >=n) row-contiguous int16 device tensor')
+        c0 = _rows.check_state(counts, (self.n_channels, 3),
+                               'expected counts: contiguous (n_channels, 3) int64 device tensor', dtype=np.int64)
+        zip_, zfp = (_rows.check_state(z, (self.n_channels, self.state_dim),
+                                       'zi / zf must be contiguous (n_channels, state_dim) float64 device tensors')
+                     for z in (zi, zf))
+        if not _rows.report_disjoint(c0, self.n_channels, 3, (y0, ys, self.n_channels, self.n, 2)):
+            raise ValueError('sampled iir dac: counts overlaps codes')
+        ini = _initial_rows(self, self.n_channels, initial, codes.device)
+        self.launch(y0, ys, c0, zip_, zfp, None if ini is None else ini.data_ptr(),
+                    torch.cuda.current_stream(codes.device).cuda_stream)
+        return codes[:, :self.n]
+
+    def to_host(self, initial=0.0, zi=None, return_counts=False, return_zf=False):
+        """NumPy codes (n_channels, n) [, counts (n_channels, 3)] [, zf (n_channels, state_dim)]; initial: a scalar or
+        one value per row; zi: (n_channels, state_dim)"""
+        D = max(self.state_dim, 1)
+        ini = np.broadcast_to(np.asarray(initial, dtype=np.float64), (self.n_channels, ))
+        with contextlib.ExitStack() as stack:
+            y = _dev(stack, self.n_channels * self.n * 2)
+            c = _dev(stack, self.n_channels * 24) if return_counts else None
+            dzi = _dev(stack, self.n_channels * D * 8) if zi is not None else None
+            dzf = _dev(stack, self.n_channels * D * 8) if return_zf else None
+            dini = _dev(stack, self.n_channels * 8) if ini.any() else None
+            if zi is not None:
+                dzi.upload(np.ascontiguousarray(np.broadcast_to(np.asarray(zi, dtype=np.float64),
+                                                                (self.n_channels, self.state_dim))))
+            if dini is not None:
+                dini.upload(np.ascontiguousarray(ini))
+            self.launch(y.ptr, None, None if c is None else c.ptr, None if dzi is None else dzi.ptr,
+                        None if dzf is None else dzf.ptr, None if dini is None else dini.ptr)
+            _engine.sync()
+            out = [y.download((self.n_channels, self.n), np.int16)]
+            if return_counts:
+                out.append(c.download((self.n_channels, 3), np.int64))
+            if return_zf:
+                out.append(dzf.download((self.n_channels, D), np.float64)[:, :self.state_dim])
+            return out[0] if len(out) == 1 else tuple(out)
 
     def close(self):
         self.plan.close()
