@@ -797,6 +797,79 @@ int wfk_curve_rows_spans(const wfk_curve_rows_plan* plan);
 const char* wfk_curve_rows_kernel_name(const wfk_curve_rows_plan* plan, int counts);
 int wfk_curve_rows_plan_destroy(wfk_curve_rows_plan* plan);   /* NULL is fine */
 
+/* -- per-row curve, IIR and DAC codes: a flux line's back end in one kernel ------------------------ */
+/* codes = wfk_iir_rows_dac(wfk_curve_rows(in)) bit for bit -- codes, both reports and zf -- without the float rows
+ * between them: the waveform in its physical unit through the line's measured curve to volts, the line's exp-decay
+ * correction, the converter.  The curves (knot_ptr, xp, fp, left, right) are those of wfk_curve_rows_plan_create; the
+ * sections, n, batch and kind those of wfk_iir_rows_plan_create; gain, offset, bits and shift those of
+ * wfk_dac_rows_plan_create with interleave 1.  Per sample u = the result of wfk_curve_rows_apply (kind F32: rounded to
+ * float once), then y and the code as wfk_iir_rows_dac_apply forms them from u; initial_dev holds levels of u.  Every
+ * refusal of the three creators applies with its text -- the curve's first, then the converter's, then the cascades'
+ * -- before any device work; no device: WFK_EHIP.  One kernel, "iir_rows_curve_dac<T,NSEC,ORD>": iir_rows_dac with the
+ * row's knots and a bucket table copied into dynamic LDS once per row (static + dynamic <= 64 KiB: the bucket table
+ * is the largest power of two, at most wfk_curve_rows' choice, that fits next to the tile -- down to none, plain
+ * bisection; the count never changes a result) and every sample looked up on its way into the tile: in_elem + 2 bytes
+ * per sample.  wfk_curve_iir_dac_apply() enqueues that kernel on `hip_stream`, and that is all it does to the device
+ * (as wfk_iir_rows_dac_apply: it may be called while the stream is being captured).  Strides, zi_dev / zf_dev / initial_dev and counts_dev (the converter's [below, above, nan] per row) as
+ * wfk_iir_rows_dac_apply takes them; beyond_dev: NULL, or batch * 3 int64, the CURVE's [below, above, nan] per row --
+ * the samples of [0, n) outside the knots or NaN -- OVERWRITTEN by every apply like counts_dev (stored by the row's
+ * workgroup: no zeroing in front).  OUT OF PLACE only: out that meets in, a report that meets either side or the other
+ * report or does not start at a multiple of 8, rows not aligned to their element, a stride below the row: WFK_EINVAL.
+ * _apply_shared_in: every row reads the SAME n samples at in_dev, each through its own curve and cascade.  n = 0: the
+ * kernel is not launched; both reports are zeroed.  The plan owns its tables and nothing else. */
+typedef struct wfk_curve_iir_dac_plan wfk_curve_iir_dac_plan;
+int wfk_curve_iir_dac_plan_create(int32_t n_sections, const int32_t* orders, const double* b_rows,
+                                  const double* a_rows, int64_t n, int32_t batch, int kind /* WFK_OUT_F64|F32 */,
+                                  const int64_t* knot_ptr /* batch + 1, from 0 */, const double* xp, const double* fp,
+                                  const double* left /* batch, or NULL */, const double* right /* batch, or NULL */,
+                                  const double* gain, const double* offset, int bits, int shift,
+                                  wfk_curve_iir_dac_plan** out);
+int wfk_curve_iir_dac_apply(wfk_curve_iir_dac_plan* plan, const void* in_dev, int64_t in_stride, int16_t* out_dev,
+                            int64_t out_stride /* in codes */, int64_t* counts_dev /* batch * 3, or NULL */,
+                            int64_t* beyond_dev /* batch * 3, or NULL */, const double* zi_dev, double* zf_dev,
+                            const double* initial_dev, void* hip_stream);
+int wfk_curve_iir_dac_apply_shared_in(wfk_curve_iir_dac_plan* plan, const void* in_dev, int16_t* out_dev,
+                                      int64_t out_stride, int64_t* counts_dev, int64_t* beyond_dev,
+                                      const double* zi_dev, double* zf_dev, const double* initial_dev,
+                                      void* hip_stream);
+int wfk_curve_iir_dac_state_dim(const wfk_curve_iir_dac_plan* plan);
+/* "iir_rows_curve_dac<f64,1,3>"; "" for NULL; owned by the plan */
+const char* wfk_curve_iir_dac_kernel_name(const wfk_curve_iir_dac_plan* plan);
+int wfk_curve_iir_dac_plan_destroy(wfk_curve_iir_dac_plan* plan);   /* NULL is fine */
+
+/* -- sampler -> per-row curve -> per-row IIR -> DAC codes: a flux line in its physical unit --------- */
+/* wfk_plan_launch (WFK_OUT_F64), wfk_curve_rows_apply in place and wfk_iir_rows_dac_apply, bit for bit -- codes, both
+ * reports and zf.  The program, grid and sections are those of wfk_chain_iir_rows_dac_plan_create, the curves those of
+ * wfk_curve_rows_plan_create (one per channel), gain, offset, bits and shift the converter's; every refusal with its
+ * text, the curve's first, then the converter's, then the chain's, before any device work.  Fused (_is_fused) exactly
+ * where wfk_chain_iir_rows_dac is, with its reasons -- and one more: a curve of more than 567 knots does not fit next to
+ * the fine-grid fill's LDS.  Fused, every sample the fill produces goes through its row's curve before it enters the
+ * filter: "iir_rows_sampled_curve_dac<f64,NSEC,ORD>" on fine grids, "iir_rows_short_curve_dac<f64,NSEC,ORD>" at AWG
+ * rates, 2 B per sample of HBM traffic, static + dynamic LDS <= 64 KiB.  Otherwise (_unfused_reason) the sampler writes
+ * float64 rows into scratch_dev (as wfk_chain_iir_rows_dac_launch takes it; it may meet neither the codes nor a report)
+ * and "iir_rows_curve_dac<f64,NSEC,ORD>" reads them.  counts_dev / beyond_dev as wfk_curve_iir_dac_apply takes them.  A
+ * launch enqueues its one or two kernels on `hip_stream`, and that is all it does to the device (it may be called
+ * while the stream is being captured).  n = 0: nothing is launched; both reports are zeroed. */
+typedef struct wfk_chain_curve_iir_dac_plan wfk_chain_curve_iir_dac_plan;
+int wfk_chain_curve_iir_dac_plan_create(const wfk_program* prog, const wfk_grid* grid, int32_t n_sections,
+                                        const int32_t* orders, const double* b_rows, const double* a_rows,
+                                        const int64_t* knot_ptr /* n_channels + 1, from 0 */, const double* xp,
+                                        const double* fp, const double* left /* n_channels, or NULL */,
+                                        const double* right /* n_channels, or NULL */, const double* gain,
+                                        const double* offset, int bits, int shift,
+                                        wfk_chain_curve_iir_dac_plan** out);
+int wfk_chain_curve_iir_dac_launch(wfk_chain_curve_iir_dac_plan* plan, int16_t* out_dev, int64_t out_stride,
+                                   int64_t* counts_dev /* n_channels * 3, or NULL */,
+                                   int64_t* beyond_dev /* n_channels * 3, or NULL */, void* scratch_dev,
+                                   int64_t scratch_stride, const double* zi_dev, double* zf_dev,
+                                   const double* initial_dev, void* hip_stream);
+int wfk_chain_curve_iir_dac_is_fused(const wfk_chain_curve_iir_dac_plan* plan);
+const char* wfk_chain_curve_iir_dac_unfused_reason(const wfk_chain_curve_iir_dac_plan* plan);   /* "" when fused */
+const char* wfk_chain_curve_iir_dac_kernel_name(const wfk_chain_curve_iir_dac_plan* plan);
+int64_t wfk_chain_curve_iir_dac_table_bytes(const wfk_chain_curve_iir_dac_plan* plan);
+int wfk_chain_curve_iir_dac_state_dim(const wfk_chain_curve_iir_dac_plan* plan);
+int wfk_chain_curve_iir_dac_plan_destroy(wfk_chain_curve_iir_dac_plan* plan);   /* NULL is fine */
+
 /* -- per-row kernel extraction: the reference's extractKernel for every row ---------------------- */
 /* ker[r] = extractKernel(sig_in[r], sig_out[r], sample_rate, bw, skip) (waveforms/distortion.py:42-48) for `batch`
  * rows of n doubles: the kernel that maps sig_out back onto sig_in, the rows of an FIR plan's kernel matrix.  Per row

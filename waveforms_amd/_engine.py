@@ -206,6 +206,26 @@ def lib():
         l.wfk_curve_rows_kernel_name.argtypes = [VP, C.c_int]
         l.wfk_curve_rows_kernel_name.restype = C.c_char_p
         l.wfk_curve_rows_plan_destroy.argtypes = [VP]
+        l.wfk_curve_iir_dac_plan_create.argtypes = [I32, VP, VP, VP, I64, I32, C.c_int, VP, VP, VP, VP, VP, VP, VP,
+                                                    C.c_int, C.c_int, P(VP)]
+        l.wfk_curve_iir_dac_state_dim.argtypes = [VP]
+        l.wfk_curve_iir_dac_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP, VP, VP, VP, VP]
+        l.wfk_curve_iir_dac_apply_shared_in.argtypes = [VP, VP, VP, I64, VP, VP, VP, VP, VP, VP]
+        l.wfk_curve_iir_dac_kernel_name.argtypes = [VP]
+        l.wfk_curve_iir_dac_kernel_name.restype = C.c_char_p
+        l.wfk_curve_iir_dac_plan_destroy.argtypes = [VP]
+        l.wfk_chain_curve_iir_dac_plan_create.argtypes = [P(wfk_program), P(wfk_grid), I32, VP, VP, VP, VP, VP, VP, VP,
+                                                          VP, VP, VP, C.c_int, C.c_int, P(VP)]
+        l.wfk_chain_curve_iir_dac_is_fused.argtypes = [VP]
+        l.wfk_chain_curve_iir_dac_unfused_reason.argtypes = [VP]
+        l.wfk_chain_curve_iir_dac_unfused_reason.restype = C.c_char_p
+        l.wfk_chain_curve_iir_dac_kernel_name.argtypes = [VP]
+        l.wfk_chain_curve_iir_dac_kernel_name.restype = C.c_char_p
+        l.wfk_chain_curve_iir_dac_table_bytes.argtypes = [VP]
+        l.wfk_chain_curve_iir_dac_table_bytes.restype = I64
+        l.wfk_chain_curve_iir_dac_state_dim.argtypes = [VP]
+        l.wfk_chain_curve_iir_dac_launch.argtypes = [VP, VP, I64, VP, VP, VP, I64, VP, VP, VP, VP]
+        l.wfk_chain_curve_iir_dac_plan_destroy.argtypes = [VP]
         l.wfk_extract_rows_plan_create.argtypes = [I64, I32, I32, VP, I32, I64, P(VP)]
         l.wfk_extract_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP, I64, VP]
         l.wfk_extract_rows_kernel_name.argtypes = [VP]
@@ -1344,6 +1364,114 @@ class CurveRowsPlan(_Handle):
 
     def kernel_name(self, counts: bool = False) -> str:
         return lib().wfk_curve_rows_kernel_name(self._h, 1 if counts else 0).decode()
+
+
+def curve_iir_dac_arguments(xp_rows, fp_rows, sections_per_row, gain, offset, n, bits=16, shift=0, left=None, right=None,
+                            batch=None, dtype=np.float64, packed=None):
+    """the arguments of a CurveIirDacPlan, checked on the host: the curve's rules first (curve_rows_arguments), then the
+    converter's (dac_rows_arguments, interleave 1), then the cascades' (pack_sections_rows), each with its own texts ->
+    (curve: curve_rows_arguments' tuple, dac: dac_rows_arguments' tuple, packed: pack_sections_rows' tuple).  The number
+    of curves decides the rows: `N gains for B rows`, `N cascades for B rows`.  Needs no device."""
+    curve = curve_rows_arguments(xp_rows, fp_rows, left, right, batch, n, dtype)
+    rows = len(curve[0]) - 1
+    dac = dac_rows_arguments(gain, offset, n, bits, shift, 1, dtype)
+    if len(dac[0]) != rows:
+        raise ValueError(f'{len(dac[0])} gains for {rows} rows')
+    packed = pack_sections_rows(sections_per_row) if packed is None else packed
+    if packed[1].shape[0] != rows:
+        raise ValueError(f'{packed[1].shape[0]} cascades for {rows} rows')
+    return curve, dac, packed
+
+
+class CurveIirDacPlan(_Handle):
+    """CurveRowsPlan(xp_rows, fp_rows, n, batch, left, right, dtype) followed by IirRowsDacPlan(sections_per_row, gain,
+    offset, n, bits, shift, dtype), bit for bit -- codes, the converter's counts, the curve's `beyond` and the final
+    states -- in one kernel, 'iir_rows_curve_dac<T,NSEC,ORD>', without the float rows between them
+    (wfk_curve_iir_dac_plan_create).  One curve, one cascade and one gain and offset per row; the errors of the three
+    parents -- the curve's first, then the converter's, then the cascades' -- before any device work
+    (`curve_iir_dac_arguments`).  `state_dim`, `own_orders`, `orders` as IirRowsPlan; `.lo` / `.hi`: the rails;
+    `.knots`: the knots per row."""
+    _destroy = 'wfk_curve_iir_dac_plan_destroy'
+
+    def __init__(self, xp_rows, fp_rows, sections_per_row, gain, offset, n: int, bits: int = 16, shift: int = 0,
+                 left=None, right=None, batch=None, dtype=np.float64, packed=None):
+        curve, dac, packed = curve_iir_dac_arguments(xp_rows, fp_rows, sections_per_row, gain, offset, n, bits, shift,
+                                                     left, right, batch, dtype, packed)
+        self.knot_ptr, self.xp, self.fp, self.left, self.right, self.n, self.dtype = curve
+        self.gain, self.offset, _, self.bits, self.shift, _, _ = dac
+        orders, bm, am, self.own_orders = packed
+        self.batch, self.orders, self.knots = len(self.knot_ptr) - 1, orders, np.diff(self.knot_ptr)
+        self.lo, self.hi = -2**(self.bits - 1), 2**(self.bits - 1) - 1
+        bm, am = np.ascontiguousarray(bm), np.ascontiguousarray(am)
+        check(lib().wfk_curve_iir_dac_plan_create(len(orders), orders.ctypes.data, bm.ctypes.data, am.ctypes.data,
+                                                  self.n, self.batch, _KIND_OF[self.dtype], self.knot_ptr.ctypes.data,
+                                                  self.xp.ctypes.data, self.fp.ctypes.data, self.left.ctypes.data,
+                                                  self.right.ctypes.data, self.gain.ctypes.data,
+                                                  self.offset.ctypes.data, self.bits, self.shift, C.byref(self._h)))
+        self.state_dim = int(orders.sum())
+
+    def apply(self, in_ptr, in_stride, out_ptr, out_stride, counts_ptr=None, beyond_ptr=None, zi_ptr=None,
+              zf_ptr=None, initial_ptr=None, stream=0):
+        """counts_ptr / beyond_ptr: None, or batch * 3 int64 on the device, overwritten with the converter's / the
+        curve's [below, above, nan] per row; initial_ptr: device array of `batch` doubles (one level per row) or None"""
+        check(lib().wfk_curve_iir_dac_apply(self._h, in_ptr, in_stride, out_ptr, out_stride, counts_ptr, beyond_ptr,
+                                            zi_ptr, zf_ptr, initial_ptr, stream))
+
+    def apply_shared_in(self, in_ptr, out_ptr, out_stride, counts_ptr=None, beyond_ptr=None, zi_ptr=None, zf_ptr=None,
+                        initial_ptr=None, stream=0):
+        """every row reads the SAME n input samples at `in_ptr`"""
+        check(lib().wfk_curve_iir_dac_apply_shared_in(self._h, in_ptr, out_ptr, out_stride, counts_ptr, beyond_ptr,
+                                                      zi_ptr, zf_ptr, initial_ptr, stream))
+
+    def kernel_name(self) -> str:
+        return lib().wfk_curve_iir_dac_kernel_name(self._h).decode()
+
+
+class ChainCurveIirDacPlan(_Handle):
+    """sampler -> per-row curve -> per-row IIR -> DAC codes for every channel of `prog` on `grid`
+    (wfk_chain_curve_iir_dac_*): Plan(prog, grid) (float64), CurveRowsPlan in place and IirRowsDacPlan, bit for bit.
+    Fused where ChainIirRowsDacPlan is -- 'iir_rows_sampled_curve_dac<f64,NSEC,ORD>' on fine grids,
+    'iir_rows_short_curve_dac<f64,NSEC,ORD>' at AWG rates: 2 B per sample of HBM traffic -- but for curves whose knots
+    do not fit next to the lean fill's LDS; everything else (`why_not`) runs the sampler into a float64 scratch the
+    caller lends, then 'iir_rows_curve_dac<f64,NSEC,ORD>'.  The errors of `curve_iir_dac_arguments`, in its order."""
+    _destroy = 'wfk_chain_curve_iir_dac_plan_destroy'
+
+    def __init__(self, prog: Program, grid: wfk_grid, xp_rows, fp_rows, sections_per_row, gain, offset, bits: int = 16,
+                 shift: int = 0, left=None, right=None, packed=None):
+        curve, dac, packed = curve_iir_dac_arguments(xp_rows, fp_rows, sections_per_row, gain, offset, int(grid.n), bits,
+                                                     shift, left, right, prog.n_channels, np.float64, packed)
+        self.knot_ptr, self.xp, self.fp, self.left, self.right, self.n, _ = curve
+        self.gain, self.offset, _, self.bits, self.shift, _, _ = dac
+        orders, bm, am, self.own_orders = packed
+        self.prog, self.grid, self.n_channels, self.orders = prog, grid, prog.n_channels, orders
+        self.knots = np.diff(self.knot_ptr)
+        self.lo, self.hi = -2**(self.bits - 1), 2**(self.bits - 1) - 1
+        bm, am = np.ascontiguousarray(bm), np.ascontiguousarray(am)
+        check(lib().wfk_chain_curve_iir_dac_plan_create(C.byref(prog.struct), C.byref(grid), len(orders),
+                                                        orders.ctypes.data, bm.ctypes.data, am.ctypes.data,
+                                                        self.knot_ptr.ctypes.data, self.xp.ctypes.data,
+                                                        self.fp.ctypes.data, self.left.ctypes.data,
+                                                        self.right.ctypes.data, self.gain.ctypes.data,
+                                                        self.offset.ctypes.data, self.bits, self.shift, C.byref(self._h)))
+        self.state_dim = int(orders.sum())
+        self.fused = bool(lib().wfk_chain_curve_iir_dac_is_fused(self._h))
+        self.why_not = lib().wfk_chain_curve_iir_dac_unfused_reason(self._h).decode()
+
+    def launch(self, out_ptr, out_stride, counts_ptr=None, beyond_ptr=None, scratch_ptr=None, scratch_stride=0,
+               zi_ptr=None, zf_ptr=None, initial_ptr=None, stream=0):
+        """counts_ptr / beyond_ptr: None, or n_channels * 3 int64 on the device, overwritten with the converter's / the
+        curve's [below, above, nan]; scratch_ptr: n_channels float64 rows `scratch_stride` apart, which an unfused plan
+        needs and a fused one does not touch"""
+        check(lib().wfk_chain_curve_iir_dac_launch(self._h, out_ptr, out_stride, counts_ptr, beyond_ptr, scratch_ptr,
+                                                   scratch_stride, zi_ptr, zf_ptr, initial_ptr, stream))
+
+    def kernel_name(self) -> str:
+        """'iir_rows_sampled_curve_dac<f64,NSEC,ORD>', 'iir_rows_short_curve_dac<f64,NSEC,ORD>', or the sampler's
+        kernels and 'iir_rows_curve_dac<f64,NSEC,ORD>' joined with ' + '"""
+        return lib().wfk_chain_curve_iir_dac_kernel_name(self._h).decode()
+
+    def table_bytes(self) -> int:
+        return int(lib().wfk_chain_curve_iir_dac_table_bytes(self._h))
 
 
 class ExtractRowsPlan(_Handle):

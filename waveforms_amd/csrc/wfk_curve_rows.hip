@@ -38,49 +38,11 @@
 
 #pragma clang fp contract(off)   // a rounded difference, a rounded product and a rounded sum, as the host formula
 
+#include "wfk_curve_dev.h"       // CurveRow, Knots, curve_at; the host's check and table builder
+
 namespace {
 
 constexpr int kMaxSpans = 16;   // spans a workgroup may walk
-
-// one row as the device reads it
-struct CurveRow {
-  int64_t off;     // of the row's knots in the knot table, in doubles: xp[K], fp[K], slope[K] from there
-  int64_t boff;    // of the row's buckets in the bucket table
-  int32_t K;
-  int32_t nb;      // buckets: a power of two >= 2 K, or 0 (none: the bracket is every knot)
-  double left, right;
-  double x0, xl;   // xp[0], xp[K - 1]
-  double scale;    // nb / (xl - x0)
-};
-
-// the knots of a row in LDS
-struct Knots {
-  const double* xp;
-  const double* fp;
-  const double* slope;
-  const uint32_t* bucket;   // lo | hi << 16: the knots j with xp[j] <= x for some x of the bucket lie in [lo, hi]
-};
-
-// the curve at x, inside [x0, xl]
-__device__ __forceinline__ double curve_at(const Knots& t, const CurveRow& row, double x) {
-  int lo = 0, hi = row.K - 1;
-  if (row.nb) {
-    const double b = fmin(fmax((x - row.x0) * row.scale, 0.0), (double)(row.nb - 1));
-    const uint32_t e = t.bucket[(int)b];
-    lo = (int)(e & 0xffffu);
-    hi = (int)(e >> 16);
-  }
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (t.xp[mid] <= x) lo = mid; else hi = mid - 1;
-  }
-  // exact whatever the bracket was: the largest j with xp[j] <= x
-  int j = lo;
-  while (j > 0 && x < t.xp[j]) --j;
-  while (j + 1 < row.K && t.xp[j + 1] <= x) ++j;
-  const double xj = t.xp[j], fj = t.fp[j];
-  return x == xj ? fj : t.slope[j] * (x - xj) + fj;
-}
 
 // One workgroup's share of row `row`: `spans` consecutive spans from span blk * spans on.
 template <typename T, bool COUNT>
@@ -240,16 +202,6 @@ void curve_launch(const wfk_curve_rows_plan* p, const void* in, int64_t in_strid
                        out_stride, rows, knots, buckets, p->n, p->blocks_per_row, p->spans, p->lds_knots);
 }
 
-// the largest j with xp[j] <= v, for v >= xp[0]
-int knot_at_or_below(const double* xp, int K, double v) {
-  int lo = 0, hi = K - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (xp[mid] <= v) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 }  // namespace
 
 extern "C" {
@@ -270,48 +222,15 @@ int wfk_curve_rows_plan_create(int64_t n, int32_t batch, int kind, const int64_t
                                wfk_curve_rows_plan** out) try {
   if (!out) return wfk_fail(WFK_EINVAL, "null out");
   *out = nullptr;
-  if (n < 0 || batch < 1 || !knot_ptr || !xp || !fp) return wfk_fail(WFK_EINVAL, "bad curve rows plan arguments");
-  if (const int rc = wfk_check_kind(kind)) return rc;
-  if (knot_ptr[0] != 0) return wfk_fail(WFK_EINVAL, "curve rows plan: knot_ptr is not non-decreasing from 0");
-  for (int32_t r = 0; r < batch; ++r)
-    if (knot_ptr[r + 1] < knot_ptr[r])
-      return wfk_fail(WFK_EINVAL, "curve rows plan: knot_ptr is not non-decreasing from 0");
-  int max_k = 0;
-  for (int32_t r = 0; r < batch; ++r) {
-    const std::string row = "row " + std::to_string(r) + ": ";
-    const int64_t k = knot_ptr[r + 1] - knot_ptr[r];
-    if (k < 2) return wfk_fail(WFK_EINVAL, row + "fewer than 2 knots");
-    if (k > WFK_CURVE_MAX_KNOTS)
-      return wfk_fail(WFK_EINVAL, row + "more than " + std::to_string(WFK_CURVE_MAX_KNOTS) + " knots");
-    const double* x = xp + knot_ptr[r];
-    const double* f = fp + knot_ptr[r];
-    for (int64_t j = 0; j < k; ++j) {
-      if (!std::isfinite(x[j])) return wfk_fail(WFK_EINVAL, row + "knot " + std::to_string(j) + " is not finite");
-      if (j && !(x[j] > x[j - 1]))
-        return wfk_fail(WFK_EINVAL, row + "knots are not strictly increasing at " + std::to_string(j));
-    }
-    for (int64_t j = 0; j < k; ++j)
-      if (!std::isfinite(f[j])) return wfk_fail(WFK_EINVAL, row + "value " + std::to_string(j) + " is not finite");
-    max_k = std::max(max_k, (int)k);
-  }
+  if (const int rc = curve_check(n, batch, kind, knot_ptr, xp, fp)) return rc;
   // the spans a workgroup walks: the copy of a row's tables (28 or 32 bytes a knot, from L2) against the 32 KiB a span
   // streams -- one span per 4 KiB of tables (DESIGN.md has the measurement), while the grid keeps >= 2048 workgroups
   const int V = 16 / (int)wfk_elem_size(kind);
   const int64_t span = (int64_t)V * kThreads * kSlots;
   const bool use_buckets = env_int("WFK_CURVE_BUCKETS", 1) != 0;
-  int max_nb = 0;
-  std::vector<int> nbs((size_t)batch, 0);
-  for (int32_t r = 0; r < batch; ++r) {
-    const int k = (int)(knot_ptr[r + 1] - knot_ptr[r]);
-    const double* x = xp + knot_ptr[r];
-    int nb = 1;
-    while (nb < 2 * k) nb *= 2;
-    const double scale = (double)nb / (x[k - 1] - x[0]);
-    // (a range that overflows, or one so narrow that the scale does: plain bisection)
-    if (use_buckets && std::isfinite(scale) && scale > 0.0) nbs[r] = nb;
-    max_nb = std::max(max_nb, nbs[r]);
-  }
-  const size_t lds_bytes = 64 + (size_t)24 * max_k + (size_t)4 * max_nb;
+  const CurveTables ct = curve_build(batch, knot_ptr, xp, fp, left, right, use_buckets, (size_t)-1);
+  const int max_k = ct.max_k;
+  const size_t lds_bytes = 64 + ct.lds_bytes();
   int spans = (int)std::min<size_t>(kMaxSpans, std::max<size_t>(1, (lds_bytes - 64 + 4095) / 4096));
   const int64_t row_spans = n / span + 1;
   while (spans > 1 && (row_spans + spans - 1) / spans * batch < 2048) --spans;
@@ -319,37 +238,6 @@ int wfk_curve_rows_plan_create(int64_t n, int32_t batch, int kind, const int64_t
   uint32_t bpr = 0;
   if (const int rc = wfk_row_blocks("curve rows plan", n, span * spans, V - 1, batch, &bpr)) return rc;
 
-  std::vector<CurveRow> rows((size_t)batch);
-  std::vector<double> knots((size_t)3 * (size_t)knot_ptr[batch]);
-  std::vector<uint32_t> buckets;
-  for (int32_t r = 0; r < batch; ++r) {
-    const int k = (int)(knot_ptr[r + 1] - knot_ptr[r]);
-    const double* x = xp + knot_ptr[r];
-    const double* f = fp + knot_ptr[r];
-    CurveRow& row = rows[r];
-    row.off = 3 * knot_ptr[r];
-    row.boff = (int64_t)buckets.size();
-    row.K = k;
-    row.nb = nbs[r];
-    row.left = left ? left[r] : f[0];
-    row.right = right ? right[r] : f[k - 1];
-    row.x0 = x[0];
-    row.xl = x[k - 1];
-    row.scale = row.nb ? (double)row.nb / (x[k - 1] - x[0]) : 0.0;
-    double* g = knots.data() + row.off;
-    for (int j = 0; j < k; ++j) {
-      g[j] = x[j];
-      g[k + j] = f[j];
-      g[2 * k + j] = j + 1 < k ? (f[j + 1] - f[j]) / (x[j + 1] - x[j]) : 0.0;
-    }
-    // bucket b covers [x0 + b w, x0 + (b + 1) w), w = (xl - x0) / nb; what rounding does to an edge the fix-up absorbs
-    const double w = (x[k - 1] - x[0]) / (double)std::max(row.nb, 1);
-    for (int b = 0; b < row.nb; ++b) {
-      const int lo = knot_at_or_below(x, k, x[0] + (double)b * w);
-      const int hi = b + 1 < row.nb ? knot_at_or_below(x, k, x[0] + (double)(b + 1) * w) : k - 1;
-      buckets.push_back((uint32_t)lo | ((uint32_t)std::max(lo, hi) << 16));
-    }
-  }
   if (!wfk_have_device()) return wfk_fail(WFK_EHIP, "no HIP device visible");
   std::unique_ptr<wfk_curve_rows_plan> p(new wfk_curve_rows_plan());
   p->n = n; p->batch = batch; p->kind = kind;
@@ -358,9 +246,9 @@ int wfk_curve_rows_plan_create(int64_t n, int32_t batch, int kind, const int64_t
   p->lds_knots = max_k;
   p->lds_bytes = lds_bytes;
   DevTables tab;
-  p->rows_off = tab.add(rows);
-  p->knots_off = tab.add(knots);
-  p->buckets_off = tab.add(buckets);
+  p->rows_off = tab.add(ct.rows);
+  p->knots_off = tab.add(ct.knots);
+  p->buckets_off = tab.add(ct.buckets);
   if (const int rc = wfk_upload_tables("curve rows plan", tab, p->tables)) return rc;
   *out = p.release();
   return WFK_OK;

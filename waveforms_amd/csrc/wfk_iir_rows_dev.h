@@ -31,7 +31,22 @@
 #define IRW_DAC_PARAMS \
   const double* __restrict__ gd, unsigned long long* __restrict__ counts, double lo, double hi, int shift
 
+// the curve side of the kernels that look every sample up in the row's calibration curve before it enters the tile
+// (iir_rows_curve_dac and the _curve_dac builds of the sampled pair; the types: wfk_curve_dev.h):
+// crows [batch], the knot and bucket tables they point into, beyond [batch][3] = [below, above, nan] or null, and the
+// knots of the plan's largest row (the pitch of xp / fp / slope in the dynamic LDS)
+#define IRW_CURVE_PARAMS                                                                                      \
+  const CurveRow* __restrict__ crows, const double* __restrict__ cknots, const uint32_t* __restrict__ cbuckets, \
+      unsigned long long* __restrict__ beyond, int lds_knots
+
 namespace {
+
+// Bytes of dynamic LDS a curve may take next to the tile of `es`-byte elements: 64 KiB less the static arrays of the
+// widest shape (tile, s_tot, s_carry, the two [waves][3] counters), the `extra` static bytes of a kernel with a fill,
+// and a line of slack for the region's alignment.
+__host__ __device__ constexpr size_t irw_curve_lds_budget(size_t es, size_t extra = 0) {
+  return 65536 - (es * IRW_THREADS * IRW_PITCH + (IRW_WAVES + 2) * IRW_MAXD * 8 + 2 * IRW_WAVES * 3 * 8) - extra - 64;
+}
 
 // per-row table (doubles): b[NC] a[NC] | pw[IRW_NPW][D][D][2] | lanep[64][D][D][2] (T^l, l = 0 .. 63)
 __host__ __device__ constexpr int irw_row_doubles(int nsec, int ord) {

@@ -34,6 +34,7 @@
 #include "wfk_internal.h"
 #include "wfk_short_dev.h"
 #include "wfk_chain_dev.h"
+#include "wfk_curve_dev.h"
 #include "wfk_iir_rows_dev.h"
 
 #define IRW_STORE_INC "wfk_iir_rows_store.inc"   // for wfk_iir_rows_body.inc: the tile is stored as T, whole lines
@@ -78,7 +79,20 @@ struct IrsShortArgs {
 #define IRS_K(name) name##_dac
 #define IRS_OUT_PARAMS int16_t* out, int64_t out_stride, IRW_DAC_PARAMS,
 #include "wfk_iir_rows_sampled_kernels.inc"
+#undef IRS_K
+#undef IRS_OUT_PARAMS
+
+// ... and a third time with the row's calibration curve in front of the tile:
+// iir_rows_sampled_curve_dac, iir_rows_short_curve_dac
+#define IRW_CURVE
+#define IRS_K(name) name##_curve_dac
+#define IRS_OUT_PARAMS int16_t* out, int64_t out_stride, IRW_DAC_PARAMS, IRW_CURVE_PARAMS,
+#include "wfk_iir_rows_sampled_kernels.inc"
+#undef IRW_CURVE
 #undef IRW_DAC
+
+// the static LDS of the lean fill next to the tile: what a curve in front of it cannot have (irw_curve_lds_budget)
+constexpr size_t kIrsLeanLds = (IRS_PAR + 2 * (IRW_RUN + 1)) * sizeof(double);
 
 // the eight cascade shapes iir_rows_tile has: f(NSEC, ORD as integral constants); false: none of them
 template <typename F>
@@ -400,6 +414,163 @@ int wfk_chain_iir_rows_dac_launch(wfk_chain_iir_rows_dac_plan* p, int16_t* out_d
     });
   }
   if (hipGetLastError() != hipSuccess) return wfk_fail(WFK_EHIP, "sampler -> per-row IIR -> codes kernel launch failed");
+  return WFK_OK;
+}
+
+}  // extern "C"
+
+// ---- the same chain with the row's calibration curve between the sampler and the IIR:
+// BatchSampler -> CurveStage -> IirDacStage in one kernel.  The plan is a float64 chain plan -- its fill decision, its
+// tables, its sampler, its rows' IIR tables -- the rows' (gain, offset) pairs and the curves' tables.  Where the chain
+// plan fuses and the curves' tables fit next to the fill's LDS, the fill's samples go through the curve on their way
+// into the sweeps (iir_rows_sampled_curve_dac / iir_rows_short_curve_dac); otherwise the sampler writes float64 rows
+// into a scratch the caller lends and iir_rows_curve_dac (wfk_iir_rows_curve_dac.hip) reads them: two launches.
+struct wfk_chain_curve_iir_dac_plan {
+  wfk_chain_iir_rows_plan* chain = nullptr;
+  bool fused = false;
+  DevBuf<double> gd;                // [n_channels][2]: gain, offset
+  DevBuf<char> tables;              // CurveRow [n_channels], the knots, the buckets
+  size_t rows_off = 0, knots_off = 0, buckets_off = 0, lds_bytes = 0, table_bytes = 0;
+  int lds_knots = 0, bits = 0, shift = 0;
+  std::string why, name;
+  ~wfk_chain_curve_iir_dac_plan() {  // (the buffers go after this body: nothing on the device reads them any more)
+    if (gd || tables) (void)hipDeviceSynchronize();
+    wfk_chain_iir_rows_plan_destroy(chain);
+  }
+};
+
+extern "C" {
+
+int wfk_chain_curve_iir_dac_plan_destroy(wfk_chain_curve_iir_dac_plan* p) {
+  delete p;
+  return WFK_OK;
+}
+
+int wfk_chain_curve_iir_dac_plan_create(const wfk_program* prog, const wfk_grid* grid, int32_t n_sections,
+                                        const int32_t* orders, const double* b_rows, const double* a_rows,
+                                        const int64_t* knot_ptr, const double* xp, const double* fp, const double* left,
+                                        const double* right, const double* gain, const double* offset, int bits,
+                                        int shift, wfk_chain_curve_iir_dac_plan** out) try {
+  if (!out) return wfk_fail(WFK_EINVAL, "null out");
+  *out = nullptr;
+  if (!prog || !grid) return wfk_fail(WFK_EINVAL, "null argument");
+  if (prog->n_channels < 1) return wfk_fail(WFK_EINVAL, "per-row IIR chain: a program without channels");
+  // the curve's refusals, then the converter's, then the chain's: all before any device work
+  if (const int rc = curve_check(grid->n, prog->n_channels, WFK_OUT_F64, knot_ptr, xp, fp)) return rc;
+  if (!gain || !offset) return wfk_fail(WFK_EINVAL, "bad dac rows plan arguments");
+  if (const int rc = wfk_internal_dac_check(prog->n_channels, gain, offset, bits, shift, 1)) return rc;
+  std::unique_ptr<wfk_chain_curve_iir_dac_plan> p(new wfk_chain_curve_iir_dac_plan());
+  if (const int rc = wfk_chain_iir_rows_plan_create(prog, grid, n_sections, orders, b_rows, a_rows, WFK_OUT_F64, &p->chain))
+    return rc;
+  const wfk_chain_iir_rows_plan* c = p->chain;
+  p->bits = bits; p->shift = shift;
+  // fused exactly where the chain plan is -- but for curves whose knots alone do not fit next to the lean fill's
+  // parameter area: those plans take the composed route, whose kernel has the room
+  int max_k = 0;
+  for (int32_t r = 0; r < c->n_channels; ++r) max_k = std::max(max_k, (int)(knot_ptr[r + 1] - knot_ptr[r]));
+  const size_t lean_budget = irw_curve_lds_budget(sizeof(double), kIrsLeanLds);
+  const bool tight = c->fill == IrsFill::Lean && (size_t)24 * max_k > lean_budget;
+  p->fused = c->fill != IrsFill::None && !tight;
+  const size_t budget = p->fused && c->fill == IrsFill::Lean ? lean_budget : irw_curve_lds_budget(sizeof(double));
+  const CurveTables ct = curve_build(c->n_channels, knot_ptr, xp, fp, left, right, true, budget);
+  p->lds_knots = ct.max_k;
+  p->lds_bytes = ct.lds_bytes();
+  DevTables tab;
+  p->rows_off = tab.add(ct.rows);
+  p->knots_off = tab.add(ct.knots);
+  p->buckets_off = tab.add(ct.buckets);
+  p->table_bytes = tab.total();
+  if (const int rc = wfk_upload_tables("per-row curve IIR dac chain", tab, p->tables)) return rc;
+  std::vector<double> gd((size_t)c->n_channels * 2);
+  for (int32_t r = 0; r < c->n_channels; ++r) { gd[2 * (size_t)r] = gain[r]; gd[2 * (size_t)r + 1] = offset[r]; }
+  if (!p->gd.upload(gd)) {
+    (void)hipGetLastError();
+    return wfk_fail(WFK_ENOMEM, "per-row curve IIR dac chain: device allocation / upload failed");
+  }
+  const std::string shape = "f64," + std::to_string(c->nsec) + "," + std::to_string(c->ord) + ">";
+  if (p->fused) p->name = (c->fill == IrsFill::Lean ? "iir_rows_sampled_curve_dac<" : "iir_rows_short_curve_dac<") + shape;
+  else {
+    p->why = (tight ? "a curve of " + std::to_string(max_k) + " knots does not fit next to the lean fill's LDS (" +
+                          std::to_string(lean_budget / 24) + " at most)"
+                    : c->why) +
+             ": the sampler writes float64 rows into the plan's scratch, iir_rows_curve_dac reads them";
+    p->name = std::string(wfk_plan_kernel_name(c->sampler, WFK_OUT_F64)) + " + iir_rows_curve_dac<" + shape;
+  }
+  *out = p.release();
+  return WFK_OK;
+} catch (const std::bad_alloc&) {
+  return wfk_fail(WFK_ENOMEM, "out of host memory while building the chain plan");
+}
+
+int wfk_chain_curve_iir_dac_is_fused(const wfk_chain_curve_iir_dac_plan* p) { return p && p->fused ? 1 : 0; }
+
+const char* wfk_chain_curve_iir_dac_unfused_reason(const wfk_chain_curve_iir_dac_plan* p) { return p ? p->why.c_str() : ""; }
+
+const char* wfk_chain_curve_iir_dac_kernel_name(const wfk_chain_curve_iir_dac_plan* p) { return p ? p->name.c_str() : ""; }
+
+int64_t wfk_chain_curve_iir_dac_table_bytes(const wfk_chain_curve_iir_dac_plan* p) {
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
+  const int64_t chain = p->fused ? wfk_chain_iir_rows_table_bytes(p->chain) : wfk_plan_table_bytes(p->chain->sampler);
+  return chain + (int64_t)p->chain->n_channels * 16 + (int64_t)p->table_bytes;
+}
+
+int wfk_chain_curve_iir_dac_state_dim(const wfk_chain_curve_iir_dac_plan* p) {
+  return p ? wfk_chain_iir_rows_state_dim(p->chain) : WFK_EINVAL;
+}
+
+int wfk_chain_curve_iir_dac_launch(wfk_chain_curve_iir_dac_plan* p, int16_t* out_dev, int64_t out_stride,
+                                   int64_t* counts_dev, int64_t* beyond_dev, void* scratch_dev, int64_t scratch_stride,
+                                   const double* zi_dev, double* zf_dev, const double* initial_dev, void* hip_stream) {
+  if (!p) return wfk_fail(WFK_EINVAL, "null plan");
+  const wfk_chain_iir_rows_plan* c = p->chain;
+  const char* stage = "per-row curve IIR dac chain";
+  hipStream_t s = (hipStream_t)hip_stream;
+  const RowReport report{counts_dev, c->n_channels, 3};
+  // nothing to sample (the pointers of empty rows may be null); the reports are still zeroed
+  if (c->n == 0) {
+    if (const int rc = curve_beyond_rule(stage, beyond_dev, c->n_channels, counts_dev, {})) return rc;
+    if (const int rc = wfk_zero_report(stage, report, s)) return rc;
+    return wfk_zero_report(stage, RowReport{beyond_dev, c->n_channels, 3}, s);
+  }
+  // a lone code row's stride is not read
+  const RowSide codes{"out", out_dev, c->n_channels, out_stride, c->n, sizeof(int16_t), false};
+  const double* tab = wfk_internal_iir_rows_table(c->iir);
+  const CurveRow* crows = DevTables::at<const CurveRow>(p->tables.get(), p->rows_off);
+  const double* cknots = DevTables::at<const double>(p->tables.get(), p->knots_off);
+  const uint32_t* cbuckets = DevTables::at<const uint32_t>(p->tables.get(), p->buckets_off);
+  if (!p->fused) {
+    if (!scratch_dev) return wfk_fail(WFK_EINVAL, std::string(stage) + ": an unfused launch needs scratch (" + p->why + ")");
+    const RowSide scratch{"scratch", scratch_dev, c->n_channels, scratch_stride, c->n, sizeof(double)};
+    if (const int rc = wfk_row_rule(stage, {scratch}, codes, kRowsAligned | kRowsDisjoint, wfk_fail, report)) return rc;
+    if (const int rc = curve_beyond_rule(stage, beyond_dev, c->n_channels, counts_dev, {scratch, codes})) return rc;
+    if (const int rc = wfk_plan_launch(c->sampler, scratch_dev, scratch_stride, WFK_OUT_F64, 0, hip_stream)) return rc;
+    if (const int rc = wfk_internal_curve_iir_dac_run(tab, c->nsec, c->ord, WFK_OUT_F64, c->n_channels, c->n, scratch_dev,
+                                                      scratch_stride, out_dev, out_stride, p->gd.get(), counts_dev, crows,
+                                                      cknots, cbuckets, beyond_dev, p->lds_knots, p->lds_bytes, zi_dev,
+                                                      zf_dev, initial_dev, p->bits, p->shift, hip_stream))
+      return rc;
+  } else {
+    // (no input side: the rule takes `out` in its place; scratch is not touched)
+    if (const int rc = wfk_row_rule(stage, {codes}, codes, kRowsAligned, wfk_fail, report)) return rc;
+    if (const int rc = curve_beyond_rule(stage, beyond_dev, c->n_channels, counts_dev, {codes})) return rc;
+    const double lo = -(double)(1 << (p->bits - 1)), hi = (double)((1 << (p->bits - 1)) - 1);
+    const dim3 grid((unsigned)c->n_channels), block(IRW_THREADS);
+    unsigned long long* counts = (unsigned long long*)counts_dev;
+    unsigned long long* beyond = (unsigned long long*)beyond_dev;
+    (void)irs_shape(c->nsec, c->ord, [&](auto ns, auto od) {
+      constexpr int NS = decltype(ns)::value, OD = decltype(od)::value;
+      if (c->fill == IrsFill::Lean)
+        hipLaunchKernelGGL((iir_rows_sampled_curve_dac<double, NS, OD>), grid, block, p->lds_bytes, s, c->la, out_dev,
+                           out_stride, p->gd.get(), counts, lo, hi, p->shift, crows, cknots, cbuckets, beyond,
+                           p->lds_knots, tab, zi_dev, zf_dev, initial_dev, c->n);
+      else
+        hipLaunchKernelGGL((iir_rows_short_curve_dac<double, NS, OD>), grid, block, p->lds_bytes, s, c->sa, out_dev,
+                           out_stride, p->gd.get(), counts, lo, hi, p->shift, crows, cknots, cbuckets, beyond,
+                           p->lds_knots, tab, zi_dev, zf_dev, initial_dev, c->n);
+    });
+  }
+  if (hipGetLastError() != hipSuccess)
+    return wfk_fail(WFK_EHIP, "sampler -> curve -> per-row IIR -> codes kernel launch failed");
   return WFK_OK;
 }
 

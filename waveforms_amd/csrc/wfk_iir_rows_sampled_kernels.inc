@@ -5,7 +5,11 @@
 //   as codes iir_rows_sampled_dac / iir_rows_short_dac   IRW_DAC defined, IRS_K(name) = name_dac, IRS_OUT_PARAMS = the int16
 //                                                        rows and IRW_DAC_PARAMS, IRW_OUT_T = int16_t, the body stores
 //                                                        through wfk_iir_rows_store_dac.inc (DESIGN.md §3.23)
-// The fills are the same text either way.
+//   as codes, the row's curve in front of the tile       IRW_DAC and IRW_CURVE defined, IRS_K(name) = name_curve_dac,
+//            iir_rows_sampled_curve_dac /                IRS_OUT_PARAMS with IRW_CURVE_PARAMS behind IRW_DAC_PARAMS
+//            iir_rows_short_curve_dac                    (DESIGN.md §3.24): every sample the fill produces goes through
+//                                                        through_curve (wfk_iir_rows_curve_row.inc) before the sweeps
+// The fills are the same text every way; what IRW_CURVE adds expands to nothing without it.
 // ---- the lean fill: stride-256 chains (the sampling phase of fir_sampled, CL = 16, no carried op state) -----------
 template <typename T, int NSEC, int ORD>
 __global__ void __launch_bounds__(IRW_THREADS) IRS_K(iir_rows_sampled)(const IrsLeanArgs a, IRS_OUT_PARAMS
@@ -17,6 +21,9 @@ __global__ void __launch_bounds__(IRW_THREADS) IRS_K(iir_rows_sampled)(const Irs
 #include "wfk_iir_rows_head.inc"
 #ifdef IRW_DAC
 #include "wfk_iir_rows_dac_row.inc"
+#endif
+#ifdef IRW_CURVE
+#include "wfk_iir_rows_curve_row.inc"
 #endif
   __shared__ __attribute__((aligned(16))) double s_par[IRS_PAR + 2 * (CL + 1)];
   double2* const unit_tab = reinterpret_cast<double2*>(s_par + IRS_PAR);
@@ -85,7 +92,11 @@ __global__ void __launch_bounds__(IRW_THREADS) IRS_K(iir_rows_sampled)(const Irs
     const int64_t left = n - s1;
     CH_EACH(CL, k)
       const int j = k * IRW_THREADS + tid;
+#ifdef IRW_CURVE
+      tile[irw_at(j)] = through_curve(acc[k] + off, j < left);   // in the register: neighbouring lanes, neighbouring samples
+#else
       tile[irw_at(j)] = j < left ? acc[k] + off : (T)0;
+#endif
     CH_END
     __syncthreads();
     {
@@ -98,6 +109,9 @@ __global__ void __launch_bounds__(IRW_THREADS) IRS_K(iir_rows_sampled)(const Irs
   }
 #ifdef IRW_DAC
 #include "wfk_iir_rows_dac_end.inc"
+#endif
+#ifdef IRW_CURVE
+#include "wfk_iir_rows_curve_end.inc"
 #endif
 }
 
@@ -113,6 +127,9 @@ __global__ void __launch_bounds__(IRW_THREADS) IRS_K(iir_rows_short)(const IrsSh
 #include "wfk_iir_rows_head.inc"
 #ifdef IRW_DAC
 #include "wfk_iir_rows_dac_row.inc"
+#endif
+#ifdef IRW_CURVE
+#include "wfk_iir_rows_curve_row.inc"
 #endif
   const DevChannel C = a.channels[row];
   const double coff = C.offset;
@@ -171,6 +188,13 @@ __global__ void __launch_bounds__(IRW_THREADS) IRS_K(iir_rows_short)(const IrsSh
       CH_END
     }
     __syncthreads();
+#ifdef IRW_CURVE
+    // entries overwrite the offset the tile was filled with, so a sample is final only here: each lane takes its own run
+    // through the curve (the run the sweeps read next: no barrier between); the zeros behind the row stay zeros
+    CH_EACH(IRW_RUN, k)
+      my[k] = through_curve(my[k], tid * IRW_RUN + k < left);
+    CH_END
+#endif
     {
       const int64_t base = h0;
       double L[MM];                                              // T^lane, read here: after the fill
@@ -181,5 +205,8 @@ __global__ void __launch_bounds__(IRW_THREADS) IRS_K(iir_rows_short)(const IrsSh
   }
 #ifdef IRW_DAC
 #include "wfk_iir_rows_dac_end.inc"
+#endif
+#ifdef IRW_CURVE
+#include "wfk_iir_rows_curve_end.inc"
 #endif
 }

@@ -401,6 +401,15 @@ int wfk_internal_iir_rows_dac_run(const double* tab, int nsec, int ord, int kind
                                   const void* in, int64_t in_stride, int16_t* out, int64_t out_stride, const double* gd,
                                   int64_t* counts, const double* zi, double* zf, const double* initial, int bits,
                                   int shift, void* hip_stream);
+// wfk_iir_rows_curve_dac.hip: the launch of iir_rows_curve_dac<kind, nsec, ord>; as wfk_internal_iir_rows_dac_run, with
+// the curve tables of curve_build (wfk_curve_dev.h; curve_rows: its CurveRow [batch]) on the device, their largest
+// row's knots and bytes (held to irw_curve_lds_budget), and beyond [batch][3] or null
+int wfk_internal_curve_iir_dac_run(const double* tab, int nsec, int ord, int kind, int32_t batch, int64_t n,
+                                   const void* in, int64_t in_stride, int16_t* out, int64_t out_stride, const double* gd,
+                                   int64_t* counts, const void* curve_rows, const double* curve_knots,
+                                   const uint32_t* curve_buckets, int64_t* beyond, int lds_knots, size_t lds_bytes,
+                                   const double* zi, double* zf, const double* initial, int bits, int shift,
+                                   void* hip_stream);
 // wfk_dac_rows.hip: what wfk_dac_rows_plan_create asks of bits, shift, interleave and the batch gains and offsets
 // (neither null), with its texts: every plan that ends in the converter holds its arguments to it
 int wfk_internal_dac_check(int32_t batch, const double* gain_host, const double* offset_host, int bits, int shift,

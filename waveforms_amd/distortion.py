@@ -1970,6 +1970,329 @@ def interp_rows(sig, xp_rows, fp_rows, left=None, right=None, return_counts=Fals
         return (y, c.download((batch, 3), np.int64)) if return_counts else y
 
 
+class CurveIirDacStage:
+    """`CurveStage(xp_rows, fp_rows, n, batch, left, right, dtype).apply_torch(x, out=v, counts=beyond)` followed by
+    `IirDacStage(sections_rows, n, gain, offset, bits, shift, dtype).apply_torch(v, codes, counts, initial, zi, zf)`,
+    device-resident and bit for bit -- codes, both reports and zf -- in ONE kernel ('iir_rows_curve_dac<T,NSEC,ORD>')
+    without the float rows between them: a flux line programmed in its physical unit (detuning, flux), through the
+    line's measured monotone curve to volts, its own exp-decay correction, and the converter.  Row r:
+        v = np.interp(x[r], xp_rows[r], fp_rows[r], left[r], right[r])     (a float32 plan rounds v to float32 once)
+        y = F_r(v - initial[r]) + initial[r]                               (`initial`: levels of v, in volts)
+        code[r, i] = saturate(rint(y[i] * gain[r] + offset[r])) * 2**shift
+    The curves follow `CurveStage`'s rules (2 .. 1024 finite, strictly increasing knots per row, finite values; rows may
+    differ in number), the cascades `IirStage`'s per-row rules, gain / offset / bits / shift `DacStage`'s; a refusal
+    names the curve first, then the converter, then the cascade.  Whoever measured f(V) and needs V(f) passes the
+    output of `CurveStage.inverse_rows(volts, detuning)` as `xp_rows, fp_rows`.  The number of curves decides the rows
+    (one 1-D pair: `batch=`, or the number of gains); ONE cascade is given to every row.  Two optional (batch, 3) int64
+    reports are OVERWRITTEN by every apply: `beyond`, the curve's [below, above, nan] per row (samples outside the
+    measured range), and `counts`, the converter's (codes that met a rail).  `interleave` is not part of this stage.
+    What the stage saves is the float rows between the two (memory of the size of the batch) and a launch, not time: as
+    measured the two stages are faster.
+
+        xs, fs = CurveStage.inverse_rows(volts, detuning)
+        st = CurveIirDacStage.from_full_scale(xs, fs, [[exp_decay_filter(A, tau, 2e9)] for A, tau in lines], n, 1.0)
+        codes = st.apply_torch(x, counts=clipped, beyond=outside, initial=levels, zf=zf)
+    """
+
+    def __init__(self, xp_rows, fp_rows, sections_rows, n: int, gain, offset=0.0, bits: int = 16, shift: int = 0,
+                 left=None, right=None, dtype=np.float64, batch=None, interleave: int = 1):
+        if interleave != 1:
+            raise NotImplementedError('CurveIirDacStage has no interleave: a workgroup owns one row; run CurveStage, '
+                                      'IirStage and then DacStage(interleave=2) for a pair')
+        xs = _engine._curve_rows_list('xp', xp_rows)
+        if batch is None:
+            batch = max(len(xs), np.size(gain) if np.ndim(gain) > 0 else 1, np.size(offset) if np.ndim(offset) > 0 else 1)
+        curve = _engine.curve_rows_arguments(xp_rows, fp_rows, left, right, batch, n, dtype)   # the curve's rules first
+        rows = len(curve[0]) - 1
+        gains, offsets = (_per_row('CurveIirDacStage', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v,
+                                   rows) for what, v in (('gain', gain), ('offset', offset)))
+        _engine.dac_rows_arguments(gains, offsets, n, bits, shift, 1, dtype)                    # then the converter's
+        depth = _nesting(sections_rows)
+        if depth == 2:                                             # an SOS matrix
+            sec = np.asarray(sections_rows, dtype=np.float64)
+            if sec.ndim != 2 or sec.shape[1] != 6:
+                raise ValueError('CurveIirDacStage: an SOS matrix has shape (n_sections, 6)')
+            sections_rows, depth = _engine.sos_sections(sec), 3
+        if depth not in (3, 4):
+            raise ValueError('CurveIirDacStage: sections is one [(b, a), ...] per row, one [(b, a), ...], or an SOS '
+                             'matrix')
+        if depth == 3:                                             # one cascade: every row gets it
+            sections_rows = [list(sections_rows)] * rows
+        sections_rows = list(sections_rows)
+        if len(sections_rows) != rows:
+            raise ValueError(f'CurveIirDacStage: {len(sections_rows)} cascades for {rows} rows')
+        self.plan = _engine.CurveIirDacPlan(xp_rows, fp_rows, sections_rows, gains, offsets, n, bits, shift, left, right,
+                                            rows, dtype)
+        p = self.plan
+        self.n, self.batch, self.dtype, self.gain, self.offset = p.n, p.batch, p.dtype, p.gain, p.offset
+        self.knots, self.left, self.right = p.knots, p.left, p.right
+        self.bits, self.shift, self.lo, self.hi = p.bits, p.shift, p.lo, p.hi
+        self.state_dim, self.own_orders, self.section_order = p.state_dim, p.own_orders, int(p.orders[0])
+        self._initial_cache = None
+
+    @classmethod
+    def from_full_scale(cls, xp_rows, fp_rows, sections_rows, n: int, full_scale, **kw):
+        """the stage whose gain[r] = hi / full_scale[r], so that a filtered +-full scale (volts) maps to +-hi (a scalar:
+        every row).  ValueError: a full scale that is not finite or not positive."""
+        bits = int(kw.get('bits', 16))
+        if not 2 <= bits <= 16:
+            raise ValueError('bits must lie in [2, 16]')
+        fs = np.asarray(full_scale, dtype=np.float64)
+        if not np.all(np.isfinite(fs) & (fs > 0.0)):
+            raise ValueError('CurveIirDacStage: every full scale must be finite and positive')
+        return cls(xp_rows, fp_rows, sections_rows, n, (2**(bits - 1) - 1) / fs, **kw)
+
+    def kernel_name(self) -> str:
+        """'iir_rows_curve_dac<T,NSEC,ORD>'"""
+        return self.plan.kernel_name()
+
+    def row_state(self, z, r: int):
+        """row r's own state (scipy layout, its sections back to back) out of a (batch, state_dim) host array"""
+        return _row_state(z, r, self.own_orders, self.section_order)
+
+    def apply_torch(self, x, codes=None, counts=None, beyond=None, initial=0.0, zi=None, zf=None):
+        """x: (batch, >= n) row-contiguous device tensor of the stage's dtype -- or ONE row, (1, >= n) or 1-D, that
+        every row reads through its own curve and cascade (the shared-input form); codes: (batch, >= n) int16 (rows
+        may be windows of a wider tensor; None: allocated); counts / beyond: None or contiguous (batch, 3) int64 device
+        tensors, overwritten with the converter's / the curve's [below, above, nan]; `initial`: a scalar, one value
+        per row, or a (batch,) float64 device tensor -- levels of the curve's OUTPUT; zi / zf: optional (batch,
+        state_dim) float64 device tensors.  Out of place: `codes` may share no memory with `x`, a report with neither
+        nor with the other report (ValueError); `x` is never written.  One kernel on torch's current stream, nothing
+        else: no memset, allocation or synchronisation (with `codes` given and `initial` a scalar or a tensor).
+        -> codes[:, :n]"""
+        import torch
+        if x.dim() == 1:
+            x = x.unsqueeze(0)
+        shared = self.batch > 1 and x.shape[0] == 1
+        in_rows = 1 if shared else self.batch
+        x0, xs = _rows.check_rows(x, in_rows, self.n, _rows.torch_dtype(self.dtype),
+                                  'expected x: (batch, >=n) row-contiguous device tensor of the stage dtype, or one row')
+        if codes is None:
+            codes = torch.empty((self.batch, self.n), dtype=torch.int16, device=x.device)
+        y0, ys = _rows.check_rows(codes, self.batch, self.n, torch.int16,
+                                  'expected codes: (batch, >=n) row-contiguous int16 device tensor')
+        c0 = _rows.check_state(counts, (self.batch, 3), 'expected counts: contiguous (batch, 3) int64 device tensor',
+                               dtype=np.int64)
+        b0 = _rows.check_state(beyond, (self.batch, 3), 'expected beyond: contiguous (batch, 3) int64 device tensor',
+                               dtype=np.int64)
+        zip_, zfp = (_rows.check_state(z, (self.batch, self.state_dim),
+                                       'zi / zf must be contiguous (batch, state_dim) float64 device tensors')
+                     for z in (zi, zf))
+        xr, yr = (x0, xs, in_rows, self.n, self.dtype.itemsize), (y0, ys, self.batch, self.n, 2)
+        if not _rows.rows_disjoint(xr, yr):
+            raise ValueError('curve iir dac stage is out of place: codes overlaps x')
+        if not _rows.report_disjoint(c0, self.batch, 3, xr, yr):
+            raise ValueError('curve iir dac stage: counts overlaps x / codes')
+        if not _rows.report_disjoint(b0, self.batch, 3, xr, yr):
+            raise ValueError('curve iir dac stage: beyond overlaps x / codes')
+        if c0 is not None and b0 is not None and abs(c0 - b0) < self.batch * 24:
+            raise ValueError('curve iir dac stage: beyond overlaps counts')
+        ini = _initial_rows(self, self.batch, initial, x.device)
+        inip = None if ini is None else ini.data_ptr()
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        if shared:
+            self.plan.apply_shared_in(x0, y0, ys, c0, b0, zip_, zfp, inip, stream)
+        else:
+            self.plan.apply(x0, xs, y0, ys, c0, b0, zip_, zfp, inip, stream)
+        return codes[:, :self.n]
+
+    def close(self):
+        self.plan.close()
+
+
+def curve_iir_dac_rows(sig, xp_rows, fp_rows, filters_rows, gain, offset=0.0, bits=16, shift=0, left=None, right=None,
+                       initial=0.0, return_counts=False):
+    """`iir_dac_rows(interp_rows(sig, xp_rows, fp_rows, left, right), filters_rows, gain, offset, bits, shift, initial)`
+    in one launch (see `CurveIirDacStage`): NumPy in, NumPy out, (rows, samples) int16.  `xp_rows` / `fp_rows`: one
+    curve per row, or one 1-D pair for every row; `filters_rows`: one list of (b, a) sections per row; `initial`: a
+    scalar or one level (of the curve's output) per row.  float32 rows stay float32 on the way in, anything else is read
+    as float64.  `return_counts`: -> (codes, counts, beyond), the converter's and the curve's (rows, 3) int64 [below,
+    above, nan].  ValueError before any device work: sig not 2-D, what `CurveIirDacStage` refuses.
+    NotImplementedError: complex rows, curves or coefficients."""
+    sig2 = _rows_signal_f32('curve_iir_dac_rows', sig)
+    batch, n = sig2.shape
+    _engine.curve_rows_arguments(xp_rows, fp_rows, left, right, batch, n, sig2.dtype)          # the curve's rules first
+    filters_rows = [list(f) for f in filters_rows]
+    gains = _per_row('curve_iir_dac_rows', 'gain', gain, batch)
+    offsets = _per_row('curve_iir_dac_rows', 'offset', offset, batch)
+    _engine.dac_rows_arguments(gains, offsets, n, bits, shift, 1, sig2.dtype)
+    if len(filters_rows) != batch:
+        raise ValueError(f'curve_iir_dac_rows: {len(filters_rows)} filter lists for {batch} rows')
+    packed = _engine.pack_sections_rows(filters_rows)
+    ini = np.asarray(initial, dtype=np.float64)
+    if ini.ndim == 0:
+        ini = np.full(batch, float(ini))
+    if ini.shape != (batch, ):
+        raise ValueError('curve_iir_dac_rows: initial is a scalar or one value per row')
+    if n == 0:
+        codes, zero = np.zeros((batch, 0), dtype=np.int16), np.zeros((batch, 3), dtype=np.int64)
+        return (codes, zero, zero.copy()) if return_counts else codes
+    with _engine.CurveIirDacPlan(xp_rows, fp_rows, filters_rows, gains, offsets, n, bits, shift, left, right, batch,
+                                 sig2.dtype, packed=packed) as plan, \
+            _engine.DeviceBuffer(sig2.nbytes) as x, _engine.DeviceBuffer(batch * n * 2) as y, \
+            _engine.DeviceBuffer(batch * 24) as c, _engine.DeviceBuffer(batch * 24) as b, \
+            _engine.DeviceBuffer(batch * 8) as lv:
+        x.upload(sig2)
+        lv.upload(np.ascontiguousarray(ini))
+        plan.apply(x.ptr, n, y.ptr, n, c.ptr if return_counts else None, b.ptr if return_counts else None, None, None,
+                   lv.ptr if ini.any() else None)
+        _engine.sync()
+        codes = y.download((batch, n), np.int16)
+        if not return_counts:
+            return codes
+        return codes, c.download((batch, 3), np.int64), b.download((batch, 3), np.int64)
+
+
+class SampledCurveIirDac:
+    """`BatchSampler(channels, grid)` (float64 rows), `CurveStage(xp_rows, fp_rows, n, left=, right=)` in place and
+    `IirDacStage(filters_rows, n, gain, offset, bits, shift)`, device-resident and bit for bit -- codes, both reports
+    and zf -- with the float64 rows left out: a whole flux line programmed in its physical unit -- waveform, measured
+    curve to volts, exp-decay correction, converter -- in ONE kernel with 2 B per sample of HBM traffic.  `fused`
+    exactly where `SampledIirDac` is (same decision, same `why_not` texts), but for curves whose knots do not fit next
+    to the fine-grid fill's LDS (more than 567 knots in a row there): `kernel_name()` is
+    'iir_rows_sampled_curve_dac<f64,NSEC,ORD>' on fine grids, 'iir_rows_short_curve_dac<f64,NSEC,ORD>' at AWG sample
+    rates, and every sample the fill produces goes through the row's curve before it enters the filter.  Plans that do
+    not fuse run the sampler into a float64 scratch taken once, here, and then 'iir_rows_curve_dac<f64,NSEC,ORD>': two
+    launches and 18 B per sample instead of three and 34.  float64 only; complex rows are refused.  The curves follow
+    `CurveStage`'s rules (whoever measured f(V) passes `CurveStage.inverse_rows(volts, detuning)`), the cascades
+    `IirStage`'s per-row rules, gain / offset / bits / shift `DacStage`'s; a refusal names the curve first, then the
+    converter, then the cascade.  `counts` is the converter's [below, above, nan] per channel, `beyond` the curve's;
+    `initial` holds levels of the curve's output (volts).  Build once, launch many times.  It saves the float64 rows and
+    two launches, not time: as measured the three launches are faster.
+
+        sd = SampledCurveIirDac.from_full_scale(channels, wl.awg_grid(n, 2e9), xs, fs, filters_rows, 1.0)
+        sd.launch_torch(codes, counts=clipped, beyond=outside, initial=levels, zf=zf)
+    """
+
+    def __init__(self, channels, grid, xp_rows, fp_rows, filters_rows, gain, offset=0.0, bits: int = 16, shift: int = 0,
+                 left=None, right=None, function_lib=None, tile=1):
+        """`tile` > 1 repeats the channel list that many times (synthetic batches, as BatchSampler's)"""
+        from . import _flatten
+        channels, filters_rows = list(channels), list(filters_rows)
+        rows = len(channels) * max(int(tile), 1)
+        if rows < 1:
+            raise ValueError('SampledCurveIirDac: no rows')
+        if not isinstance(grid, _flatten.wfk_grid):
+            grid = _flatten.grid_from_desc(grid)
+        # argument errors before any device work: the curve's, the converter's, the cascades'
+        _engine.curve_rows_arguments(xp_rows, fp_rows, left, right, rows, int(grid.n), np.float64)
+        gains, offsets = (_per_row('SampledCurveIirDac', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v,
+                                   rows) for what, v in (('gain', gain), ('offset', offset)))
+        _engine.dac_rows_arguments(gains, offsets, int(grid.n), bits, shift, 1)
+        if len(filters_rows) != rows:
+            raise ValueError(f'SampledCurveIirDac: {len(filters_rows)} cascades for {rows} rows')
+        packed = _engine.pack_sections_rows(filters_rows)
+        self.prog = _flatten.tile_program(_flatten.flatten(channels, grid, function_lib), tile)
+        if self.prog.n_channels != rows:
+            raise ValueError(f'SampledCurveIirDac: {rows} cascades for {self.prog.n_channels} rows')
+        if self.prog.complex_amp or self.prog.host_complex:
+            raise NotImplementedError('complex rows')
+        self.plan = _engine.ChainCurveIirDacPlan(self.prog, grid, xp_rows, fp_rows, filters_rows, gains, offsets, bits,
+                                                 shift, left, right, packed=packed)
+        p = self.plan
+        self.n, self.n_channels, self.gain, self.offset = p.n, p.n_channels, p.gain, p.offset
+        self.knots, self.left, self.right = p.knots, p.left, p.right
+        self.bits, self.shift, self.lo, self.hi = p.bits, p.shift, p.lo, p.hi
+        self.state_dim, self.own_orders, self.section_order = p.state_dim, packed[3], int(packed[0][0])
+        self.fused, self.why_not = p.fused, p.why_not
+        self._initial_cache = None
+        # the unfused path's float64 rows: taken once, here
+        self._scratch = None if self.fused else _engine.DeviceBuffer(max(self.n_channels * self.n, 1) * 8)
+
+    @classmethod
+    def from_full_scale(cls, channels, grid, xp_rows, fp_rows, filters_rows, full_scale, **kw):
+        """the plan whose gain[r] = hi / full_scale[r], so that a filtered +-full scale (volts) maps to +-hi (a scalar:
+        every row).  ValueError: a full scale that is not finite or not positive."""
+        bits = int(kw.get('bits', 16))
+        if not 2 <= bits <= 16:
+            raise ValueError('bits must lie in [2, 16]')
+        fs = np.asarray(full_scale, dtype=np.float64)
+        if not np.all(np.isfinite(fs) & (fs > 0.0)):
+            raise ValueError('SampledCurveIirDac: every full scale must be finite and positive')
+        return cls(channels, grid, xp_rows, fp_rows, filters_rows, (2**(bits - 1) - 1) / fs, **kw)
+
+    def row_state(self, z, r: int):
+        """row r's own state (scipy layout, its sections back to back) out of a (n_channels, state_dim) host array"""
+        return _row_state(z, r, self.own_orders, self.section_order)
+
+    def kernel_name(self) -> str:
+        """'iir_rows_sampled_curve_dac<f64,NSEC,ORD>' | 'iir_rows_short_curve_dac<f64,NSEC,ORD>' | '<sampler kernels> +
+        iir_rows_curve_dac<f64,NSEC,ORD>'"""
+        return self.plan.kernel_name()
+
+    def launch(self, out_ptr, out_stride=None, counts_ptr=None, beyond_ptr=None, zi_ptr=None, zf_ptr=None,
+               initial_ptr=None, stream=0):
+        """raw pointers; out_stride in codes (None: n); initial_ptr: device array of n_channels doubles or None"""
+        s = self._scratch
+        self.plan.launch(out_ptr, self.n if out_stride is None else out_stride, counts_ptr, beyond_ptr,
+                         None if s is None else s.ptr, self.n, zi_ptr, zf_ptr, initial_ptr, stream)
+
+    def launch_torch(self, codes, counts=None, beyond=None, initial=0.0, zi=None, zf=None):
+        """codes: (n_channels, >= n) row-contiguous int16 device tensor (rows may be a window of a wider tensor);
+        counts / beyond: None or contiguous (n_channels, 3) int64 device tensors, overwritten with the converter's /
+        the curve's [below, above, nan] per channel; a report may share no memory with `codes` or with the other
+        (ValueError); `initial`: a scalar, one value per row, or a (n_channels,) float64 device tensor; zi / zf:
+        optional (n_channels, state_dim) float64 device tensors.  Asynchronous on torch's current stream: one kernel
+        (two where not `fused`), no memset, allocation or synchronisation.  -> codes[:, :n]"""
+        import torch
+        y0, ys = _rows.check_rows(codes, self.n_channels, self.n, torch.int16,
+                                  'expected codes: (n_channels, >=n) row-contiguous int16 device tensor')
+        c0 = _rows.check_state(counts, (self.n_channels, 3),
+                               'expected counts: contiguous (n_channels, 3) int64 device tensor', dtype=np.int64)
+        b0 = _rows.check_state(beyond, (self.n_channels, 3),
+                               'expected beyond: contiguous (n_channels, 3) int64 device tensor', dtype=np.int64)
+        zip_, zfp = (_rows.check_state(z, (self.n_channels, self.state_dim),
+                                       'zi / zf must be contiguous (n_channels, state_dim) float64 device tensors')
+                     for z in (zi, zf))
+        yr = (y0, ys, self.n_channels, self.n, 2)
+        if not _rows.report_disjoint(c0, self.n_channels, 3, yr):
+            raise ValueError('sampled curve iir dac: counts overlaps codes')
+        if not _rows.report_disjoint(b0, self.n_channels, 3, yr):
+            raise ValueError('sampled curve iir dac: beyond overlaps codes')
+        if c0 is not None and b0 is not None and abs(c0 - b0) < self.n_channels * 24:
+            raise ValueError('sampled curve iir dac: beyond overlaps counts')
+        ini = _initial_rows(self, self.n_channels, initial, codes.device)
+        self.launch(y0, ys, c0, b0, zip_, zfp, None if ini is None else ini.data_ptr(),
+                    torch.cuda.current_stream(codes.device).cuda_stream)
+        return codes[:, :self.n]
+
+    def to_host(self, initial=0.0, zi=None, return_counts=False, return_beyond=False, return_zf=False):
+        """NumPy codes (n_channels, n) [, counts (n_channels, 3)] [, beyond (n_channels, 3)] [, zf (n_channels,
+        state_dim)]; initial: a scalar or one value per row; zi: (n_channels, state_dim)"""
+        D = max(self.state_dim, 1)
+        ini = np.broadcast_to(np.asarray(initial, dtype=np.float64), (self.n_channels, ))
+        with contextlib.ExitStack() as stack:
+            y = _dev(stack, self.n_channels * self.n * 2)
+            c = _dev(stack, self.n_channels * 24) if return_counts else None
+            b = _dev(stack, self.n_channels * 24) if return_beyond else None
+            dzi = _dev(stack, self.n_channels * D * 8) if zi is not None else None
+            dzf = _dev(stack, self.n_channels * D * 8) if return_zf else None
+            dini = _dev(stack, self.n_channels * 8) if ini.any() else None
+            if zi is not None:
+                dzi.upload(np.ascontiguousarray(np.broadcast_to(np.asarray(zi, dtype=np.float64),
+                                                                (self.n_channels, self.state_dim))))
+            if dini is not None:
+                dini.upload(np.ascontiguousarray(ini))
+            self.launch(y.ptr, None, None if c is None else c.ptr, None if b is None else b.ptr,
+                        None if dzi is None else dzi.ptr, None if dzf is None else dzf.ptr,
+                        None if dini is None else dini.ptr)
+            _engine.sync()
+            out = [y.download((self.n_channels, self.n), np.int16)]
+            if return_counts:
+                out.append(c.download((self.n_channels, 3), np.int64))
+            if return_beyond:
+                out.append(b.download((self.n_channels, 3), np.int64))
+            if return_zf:
+                out.append(dzf.download((self.n_channels, D), np.float64)[:, :self.state_dim])
+            return out[0] if len(out) == 1 else tuple(out)
+
+    def close(self):
+        self.plan.close()
+        if self._scratch is not None:
+            self._scratch.close()
+            self._scratch = None
+
+
 class MarkerStage:
     """Device-resident gate markers for `batch` rows of `n` samples (build once, apply many times): the marker line
     that opens a switch or blanks an amplifier around every pulse, from the IDEAL gate rows (exact zeros outside the
