@@ -612,6 +612,59 @@ int64_t wfk_marker_rows_span(const wfk_marker_rows_plan* plan, int into_codes);
 const char* wfk_marker_rows_kernel_name(const wfk_marker_rows_plan* plan, int into_codes, int with_counts);
 int wfk_marker_rows_plan_destroy(wfk_marker_rows_plan* plan);
 
+/* -- cutting code rows at their marker: a segment table and the kept codes, packed ---------------- */
+/* `rows` rows of n samples, width = k in {1, 2} int16 codes per sample (k = 2: the interleaved layout of
+ * wfk_dac_rows(interleave = 2) and wfk_marker_rows(group = 2)), are cut where their marker is low, so that only the
+ * stretches around the pulses are sent on.  The mask m[g, i] is, per apply,
+ *   wfk_segment_rows_apply_bit():    any_j ((codes[g, i k + j] >> bit) & 1), 0 <= bit <= 15 -- the codes alone;
+ *   wfk_segment_rows_apply_marks():  marks[g, i] != 0, rows of n bytes as wfk_marker_rows_apply() writes them.
+ * align = A, a power of two in [1, WFK_SEGMENT_MAX_ALIGN], is the instrument's granularity: with Q = ceil(n / A),
+ * granule q is kept when any m[g, i], i in [q A, min((q + 1) A, n)), is set, and the segments of a row are the maximal
+ * runs [q0, q1) of kept granules, in ascending order, j = 0 .. count - 1:
+ *   start_j = q0 A,   length_j = min(q1 A, n) - start_j,   offset_j = length_0 + ... + length_(j-1),   kept = all of them.
+ * Every start and offset is a multiple of A, every length but possibly a row's last.  Outputs, all the caller's,
+ * their sizes fixed at plan creation:
+ *   table  rows of 3 max_segments int32: entry j < min(count, max_segments) is [start_j, length_j, offset_j]; no
+ *          other entry is touched;
+ *   packed rows of k capacity int16: for p < min(kept, capacity) the k codes of the p-th kept sample, verbatim (the
+ *          marker bit with them); nothing else is touched.  The cut at `capacity` is by position alone, independent of
+ *          the table's; a segment that straddles it is written up to it;
+ *   used   rows * 2 int64, [count, kept] per row: the TRUE totals whatever was cut, overwritten by every apply
+ *          (written by the kernel that owns the row: no atomics, no zeroing).  Required.
+ * The caller compares used with max_segments and capacity.  table = packed = NULL is the sizing pass: only used is
+ * written.  A side that holds nothing (max_segments = 0, capacity = 0) is not looked at and may be NULL next to the
+ * other.  n = 0 zeroes used and does nothing else.  codes and marks are never written.  The result is a pure function
+ * of the inputs: two applies agree to the bit.
+ * n < 0 or n > 2^31 - 1, rows < 1, a width other than 1 or 2, an align that is no power of two in [1, 4096],
+ * max_segments < 0, capacity < 0 or > n, more than 2^31 - 1 workgroups: WFK_EINVAL with the argument named, before any
+ * device work; no device: WFK_EHIP.
+ * wfk_segment_rows_apply_bit() and wfk_segment_rows_apply_marks() enqueue their three kernels (two in the sizing pass;
+ * for n = 0 the zeroing of used alone) on `hip_stream`, and that is all they do to the device (as wfk_avg_apply: they
+ * may be called while the stream is being captured; a replay reads the codes and marks anew and overwrites used).
+ * Strides are in elements of their side and, where there is more than one row, at least the row: codes_stride >= k n,
+ * marks_stride >= n, table_stride >= 3 max_segments (int32), packed_stride >= k capacity.  Every side is aligned to its
+ * element, no output meets an input or another output, used (8-byte aligned) meets none of them; a bit outside
+ * [0, 15], a NULL table with a packed buffer or the reverse, a NULL used: WFK_EINVAL.
+ * The plan owns a workspace of rows x blocks x 4 int64 that the three launches of an apply hand to each other, so a
+ * plan serves ONE STREAM AT A TIME (and one graph at a time). */
+#define WFK_SEGMENT_MAX_ALIGN 4096
+typedef struct wfk_segment_rows_plan wfk_segment_rows_plan;
+int wfk_segment_rows_plan_create(int64_t n, int32_t rows, int width, int64_t align, int64_t max_segments,
+                                 int64_t capacity, wfk_segment_rows_plan** out);
+int wfk_segment_rows_apply_bit(wfk_segment_rows_plan* plan, const int16_t* codes_dev, int64_t codes_stride, int bit,
+                               int32_t* table_dev, int64_t table_stride, int16_t* packed_dev, int64_t packed_stride,
+                               int64_t* used_dev /* rows * 2 */, void* hip_stream);
+int wfk_segment_rows_apply_marks(wfk_segment_rows_plan* plan, const int16_t* codes_dev, int64_t codes_stride,
+                                 const uint8_t* marks_dev, int64_t marks_stride, int32_t* table_dev,
+                                 int64_t table_stride, int16_t* packed_dev, int64_t packed_stride,
+                                 int64_t* used_dev /* rows * 2 */, void* hip_stream);
+/* the samples one workgroup covers: max(8192, 64 align) (0 for a null plan) */
+int64_t wfk_segment_rows_span(const wfk_segment_rows_plan* plan);
+/* launch 0, 1, 2: "segment_count<1, false>", "segment_scan", "segment_pack<1, false>" -- <width, marks form>; a
+ * static string ("" for another launch or a null plan) */
+const char* wfk_segment_rows_kernel_name(const wfk_segment_rows_plan* plan, int launch, int with_marks);
+int wfk_segment_rows_plan_destroy(wfk_segment_rows_plan* plan);
+
 /* -- mixing across rows: a sparse matrix and an offset, per sample -------------------------------- */
 /* rows_in real rows of n samples (kind: WFK_OUT_F64 or WFK_OUT_F32) become rows_out rows of the same kind through a
  * rows_out x rows_in matrix M and an offset per output row: flux crosstalk compensation (a band), IQ mixer correction

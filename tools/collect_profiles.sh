@@ -26,6 +26,7 @@ case "$WL" in
   states) ARGS="tools/states_bench.py --cases S1,S2 --no-baseline --reps 5" ;;
   dac) ARGS="tools/dac_rows_bench.py --cases D2 --reps 5" ;;
   marker) ARGS="tools/marker_rows_bench.py --cases M1 --dtypes f64 --reps 5 --chain-reps 1" ;;
+  segment) ARGS="tools/segment_rows_bench.py --cases M1 --widths 2 --duties 20 --forms bit --reps 5 --no-chain --no-copy" ;;
   awg_f32) ARGS="bench.py --workload awg --dtype f32 --steps 5 --warmup 1 --no-cpu-baseline --no-also" ;;
 esac
 echo "== stats pass ($WL)"

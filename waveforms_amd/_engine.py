@@ -183,6 +183,14 @@ def lib():
         l.wfk_marker_rows_kernel_name.argtypes = [VP, C.c_int, C.c_int]
         l.wfk_marker_rows_kernel_name.restype = C.c_char_p
         l.wfk_marker_rows_plan_destroy.argtypes = [VP]
+        l.wfk_segment_rows_plan_create.argtypes = [I64, I32, C.c_int, I64, I64, I64, P(VP)]
+        l.wfk_segment_rows_apply_bit.argtypes = [VP, VP, I64, C.c_int, VP, I64, VP, I64, VP, VP]
+        l.wfk_segment_rows_apply_marks.argtypes = [VP, VP, I64, VP, I64, VP, I64, VP, I64, VP, VP]
+        l.wfk_segment_rows_span.argtypes = [VP]
+        l.wfk_segment_rows_span.restype = I64
+        l.wfk_segment_rows_kernel_name.argtypes = [VP, C.c_int, C.c_int]
+        l.wfk_segment_rows_kernel_name.restype = C.c_char_p
+        l.wfk_segment_rows_plan_destroy.argtypes = [VP]
         l.wfk_mix_rows_plan_create.argtypes = [I64, I32, I32, C.c_int, VP, VP, VP, VP, P(VP)]
         l.wfk_mix_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP]
         l.wfk_mix_rows_reads.argtypes = [VP]
@@ -1080,6 +1088,77 @@ class MarkerRowsPlan(_Handle):
 
     def kernel_name(self, codes: bool = False, counts: bool = False) -> str:
         return lib().wfk_marker_rows_kernel_name(self._h, 1 if codes else 0, 1 if counts else 0).decode()
+
+
+SEGMENT_MAX_ALIGN = 4096   # WFK_SEGMENT_MAX_ALIGN
+
+
+def _whole(name, v):
+    """v as an int; ValueError where it is no whole number"""
+    a = np.asarray(v)
+    if a.ndim != 0 or a.dtype.kind == 'b' or not (a.dtype.kind in 'iu' or (a.dtype.kind == 'f' and np.isfinite(a)
+                                                                          and a == np.rint(a))):
+        raise ValueError(f'{name} must be a whole number')
+    return int(a)
+
+
+def segment_rows_arguments(n, rows=1, width=1, align=1, max_segments=None, capacity=None):
+    """the arguments of a SegmentRowsPlan, checked on the host (no device, no library) -> (n, rows, width, align,
+    max_segments, capacity) as ints.  `max_segments` None: ceil(ceil(n / align) / 2), the most segments a row can
+    have; `capacity` None: n.  ValueError, the argument named: n outside [0, 2^31 - 1], rows < 1, a width other than 1
+    or 2, an align that is no power of two in [1, SEGMENT_MAX_ALIGN], max_segments < 0, capacity outside [0, n]."""
+    n, rows, width, align = _whole('n', n), _whole('rows', rows), _whole('width', width), _whole('align', align)
+    if not 0 <= n <= 2**31 - 1:
+        raise ValueError('n must lie in [0, 2^31 - 1]')
+    if rows < 1:
+        raise ValueError('rows must be at least 1')
+    if width not in (1, 2):
+        raise ValueError('width must be 1 or 2')
+    if not 1 <= align <= SEGMENT_MAX_ALIGN or align & (align - 1):
+        raise ValueError(f'align must be a power of two in [1, {SEGMENT_MAX_ALIGN}]')
+    granules = -(-n // align)
+    max_segments = (granules + 1) // 2 if max_segments is None else _whole('max_segments', max_segments)
+    capacity = n if capacity is None else _whole('capacity', capacity)
+    if max_segments < 0:
+        raise ValueError('max_segments must not be negative')
+    if not 0 <= capacity <= n:
+        raise ValueError('capacity must lie in [0, n]')
+    return n, rows, width, align, max_segments, capacity
+
+
+class SegmentRowsPlan(_Handle):
+    """`rows` rows of `width` * n int16 codes cut at their marker in granules of `align` samples: a table of
+    [start, length, offset] per segment, the kept codes packed back to back and [count, kept] per row
+    (wfk_segment_rows_plan_create; the semantics are in include/wfk.h).  The plan owns the workspace its three launches
+    share: one stream at a time.  ValueError before any device work as `segment_rows_arguments` lists them."""
+    _destroy = 'wfk_segment_rows_plan_destroy'
+
+    def __init__(self, n, rows=1, width=1, align=1, max_segments=None, capacity=None):
+        (self.n, self.rows, self.width, self.align, self.max_segments,
+         self.capacity) = segment_rows_arguments(n, rows, width, align, max_segments, capacity)
+        check(lib().wfk_segment_rows_plan_create(self.n, self.rows, self.width, self.align, self.max_segments,
+                                                 self.capacity, C.byref(self._h)))
+
+    def apply_bit(self, codes_ptr, codes_stride, bit, table_ptr, table_stride, packed_ptr, packed_stride, used_ptr,
+                  stream=0):
+        """table_ptr = packed_ptr = None: the sizing pass; used_ptr: rows * 2 int64, overwritten with [count, kept]"""
+        if not 0 <= int(bit) <= 15:
+            raise ValueError('bit must lie in [0, 15]')
+        check(lib().wfk_segment_rows_apply_bit(self._h, codes_ptr, codes_stride, int(bit), table_ptr, table_stride,
+                                               packed_ptr, packed_stride, used_ptr, stream))
+
+    def apply_marks(self, codes_ptr, codes_stride, marks_ptr, marks_stride, table_ptr, table_stride, packed_ptr,
+                    packed_stride, used_ptr, stream=0):
+        check(lib().wfk_segment_rows_apply_marks(self._h, codes_ptr, codes_stride, marks_ptr, marks_stride, table_ptr,
+                                                 table_stride, packed_ptr, packed_stride, used_ptr, stream))
+
+    def span(self) -> int:
+        """the samples one workgroup covers"""
+        return int(lib().wfk_segment_rows_span(self._h))
+
+    def kernel_name(self, launch: int = 0, marks: bool = False) -> str:
+        """launch 0, 1, 2: the count, scan and pack kernels"""
+        return lib().wfk_segment_rows_kernel_name(self._h, int(launch), 1 if marks else 0).decode()
 
 
 MIX_TILE_ROWS = 8          # WFK_MIX_TILE_ROWS

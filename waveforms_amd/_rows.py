@@ -10,12 +10,13 @@ _TORCH = {}
 
 def torch_dtype(dtype):
     """the torch dtype of a plan's NumPy dtype: float64 / float32 rows, int16 codes (the demodulator's input, the DAC
-    stage's output), the DAC and marker stages' int64 counts, the marker stage's uint8 markers and the demodulator's
-    complex128 result"""
+    stage's output), the DAC and marker stages' int64 counts, the marker stage's uint8 markers, the segment stage's
+    int32 table and the demodulator's complex128 result"""
     if not _TORCH:
         import torch
         _TORCH.update({np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32,
-                       np.dtype(np.int16): torch.int16, np.dtype(np.int64): torch.int64, np.dtype(np.uint8): torch.uint8,
+                       np.dtype(np.int16): torch.int16, np.dtype(np.int32): torch.int32,
+                       np.dtype(np.int64): torch.int64, np.dtype(np.uint8): torch.uint8,
                        np.dtype(np.complex128): torch.complex128})
     return _TORCH[np.dtype(dtype)]
 

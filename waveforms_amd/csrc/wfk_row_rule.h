@@ -85,4 +85,33 @@ int wfk_row_rule(const char* stage, std::initializer_list<RowSide> in, const Row
   return WFK_OK;
 }
 
+// The segment stage has two inputs and two outputs next to its report `used` (rows x [count, kept]): `rows` rows of
+// k n codes, of n marks (marks null: the bit form, which reads the codes alone), of 3 max_segments int32 and of
+// k capacity codes.  table = packed = null is the sizing pass: the inputs and the report alone.  A side that holds
+// nothing (max_segments = 0, capacity = 0) is not looked at.  The rule runs once per output: packed against the
+// inputs, then the table against the inputs and packed; the report meets no side.
+struct SegmentShape { int64_t rows, n, k, max_segments, capacity; };
+template <typename Fail>
+int wfk_segment_row_rule(const SegmentShape& s, const void* codes, int64_t codes_stride, const void* marks,
+                         int64_t marks_stride, const void* table, int64_t table_stride, const void* packed,
+                         int64_t packed_stride, const void* used, Fail&& fail) {
+  const char* stage = "segment rows";
+  const bool sizing = !table && !packed;
+  const bool has_table = !sizing && s.max_segments > 0, has_packed = !sizing && s.capacity > 0;
+  const RowReport report{used, s.rows, 2};
+  const RowSide c{"codes", codes, s.rows, codes_stride, s.k * s.n, sizeof(int16_t), false};
+  const RowSide m = marks ? RowSide{"marks", marks, s.rows, marks_stride, s.n, sizeof(uint8_t), false} : c;
+  const RowSide y{"packed", packed, s.rows, packed_stride, s.k * s.capacity, sizeof(int16_t), false};
+  const RowSide t{"table", table, s.rows, table_stride, 3 * s.max_segments, sizeof(int32_t), false};
+  if (has_packed) {
+    if (const int rc = wfk_row_rule(stage, {c, m}, y, kRowsAligned | kRowsDisjoint, fail, report)) return rc;
+  }
+  if (has_table) {
+    if (const int rc = wfk_row_rule(stage, {c, m, has_packed ? y : c}, t, kRowsAligned | kRowsDisjoint, fail, report))
+      return rc;
+  }
+  if (!has_packed && !has_table) return wfk_row_rule(stage, {m}, c, kRowsAligned, fail, report);
+  return WFK_OK;
+}
+
 }  // namespace

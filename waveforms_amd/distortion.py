@@ -2438,6 +2438,239 @@ def marker_rows(sig, lead=0, trail=0, threshold=0.0, group=1, codes=None, bit=0,
         return (res, c.download((rows, 2), np.int64)) if return_counts else res
 
 
+class SegmentStage:
+    """Device-resident cut of `batch` rows of `width` * n int16 DAC codes at their marker (build once, apply many
+    times): what an AWG with a sequencer is programmed with -- a short table of (play this stretch, from here) and
+    the kept samples packed back to back -- so that only the stretches around the pulses are downloaded.
+    `width` = k in {1, 2} codes per sample (k = 2: the layout of `DacStage(interleave=2)` / `MarkerStage(group=2)`).
+    The mask is, per apply, one bit of the codes (`bit=`: any of a sample's k codes) or a (batch, n) uint8 tensor as
+    `MarkerStage.apply_torch` writes it (`marks=`).  `align` = A, a power of two in [1, 4096], is the instrument's
+    granularity: granule q = samples [q A, min((q + 1) A, n)) is kept when any of them is marked; a segment is a
+    maximal run [q0, q1) of kept granules, in ascending order:
+        start = q0 A,   length = min(q1 A, n) - start,   offset = the lengths before it,   kept = all lengths.
+    An apply writes `table` (batch, max_segments, 3) int32 [start, length, offset] for the first min(count,
+    max_segments) segments of each row, `packed` (batch, width * capacity) int16, the codes of the first min(kept,
+    capacity) kept samples verbatim, and `used` (batch, 2) int64 [count, kept] -- the TRUE totals, overwritten by
+    every apply; nothing else of table and packed is touched.  `max_segments` defaults to ceil(ceil(n / A) / 2) and
+    `capacity` to n, the sizes that cannot overflow.  Building a stage needs no device; the plan is made by the first
+    apply and owns a workspace, so a stage serves one stream at a time.
+
+        seg = SegmentStage(n, batch=rows, width=2, align=16)
+        rows_out = seg.download(*seg.apply_torch(codes, bit=0))     # [(table_r, packed_r), ...]
+    """
+
+    def __init__(self, n: int, batch: int = 1, width: int = 1, align: int = 1, max_segments=None, capacity=None):
+        try:
+            (self.n, self.batch, self.width, self.align, self.max_segments,
+             self.capacity) = _engine.segment_rows_arguments(n, batch, width, align, max_segments, capacity)
+        except ValueError as e:
+            raise ValueError(f'SegmentStage: {e}') from None
+        self.plan = None
+
+    def _plan(self):
+        if self.plan is None:
+            self.plan = _engine.SegmentRowsPlan(self.n, self.batch, self.width, self.align, self.max_segments,
+                                                self.capacity)
+        return self.plan
+
+    def span(self) -> int:
+        """the samples one workgroup covers"""
+        return self._plan().span()
+
+    def kernel_name(self, launch: int = 0, marks: bool = False) -> str:
+        return self._plan().kernel_name(launch, marks)
+
+    def _inputs(self, codes, bit, marks):
+        """-> (sides of the inputs as _rows.rows_disjoint takes them, codes ptr, stride, marks ptr or None, stride)"""
+        if (bit is None) == (marks is None):
+            raise ValueError('segment stage: give exactly one of bit= and marks=')
+        if bit is not None and not 0 <= int(bit) <= 15:
+            raise ValueError('segment stage: bit must lie in [0, 15]')
+        k = self.width
+        c0, cs = _rows.check_rows(codes, self.batch, k * self.n, _rows.torch_dtype(np.int16),
+                                  'expected codes: (batch, >=width * n) row-contiguous int16 device tensor')
+        sides = [(c0, cs, self.batch, k * self.n, 2)]
+        m0 = ms = None
+        if marks is not None:
+            m0, ms = _rows.check_rows(marks, self.batch, self.n, _rows.torch_dtype(np.uint8),
+                                      'expected marks: (batch, >=n) row-contiguous uint8 device tensor')
+            sides.append((m0, ms, self.batch, self.n, 1))
+        return sides, c0, cs, m0, ms
+
+    def _used(self, used, sides):
+        u0 = _rows.check_state(used, (self.batch, 2), 'expected used: contiguous (batch, 2) int64 device tensor',
+                               dtype=np.int64)
+        if not _rows.report_disjoint(u0, self.batch, 2, *sides):
+            raise ValueError('segment stage: used overlaps codes / marks / table / packed')
+        return u0
+
+    def _launch(self, codes, bit, c0, cs, m0, ms, t0, ts, p0, ps, u0):
+        import torch
+        stream = torch.cuda.current_stream(codes.device).cuda_stream
+        if bit is not None:
+            self._plan().apply_bit(c0, cs, int(bit), t0, ts, p0, ps, u0, stream)
+        else:
+            self._plan().apply_marks(c0, cs, m0, ms, t0, ts, p0, ps, u0, stream)
+
+    def apply_torch(self, codes, *, bit=None, marks=None, table=None, packed=None, used=None):
+        """codes: (batch, >= width * n) row-contiguous int16 device tensor; exactly one of `bit` (0 .. 15) and `marks`
+        ((batch, >= n) uint8); table: (batch, max_segments, 3) int32, rows may be windows of a wider tensor; packed:
+        (batch, >= width * capacity) int16; used: contiguous (batch, 2) int64 -- each allocated when None.  No output
+        may share memory with an input or another output (ValueError); codes and marks are never written.
+        Asynchronous on torch's current stream, no allocation when the outputs are given.  -> (table, packed[:, :width
+        * capacity], used)"""
+        import torch
+        k, rows = self.width, self.batch
+        sides, c0, cs, m0, ms = self._inputs(codes, bit, marks)
+        if table is None:
+            table = torch.empty((rows, max(self.max_segments, 1), 3), dtype=torch.int32,
+                                device=codes.device)[:, :self.max_segments]
+        if packed is None:
+            packed = torch.empty((rows, max(k * self.capacity, 1)), dtype=torch.int16,
+                                 device=codes.device)[:, :k * self.capacity]
+        if used is None:
+            used = torch.empty((rows, 2), dtype=torch.int64, device=codes.device)
+        width3 = 3 * self.max_segments
+        if (table.dim() != 3 or tuple(table.shape) != (rows, self.max_segments, 3)
+                or (self.max_segments > 1 and table.stride(1) != 3) or (self.max_segments > 0 and table.stride(2) != 1)):
+            raise ValueError('expected table: (batch, max_segments, 3) int32 device tensor, each row contiguous')
+        t0, ts = _rows.check_rows(table.as_strided((rows, width3), (table.stride(0), 1)), rows, width3,
+                                  _rows.torch_dtype(np.int32),
+                                  'expected table: (batch, max_segments, 3) int32 device tensor, each row contiguous')
+        p0, ps = _rows.check_rows(packed, rows, k * self.capacity, _rows.torch_dtype(np.int16),
+                                  'expected packed: (batch, >=width * capacity) row-contiguous int16 device tensor')
+        tr, pr = (t0, ts, rows, width3, 4), (p0, ps, rows, k * self.capacity, 2)
+        for s, what in zip(sides, ('codes', 'marks')):
+            if not _rows.rows_disjoint(s, tr):
+                raise ValueError(f'segment stage: table overlaps {what}')
+            if not _rows.rows_disjoint(s, pr):
+                raise ValueError(f'segment stage: packed overlaps {what}')
+        if not _rows.rows_disjoint(tr, pr):
+            raise ValueError('segment stage: table overlaps packed')
+        u0 = self._used(used, sides + [tr, pr])
+        # a side that holds nothing is not looked at; both: the sizing pass, which writes the same `used`
+        self._launch(codes, bit, c0, cs, m0, ms, t0 if width3 else None, ts, p0 if self.capacity else None, ps, u0)
+        return table, packed[:, :k * self.capacity], used
+
+    def measure_torch(self, codes, *, bit=None, marks=None, used=None):
+        """the sizing pass: only `used` (allocated when None) is written.  -> used"""
+        import torch
+        sides, c0, cs, m0, ms = self._inputs(codes, bit, marks)
+        if used is None:
+            used = torch.empty((self.batch, 2), dtype=torch.int64, device=codes.device)
+        u0 = self._used(used, sides)
+        self._launch(codes, bit, c0, cs, m0, ms, None, 0, None, 0, u0)
+        return used
+
+    def download(self, table, packed, used):
+        """what an apply wrote, on the host: `used` is copied first (this waits for the stream), then only
+        [:, :max count] of the table and [:, :width * max kept] of packed, through pinned host memory (torch's cache of
+        it: the arrays returned are views of that memory and keep it alive).  -> a list of (table_r (count_r, 3) int32,
+        packed_r (width * kept_r,) int16), one per row.  ValueError when a row overflowed max_segments or capacity:
+        what came out would not be the row."""
+        import torch
+
+        def to_host(x):
+            if x.numel() == 0:
+                return np.empty(tuple(x.shape), dtype=x.cpu().numpy().dtype)
+            h = torch.empty(tuple(x.shape), dtype=x.dtype, pin_memory=True)
+            h.copy_(x, non_blocking=True)
+            torch.cuda.current_stream(x.device).synchronize()
+            return h.numpy()
+
+        u = used.cpu().numpy()
+        for r in range(self.batch):
+            if u[r, 0] > self.max_segments or u[r, 1] > self.capacity:
+                raise ValueError(f'segment stage: row {r} overflowed: {int(u[r, 0])} segments of {int(u[r, 1])} samples, '
+                                 f'room for {self.max_segments} of {self.capacity}')
+        k = self.width
+        count, kept = (int(u[:, 0].max()), int(u[:, 1].max())) if self.batch else (0, 0)
+        t, p = to_host(table[:, :count]), to_host(packed[:, :k * kept])
+        return [(t[r, :int(u[r, 0])], p[r, :k * int(u[r, 1])]) for r in range(self.batch)]
+
+    def close(self):
+        if self.plan is not None:
+            self.plan.close()
+            self.plan = None
+
+
+def segment_rows(codes, marks=None, bit=None, width=1, align=1):
+    """The rows of a 2-D int16 `codes` ((rows, width * n)) cut at their marker (see `SegmentStage`), all rows in one
+    apply with the sizes that cannot overflow: NumPy in, NumPy out.  Exactly one of `marks` ((rows, n), non-zero =
+    marked) and `bit` (0 .. 15).  -> a list of (table_r (count_r, 3) int32 [start, length, offset], packed_r
+    (width * kept_r,) int16), one per row.  ValueError before any device work: codes not 2-D int16, a row length that
+    is no multiple of the width, marks of another shape, neither or both of marks and bit, a bit outside 0 .. 15, what
+    `SegmentStage` refuses."""
+    codes = np.asarray(codes)
+    if codes.ndim != 2 or codes.dtype != np.int16:
+        raise ValueError('segment_rows: codes must be a 2-D int16 array')
+    if (bit is None) == (marks is None):
+        raise ValueError('segment_rows: give exactly one of bit= and marks=')
+    if width not in (1, 2):
+        raise ValueError('segment_rows: width must be 1 or 2')
+    rows, nk = codes.shape
+    if nk % width:
+        raise ValueError(f'segment_rows: rows of {nk} codes are no multiple of the width {width}')
+    try:
+        n, rows, k, align, max_segments, _ = _engine.segment_rows_arguments(nk // width, rows, width, align)
+    except ValueError as e:
+        raise ValueError(f'segment_rows: {e}') from None
+    if bit is not None and not 0 <= int(bit) <= 15:
+        raise ValueError('segment_rows: bit must lie in [0, 15]')
+    if marks is not None:
+        marks = np.asarray(marks)
+        if marks.shape != (rows, n):
+            raise ValueError(f'segment_rows: marks must have the shape ({rows}, {n})')
+        marks = np.ascontiguousarray(marks != 0, dtype=np.uint8)
+    if n == 0:
+        return [(np.zeros((0, 3), dtype=np.int32), np.zeros(0, dtype=np.int16)) for _ in range(rows)]
+    codes = np.ascontiguousarray(codes)
+    with _engine.SegmentRowsPlan(n, rows, k, align, max_segments, n) as plan, \
+            _engine.DeviceBuffer(codes.nbytes) as x, _engine.DeviceBuffer(rows * n if marks is not None else 16) as m, \
+            _engine.DeviceBuffer(rows * max_segments * 12) as t, _engine.DeviceBuffer(codes.nbytes) as y, \
+            _engine.DeviceBuffer(rows * 16) as u:
+        x.upload(codes)
+        if marks is not None:
+            m.upload(marks)
+            plan.apply_marks(x.ptr, k * n, m.ptr, n, t.ptr, 3 * max_segments, y.ptr, k * n, u.ptr)
+        else:
+            plan.apply_bit(x.ptr, k * n, int(bit), t.ptr, 3 * max_segments, y.ptr, k * n, u.ptr)
+        _engine.sync()
+        used = u.download((rows, 2), np.int64)
+        table = t.download((rows, max_segments, 3), np.int32)
+        packed = y.download((rows, k * n), np.int16)
+    return [(table[r, :int(used[r, 0])].copy(), packed[r, :k * int(used[r, 1])].copy()) for r in range(rows)]
+
+
+def expand_segments(table_row, packed_row, n, idle, width=1):
+    """The inverse of the cut, on the host: a row of `width` * n int16 codes filled with `idle` (one code, or one per
+    code of a sample) with the segments of `table_row` ((count, 3) [start, length, offset]) laid back from
+    `packed_row`.  What an upload is checked against.  ValueError: a width other than 1 or 2, a table of another shape,
+    a segment outside the row or outside the packed codes."""
+    n, k = int(n), int(width)
+    if k not in (1, 2):
+        raise ValueError('expand_segments: width must be 1 or 2')
+    if n < 0:
+        raise ValueError('expand_segments: n must not be negative')
+    table = np.asarray(table_row)
+    packed = np.asarray(packed_row)
+    if table.ndim != 2 or table.shape[1] != 3 or table.dtype.kind not in 'iu':
+        raise ValueError('expand_segments: the table must be (count, 3) integers')
+    if packed.ndim != 1 or packed.dtype != np.int16:
+        raise ValueError('expand_segments: the packed codes must be 1-D int16')
+    idle = np.asarray(idle, dtype=np.int16).reshape(-1)
+    if len(idle) not in (1, k):
+        raise ValueError('expand_segments: idle is one code or one per code of a sample')
+    out = np.tile(idle, n * k // len(idle)).astype(np.int16)
+    for j, (start, length, offset) in enumerate(table.astype(np.int64).tolist()):
+        if start < 0 or length < 0 or start + length > n:
+            raise ValueError(f'expand_segments: segment {j} lies outside the row')
+        if offset < 0 or k * (offset + length) > len(packed):
+            raise ValueError(f'expand_segments: segment {j} lies outside the packed codes')
+        out[k * start:k * (start + length)] = packed[k * offset:k * (offset + length)]
+    return out
+
+
 def _extract_taps(name, n, sample_rate, bw):
     """the smoothing taps of extractKernel for rows of n samples, by the reference's own expressions
     (distortion.py:45-47), or None where it does not smooth (bw is None or bw >= sample_rate / 2).  ValueError: a
