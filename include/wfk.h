@@ -665,6 +665,65 @@ int64_t wfk_segment_rows_span(const wfk_segment_rows_plan* plan);
 const char* wfk_segment_rows_kernel_name(const wfk_segment_rows_plan* plan, int launch, int with_marks);
 int wfk_segment_rows_plan_destroy(wfk_segment_rows_plan* plan);
 
+/* -- the waveform library of a segment table: equal segments of a row share one slot -------------- */
+/* A gate sequence plays the same few pulses many times per channel, and the packed side of wfk_segment_rows holds each
+ * of them again.  The library keeps one copy per row of every distinct segment.  The plan is made for `rows` rows,
+ * width = k in {1, 2}, max_segments and capacity (those of the wfk_segment_rows plan whose outputs it reads) and
+ * lib_capacity in [0, capacity].  Inputs per apply, device memory, never written, as wfk_segment_rows wrote them:
+ *   table   rows of 3 max_segments int32;   packed  rows of k capacity int16;   used  rows * 2 int64 [count, kept].
+ * Two segments of a row are EQUAL when their lengths are equal and their k length codes are equal verbatim, marker bits
+ * included.  Among equal segments the one with the lowest j is the FIRST.  The firsts, in ascending j, are the row's
+ * slots u = 0, 1, ...:
+ *   lib_offset_u = length of slot 0 + ... + length of slot u - 1,   unique = the number of slots,
+ *   lib_kept = the lengths of all slots.
+ * Outputs, all the caller's; each of the first three is optional, NULL: not written:
+ *   plays    rows of 3 max_segments int32: entry j < count is [start_j, length_j, lib_offset of the slot of j]; no
+ *            other entry is touched.  The layout of table: (plays, library) expand as (table, packed) do;
+ *   slots    rows of max_segments int32: entry j < count is the slot u of segment j; no other entry is touched;
+ *   library  rows of k lib_capacity int16: the codes of slot u lie at k lib_offset_u, verbatim, for the samples
+ *            p < min(lib_kept, lib_capacity); nothing else is touched.  The cut at `lib_capacity` is by position, as
+ *            for packed; plays holds the true offsets whatever the cut;
+ *   lib_used rows * 2 int64, [unique, lib_kept] per row: the TRUE totals, overwritten by every apply (written by the
+ *            kernel that owns the row: no atomics onto it, no zeroing).  Required.
+ * plays = slots = library = NULL is the sizing pass: only lib_used is written.  A side that holds nothing
+ * (max_segments = 0, capacity = 0, lib_capacity = 0) is not looked at and may be NULL.
+ * A ROW THAT CANNOT BE READ is reported, not trusted: used[row] with count < 0, count > max_segments, kept < 0 or
+ * kept > capacity, or an entry j < count with length <= 0, offset < 0 or offset + length > capacity (formed in 64
+ * bits).  Such a row gets lib_used[row] = [-1, -1] and nothing else of it is written; the other rows are unaffected.
+ * No content of table / packed / used makes a kernel read or write outside the sides it was given.  (In a row that the
+ * segment stage wrote, lib_kept <= kept; where the entries of a row overlap each other, the third column of plays is
+ * lib_offset modulo 2^32.)  Every output is a pure function of the inputs: two applies agree to the bit, whatever
+ * the order in which segments met in the kernels.
+ * rows < 1, a width other than 1 or 2, max_segments < 0 or > 2^30, capacity < 0 or > 2^31 - 1, lib_capacity outside
+ * [0, capacity], more than 2^31 - 1 workgroups: WFK_EINVAL with the argument named, before any device work; no device:
+ * WFK_EHIP.
+ * wfk_segment_library_apply() enqueues its four kernels (three in the sizing pass; with max_segments = 0 the one that
+ * writes lib_used alone) on `hip_stream`, and that is all it does to the device (as wfk_avg_apply: it may be called
+ * while the stream is being captured; a replay reads table, packed and used anew and overwrites lib_used).
+ * Strides are in elements of their side and, where there is more than one row, at least the row: table_stride and
+ * plays_stride >= 3 max_segments, slots_stride >= max_segments (int32), packed_stride >= k capacity, library_stride >=
+ * k lib_capacity.  Every side is aligned to its element, no output meets an input or another output, lib_used (8-byte
+ * aligned) meets none of them; a NULL used or lib_used: WFK_EINVAL.
+ * The plan owns a workspace (a hash, a slot and two sums per segment, a hash table of the power of two >= 2
+ * max_segments ids per row) that the launches of an apply hand to each other and that an apply rewrites before it
+ * reads it, so a plan serves ONE STREAM AT A TIME (and one graph at a time).
+ * The environment's WFK_SEGLIB_HASH_BITS = b, 0 <= b <= 64, read when the plan is made, keeps only the low b bits of
+ * every hash: more segments meet in the table, and no result changes.  A value that is no whole number in [0, 64]
+ * is ignored, as an unknown WFK_STATES_COUNTERS is: the plan keeps the full hash, and its kernel names show that. */
+typedef struct wfk_segment_library_plan wfk_segment_library_plan;
+int wfk_segment_library_plan_create(int32_t rows, int width, int64_t max_segments, int64_t capacity,
+                                    int64_t lib_capacity, wfk_segment_library_plan** out);
+int wfk_segment_library_apply(wfk_segment_library_plan* plan, const int32_t* table_dev, int64_t table_stride,
+                              const int16_t* packed_dev, int64_t packed_stride, const int64_t* used_dev /* rows * 2 */,
+                              int32_t* plays_dev /* or NULL */, int64_t plays_stride, int32_t* slots_dev /* or NULL */,
+                              int64_t slots_stride, int16_t* library_dev /* or NULL */, int64_t library_stride,
+                              int64_t* lib_used_dev /* rows * 2 */, void* hip_stream);
+/* launch 0 .. 3: "seglib_hash", "seglib_match", "seglib_scan", "seglib_copy"; where WFK_SEGLIB_HASH_BITS cut the hash,
+ * the first two end in " [hash bits b]".  The string lives as long as the plan ("" for another launch or a null
+ * plan) */
+const char* wfk_segment_library_kernel_name(const wfk_segment_library_plan* plan, int launch);
+int wfk_segment_library_plan_destroy(wfk_segment_library_plan* plan);
+
 /* -- mixing across rows: a sparse matrix and an offset, per sample -------------------------------- */
 /* rows_in real rows of n samples (kind: WFK_OUT_F64 or WFK_OUT_F32) become rows_out rows of the same kind through a
  * rows_out x rows_in matrix M and an offset per output row: flux crosstalk compensation (a band), IQ mixer correction

@@ -16,7 +16,7 @@ OUT=gpurun_out/prof_${TAG}_${WL}
 mkdir -p "$OUT" gpurun_out/profiles
 export TMPDIR=/tmp
 ARGS="bench.py --workload $WL --steps 5 --warmup 1 --no-cpu-baseline --no-also"   # (--no-also: the c2 / c3 / c4 legs of the default line run the same kernel symbols; each is profiled by its own workload)
-# stage benches outside bench.py (their own scripts): iir, readout, multitone, demod, avg, states, dac, marker
+# stage benches outside bench.py (their own scripts): iir, readout, multitone, demod, avg, states, dac, marker, segment, seglib
 case "$WL" in
   iir) ARGS="tools/iir_bench.py" ;;
   readout) ARGS="tools/readout_bench.py" ;;
@@ -27,6 +27,7 @@ case "$WL" in
   dac) ARGS="tools/dac_rows_bench.py --cases D2 --reps 5" ;;
   marker) ARGS="tools/marker_rows_bench.py --cases M1 --dtypes f64 --reps 5 --chain-reps 1" ;;
   segment) ARGS="tools/segment_rows_bench.py --cases M1 --widths 2 --duties 20 --forms bit --reps 5 --no-chain --no-copy" ;;
+  seglib) ARGS="tools/segment_library_bench.py --cases M1 --widths 1,2 --shapes 16 --reps 5" ;;
   awg_f32) ARGS="bench.py --workload awg --dtype f32 --steps 5 --warmup 1 --no-cpu-baseline --no-also" ;;
 esac
 echo "== stats pass ($WL)"

@@ -191,6 +191,11 @@ def lib():
         l.wfk_segment_rows_kernel_name.argtypes = [VP, C.c_int, C.c_int]
         l.wfk_segment_rows_kernel_name.restype = C.c_char_p
         l.wfk_segment_rows_plan_destroy.argtypes = [VP]
+        l.wfk_segment_library_plan_create.argtypes = [I32, C.c_int, I64, I64, I64, P(VP)]
+        l.wfk_segment_library_apply.argtypes = [VP, VP, I64, VP, I64, VP, VP, I64, VP, I64, VP, I64, VP, VP]
+        l.wfk_segment_library_kernel_name.argtypes = [VP, C.c_int]
+        l.wfk_segment_library_kernel_name.restype = C.c_char_p
+        l.wfk_segment_library_plan_destroy.argtypes = [VP]
         l.wfk_mix_rows_plan_create.argtypes = [I64, I32, I32, C.c_int, VP, VP, VP, VP, P(VP)]
         l.wfk_mix_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP]
         l.wfk_mix_rows_reads.argtypes = [VP]
@@ -1159,6 +1164,55 @@ class SegmentRowsPlan(_Handle):
     def kernel_name(self, launch: int = 0, marks: bool = False) -> str:
         """launch 0, 1, 2: the count, scan and pack kernels"""
         return lib().wfk_segment_rows_kernel_name(self._h, int(launch), 1 if marks else 0).decode()
+
+
+def segment_library_arguments(rows=1, width=1, max_segments=0, capacity=0, lib_capacity=None):
+    """the arguments of a SegmentLibraryPlan, checked on the host (no device, no library) -> (rows, width,
+    max_segments, capacity, lib_capacity) as ints.  `lib_capacity` None: capacity.  ValueError, the argument named:
+    rows < 1, a width other than 1 or 2, max_segments outside [0, 2^30], capacity outside [0, 2^31 - 1], lib_capacity
+    outside [0, capacity]."""
+    rows, width = _whole('rows', rows), _whole('width', width)
+    max_segments, capacity = _whole('max_segments', max_segments), _whole('capacity', capacity)
+    if rows < 1:
+        raise ValueError('rows must be at least 1')
+    if width not in (1, 2):
+        raise ValueError('width must be 1 or 2')
+    if max_segments < 0:
+        raise ValueError('max_segments must not be negative')
+    if max_segments > 2**30:
+        raise ValueError('max_segments must not exceed 2^30')
+    if not 0 <= capacity <= 2**31 - 1:
+        raise ValueError('capacity must lie in [0, 2^31 - 1]')
+    lib_capacity = capacity if lib_capacity is None else _whole('lib_capacity', lib_capacity)
+    if not 0 <= lib_capacity <= capacity:
+        raise ValueError('lib_capacity must lie in [0, capacity]')
+    return rows, width, max_segments, capacity, lib_capacity
+
+
+class SegmentLibraryPlan(_Handle):
+    """The waveform library of `rows` rows that a SegmentRowsPlan of this width, max_segments and capacity cut: equal
+    segments of a row share one slot (wfk_segment_library_plan_create; the semantics are in include/wfk.h).  The plan
+    owns the workspace its launches share: one stream at a time.  WFK_SEGLIB_HASH_BITS is read here.  ValueError
+    before any device work as `segment_library_arguments` lists them."""
+    _destroy = 'wfk_segment_library_plan_destroy'
+
+    def __init__(self, rows=1, width=1, max_segments=0, capacity=0, lib_capacity=None):
+        (self.rows, self.width, self.max_segments, self.capacity,
+         self.lib_capacity) = segment_library_arguments(rows, width, max_segments, capacity, lib_capacity)
+        check(lib().wfk_segment_library_plan_create(self.rows, self.width, self.max_segments, self.capacity,
+                                                    self.lib_capacity, C.byref(self._h)))
+
+    def apply(self, table_ptr, table_stride, packed_ptr, packed_stride, used_ptr, plays_ptr, plays_stride, slots_ptr,
+              slots_stride, library_ptr, library_stride, lib_used_ptr, stream=0):
+        """plays_ptr, slots_ptr, library_ptr: each None or an output; all None: the sizing pass; lib_used_ptr: rows * 2
+        int64, overwritten with [unique, lib_kept], [-1, -1] for a row that cannot be read"""
+        check(lib().wfk_segment_library_apply(self._h, table_ptr, table_stride, packed_ptr, packed_stride, used_ptr,
+                                              plays_ptr, plays_stride, slots_ptr, slots_stride, library_ptr,
+                                              library_stride, lib_used_ptr, stream))
+
+    def kernel_name(self, launch: int = 0) -> str:
+        """launch 0 .. 3: the hash, match, scan and copy kernels"""
+        return lib().wfk_segment_library_kernel_name(self._h, int(launch)).decode()
 
 
 MIX_TILE_ROWS = 8          # WFK_MIX_TILE_ROWS

@@ -114,4 +114,44 @@ int wfk_segment_row_rule(const SegmentShape& s, const void* codes, int64_t codes
   return WFK_OK;
 }
 
+// The segment library reads what the segment stage wrote -- `rows` rows of 3 max_segments int32 (table), of k capacity
+// codes (packed) and the contiguous rows x [count, kept] int64 (used) -- and has three outputs next to its report
+// `lib_used` (rows x [unique, lib_kept]): rows of 3 max_segments int32 (plays), of max_segments int32 (slots) and of
+// k lib_capacity codes (library).  An output that is null is not written; all three null is the sizing pass: the
+// inputs and the report alone.  A side that holds nothing (max_segments = 0, capacity = 0, lib_capacity = 0) is not
+// looked at.  The rule runs once per output: the library against the inputs, then plays against the inputs and the
+// library, then slots against all of them; the report meets no side.
+struct SegmentLibraryShape { int64_t rows, k, max_segments, capacity, lib_capacity; };
+template <typename Fail>
+int wfk_segment_library_row_rule(const SegmentLibraryShape& s, const void* table, int64_t table_stride,
+                                 const void* packed, int64_t packed_stride, const void* used, const void* plays,
+                                 int64_t plays_stride, const void* slots, int64_t slots_stride, const void* library,
+                                 int64_t library_stride, const void* lib_used, Fail&& fail) {
+  const char* stage = "segment library";
+  const bool has_plays = plays && s.max_segments > 0, has_slots = slots && s.max_segments > 0;
+  const bool has_library = library && s.lib_capacity > 0;
+  const RowReport report{lib_used, s.rows, 2};
+  const RowSide u{"used", used, s.rows, 2, 2, sizeof(int64_t), false};
+  const RowSide t = s.max_segments > 0 ? RowSide{"table", table, s.rows, table_stride, 3 * s.max_segments,
+                                                 sizeof(int32_t), false} : u;
+  const RowSide y = s.capacity > 0 ? RowSide{"packed", packed, s.rows, packed_stride, s.k * s.capacity,
+                                             sizeof(int16_t), false} : u;
+  const RowSide l = has_library ? RowSide{"library", library, s.rows, library_stride, s.k * s.lib_capacity,
+                                          sizeof(int16_t), false} : u;
+  const RowSide p = has_plays ? RowSide{"plays", plays, s.rows, plays_stride, 3 * s.max_segments, sizeof(int32_t),
+                                        false} : u;
+  const RowSide o{"slots", slots, s.rows, slots_stride, s.max_segments, sizeof(int32_t), false};
+  if (has_library) {
+    if (const int rc = wfk_row_rule(stage, {t, y, u}, l, kRowsAligned | kRowsDisjoint, fail, report)) return rc;
+  }
+  if (has_plays) {
+    if (const int rc = wfk_row_rule(stage, {t, y, u, l}, p, kRowsAligned | kRowsDisjoint, fail, report)) return rc;
+  }
+  if (has_slots) {
+    if (const int rc = wfk_row_rule(stage, {t, y, u, l, p}, o, kRowsAligned | kRowsDisjoint, fail, report)) return rc;
+  }
+  if (!has_library && !has_plays && !has_slots) return wfk_row_rule(stage, {t, y}, u, kRowsAligned, fail, report);
+  return WFK_OK;
+}
+
 }  // namespace

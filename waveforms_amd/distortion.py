@@ -2671,6 +2671,230 @@ def expand_segments(table_row, packed_row, n, idle, width=1):
     return out
 
 
+class SegmentLibrary:
+    """Device-resident waveform library of what a `SegmentStage` wrote (build once, apply many times): the segments
+    of a row whose codes are equal share one slot, so that the waveform memory and the download scale with the
+    distinct pulses of a channel, not with the pulses played.  `batch`, `max_segments`, `capacity` and `width` are
+    those of the stage (`SegmentLibrary.of(stage)` takes them from it); `lib_capacity` in [0, capacity], default
+    capacity, is the room of a library row in samples.
+    Two segments of a row are equal when their lengths and their `width` * length codes are equal verbatim, marker
+    bits included; among equal segments the one with the lowest j is the first.  The firsts in ascending j are the
+    row's slots u = 0, 1, ...:
+        lib_offset_u = the lengths of the slots before u,   unique = the slots,   lib_kept = the lengths of all slots.
+    An apply reads `table`, `packed` and `used` as the stage wrote them, never writes them, and writes `plays`
+    (batch, max_segments, 3) int32, entry j < count [start_j, length_j, lib_offset of the slot of j] -- the layout of
+    `table`, so `expand_segments(plays_r, library_r, n, idle, width)` is the round trip -- `slots` (batch,
+    max_segments) int32, the slot u of segment j < count, `library` (batch, width * lib_capacity) int16, the codes of
+    slot u at width * lib_offset_u for the samples p < min(lib_kept, lib_capacity) (the cut is by position; `plays`
+    holds the true offsets whatever the cut), and `lib_used` (batch, 2) int64 [unique, lib_kept] -- the TRUE totals,
+    overwritten by every apply; nothing else of plays, slots and library is touched.
+    A row that cannot be read -- `used` with count outside [0, max_segments] or kept outside [0, capacity], an entry
+    j < count with length <= 0, offset < 0 or offset + length > capacity -- gets lib_used = [-1, -1] and nothing else
+    of it is written; the other rows are unaffected.  Every output is a pure function of the inputs.
+    Building a library needs no device; the plan is made by the first apply (WFK_SEGLIB_HASH_BITS is read then) and
+    owns a workspace, so a library serves one stream at a time.
+
+        lib = SegmentLibrary.of(seg)
+        rows_out = lib.download(*lib.apply_torch(table, packed, used), used)    # [(plays_r, slots_r, library_r), ...]
+    """
+
+    def __init__(self, batch: int = 1, max_segments: int = 0, capacity: int = 0, width: int = 1, lib_capacity=None):
+        try:
+            (self.batch, self.width, self.max_segments, self.capacity,
+             self.lib_capacity) = _engine.segment_library_arguments(batch, width, max_segments, capacity, lib_capacity)
+        except ValueError as e:
+            raise ValueError(f'SegmentLibrary: {e}') from None
+        self.plan = None
+
+    @classmethod
+    def of(cls, stage, lib_capacity=None):
+        """the library of what `stage` (a SegmentStage) writes"""
+        return cls(stage.batch, stage.max_segments, stage.capacity, stage.width, lib_capacity)
+
+    def _plan(self):
+        if self.plan is None:
+            self.plan = _engine.SegmentLibraryPlan(self.batch, self.width, self.max_segments, self.capacity,
+                                                   self.lib_capacity)
+        return self.plan
+
+    def kernel_name(self, launch: int = 0) -> str:
+        return self._plan().kernel_name(launch)
+
+    def _table_like(self, t, what):
+        """(batch, max_segments, 3) int32, each row contiguous -> (ptr, stride, side)"""
+        rows, ms = self.batch, self.max_segments
+        message = f'expected {what}: (batch, max_segments, 3) int32 device tensor, each row contiguous'
+        if (t.dim() != 3 or tuple(t.shape) != (rows, ms, 3) or (ms > 1 and t.stride(1) != 3)
+                or (ms > 0 and t.stride(2) != 1)):
+            raise ValueError(message)
+        p0, ps = _rows.check_rows(t.as_strided((rows, 3 * ms), (t.stride(0), 1)), rows, 3 * ms,
+                                  _rows.torch_dtype(np.int32), message)
+        return p0, ps, (p0, ps, rows, 3 * ms, 4)
+
+    def _inputs(self, table, packed, used):
+        """-> (the sides of the inputs with their names, table ptr, stride, packed ptr, stride, used ptr)"""
+        rows, k = self.batch, self.width
+        t0, ts, tr = self._table_like(table, 'table')
+        p0, ps = _rows.check_rows(packed, rows, k * self.capacity, _rows.torch_dtype(np.int16),
+                                  'expected packed: (batch, >=width * capacity) row-contiguous int16 device tensor')
+        u0 = _rows.check_state(used, (rows, 2), 'expected used: contiguous (batch, 2) int64 device tensor',
+                               dtype=np.int64)
+        if u0 is None:
+            raise ValueError('expected used: contiguous (batch, 2) int64 device tensor')
+        sides = [('table', tr), ('packed', (p0, ps, rows, k * self.capacity, 2)), ('used', (u0, 2, rows, 2, 8))]
+        return sides, t0, ts, p0, ps, u0
+
+    def _lib_used(self, lib_used, sides):
+        r0 = _rows.check_state(lib_used, (self.batch, 2),
+                               'expected lib_used: contiguous (batch, 2) int64 device tensor', dtype=np.int64)
+        if not _rows.report_disjoint(r0, self.batch, 2, *(s for _, s in sides)):
+            raise ValueError('segment library: lib_used overlaps table / packed / used / plays / slots / library')
+        return r0
+
+    def apply_torch(self, table, packed, used, *, plays=None, slots=None, library=None, lib_used=None):
+        """table: (batch, max_segments, 3) int32, packed: (batch, >= width * capacity) int16, used: contiguous
+        (batch, 2) int64, as `SegmentStage.apply_torch` returns them (rows may be windows of wider tensors); plays:
+        (batch, max_segments, 3) int32; slots: (batch, >= max_segments) int32; library: (batch, >= width *
+        lib_capacity) int16; lib_used: contiguous (batch, 2) int64 -- each allocated when None.  No output may share
+        memory with an input or another output (ValueError); the inputs are never written.  Asynchronous on torch's
+        current stream, no allocation when the outputs are given.  -> (plays, slots, library[:, :width *
+        lib_capacity], lib_used)"""
+        import torch
+        k, rows, ms = self.width, self.batch, self.max_segments
+        sides, t0, ts, p0, ps, u0 = self._inputs(table, packed, used)
+        device = table.device
+        if plays is None:
+            plays = torch.empty((rows, max(ms, 1), 3), dtype=torch.int32, device=device)[:, :ms]
+        if slots is None:
+            slots = torch.empty((rows, max(ms, 1)), dtype=torch.int32, device=device)[:, :ms]
+        if library is None:
+            library = torch.empty((rows, max(k * self.lib_capacity, 1)), dtype=torch.int16,
+                                  device=device)[:, :k * self.lib_capacity]
+        if lib_used is None:
+            lib_used = torch.empty((rows, 2), dtype=torch.int64, device=device)
+        y0, ys, yr = self._table_like(plays, 'plays')
+        s0, ss = _rows.check_rows(slots, rows, ms, _rows.torch_dtype(np.int32),
+                                  'expected slots: (batch, >=max_segments) row-contiguous int32 device tensor')
+        l0, ls = _rows.check_rows(library, rows, k * self.lib_capacity, _rows.torch_dtype(np.int16),
+                                  'expected library: (batch, >=width * lib_capacity) row-contiguous int16 device tensor')
+        outs = [('library', (l0, ls, rows, k * self.lib_capacity, 2)), ('plays', yr), ('slots', (s0, ss, rows, ms, 4))]
+        for i, (name, side) in enumerate(outs):
+            for other, o in sides + outs[:i]:
+                if not _rows.rows_disjoint(side, o):
+                    raise ValueError(f'segment library: {name} overlaps {other}')
+        r0 = self._lib_used(lib_used, sides + outs)
+        stream = torch.cuda.current_stream(device).cuda_stream
+        self._plan().apply(t0 if ms else None, ts, p0 if self.capacity else None, ps, u0, y0 if ms else None, ys,
+                           s0 if ms else None, ss, l0 if self.lib_capacity else None, ls, r0, stream)
+        return plays, slots, library[:, :k * self.lib_capacity], lib_used
+
+    def measure_torch(self, table, packed, used, lib_used=None):
+        """the sizing pass: only `lib_used` (allocated when None) is written.  -> lib_used"""
+        import torch
+        sides, t0, ts, p0, ps, u0 = self._inputs(table, packed, used)
+        if lib_used is None:
+            lib_used = torch.empty((self.batch, 2), dtype=torch.int64, device=table.device)
+        r0 = self._lib_used(lib_used, sides)
+        stream = torch.cuda.current_stream(table.device).cuda_stream
+        self._plan().apply(t0 if self.max_segments else None, ts, p0 if self.capacity else None, ps, u0, None, 0, None,
+                           0, None, 0, r0, stream)
+        return lib_used
+
+    def download(self, plays, slots, library, lib_used, used):
+        """what an apply wrote, on the host: `lib_used` and `used` are copied first (this waits for the stream), then
+        only [:, :max count] of plays and slots and [:, :width * max lib_kept] of the library, through pinned host
+        memory (torch's cache of it: the arrays returned are views of that memory and keep it alive).  -> a list of
+        (plays_r (count_r, 3) int32, slots_r (count_r,) int32, library_r (width * lib_kept_r,) int16), one per row.
+        ValueError when a row could not be read or its library overflowed lib_capacity: what came out would not be
+        the row."""
+        import torch
+
+        def to_host(x):
+            if x.numel() == 0:
+                return np.empty(tuple(x.shape), dtype=x.cpu().numpy().dtype)
+            h = torch.empty(tuple(x.shape), dtype=x.dtype, pin_memory=True)
+            h.copy_(x, non_blocking=True)
+            torch.cuda.current_stream(x.device).synchronize()
+            return h.numpy()
+
+        lu, u = lib_used.cpu().numpy(), used.cpu().numpy()
+        for r in range(self.batch):
+            if lu[r, 0] < 0:
+                raise ValueError(f'segment library: row {r} could not be read: its table, packed codes and totals do '
+                                 f'not fit max_segments {self.max_segments} and capacity {self.capacity}')
+            if lu[r, 1] > self.lib_capacity:
+                raise ValueError(f'segment library: row {r} overflowed: {int(lu[r, 0])} slots of {int(lu[r, 1])} '
+                                 f'samples, room for {self.lib_capacity}')
+        k = self.width
+        count, kept = (int(u[:, 0].max()), int(lu[:, 1].max())) if self.batch else (0, 0)
+        p, s, y = to_host(plays[:, :count]), to_host(slots[:, :count]), to_host(library[:, :k * kept])
+        return [(p[r, :int(u[r, 0])], s[r, :int(u[r, 0])], y[r, :k * int(lu[r, 1])]) for r in range(self.batch)]
+
+    def close(self):
+        if self.plan is not None:
+            self.plan.close()
+            self.plan = None
+
+
+def library_rows(segments, width=1):
+    """The waveform libraries of the rows that `segment_rows` returned (see `SegmentLibrary`), all rows in one apply:
+    NumPy in, NumPy out.  `segments`: a list of (table_r (count_r, 3) int32, packed_r (width * kept_r,) int16), one
+    per row.  -> a list of (plays_r (count_r, 3) int32, slots_r (count_r,) int32, library_r (width * lib_kept_r,)
+    int16).  ValueError before any device work: no rows, a width other than 1 or 2, a table that is not (count, 3)
+    int32, packed codes that are not 1-D int16 or no multiple of the width; ValueError after it: a row whose table
+    does not fit its packed codes."""
+    if width not in (1, 2):
+        raise ValueError('library_rows: width must be 1 or 2')
+    k = int(width)
+    try:
+        segments = [(np.asarray(t), np.asarray(p)) for t, p in segments]
+    except (TypeError, ValueError):
+        raise ValueError('library_rows: segments must be a list of (table, packed) pairs') from None
+    rows = len(segments)
+    if rows < 1:
+        raise ValueError('library_rows: no rows')
+    for r, (t, p) in enumerate(segments):
+        if t.ndim != 2 or t.shape[1] != 3 or t.dtype != np.int32:
+            raise ValueError(f'library_rows: row {r}: the table must be (count, 3) int32')
+        if p.ndim != 1 or p.dtype != np.int16 or len(p) % k:
+            raise ValueError(f'library_rows: row {r}: the packed codes must be 1-D int16, a multiple of the width long')
+    ms, cap = max(len(t) for t, _ in segments), max(len(p) for _, p in segments) // k
+    empty = [(np.zeros((0, 3), dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int16))
+             for _ in range(rows)]
+    if ms == 0:
+        return empty
+    try:
+        _engine.segment_library_arguments(rows, k, ms, cap)
+    except ValueError as e:
+        raise ValueError(f'library_rows: {e}') from None
+    table = np.zeros((rows, ms, 3), dtype=np.int32)
+    packed = np.zeros((rows, max(k * cap, 1)), dtype=np.int16)
+    used = np.zeros((rows, 2), dtype=np.int64)
+    for r, (t, p) in enumerate(segments):
+        table[r, :len(t)] = t
+        packed[r, :len(p)] = p
+        used[r] = len(t), len(p) // k
+    with _engine.SegmentLibraryPlan(rows, k, ms, cap) as plan, _engine.DeviceBuffer(table.nbytes) as t, \
+            _engine.DeviceBuffer(packed.nbytes) as y, _engine.DeviceBuffer(used.nbytes) as u, \
+            _engine.DeviceBuffer(table.nbytes) as pl, _engine.DeviceBuffer(rows * ms * 4) as sl, \
+            _engine.DeviceBuffer(packed.nbytes) as lb, _engine.DeviceBuffer(rows * 16) as lu:
+        t.upload(table)
+        y.upload(packed)
+        u.upload(used)
+        plan.apply(t.ptr, 3 * ms, y.ptr if cap else None, packed.shape[1], u.ptr, pl.ptr, 3 * ms, sl.ptr, ms,
+                   lb.ptr if cap else None, packed.shape[1], lu.ptr)
+        _engine.sync()
+        lib_used = lu.download((rows, 2), np.int64)
+        plays = pl.download((rows, ms, 3), np.int32)
+        slots = sl.download((rows, ms), np.int32)
+        library = lb.download(packed.shape, np.int16)
+    for r in range(rows):
+        if lib_used[r, 0] < 0:
+            raise ValueError(f'library_rows: row {r}: the table does not fit the packed codes')
+    return [(plays[r, :len(segments[r][0])].copy(), slots[r, :len(segments[r][0])].copy(),
+             library[r, :k * int(lib_used[r, 1])].copy()) for r in range(rows)]
+
+
 def _extract_taps(name, n, sample_rate, bw):
     """the smoothing taps of extractKernel for rows of n samples, by the reference's own expressions
     (distortion.py:45-47), or None where it does not smooth (bw is None or bw >= sample_rate / 2).  ValueError: a
