@@ -724,6 +724,65 @@ int wfk_segment_library_apply(wfk_segment_library_plan* plan, const int32_t* tab
 const char* wfk_segment_library_kernel_name(const wfk_segment_library_plan* plan, int launch);
 int wfk_segment_library_plan_destroy(wfk_segment_library_plan* plan);
 
+/* -- playing a segment table back: table + waveform memory -> code rows, compared on the way ------ */
+/* The inverse of the cut, on the device: what a sequencer plays from a table and a waveform memory, as dense rows, with
+ * an optional comparison against the rows the table was cut from.  The plan is made for `rows` rows of n samples,
+ * width = k in {1, 2} codes per sample, max_segments and capacity (the room of a packed / library row, in samples).
+ * Inputs per apply, device memory, never written:
+ *   table   rows of 3 max_segments int32 [start, length, offset], as wfk_segment_rows writes table or
+ *           wfk_segment_library writes plays, or as the caller wrote it;
+ *   packed  rows of k capacity int16: the packed side of wfk_segment_rows, or a library;
+ *   used    rows * 2 int64, of which only the first of a row (count) is read;
+ *   idle0, idle1  the idle code of each code of a sample (k = 1: idle0 alone), passed BY VALUE per apply: a captured
+ *           graph replays the captured values;
+ *   expect  rows of k n int16, or NULL: the rows the table was cut from.
+ * A row is GOOD when 0 <= count <= max_segments, every entry j < count has length > 0, start >= 0, start + length <= n,
+ * offset >= 0 and offset + length <= capacity (formed in 64 bits), and every entry 1 <= j < count has start_j >=
+ * start_(j-1) + length_(j-1): ascending and disjoint (touching is good).  Everything the two stages write is good; a row
+ * whose table overflowed max_segments is bad, as is a library cut at lib_capacity, whose offsets point past the room.
+ * This is NARROWER than expand_segments of the Python package, which takes empty and overlapping entries (the later
+ * one wins).  Outputs:
+ *   out     rows of k n int16, or NULL.  For a good row, sample i holds the k codes at k (offset_j + i - start_j) of
+ *           packed where start_j <= i < start_j + length_j, and (idle0, idle1) elsewhere -- by code index in the row,
+ *           wherever the row starts.  All k n codes of a good row are written and nothing else: no gap of a strided
+ *           row, nothing of a bad row;
+ *   report  rows * 4 int64, [played, differ, stray, first] per row, required, overwritten by every apply:
+ *           played = the lengths of the row's entries; differ = the samples inside a play where any of the k codes
+ *           differs from expect; stray = the samples outside every play where any code of expect differs from its
+ *           idle; first = the lowest sample counted by either, or -1.  Without expect: [played, 0, 0, -1].  A bad row:
+ *           [-1, -1, -1, -1], and the other rows are unaffected.
+ * out = NULL with expect is the verifying pass, out = expect = NULL the checking pass: only the report is written.
+ * n = 0 writes the report and nothing else.  No content of table / packed / used makes a kernel read or write outside
+ * the sides it was given.  Every output is a pure function of the inputs: two applies agree to the bit (the counts are
+ * integer sums and a minimum, whatever the order in which workgroups arrive).
+ * n outside [0, 2^31 - 1], rows < 1, a width other than 1 or 2, max_segments < 0 or > 2^30, capacity < 0 or > 2^31 - 1,
+ * more than 2^31 - 1 workgroups: WFK_EINVAL with the argument named, before any device work; no device: WFK_EHIP.
+ * wfk_segment_play_apply() enqueues its two kernels (one in the checking pass and for n = 0) on `hip_stream`, and that
+ * is all it does to the device (as wfk_avg_apply: it may be called while the stream is being captured; a replay reads
+ * table, packed, used and expect anew and overwrites the report).
+ * Strides are in elements of their side and, where there is more than one row, at least the row: table_stride >= 3
+ * max_segments (int32), packed_stride >= k capacity, out_stride and expect_stride >= k n.  Every side is aligned to its
+ * element, out meets no input (expect among them), report (8-byte aligned) meets none of them; a side that holds
+ * nothing (max_segments = 0, capacity = 0; n = 0 for out and expect) is not looked at; a NULL used or report:
+ * WFK_EINVAL.
+ * The plan owns a workspace of `rows` ints (the verdicts) that the first launch hands to the second, so a plan serves
+ * ONE STREAM AT A TIME (and one graph at a time). */
+typedef struct wfk_segment_play_plan wfk_segment_play_plan;
+int wfk_segment_play_plan_create(int64_t n, int32_t rows, int width, int64_t max_segments, int64_t capacity,
+                                 wfk_segment_play_plan** out);
+int wfk_segment_play_apply(wfk_segment_play_plan* plan, const int32_t* table_dev, int64_t table_stride,
+                           const int16_t* packed_dev, int64_t packed_stride, const int64_t* used_dev /* rows * 2 */,
+                           int16_t idle0, int16_t idle1, int16_t* out_dev /* or NULL */, int64_t out_stride,
+                           const int16_t* expect_dev /* or NULL */, int64_t expect_stride,
+                           int64_t* report_dev /* rows * 4 */, void* hip_stream);
+/* the samples one workgroup of the second launch covers: 8192 (0 for a null plan) */
+int64_t wfk_segment_play_span(const wfk_segment_play_plan* plan);
+/* launch 0: "segplay_check"; launch 1, 2, 3: the second launch of a play, of a verifying pass and of both,
+ * "segplay_fill<1, true, false>", "segplay_fill<1, false, true>", "segplay_fill<1, true, true>" -- <width, out,
+ * expect>; a static string ("" for another launch or a null plan) */
+const char* wfk_segment_play_kernel_name(const wfk_segment_play_plan* plan, int launch);
+int wfk_segment_play_plan_destroy(wfk_segment_play_plan* plan);
+
 /* -- mixing across rows: a sparse matrix and an offset, per sample -------------------------------- */
 /* rows_in real rows of n samples (kind: WFK_OUT_F64 or WFK_OUT_F32) become rows_out rows of the same kind through a
  * rows_out x rows_in matrix M and an offset per output row: flux crosstalk compensation (a band), IQ mixer correction

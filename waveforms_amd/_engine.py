@@ -196,6 +196,13 @@ def lib():
         l.wfk_segment_library_kernel_name.argtypes = [VP, C.c_int]
         l.wfk_segment_library_kernel_name.restype = C.c_char_p
         l.wfk_segment_library_plan_destroy.argtypes = [VP]
+        l.wfk_segment_play_plan_create.argtypes = [I64, I32, C.c_int, I64, I64, P(VP)]
+        l.wfk_segment_play_apply.argtypes = [VP, VP, I64, VP, I64, VP, C.c_int16, C.c_int16, VP, I64, VP, I64, VP, VP]
+        l.wfk_segment_play_span.argtypes = [VP]
+        l.wfk_segment_play_span.restype = I64
+        l.wfk_segment_play_kernel_name.argtypes = [VP, C.c_int]
+        l.wfk_segment_play_kernel_name.restype = C.c_char_p
+        l.wfk_segment_play_plan_destroy.argtypes = [VP]
         l.wfk_mix_rows_plan_create.argtypes = [I64, I32, I32, C.c_int, VP, VP, VP, VP, P(VP)]
         l.wfk_mix_rows_apply.argtypes = [VP, VP, I64, VP, I64, VP]
         l.wfk_mix_rows_reads.argtypes = [VP]
@@ -1213,6 +1220,70 @@ class SegmentLibraryPlan(_Handle):
     def kernel_name(self, launch: int = 0) -> str:
         """launch 0 .. 3: the hash, match, scan and copy kernels"""
         return lib().wfk_segment_library_kernel_name(self._h, int(launch)).decode()
+
+
+def segment_play_arguments(n, rows=1, width=1, max_segments=0, capacity=0):
+    """the arguments of a SegmentPlayPlan, checked on the host (no device, no library) -> (n, rows, width,
+    max_segments, capacity) as ints.  ValueError, the argument named: n outside [0, 2^31 - 1], rows < 1, a width other
+    than 1 or 2, max_segments outside [0, 2^30], capacity outside [0, 2^31 - 1]."""
+    n, rows, width = _whole('n', n), _whole('rows', rows), _whole('width', width)
+    max_segments, capacity = _whole('max_segments', max_segments), _whole('capacity', capacity)
+    if not 0 <= n <= 2**31 - 1:
+        raise ValueError('n must lie in [0, 2^31 - 1]')
+    if rows < 1:
+        raise ValueError('rows must be at least 1')
+    if width not in (1, 2):
+        raise ValueError('width must be 1 or 2')
+    if max_segments < 0:
+        raise ValueError('max_segments must not be negative')
+    if max_segments > 2**30:
+        raise ValueError('max_segments must not exceed 2^30')
+    if not 0 <= capacity <= 2**31 - 1:
+        raise ValueError('capacity must lie in [0, 2^31 - 1]')
+    return n, rows, width, max_segments, capacity
+
+
+def segment_play_idle(idle, width):
+    """`idle` -- one int16 code, or one per code of a sample -- as the `width` codes an apply is given -> (idle0,
+    idle1) as ints (width 1: idle1 = idle0).  ValueError: another number of codes, a code that is no whole number in
+    [-32768, 32767]."""
+    a = np.asarray(idle).reshape(-1)
+    if len(a) not in (1, int(width)):
+        raise ValueError('idle is one code or one per code of a sample')
+    codes = [_whole('idle', v) for v in a]
+    if not all(-32768 <= c <= 32767 for c in codes):
+        raise ValueError('idle must lie in [-32768, 32767]')
+    return codes[0], codes[-1]
+
+
+class SegmentPlayPlan(_Handle):
+    """`rows` rows of `width` * n int16 codes played back from a segment table and a waveform memory, with the report
+    [played, differ, stray, first] per row (wfk_segment_play_plan_create; the semantics are in include/wfk.h).  The plan
+    owns the workspace its two launches share: one stream at a time.  ValueError before any device work as
+    `segment_play_arguments` lists them."""
+    _destroy = 'wfk_segment_play_plan_destroy'
+
+    def __init__(self, n, rows=1, width=1, max_segments=0, capacity=0):
+        (self.n, self.rows, self.width, self.max_segments,
+         self.capacity) = segment_play_arguments(n, rows, width, max_segments, capacity)
+        check(lib().wfk_segment_play_plan_create(self.n, self.rows, self.width, self.max_segments, self.capacity,
+                                                 C.byref(self._h)))
+
+    def apply(self, table_ptr, table_stride, packed_ptr, packed_stride, used_ptr, idle, out_ptr, out_stride,
+              expect_ptr, expect_stride, report_ptr, stream=0):
+        """idle: (idle0, idle1), by value; out_ptr, expect_ptr: each None or a side; both None: the checking pass;
+        report_ptr: rows * 4 int64, overwritten with [played, differ, stray, first], all -1 for a bad row"""
+        check(lib().wfk_segment_play_apply(self._h, table_ptr, table_stride, packed_ptr, packed_stride, used_ptr,
+                                           int(idle[0]), int(idle[1]), out_ptr, out_stride, expect_ptr, expect_stride,
+                                           report_ptr, stream))
+
+    def span(self) -> int:
+        """the samples one workgroup of the second launch covers"""
+        return int(lib().wfk_segment_play_span(self._h))
+
+    def kernel_name(self, launch: int = 0) -> str:
+        """launch 0: the check; 1, 2, 3: the fill of a play, of a verifying pass, of both"""
+        return lib().wfk_segment_play_kernel_name(self._h, int(launch)).decode()
 
 
 MIX_TILE_ROWS = 8          # WFK_MIX_TILE_ROWS

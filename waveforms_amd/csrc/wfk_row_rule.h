@@ -154,4 +154,30 @@ int wfk_segment_library_row_rule(const SegmentLibraryShape& s, const void* table
   return WFK_OK;
 }
 
+// The segment player reads a table, a waveform memory and the totals as the two stages above write them -- `rows` rows
+// of 3 max_segments int32 (table), of k capacity codes (packed) and the contiguous rows x [count, kept] int64 (used) --
+// and, where it is given, `expect`, rows of k n codes.  It has one output, `out`, rows of k n codes, next to its
+// report (rows x [played, differ, stray, first]).  out null: the verifying pass (expect given) or the checking pass
+// (neither): the inputs and the report alone.  A side that holds nothing (max_segments = 0, capacity = 0; n = 0 for
+// out and expect) is not looked at.  out meets no input, expect among them; the report meets no side.
+struct SegmentPlayShape { int64_t rows, n, k, max_segments, capacity; };
+template <typename Fail>
+int wfk_segment_play_row_rule(const SegmentPlayShape& s, const void* table, int64_t table_stride, const void* packed,
+                              int64_t packed_stride, const void* used, const void* out, int64_t out_stride,
+                              const void* expect, int64_t expect_stride, const void* report_ptr, Fail&& fail) {
+  const char* stage = "segment play";
+  const bool has_out = out && s.n > 0, has_expect = expect && s.n > 0;
+  const RowReport report{report_ptr, s.rows, 4};
+  const RowSide u{"used", used, s.rows, 2, 2, sizeof(int64_t), false};
+  const RowSide t = s.max_segments > 0 ? RowSide{"table", table, s.rows, table_stride, 3 * s.max_segments,
+                                                 sizeof(int32_t), false} : u;
+  const RowSide y = s.capacity > 0 ? RowSide{"packed", packed, s.rows, packed_stride, s.k * s.capacity,
+                                             sizeof(int16_t), false} : u;
+  const RowSide e = has_expect ? RowSide{"expect", expect, s.rows, expect_stride, s.k * s.n, sizeof(int16_t), false}
+                               : u;
+  const RowSide o{"out", out, s.rows, out_stride, s.k * s.n, sizeof(int16_t), false};
+  if (has_out) return wfk_row_rule(stage, {t, y, u, e}, o, kRowsAligned | kRowsDisjoint, fail, report);
+  return wfk_row_rule(stage, {t, y, e}, u, kRowsAligned, fail, report);
+}
+
 }  // namespace

@@ -2895,6 +2895,227 @@ def library_rows(segments, width=1):
              library[r, :k * int(lib_used[r, 1])].copy()) for r in range(rows)]
 
 
+class SegmentPlayer:
+    """Device-resident playback of a segment table (build once, apply many times): the inverse of the cut, what a
+    sequencer plays from a table and a waveform memory, as `batch` dense rows of `width` * n int16 codes -- with an
+    optional comparison against the rows the table was cut from, in the same pass.  `max_segments` and `capacity` (the
+    room of a packed / library row, in samples) are those of the tensors it is given: `SegmentPlayer.of(stage)` takes
+    them from a `SegmentStage`, `SegmentPlayer.of(library, n)` from a `SegmentLibrary` (capacity = its lib_capacity).
+    An apply reads `table` (batch, max_segments, 3) int32 [start, length, offset] -- the stage's `table`, the
+    library's `plays`, or one the user wrote --, `packed` (batch, >= width * capacity) int16 and `used` (batch, 2)
+    int64, of which only the count of a row is read, and never writes them.  A row is GOOD when 0 <= count <=
+    max_segments, every entry j < count has length > 0, start >= 0, start + length <= n, offset >= 0 and offset +
+    length <= capacity, and every entry after the first starts at or after the end of the one before: ascending and
+    disjoint.  Everything the two stages write is good; a table that overflowed max_segments, or a library cut at
+    lib_capacity, is not.  This is NARROWER than `expand_segments`, which takes empty and overlapping entries (the
+    later one wins).  For a good row, sample i of `out` holds the `width` codes at width * (offset_j + i - start_j) of
+    packed where start_j <= i < start_j + length_j, and `idle` (one code, or one per code of a sample; passed by value,
+    so a captured graph replays the captured codes) elsewhere: `expand_segments(table_r[:count], packed_r, n, idle,
+    width)`, bit for bit.  All width * n codes of a good row are written and nothing else.  `report` (batch, 4) int64 is
+    [played, differ, stray, first] per row, overwritten by every apply: played = the lengths of the entries; differ =
+    the samples inside a play where any code differs from `expect`; stray = the samples outside every play where any
+    code of `expect` differs from its idle -- what the cut threw away; first = the lowest sample counted by either, or
+    -1; without `expect` [played, 0, 0, -1].  A bad row gets [-1, -1, -1, -1], nothing of its `out` is written, and the
+    other rows are unaffected.  Building a player needs no device; the plan is made by the first apply and owns a
+    workspace, so a player serves one stream at a time.
+
+        player = SegmentPlayer.of(seg)
+        played, report = player.apply_torch(table, packed, used, idle=idle, expect=codes)
+    """
+
+    def __init__(self, n: int, batch: int = 1, width: int = 1, max_segments: int = 0, capacity: int = 0):
+        try:
+            (self.n, self.batch, self.width, self.max_segments,
+             self.capacity) = _engine.segment_play_arguments(n, batch, width, max_segments, capacity)
+        except ValueError as e:
+            raise ValueError(f'SegmentPlayer: {e}') from None
+        self.plan = None
+
+    @classmethod
+    def of(cls, source, n=None):
+        """the player of what `source` writes: a SegmentStage (its table / packed; n is the stage's), or a
+        SegmentLibrary with the rows' n (its plays / library)"""
+        if isinstance(source, SegmentStage):
+            if n is not None and int(n) != source.n:
+                raise ValueError(f'SegmentPlayer: n = {n} is not the n of the stage, {source.n}')
+            return cls(source.n, source.batch, source.width, source.max_segments, source.capacity)
+        if isinstance(source, SegmentLibrary):
+            if n is None:
+                raise ValueError('SegmentPlayer: a SegmentLibrary does not know n: give SegmentPlayer.of(library, n)')
+            return cls(n, source.batch, source.width, source.max_segments, source.lib_capacity)
+        raise ValueError('SegmentPlayer: of() takes a SegmentStage or a SegmentLibrary')
+
+    def _plan(self):
+        if self.plan is None:
+            self.plan = _engine.SegmentPlayPlan(self.n, self.batch, self.width, self.max_segments, self.capacity)
+        return self.plan
+
+    def span(self) -> int:
+        """the samples one workgroup of the second launch covers"""
+        return self._plan().span()
+
+    def kernel_name(self, launch: int = 0) -> str:
+        return self._plan().kernel_name(launch)
+
+    def _inputs(self, table, packed, used, expect):
+        """-> (the sides of the inputs with their names, table ptr, stride, packed ptr, stride, used ptr, expect ptr
+        or None, stride)"""
+        rows, k, ms = self.batch, self.width, self.max_segments
+        message = 'expected table: (batch, max_segments, 3) int32 device tensor, each row contiguous'
+        if (table.dim() != 3 or tuple(table.shape) != (rows, ms, 3) or (ms > 1 and table.stride(1) != 3)
+                or (ms > 0 and table.stride(2) != 1)):
+            raise ValueError(message)
+        t0, ts = _rows.check_rows(table.as_strided((rows, 3 * ms), (table.stride(0), 1)), rows, 3 * ms,
+                                  _rows.torch_dtype(np.int32), message)
+        p0, ps = _rows.check_rows(packed, rows, k * self.capacity, _rows.torch_dtype(np.int16),
+                                  'expected packed: (batch, >=width * capacity) row-contiguous int16 device tensor')
+        u0 = _rows.check_state(used, (rows, 2), 'expected used: contiguous (batch, 2) int64 device tensor',
+                               dtype=np.int64)
+        if u0 is None:
+            raise ValueError('expected used: contiguous (batch, 2) int64 device tensor')
+        sides = [('table', (t0, ts, rows, 3 * ms, 4)), ('packed', (p0, ps, rows, k * self.capacity, 2)),
+                 ('used', (u0, 2, rows, 2, 8))]
+        e0 = es = None
+        if expect is not None:
+            e0, es = _rows.check_rows(expect, rows, k * self.n, _rows.torch_dtype(np.int16),
+                                      'expected expect: (batch, >=width * n) row-contiguous int16 device tensor')
+            sides.append(('expect', (e0, es, rows, k * self.n, 2)))
+        return sides, t0, ts, p0, ps, u0, e0, es
+
+    def _report(self, report, sides, device):
+        import torch
+        if report is None:
+            report = torch.empty((self.batch, 4), dtype=torch.int64, device=device)
+        r0 = _rows.check_state(report, (self.batch, 4), 'expected report: contiguous (batch, 4) int64 device tensor',
+                               dtype=np.int64)
+        if not _rows.report_disjoint(r0, self.batch, 4, *(s for _, s in sides)):
+            raise ValueError('segment play: report overlaps table / packed / used / expect / out')
+        return report, r0
+
+    def _launch(self, device, t0, ts, p0, ps, u0, idle, o0, os_, e0, es, r0):
+        import torch
+        ms, cap, n = self.max_segments, self.capacity, self.n
+        self._plan().apply(t0 if ms else None, ts, p0 if cap else None, ps, u0, idle, o0 if n else None, os_ or 0,
+                           e0 if n else None, es or 0, r0, torch.cuda.current_stream(device).cuda_stream)
+
+    def apply_torch(self, table, packed, used, *, idle=0, out=None, expect=None, report=None):
+        """table: (batch, max_segments, 3) int32, packed: (batch, >= width * capacity) int16, used: contiguous
+        (batch, 2) int64 (rows may be windows of wider tensors); idle: one int16 code or one per code of a sample; out:
+        (batch, >= width * n) int16; expect: the same, or None; report: contiguous (batch, 4) int64 -- out and report
+        allocated when None.  out may share memory with no input, expect among them (ValueError); the inputs are never
+        written.  Asynchronous on torch's current stream, no allocation when the outputs are given.
+        -> (out[:, :width * n], report)"""
+        import torch
+        k, rows = self.width, self.batch
+        try:
+            idle = _engine.segment_play_idle(idle, k)
+        except ValueError as e:
+            raise ValueError(f'segment play: {e}') from None
+        sides, t0, ts, p0, ps, u0, e0, es = self._inputs(table, packed, used, expect)
+        if out is None:
+            out = torch.empty((rows, max(k * self.n, 1)), dtype=torch.int16, device=table.device)[:, :k * self.n]
+        o0, os_ = _rows.check_rows(out, rows, k * self.n, _rows.torch_dtype(np.int16),
+                                   'expected out: (batch, >=width * n) row-contiguous int16 device tensor')
+        side = (o0, os_, rows, k * self.n, 2)
+        for name, s in sides:
+            if not _rows.rows_disjoint(side, s):
+                raise ValueError(f'segment play: out overlaps {name}')
+        report, r0 = self._report(report, sides + [('out', side)], table.device)
+        self._launch(table.device, t0, ts, p0, ps, u0, idle, o0, os_, e0, es, r0)
+        return out[:, :k * self.n], report
+
+    def verify_torch(self, table, packed, used, expect, *, idle=0, report=None):
+        """the verifying pass: the comparison of what would be played with `expect`, without an `out`; only `report`
+        (allocated when None) is written.  -> report"""
+        if expect is None:
+            raise ValueError('expected expect: (batch, >=width * n) row-contiguous int16 device tensor')
+        try:
+            idle = _engine.segment_play_idle(idle, self.width)
+        except ValueError as e:
+            raise ValueError(f'segment play: {e}') from None
+        sides, t0, ts, p0, ps, u0, e0, es = self._inputs(table, packed, used, expect)
+        report, r0 = self._report(report, sides, table.device)
+        self._launch(table.device, t0, ts, p0, ps, u0, idle, None, 0, e0, es, r0)
+        return report
+
+    def check_torch(self, table, packed, used, report=None):
+        """the checking pass: is every row good, and how much does it play; only `report` (allocated when None) is
+        written, [played, 0, 0, -1] or all -1.  -> report"""
+        sides, t0, ts, p0, ps, u0, _, _ = self._inputs(table, packed, used, None)
+        report, r0 = self._report(report, sides, table.device)
+        self._launch(table.device, t0, ts, p0, ps, u0, (0, 0), None, 0, None, 0, r0)
+        return report
+
+    def close(self):
+        if self.plan is not None:
+            self.plan.close()
+            self.plan = None
+
+
+def play_rows(segments, n, idle=0, width=1, expect=None, return_report=False):
+    """The rows that `segments` play (see `SegmentPlayer`), all rows in one apply: NumPy in, NumPy out.  `segments`: a
+    list of (table_r (count_r, 3) int32, packed_r int16), one per row, as `segment_rows` returns them -- or
+    (plays_r, library_r) of what `library_rows` returns; `idle`: one int16 code or one per code of a sample; `expect`:
+    (rows, width * n) int16 or None.  -> out (rows, width * n) int16, with `return_report` (out, report (rows, 4) int64
+    [played, differ, stray, first]).  ValueError before any device work: no rows, a width other than 1 or 2, a table
+    that is not (count, 3) int32, packed codes that are not 1-D int16 or no multiple of the width, an expect of
+    another shape or dtype, an idle that is not one code or one per code of a sample, what `SegmentPlayer` refuses;
+    ValueError after it, naming the row: a row that is not good."""
+    if width not in (1, 2):
+        raise ValueError('play_rows: width must be 1 or 2')
+    k = int(width)
+    try:
+        segments = [(np.asarray(t), np.asarray(p)) for t, p in segments]
+    except (TypeError, ValueError):
+        raise ValueError('play_rows: segments must be a list of (table, packed) pairs') from None
+    rows = len(segments)
+    if rows < 1:
+        raise ValueError('play_rows: no rows')
+    for r, (t, p) in enumerate(segments):
+        if t.ndim != 2 or t.shape[1] != 3 or t.dtype != np.int32:
+            raise ValueError(f'play_rows: row {r}: the table must be (count, 3) int32')
+        if p.ndim != 1 or p.dtype != np.int16 or len(p) % k:
+            raise ValueError(f'play_rows: row {r}: the packed codes must be 1-D int16, a multiple of the width long')
+    ms, cap = max(len(t) for t, _ in segments), max(len(p) for _, p in segments) // k
+    try:
+        n, rows, k, ms, cap = _engine.segment_play_arguments(n, rows, k, ms, cap)
+        idle = _engine.segment_play_idle(idle, k)
+    except ValueError as e:
+        raise ValueError(f'play_rows: {e}') from None
+    if expect is not None:
+        expect = np.asarray(expect)
+        if expect.shape != (rows, k * n) or expect.dtype != np.int16:
+            raise ValueError(f'play_rows: expect must be an int16 array of the shape ({rows}, {k * n})')
+        expect = np.ascontiguousarray(expect)
+    table = np.zeros((rows, max(ms, 1), 3), dtype=np.int32)
+    packed = np.zeros((rows, max(k * cap, 1)), dtype=np.int16)
+    used = np.zeros((rows, 2), dtype=np.int64)
+    for r, (t, p) in enumerate(segments):
+        table[r, :len(t)] = t
+        packed[r, :len(p)] = p
+        used[r] = len(t), len(p) // k
+    nbytes = max(rows * k * n * 2, 16)
+    with _engine.SegmentPlayPlan(n, rows, k, ms, cap) as plan, _engine.DeviceBuffer(table.nbytes) as t, \
+            _engine.DeviceBuffer(packed.nbytes) as y, _engine.DeviceBuffer(used.nbytes) as u, \
+            _engine.DeviceBuffer(nbytes) as o, _engine.DeviceBuffer(nbytes) as e, \
+            _engine.DeviceBuffer(rows * 32) as rp:
+        t.upload(table)
+        y.upload(packed)
+        u.upload(used)
+        if expect is not None and n:
+            e.upload(expect)
+        plan.apply(t.ptr if ms else None, table.shape[1] * 3, y.ptr if cap else None, packed.shape[1], u.ptr, idle,
+                   o.ptr if n else None, k * n, e.ptr if expect is not None and n else None, k * n, rp.ptr)
+        _engine.sync()
+        report = rp.download((rows, 4), np.int64)
+        out = o.download((rows, k * n), np.int16) if n else np.zeros((rows, 0), dtype=np.int16)
+    for r in range(rows):
+        if report[r, 0] < 0:
+            raise ValueError(f'play_rows: row {r}: the table cannot be played: its entries must be non-empty, '
+                             f'ascending, disjoint, inside the row of {n} samples and inside the packed codes')
+    return (out, report) if return_report else out
+
+
 def _extract_taps(name, n, sample_rate, bw):
     """the smoothing taps of extractKernel for rows of n samples, by the reference's own expressions
     (distortion.py:45-47), or None where it does not smooth (bw is None or bw >= sample_rate / 2).  ValueError: a
