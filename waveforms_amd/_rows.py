@@ -49,11 +49,18 @@ def rows_disjoint(a, b) -> bool:
     """a, b: (ptr, row stride, batch, n, itemsize) of two row batches.  A batch occupies the bytes from the first
     sample of row 0 to the END of row batch - 1 (not batch * stride); two batches are disjoint when these half-open
     ranges do not meet.  Rows of no samples occupy nothing.  (RowSide::bytes / wfk_ranges_overlap of wfk_row_rule.h)"""
-    (a0, a1), (b0, b1) = ((p, p + ((batch - 1) * stride + n) * es) for p, stride, batch, n, es in (a, b))
-    return a[3] == 0 or b[3] == 0 or not (a0 < b1 and b0 < a1)
+    a0, a_stride, a_batch, a_n, a_es = a
+    b0, b_stride, b_batch, b_n, b_es = b
+    return a_n == 0 or b_n == 0 or not (a0 < b0 + ((b_batch - 1) * b_stride + b_n) * b_es
+                                        and b0 < a0 + ((a_batch - 1) * a_stride + a_n) * a_es)
 
 
 def report_disjoint(ptr, rows, counters, *sides) -> bool:
     """the contiguous int64 report of `rows` x `counters` at `ptr` (None: no report) meets none of `sides`, tuples as
     rows_disjoint takes them  (RowReport of wfk_row_rule.h)"""
-    return ptr is None or all(rows_disjoint((ptr, counters, rows, counters, 8), s) for s in sides)
+    if ptr is not None:
+        report = (ptr, counters, rows, counters, 8)
+        for side in sides:
+            if not rows_disjoint(report, side):
+                return False
+    return True

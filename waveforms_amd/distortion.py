@@ -58,6 +58,16 @@ def _row_state(z, r, own_orders, section_order):
     return np.concatenate([z[r, s * m:s * m + o] for s, o in enumerate(own_orders[r])] or [z[r, :0]])
 
 
+def _initial_host(initial, rows, message):
+    """a scalar (every row) or one value per row -> (rows,) float64 array; ValueError(message) for any other shape"""
+    arr = np.asarray(initial, dtype=np.float64)
+    if arr.ndim == 0:
+        arr = np.full(rows, float(arr))
+    if arr.shape != (rows, ):
+        raise ValueError(message)
+    return arr
+
+
 def _initial_rows(owner, rows, initial, device):
     """the per-row `initial` of a stage: a scalar, one value per row, or a (rows,) float64 device tensor -> None (all
     zero) or a (rows,) float64 device tensor; a tensor of the last values is kept in `owner._initial_cache`"""
@@ -65,17 +75,29 @@ def _initial_rows(owner, rows, initial, device):
     if isinstance(initial, torch.Tensor):
         _rows.check_state(initial, (rows, ), 'initial: a (batch,) contiguous float64 device tensor')
         return initial
-    arr = np.asarray(initial, dtype=np.float64)
-    if arr.ndim == 0:
-        arr = np.full(rows, float(arr))
-    if arr.shape != (rows, ):
-        raise ValueError('initial: a scalar or one value per row')
+    arr = _initial_host(initial, rows, 'initial: a scalar or one value per row')
     if not arr.any():
         return None
     c = owner._initial_cache
     if c is None or c[1] != device or not np.array_equal(c[0], arr):
         owner._initial_cache = c = (arr.copy(), device, torch.from_numpy(arr.copy()).to(device))
     return c[2]
+
+
+# what a stage calls its rows -> the refusals of its counts, its beyond and its zi / zf, ready made: an apply formats nothing
+_FRONT_TEXTS = {who: (f'expected counts: contiguous ({who}, 3) int64 device tensor',
+                      f'expected beyond: contiguous ({who}, 3) int64 device tensor',
+                      f'zi / zf must be contiguous ({who}, state_dim) float64 device tensors')
+                for who in ('batch', 'rows_out', 'n_channels')}
+
+
+def _state_ptrs(zi, zf, rows, state_dim, rows_name):
+    """the optional zi / zf of a stage with state, (rows, state_dim) float64 device tensors, -> (zi pointer or None,
+    zf pointer or None); `rows_name`: what the refusal calls the rows ('batch', 'n_channels')"""
+    if zi is None and zf is None:
+        return None, None
+    message = _FRONT_TEXTS[rows_name][2]
+    return _rows.check_state(zi, (rows, state_dim), message), _rows.check_state(zf, (rows, state_dim), message)
 
 
 class IirStage:
@@ -102,26 +124,18 @@ class IirStage:
             raise ValueError('IirStage: dtype must be float64 or float32')
         if self.batch < 1 or self.n < 0:
             raise ValueError('IirStage: batch >= 1 and n >= 0')
-        depth = _nesting(sections)
-        if depth == 2:                                             # an SOS matrix (scipy.signal.sosfilt)
-            sec = np.asarray(sections, dtype=np.float64)
-            if sec.ndim != 2 or sec.shape[1] != 6:
-                raise ValueError('IirStage: an SOS matrix has shape (n_sections, 6)')
-            sections, depth = _engine.sos_sections(sec), 3
-        if depth not in (3, 4):
-            raise ValueError('IirStage: sections is [(b, a), ...], an SOS matrix, or one [(b, a), ...] per row')
-        self.per_row = depth == 4
+        cascades, shared = _cascade_rows('IirStage', sections, self.batch,
+                                         '[(b, a), ...], an SOS matrix, or one [(b, a), ...] per row')
+        self.per_row = shared is None
         self._initial_cache = None
         if self.per_row:
-            if len(sections) != self.batch:
-                raise ValueError(f'IirStage: {len(sections)} cascades for {self.batch} rows')
-            self.plan = _engine.IirRowsPlan(sections, self.n, self.dtype)
+            self.plan = _engine.IirRowsPlan(cascades, self.n, self.dtype)
             self.own_orders = self.plan.own_orders
             self.section_order = int(self.plan.orders[0])
         else:
-            if any(np.iscomplexobj(np.asarray(c)) for sec in sections for c in sec):
+            if any(np.iscomplexobj(np.asarray(c)) for sec in shared for c in sec):
                 raise NotImplementedError('IIR sections with complex coefficients')
-            self.plan = _engine.IirPlan(sections, self.n, self.batch, self.dtype)
+            self.plan = _engine.IirPlan(shared, self.n, self.batch, self.dtype)
         self.state_dim = self.plan.state_dim
 
     def kernel_name(self) -> str:
@@ -133,9 +147,6 @@ class IirStage:
         """row r's own state (scipy layout, its sections back to back) out of a (batch, state_dim) host array"""
         return _row_state(z, r, self.own_orders, self.section_order) if self.per_row else np.asarray(z)[r]
 
-    def _initial_tensor(self, initial, device):
-        return _initial_rows(self, self.batch, initial, device)
-
     def apply_torch(self, x, out=None, initial=0.0, zi=None, zf=None):
         """x, out: (batch, >= n) row-contiguous device tensors of the stage's dtype (rows may be windows of a wider
         tensor); out=None or out is x: in place.  `initial`: a scalar, one value per row, or a (batch,) float64 device
@@ -145,12 +156,10 @@ class IirStage:
         (x0, xs), (y0, ys) = (_rows.check_rows(
             t, self.batch, self.n, _rows.torch_dtype(self.dtype),
             'expected (batch, >=n) row-contiguous device tensors of the stage dtype') for t in (x, out))
-        zip_, zfp = (_rows.check_state(z, (self.batch, self.state_dim),
-                                       'zi / zf must be contiguous (batch, state_dim) float64 device tensors')
-                     for z in (zi, zf))
+        zip_, zfp = _state_ptrs(zi, zf, self.batch, self.state_dim, 'batch')
         stream = torch.cuda.current_stream(x.device).cuda_stream
         if self.per_row:
-            ini = self._initial_tensor(initial, x.device)
+            ini = _initial_rows(self, self.batch, initial, x.device)
             self.plan.apply(x0, xs, y0, ys, zip_, zfp, None if ini is None else ini.data_ptr(), stream)
             return out
         if isinstance(initial, torch.Tensor) or np.ndim(initial) != 0:
@@ -175,6 +184,55 @@ def _nesting(x) -> int:
     while isinstance(x, (list, tuple, np.ndarray)) and len(x) > 0:
         x, d = x[0], d + 1
     return d
+
+
+def _cascade_rows(who, sections, rows, spelling, one_for=None):
+    """`sections` as the per-row IIR stages take it -- an SOS matrix, ONE cascade [(b, a), ...], or one cascade per
+    row -- -> (one cascade per row, the ONE cascade that every row got or None).  `rows` None: the cascades decide
+    the number, and ONE cascade goes to `one_for` rows.  ValueError, begun with `who`: an SOS matrix of another
+    shape, another nesting ('sections is ' + `spelling`), a number of cascades that is not `rows`."""
+    depth, one = _nesting(sections), None
+    if depth == 2:                                             # an SOS matrix (scipy.signal.sosfilt)
+        sec = np.asarray(sections, dtype=np.float64)
+        if sec.ndim != 2 or sec.shape[1] != 6:
+            raise ValueError(f'{who}: an SOS matrix has shape (n_sections, 6)')
+        sections, depth = _engine.sos_sections(sec), 3
+    if depth not in (3, 4):
+        raise ValueError(f'{who}: sections is {spelling}')
+    if depth == 3:                                             # one cascade: every row gets it
+        one, rows = sections, one_for if rows is None else rows
+        sections = [list(one)] * int(rows)
+    sections = list(sections)
+    if len(sections) < 1 or (rows is not None and int(rows) != len(sections)):
+        raise ValueError(f'{who}: {len(sections)} cascades for {rows} rows')
+    return sections, one
+
+
+def _host_trip(launch, shape, dtype, rows=0, reports=(), state_dim=0, zi=None, return_zf=False, initial=None):
+    """The round trip of a sampled chain's `to_host` through device buffers that live as long as the call: the result
+    (`shape`, `dtype`), a (rows, 3) int64 report for every true flag in `reports`, zi and zf (rows, state_dim) where
+    given / wanted, and the levels `initial` (a scalar or one per row), uploaded only where one of them is not zero.
+    `launch(result, [a pointer or None per flag], zi, zf, levels)` gets the pointers (None: not there); then one
+    synchronise and the downloads.  -> the result alone, or (result, the wanted reports in order, zf)"""
+    D = max(state_dim, 1)
+    ini = None if initial is None else np.broadcast_to(np.asarray(initial, dtype=np.float64), (rows, ))
+    with contextlib.ExitStack() as stack:
+        y = _dev(stack, shape[0] * shape[1] * np.dtype(dtype).itemsize)
+        rep = [_dev(stack, rows * 24) if wanted else None for wanted in reports]
+        dzi = _dev(stack, rows * D * 8) if zi is not None else None
+        dzf = _dev(stack, rows * D * 8) if return_zf else None
+        dini = _dev(stack, rows * 8) if ini is not None and ini.any() else None
+        if zi is not None:
+            dzi.upload(np.ascontiguousarray(np.broadcast_to(np.asarray(zi, dtype=np.float64), (rows, state_dim))))
+        if dini is not None:
+            dini.upload(np.ascontiguousarray(ini))
+        ptr = (lambda b: None if b is None else b.ptr)
+        launch(y.ptr, [ptr(r) for r in rep], ptr(dzi), ptr(dzf), ptr(dini))
+        _engine.sync()
+        out = [y.download(shape, dtype)] + [r.download((rows, 3), np.int64) for r in rep if r is not None]
+        if return_zf:
+            out.append(dzf.download((rows, D), np.float64)[:, :state_dim])
+        return out[0] if len(out) == 1 else tuple(out)
 
 
 class SampledFir:
@@ -261,9 +319,7 @@ class SampledIir:
         ptr, stride = _rows.check_rows(
             out, self.n_channels, self.n, _rows.torch_dtype(self.dtype),
             'out must be a (n_channels, >=n) row-contiguous device tensor of the plan dtype')
-        zip_, zfp = (_rows.check_state(z, (self.n_channels, self.state_dim),
-                                       'zi / zf must be contiguous (n_channels, state_dim) float64 device tensors')
-                     for z in (zi, zf))
+        zip_, zfp = _state_ptrs(zi, zf, self.n_channels, self.state_dim, 'n_channels')
         s = torch.cuda.current_stream(out.device).cuda_stream
         for attempt in range(2):
             if self.launch(ptr, stride, zip_, zfp, initial, s):
@@ -272,24 +328,14 @@ class SampledIir:
 
     def to_host(self, initial=0.0, zi=None, return_zf=False):
         """NumPy result (n_channels, n); a look-back timeout (outputs NaN) is retried once in the unfused form"""
-        D = max(self.state_dim, 1)
-        with contextlib.ExitStack() as stack:
-            buf = _dev(stack, max(self.n_channels * self.n, 1) * self.dtype.itemsize)
-            dzi = _dev(stack, self.n_channels * D * 8) if zi is not None else None
-            dzf = _dev(stack, self.n_channels * D * 8) if return_zf else None
-            if zi is not None:
-                z = np.broadcast_to(np.asarray(zi, dtype=np.float64).reshape(-1, self.state_dim)
-                                    if np.ndim(zi) > 1 else np.asarray(zi, dtype=np.float64),
-                                    (self.n_channels, self.state_dim))
-                dzi.upload(np.ascontiguousarray(z))
-            if not _engine.iir_run_checked(
-                    lambda: self.launch(buf.ptr, None, None if dzi is None else dzi.ptr,
-                                        None if dzf is None else dzf.ptr, initial), self.plan.status):
+        if np.ndim(zi) > 1:
+            zi = np.asarray(zi, dtype=np.float64).reshape(-1, self.state_dim)
+
+        def run(out, reports, dzi, dzf, levels):          # (`initial` is one scalar here: an argument, not a buffer)
+            if not _engine.iir_run_checked(lambda: self.launch(out, None, dzi, dzf, initial), self.plan.status):
                 raise _engine.EngineError('IIR chain failed twice')
-            out = buf.download((self.n_channels, self.n), self.dtype)
-            if return_zf:
-                return out, dzf.download((self.n_channels, D), np.float64)[:, :self.state_dim]
-            return out
+        return _host_trip(run, shape=(self.n_channels, self.n), dtype=self.dtype, rows=self.n_channels,
+                          state_dim=self.state_dim, zi=zi, return_zf=return_zf)
 
     def close(self):
         self.plan.close()
@@ -353,9 +399,7 @@ class SampledIirRows:
         ptr, stride = _rows.check_rows(
             out, self.n_channels, self.n, _rows.torch_dtype(self.dtype),
             'out must be a (n_channels, >=n) row-contiguous device tensor of the plan dtype')
-        zip_, zfp = (_rows.check_state(z, (self.n_channels, self.state_dim),
-                                       'zi / zf must be contiguous (n_channels, state_dim) float64 device tensors')
-                     for z in (zi, zf))
+        zip_, zfp = _state_ptrs(zi, zf, self.n_channels, self.state_dim, 'n_channels')
         ini = _initial_rows(self, self.n_channels, initial, out.device)
         self.launch(ptr, stride, zip_, zfp, None if ini is None else ini.data_ptr(),
                     torch.cuda.current_stream(out.device).cuda_stream)
@@ -364,25 +408,9 @@ class SampledIirRows:
     def to_host(self, initial=0.0, zi=None, return_zf=False):
         """NumPy result (n_channels, n) [, zf (n_channels, state_dim)]; initial: a scalar or one value per row;
         zi: (n_channels, state_dim)"""
-        D = max(self.state_dim, 1)
-        ini = np.broadcast_to(np.asarray(initial, dtype=np.float64), (self.n_channels, ))
-        with contextlib.ExitStack() as stack:
-            buf = _dev(stack, max(self.n_channels * self.n, 1) * self.dtype.itemsize)
-            dzi = _dev(stack, self.n_channels * D * 8) if zi is not None else None
-            dzf = _dev(stack, self.n_channels * D * 8) if return_zf else None
-            dini = _dev(stack, self.n_channels * 8) if ini.any() else None
-            if zi is not None:
-                dzi.upload(np.ascontiguousarray(np.broadcast_to(np.asarray(zi, dtype=np.float64),
-                                                                (self.n_channels, self.state_dim))))
-            if dini is not None:
-                dini.upload(np.ascontiguousarray(ini))
-            self.launch(buf.ptr, None, None if dzi is None else dzi.ptr, None if dzf is None else dzf.ptr,
-                        None if dini is None else dini.ptr)
-            _engine.sync()
-            out = buf.download((self.n_channels, self.n), self.dtype)
-            if return_zf:
-                return out, dzf.download((self.n_channels, D), np.float64)[:, :self.state_dim]
-            return out
+        return _host_trip(lambda out, reports, dzi, dzf, levels: self.launch(out, None, dzi, dzf, levels),
+                          shape=(self.n_channels, self.n), dtype=self.dtype, rows=self.n_channels,
+                          state_dim=self.state_dim, zi=zi, return_zf=return_zf, initial=initial)
 
     def close(self):
         self.plan.close()
@@ -1005,6 +1033,102 @@ def _per_row(name, what, value, batch):
     return value
 
 
+def _per_row_flat(name, what, v, batch):
+    """`_per_row` for a stage's numbers: an array of any shape counts as its entries in order, a 0-d one as a scalar"""
+    return _per_row(name, what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v, batch)
+
+
+def _gain_offset_rows(who, gain, offset, rows):
+    """the converter's per-row arguments: each a scalar (every row) or one value per row -> (gains, offsets), lists"""
+    return _per_row_flat(who, 'gain', gain, rows), _per_row_flat(who, 'offset', offset, rows)
+
+
+def _given_rows(gain, offset):
+    """the number of rows that a gain or an offset given per row speaks of; 1 where both are scalars"""
+    return max(np.size(gain) if np.ndim(gain) > 0 else 1, np.size(offset) if np.ndim(offset) > 0 else 1)
+
+
+def _full_scale_gain(who, full_scale, kw):
+    """the gain of a `from_full_scale`, hi / full scale, with `bits` as the constructor's keywords `kw` have it (16
+    without); ValueError: bits outside [2, 16], a full scale that is not finite or not positive"""
+    bits = int(kw.get('bits', 16))
+    if not 2 <= bits <= 16:
+        raise ValueError('bits must lie in [2, 16]')
+    fs = np.asarray(full_scale, dtype=np.float64)
+    if not np.all(np.isfinite(fs) & (fs > 0.0)):
+        raise ValueError(f'{who}: every full scale must be finite and positive')
+    return (2**(bits - 1) - 1) / fs
+
+
+def _check_reports(stage, name, rows_name, rows, sides, counts=None, beyond=None, zi=None, zf=None, state_dim=0):
+    """What goes with the int16 codes of an `apply_torch` / `launch_torch`, once x and the codes have passed
+    `_rows.check_rows` in that order: `sides` are the two, (x, codes) or (codes, ) for a sampled chain, as
+    `_rows.rows_disjoint` takes them.  counts / beyond: None or contiguous (rows, 3) int64 device tensors; zi / zf: None
+    or (rows, state_dim) float64.  Tensor metadata only, texts ready made: nothing is built, formatted or read from
+    the device unless a refusal is raised, and those come in ONE order: counts, beyond, zi / zf, the codes over x,
+    counts over x / codes, beyond over x / codes, beyond over counts.  `stage`: the short name the overlap texts
+    begin with; `name`: what they call the codes; `rows_name`: what the other texts call the rows.
+    -> (counts pointer, beyond pointer, zi pointer, zf pointer), None for what is not there"""
+    counts_text, beyond_text, _ = _FRONT_TEXTS[rows_name]
+    c0 = _rows.check_state(counts, (rows, 3), counts_text, dtype=np.int64)
+    b0 = _rows.check_state(beyond, (rows, 3), beyond_text, dtype=np.int64)
+    zip_, zfp = _state_ptrs(zi, zf, rows, state_dim, rows_name)
+    if len(sides) == 2 and not _rows.rows_disjoint(*sides):
+        raise ValueError(f'{stage} is out of place: {name} overlaps x')
+    if not _rows.report_disjoint(c0, rows, 3, *sides):
+        raise ValueError(f'{stage}: counts overlaps {"x / " * (len(sides) == 2)}{name}')
+    if b0 is not None:
+        if not _rows.report_disjoint(b0, rows, 3, *sides):
+            raise ValueError(f'{stage}: beyond overlaps {"x / " * (len(sides) == 2)}{name}')
+        if c0 is not None and not _rows.report_disjoint(b0, rows, 3, (c0, 3, rows, 3, 8)):
+            raise ValueError(f'{stage}: beyond overlaps counts')
+    return c0, b0, zip_, zfp
+
+
+class _LentScratch:
+    """For the sampled chains whose unfused path runs through float64 rows (`fused`, `n_channels`, `n`, `plan`): the
+    rows are taken once, by the constructor, lent to every launch, and freed with the plan."""
+
+    def _take_scratch(self):
+        self._scratch = None if self.fused else _engine.DeviceBuffer(max(self.n_channels * self.n, 1) * 8)
+
+    def close(self):
+        self.plan.close()
+        if self._scratch is not None:
+            self._scratch.close()
+            self._scratch = None
+
+
+def _one_shot(sig2, plan, apply, shape, dtype, report_rows, reports, return_counts, initial=None):
+    """The round trip of a NumPy one-shot wrapper whose arguments have passed: `plan()` opens the plan, the rows
+    `sig2` go up, `apply(plan, x, y, [report pointers], levels)` launches on pointers -- y the result of `shape` and
+    `dtype` (None: in place, y is x), the report pointers those of `reports` (report_rows, 3) int64 reports (None
+    each unless `return_counts`), levels the (rows,) float64 `initial` or None where all are zero -- then one
+    synchronise and the downloads.  Rows of no samples are answered with zeros, without a device.
+    -> the result, or (result, the reports in order) with `return_counts`"""
+    in_place = shape is None
+    if in_place:
+        shape, dtype = sig2.shape, sig2.dtype
+    if sig2.shape[1] == 0:
+        out = [np.zeros(shape, dtype=dtype)] + [np.zeros((report_rows, 3), dtype=np.int64) for _ in range(reports)]
+        return tuple(out) if return_counts else out[0]
+    with contextlib.ExitStack() as stack:
+        plan = stack.enter_context(plan())
+        x = _dev(stack, sig2.nbytes)
+        y = x if in_place else _dev(stack, shape[0] * shape[1] * np.dtype(dtype).itemsize)
+        rep = [_dev(stack, report_rows * 24) for _ in range(reports if return_counts else 0)]
+        x.upload(sig2)
+        levels = None
+        if initial is not None and initial.any():
+            lv = _dev(stack, initial.nbytes)
+            lv.upload(np.ascontiguousarray(initial))
+            levels = lv.ptr
+        apply(plan, x.ptr, y.ptr, [r.ptr for r in rep] or [None] * reports, levels)
+        _engine.sync()
+        out = [y.download(shape, dtype)] + [r.download((report_rows, 3), np.int64) for r in rep]
+        return tuple(out) if return_counts else out[0]
+
+
 def _reflection_rows_terms(name, kind, batch, A_rows, tau_rows):
     """term lists of reflection_rows / correct_reflection_rows: A and tau each a scalar, or one entry per row, an entry
     a scalar or a sequence (several reflections on that row); within a row a scalar goes with every entry of the
@@ -1308,8 +1432,7 @@ class DacStage:
         batch = int(batch)
         if batch < 1:
             raise ValueError('DacStage: no rows')
-        gains, offsets = (_per_row('DacStage', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v, batch)
-                          for what, v in (('gain', gain), ('offset', offset)))
+        gains, offsets = _gain_offset_rows('DacStage', gain, offset, batch)
         self.plan = _engine.DacRowsPlan(gains, offsets, n, bits, shift, interleave, dtype)
         p = self.plan
         self.n, self.batch, self.dtype, self.gain, self.offset = p.n, p.batch, p.dtype, p.gain, p.offset
@@ -1320,13 +1443,7 @@ class DacStage:
     def from_full_scale(cls, full_scale_rows, n: int, **kw):
         """the stage whose gain[r] = hi / full_scale_rows[r], so that +-full scale maps to +-hi (a scalar: every row;
         give `batch`).  ValueError: a full scale that is not finite or not positive."""
-        bits = int(kw.get('bits', 16))
-        if not 2 <= bits <= 16:
-            raise ValueError('bits must lie in [2, 16]')
-        fs = np.asarray(full_scale_rows, dtype=np.float64)
-        if not np.all(np.isfinite(fs) & (fs > 0.0)):
-            raise ValueError('DacStage: every full scale must be finite and positive')
-        return cls((2**(bits - 1) - 1) / fs, n, **kw)
+        return cls(_full_scale_gain('DacStage', full_scale_rows, kw), n, **kw)
 
     def apply(self, in_ptr, in_stride, out_ptr, out_stride, counts_ptr=None, stream=0):
         self.plan.apply(in_ptr, in_stride, out_ptr, out_stride, counts_ptr, stream)
@@ -1346,13 +1463,8 @@ class DacStage:
             out = torch.empty((self.out_rows, self.out_n), dtype=torch.int16, device=x.device)
         y0, ys = _rows.check_rows(out, self.out_rows, self.out_n, torch.int16,
                                   'expected out: (out_rows, >=out_n) row-contiguous int16 device tensor')
-        c0 = _rows.check_state(counts, (self.batch, 3), 'expected counts: contiguous (batch, 3) int64 device tensor',
-                               dtype=np.int64)
-        xr, yr = (x0, xs, self.batch, self.n, self.dtype.itemsize), (y0, ys, self.out_rows, self.out_n, 2)
-        if not _rows.rows_disjoint(xr, yr):
-            raise ValueError('dac stage is out of place: out overlaps x')
-        if not _rows.report_disjoint(c0, self.batch, 3, xr, yr):
-            raise ValueError('dac stage: counts overlaps x / out')
+        sides = (x0, xs, self.batch, self.n, self.dtype.itemsize), (y0, ys, self.out_rows, self.out_n, 2)
+        c0 = _check_reports('dac stage', 'out', 'batch', self.batch, sides, counts)[0]
         self.apply(x0, xs, y0, ys, c0, torch.cuda.current_stream(x.device).cuda_stream)
         return out[:, :self.out_n]
 
@@ -1372,16 +1484,10 @@ def dac_codes_rows(sig, gain, offset=0.0, bits=16, shift=0, interleave=1, return
     gains = _per_row('dac_codes_rows', 'gain', gain, batch)
     offsets = _per_row('dac_codes_rows', 'offset', offset, batch)
     g, o, n, bits, shift, k, dtype = _engine.dac_rows_arguments(gains, offsets, n, bits, shift, interleave, sig2.dtype)
-    if n == 0:
-        codes, counts = np.zeros((batch // k, 0), dtype=np.int16), np.zeros((batch, 3), dtype=np.int64)
-        return (codes, counts) if return_counts else codes
-    with _engine.DacRowsPlan(g, o, n, bits, shift, k, dtype) as plan, _engine.DeviceBuffer(sig2.nbytes) as x, \
-            _engine.DeviceBuffer(batch * n * 2) as y, _engine.DeviceBuffer(batch * 24) as c:
-        x.upload(sig2)
-        plan.apply(x.ptr, n, y.ptr, k * n, c.ptr if return_counts else None)
-        _engine.sync()
-        codes = y.download((batch // k, k * n), np.int16)
-        return (codes, c.download((batch, 3), np.int64)) if return_counts else codes
+    return _one_shot(sig2, lambda: _engine.DacRowsPlan(g, o, n, bits, shift, k, dtype),
+                     lambda plan, x, y, reports, levels: plan.apply(x, n, y, k * n, reports[0]),
+                     shape=(batch // k, k * n), dtype=np.int16, report_rows=batch, reports=1,
+                     return_counts=return_counts)
 
 
 class MixDacStage:
@@ -1405,9 +1511,8 @@ class MixDacStage:
     def __init__(self, matrix, n: int, gain, mix_offset=None, dac_offset=0.0, bits: int = 16, shift: int = 0,
                  interleave: int = 1, dtype=np.float64):
         rows_out = _engine._mix_rows_csr(matrix)[0]
-        gains, offsets = (_per_row('MixDacStage', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v,
-                                   rows_out) if rows_out >= 1 else [0.0]
-                          for what, v in (('gain', gain), ('offset', dac_offset)))
+        gains, offsets = (_gain_offset_rows('MixDacStage', gain, dac_offset, rows_out) if rows_out >= 1
+                          else ([0.0], [0.0]))
         self.plan = _engine.MixDacPlan(matrix, mix_offset, gains, offsets, n, bits, shift, interleave, dtype)
         p = self.plan
         self.n, self.dtype, self.mix_offset, self.gain, self.offset = p.n, p.dtype, p.mix_offset, p.gain, p.dac_offset
@@ -1425,13 +1530,7 @@ class MixDacStage:
     def from_full_scale(cls, matrix, n: int, full_scale, **kw):
         """the stage whose gain[o] = hi / full_scale[o], so that a mixed +-full scale maps to +-hi (a scalar: every
         row).  ValueError: a full scale that is not finite or not positive."""
-        bits = int(kw.get('bits', 16))
-        if not 2 <= bits <= 16:
-            raise ValueError('bits must lie in [2, 16]')
-        fs = np.asarray(full_scale, dtype=np.float64)
-        if not np.all(np.isfinite(fs) & (fs > 0.0)):
-            raise ValueError('MixDacStage: every full scale must be finite and positive')
-        return cls(matrix, n, (2**(bits - 1) - 1) / fs, **kw)
+        return cls(matrix, n, _full_scale_gain('MixDacStage', full_scale, kw), **kw)
 
     def apply(self, in_ptr, in_stride, out_ptr, out_stride, counts_ptr=None, stream=0):
         self.plan.apply(in_ptr, in_stride, out_ptr, out_stride, counts_ptr, stream)
@@ -1451,13 +1550,8 @@ class MixDacStage:
             out = torch.empty((self.out_rows, self.out_n), dtype=torch.int16, device=x.device)
         y0, ys = _rows.check_rows(out, self.out_rows, self.out_n, torch.int16,
                                   'expected out: (out_rows, >=out_n) row-contiguous int16 device tensor')
-        c0 = _rows.check_state(counts, (self.rows_out, 3),
-                               'expected counts: contiguous (rows_out, 3) int64 device tensor', dtype=np.int64)
-        xr, yr = (x0, xs, self.rows_in, self.n, self.dtype.itemsize), (y0, ys, self.out_rows, self.out_n, 2)
-        if not _rows.rows_disjoint(xr, yr):
-            raise ValueError('mix dac stage is out of place: out overlaps x')
-        if not _rows.report_disjoint(c0, self.rows_out, 3, xr, yr):
-            raise ValueError('mix dac stage: counts overlaps x / out')
+        sides = (x0, xs, self.rows_in, self.n, self.dtype.itemsize), (y0, ys, self.out_rows, self.out_n, 2)
+        c0 = _check_reports('mix dac stage', 'out', 'rows_out', self.rows_out, sides, counts)[0]
         self.apply(x0, xs, y0, ys, c0, torch.cuda.current_stream(x.device).cuda_stream)
         return out[:, :self.out_n]
 
@@ -1481,17 +1575,10 @@ def mix_dac_rows(sig, matrix, gain, mix_offset=None, dac_offset=0.0, bits=16, sh
     if rows_in != batch:
         raise ValueError(f'mix_dac_rows: a matrix of {rows_in} columns for {batch} rows')
     k = int(interleave)
-    if n == 0:
-        codes, counts = np.zeros((rows_out // k, 0), dtype=np.int16), np.zeros((rows_out, 3), dtype=np.int64)
-        return (codes, counts) if return_counts else codes
-    with _engine.MixDacPlan(matrix, mix_offset, gains, offsets, n, bits, shift, k, sig2.dtype) as plan, \
-            _engine.DeviceBuffer(sig2.nbytes) as x, _engine.DeviceBuffer(rows_out * n * 2) as y, \
-            _engine.DeviceBuffer(rows_out * 24) as c:
-        x.upload(sig2)
-        plan.apply(x.ptr, n, y.ptr, k * n, c.ptr if return_counts else None)
-        _engine.sync()
-        codes = y.download((rows_out // k, k * n), np.int16)
-        return (codes, c.download((rows_out, 3), np.int64)) if return_counts else codes
+    return _one_shot(sig2, lambda: _engine.MixDacPlan(matrix, mix_offset, gains, offsets, n, bits, shift, k, sig2.dtype),
+                     lambda plan, x, y, reports, levels: plan.apply(x, n, y, k * n, reports[0]),
+                     shape=(rows_out // k, k * n), dtype=np.int16, report_rows=rows_out, reports=1,
+                     return_counts=return_counts)
 
 
 class IirDacStage:
@@ -1517,24 +1604,10 @@ class IirDacStage:
         if interleave != 1:
             raise NotImplementedError('IirDacStage has no interleave: a workgroup owns one row; run IirStage and then '
                                       'DacStage(interleave=2) for a pair')
-        depth = _nesting(sections_rows)
-        if depth == 2:                                             # an SOS matrix
-            sec = np.asarray(sections_rows, dtype=np.float64)
-            if sec.ndim != 2 or sec.shape[1] != 6:
-                raise ValueError('IirDacStage: an SOS matrix has shape (n_sections, 6)')
-            sections_rows, depth = _engine.sos_sections(sec), 3
-        if depth not in (3, 4):
-            raise ValueError('IirDacStage: sections is one [(b, a), ...] per row, one [(b, a), ...], or an SOS matrix')
-        if depth == 3:                                             # one cascade: every row gets it
-            if batch is None:
-                batch = max(np.size(gain) if np.ndim(gain) > 0 else 1, np.size(offset) if np.ndim(offset) > 0 else 1)
-            sections_rows = [list(sections_rows)] * int(batch)
-        sections_rows = list(sections_rows)
-        rows = len(sections_rows)
-        if rows < 1 or (batch is not None and int(batch) != rows):
-            raise ValueError(f'IirDacStage: {rows} cascades for {batch} rows')
-        gains, offsets = (_per_row('IirDacStage', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v, rows)
-                          for what, v in (('gain', gain), ('offset', offset)))
+        sections_rows, _ = _cascade_rows(
+            'IirDacStage', sections_rows, batch, 'one [(b, a), ...] per row, one [(b, a), ...], or an SOS matrix',
+            one_for=_given_rows(gain, offset))
+        gains, offsets = _gain_offset_rows('IirDacStage', gain, offset, len(sections_rows))
         self.plan = _engine.IirRowsDacPlan(sections_rows, gains, offsets, n, bits, shift, dtype)
         p = self.plan
         self.n, self.batch, self.dtype, self.gain, self.offset = p.n, p.batch, p.dtype, p.gain, p.offset
@@ -1546,13 +1619,7 @@ class IirDacStage:
     def from_full_scale(cls, sections_rows, n: int, full_scale, **kw):
         """the stage whose gain[r] = hi / full_scale[r], so that a filtered +-full scale maps to +-hi (a scalar: every
         row).  ValueError: a full scale that is not finite or not positive."""
-        bits = int(kw.get('bits', 16))
-        if not 2 <= bits <= 16:
-            raise ValueError('bits must lie in [2, 16]')
-        fs = np.asarray(full_scale, dtype=np.float64)
-        if not np.all(np.isfinite(fs) & (fs > 0.0)):
-            raise ValueError('IirDacStage: every full scale must be finite and positive')
-        return cls(sections_rows, n, (2**(bits - 1) - 1) / fs, **kw)
+        return cls(sections_rows, n, _full_scale_gain('IirDacStage', full_scale, kw), **kw)
 
     def kernel_name(self) -> str:
         """'iir_rows_dac<T,NSEC,ORD>'"""
@@ -1580,16 +1647,9 @@ class IirDacStage:
             codes = torch.empty((self.batch, self.n), dtype=torch.int16, device=x.device)
         y0, ys = _rows.check_rows(codes, self.batch, self.n, torch.int16,
                                   'expected codes: (batch, >=n) row-contiguous int16 device tensor')
-        c0 = _rows.check_state(counts, (self.batch, 3), 'expected counts: contiguous (batch, 3) int64 device tensor',
-                               dtype=np.int64)
-        zip_, zfp = (_rows.check_state(z, (self.batch, self.state_dim),
-                                       'zi / zf must be contiguous (batch, state_dim) float64 device tensors')
-                     for z in (zi, zf))
-        xr, yr = (x0, xs, in_rows, self.n, self.dtype.itemsize), (y0, ys, self.batch, self.n, 2)
-        if not _rows.rows_disjoint(xr, yr):
-            raise ValueError('iir dac stage is out of place: codes overlaps x')
-        if not _rows.report_disjoint(c0, self.batch, 3, xr, yr):
-            raise ValueError('iir dac stage: counts overlaps x / codes')
+        sides = (x0, xs, in_rows, self.n, self.dtype.itemsize), (y0, ys, self.batch, self.n, 2)
+        c0, _, zip_, zfp = _check_reports('iir dac stage', 'codes', 'batch', self.batch, sides, counts,
+                                          zi=zi, zf=zf, state_dim=self.state_dim)
         ini = _initial_rows(self, self.batch, initial, x.device)
         inip = None if ini is None else ini.data_ptr()
         stream = torch.cuda.current_stream(x.device).cuda_stream
@@ -1620,26 +1680,14 @@ def iir_dac_rows(sig, filters_rows, gain, offset=0.0, bits=16, shift=0, initial=
     offsets = _per_row('iir_dac_rows', 'offset', offset, batch)
     g, o, n, bits, shift, _, dtype = _engine.dac_rows_arguments(gains, offsets, n, bits, shift, 1, sig2.dtype)
     packed = _engine.pack_sections_rows(filters_rows)
-    ini = np.asarray(initial, dtype=np.float64)
-    if ini.ndim == 0:
-        ini = np.full(batch, float(ini))
-    if ini.shape != (batch, ):
-        raise ValueError('iir_dac_rows: initial is a scalar or one value per row')
-    if n == 0:
-        codes, counts = np.zeros((batch, 0), dtype=np.int16), np.zeros((batch, 3), dtype=np.int64)
-        return (codes, counts) if return_counts else codes
-    with _engine.IirRowsDacPlan(filters_rows, g, o, n, bits, shift, dtype, packed=packed) as plan, \
-            _engine.DeviceBuffer(sig2.nbytes) as x, _engine.DeviceBuffer(batch * n * 2) as y, \
-            _engine.DeviceBuffer(batch * 24) as c, _engine.DeviceBuffer(batch * 8) as lv:
-        x.upload(sig2)
-        lv.upload(np.ascontiguousarray(ini))
-        plan.apply(x.ptr, n, y.ptr, n, c.ptr if return_counts else None, None, None, lv.ptr if ini.any() else None)
-        _engine.sync()
-        codes = y.download((batch, n), np.int16)
-        return (codes, c.download((batch, 3), np.int64)) if return_counts else codes
+    ini = _initial_host(initial, batch, 'iir_dac_rows: initial is a scalar or one value per row')
+    return _one_shot(sig2, lambda: _engine.IirRowsDacPlan(filters_rows, g, o, n, bits, shift, dtype, packed=packed),
+                     lambda plan, x, y, reports, levels: plan.apply(x, n, y, n, reports[0], None, None, levels),
+                     shape=(batch, n), dtype=np.int16, report_rows=batch, reports=1, return_counts=return_counts,
+                     initial=ini)
 
 
-class SampledDac:
+class SampledDac(_LentScratch):
     """`BatchSampler(channels, grid).launch_torch(z)` (float64) followed by `DacStage(gain, n, offset, ...)
     .apply_torch(z)`, device-resident and bit for bit -- codes and counts -- with the float64 rows left out: a
     microwave drive line has no predistortion between its waveform and its converter, so at AWG sample rates the
@@ -1662,8 +1710,7 @@ class SampledDac:
         rows = len(channels) * max(int(tile), 1)
         if rows < 1:
             raise ValueError('SampledDac: no rows')
-        gains, offsets = (_per_row('SampledDac', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v, rows)
-                          for what, v in (('gain', gain), ('offset', offset)))
+        gains, offsets = _gain_offset_rows('SampledDac', gain, offset, rows)
         if not isinstance(grid, _flatten.wfk_grid):
             grid = _flatten.grid_from_desc(grid)
         # argument errors before any device work
@@ -1679,20 +1726,13 @@ class SampledDac:
         self.bits, self.shift, self.interleave = p.bits, p.shift, p.interleave
         self.lo, self.hi, self.out_rows, self.out_n = p.lo, p.hi, p.out_rows, p.out_n
         self.fused, self.why_not = p.fused, p.why_not
-        # the unfused path's float64 rows: taken once, here
-        self._scratch = None if self.fused else _engine.DeviceBuffer(max(self.n_channels * self.n, 1) * 8)
+        self._take_scratch()                                       # the unfused path's float64 rows: taken once, here
 
     @classmethod
     def from_full_scale(cls, channels, grid, full_scale, **kw):
         """the plan whose gain[r] = hi / full_scale[r], so that +-full scale maps to +-hi (a scalar: every row).
         ValueError: a full scale that is not finite or not positive."""
-        bits = int(kw.get('bits', 16))
-        if not 2 <= bits <= 16:
-            raise ValueError('bits must lie in [2, 16]')
-        fs = np.asarray(full_scale, dtype=np.float64)
-        if not np.all(np.isfinite(fs) & (fs > 0.0)):
-            raise ValueError('SampledDac: every full scale must be finite and positive')
-        return cls(channels, grid, (2**(bits - 1) - 1) / fs, **kw)
+        return cls(channels, grid, _full_scale_gain('SampledDac', full_scale, kw), **kw)
 
     def kernel_name(self, counts: bool = False) -> str:
         """'wfk_sample_short_dac<16,FAM,COUNT>' | '<sampler kernels> + dac_rows<double>' (dac_rows_count with counts)"""
@@ -1712,31 +1752,19 @@ class SampledDac:
         import torch
         y0, ys = _rows.check_rows(codes, self.out_rows, self.out_n, torch.int16,
                                   'expected codes: (out_rows, >=out_n) row-contiguous int16 device tensor')
-        c0 = _rows.check_state(counts, (self.n_channels, 3),
-                               'expected counts: contiguous (n_channels, 3) int64 device tensor', dtype=np.int64)
-        if not _rows.report_disjoint(c0, self.n_channels, 3, (y0, ys, self.out_rows, self.out_n, 2)):
-            raise ValueError('sampled dac: counts overlaps codes')
+        c0 = _check_reports('sampled dac', 'codes', 'n_channels', self.n_channels,
+                            ((y0, ys, self.out_rows, self.out_n, 2), ), counts)[0]
         self.launch(y0, ys, c0, torch.cuda.current_stream(codes.device).cuda_stream)
         return codes[:, :self.out_n]
 
     def to_host(self, return_counts=False):
         """NumPy codes (out_rows, out_n) [, counts (n_channels, 3)]"""
-        with contextlib.ExitStack() as stack:
-            y = _dev(stack, self.out_rows * self.out_n * 2)
-            c = _dev(stack, self.n_channels * 24) if return_counts else None
-            self.launch(y.ptr, None, None if c is None else c.ptr)
-            _engine.sync()
-            codes = y.download((self.out_rows, self.out_n), np.int16)
-            return (codes, c.download((self.n_channels, 3), np.int64)) if return_counts else codes
-
-    def close(self):
-        self.plan.close()
-        if self._scratch is not None:
-            self._scratch.close()
-            self._scratch = None
+        return _host_trip(lambda y, reports, dzi, dzf, levels: self.launch(y, None, reports[0]),
+                          shape=(self.out_rows, self.out_n), dtype=np.int16, rows=self.n_channels,
+                          reports=(return_counts, ))
 
 
-class SampledIirDac:
+class SampledIirDac(_LentScratch):
     """`SampledIirRows(channels, grid, filters_rows).launch_torch(z, initial=, zi=, zf=)` (float64) followed by
     `DacStage(gain, n, offset, bits, shift).apply_torch(z, counts=)`, device-resident and bit for bit -- codes, counts
     and zf -- with the float64 rows left out: a whole flux line, waveform, exp-decay correction and converter, in ONE
@@ -1762,8 +1790,7 @@ class SampledIirDac:
             raise ValueError('SampledIirDac: no rows')
         if len(filters_rows) != rows:
             raise ValueError(f'SampledIirDac: {len(filters_rows)} cascades for {rows} rows')
-        gains, offsets = (_per_row('SampledIirDac', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v, rows)
-                          for what, v in (('gain', gain), ('offset', offset)))
+        gains, offsets = _gain_offset_rows('SampledIirDac', gain, offset, rows)
         if not isinstance(grid, _flatten.wfk_grid):
             grid = _flatten.grid_from_desc(grid)
         # argument errors before any device work
@@ -1781,20 +1808,13 @@ class SampledIirDac:
         self.state_dim, self.own_orders, self.section_order = p.state_dim, packed[3], int(packed[0][0])
         self.fused, self.why_not = p.fused, p.why_not
         self._initial_cache = None
-        # the unfused path's float64 rows: taken once, here
-        self._scratch = None if self.fused else _engine.DeviceBuffer(max(self.n_channels * self.n, 1) * 8)
+        self._take_scratch()                                       # the unfused path's float64 rows: taken once, here
 
     @classmethod
     def from_full_scale(cls, channels, grid, filters_rows, full_scale, **kw):
         """the plan whose gain[r] = hi / full_scale[r], so that a filtered +-full scale maps to +-hi (a scalar: every
         row).  ValueError: a full scale that is not finite or not positive."""
-        bits = int(kw.get('bits', 16))
-        if not 2 <= bits <= 16:
-            raise ValueError('bits must lie in [2, 16]')
-        fs = np.asarray(full_scale, dtype=np.float64)
-        if not np.all(np.isfinite(fs) & (fs > 0.0)):
-            raise ValueError('SampledIirDac: every full scale must be finite and positive')
-        return cls(channels, grid, filters_rows, (2**(bits - 1) - 1) / fs, **kw)
+        return cls(channels, grid, filters_rows, _full_scale_gain('SampledIirDac', full_scale, kw), **kw)
 
     def row_state(self, z, r: int):
         """row r's own state (scipy layout, its sections back to back) out of a (n_channels, state_dim) host array"""
@@ -1820,13 +1840,9 @@ class SampledIirDac:
         import torch
         y0, ys = _rows.check_rows(codes, self.n_channels, self.n, torch.int16,
                                   'expected codes: (n_channels, >=n) row-contiguous int16 device tensor')
-        c0 = _rows.check_state(counts, (self.n_channels, 3),
-                               'expected counts: contiguous (n_channels, 3) int64 device tensor', dtype=np.int64)
-        zip_, zfp = (_rows.check_state(z, (self.n_channels, self.state_dim),
-                                       'zi / zf must be contiguous (n_channels, state_dim) float64 device tensors')
-                     for z in (zi, zf))
-        if not _rows.report_disjoint(c0, self.n_channels, 3, (y0, ys, self.n_channels, self.n, 2)):
-            raise ValueError('sampled iir dac: counts overlaps codes')
+        c0, _, zip_, zfp = _check_reports('sampled iir dac', 'codes', 'n_channels', self.n_channels,
+                                          ((y0, ys, self.n_channels, self.n, 2), ), counts,
+                                          zi=zi, zf=zf, state_dim=self.state_dim)
         ini = _initial_rows(self, self.n_channels, initial, codes.device)
         self.launch(y0, ys, c0, zip_, zfp, None if ini is None else ini.data_ptr(),
                     torch.cuda.current_stream(codes.device).cuda_stream)
@@ -1835,34 +1851,10 @@ class SampledIirDac:
     def to_host(self, initial=0.0, zi=None, return_counts=False, return_zf=False):
         """NumPy codes (n_channels, n) [, counts (n_channels, 3)] [, zf (n_channels, state_dim)]; initial: a scalar or
         one value per row; zi: (n_channels, state_dim)"""
-        D = max(self.state_dim, 1)
-        ini = np.broadcast_to(np.asarray(initial, dtype=np.float64), (self.n_channels, ))
-        with contextlib.ExitStack() as stack:
-            y = _dev(stack, self.n_channels * self.n * 2)
-            c = _dev(stack, self.n_channels * 24) if return_counts else None
-            dzi = _dev(stack, self.n_channels * D * 8) if zi is not None else None
-            dzf = _dev(stack, self.n_channels * D * 8) if return_zf else None
-            dini = _dev(stack, self.n_channels * 8) if ini.any() else None
-            if zi is not None:
-                dzi.upload(np.ascontiguousarray(np.broadcast_to(np.asarray(zi, dtype=np.float64),
-                                                                (self.n_channels, self.state_dim))))
-            if dini is not None:
-                dini.upload(np.ascontiguousarray(ini))
-            self.launch(y.ptr, None, None if c is None else c.ptr, None if dzi is None else dzi.ptr,
-                        None if dzf is None else dzf.ptr, None if dini is None else dini.ptr)
-            _engine.sync()
-            out = [y.download((self.n_channels, self.n), np.int16)]
-            if return_counts:
-                out.append(c.download((self.n_channels, 3), np.int64))
-            if return_zf:
-                out.append(dzf.download((self.n_channels, D), np.float64)[:, :self.state_dim])
-            return out[0] if len(out) == 1 else tuple(out)
-
-    def close(self):
-        self.plan.close()
-        if self._scratch is not None:
-            self._scratch.close()
-            self._scratch = None
+        return _host_trip(lambda y, reports, dzi, dzf, levels: self.launch(y, None, reports[0], dzi, dzf, levels),
+                          shape=(self.n_channels, self.n), dtype=np.int16, rows=self.n_channels,
+                          reports=(return_counts, ), state_dim=self.state_dim, zi=zi, return_zf=return_zf,
+                          initial=initial)
 
 
 class CurveStage:
@@ -1958,16 +1950,9 @@ def interp_rows(sig, xp_rows, fp_rows, left=None, right=None, return_counts=Fals
     sig2 = _rows_signal_f32('interp_rows', sig)
     batch, n = sig2.shape
     _engine.curve_rows_arguments(xp_rows, fp_rows, left, right, batch, n, sig2.dtype)   # every refusal comes first
-    if n == 0:
-        y, counts = np.zeros((batch, 0), dtype=sig2.dtype), np.zeros((batch, 3), dtype=np.int64)
-        return (y, counts) if return_counts else y
-    with _engine.CurveRowsPlan(xp_rows, fp_rows, n, batch, left, right, sig2.dtype) as plan, \
-            _engine.DeviceBuffer(sig2.nbytes) as x, _engine.DeviceBuffer(batch * 24) as c:
-        x.upload(sig2)
-        plan.apply(x.ptr, n, x.ptr, n, c.ptr if return_counts else None)          # in place
-        _engine.sync()
-        y = x.download(sig2.shape, sig2.dtype)
-        return (y, c.download((batch, 3), np.int64)) if return_counts else y
+    return _one_shot(sig2, lambda: _engine.CurveRowsPlan(xp_rows, fp_rows, n, batch, left, right, sig2.dtype),
+                     lambda plan, x, y, reports, levels: plan.apply(x, n, y, n, reports[0]),
+                     shape=None, dtype=None, report_rows=batch, reports=1, return_counts=return_counts)   # in place
 
 
 class CurveIirDacStage:
@@ -2001,26 +1986,13 @@ class CurveIirDacStage:
                                       'IirStage and then DacStage(interleave=2) for a pair')
         xs = _engine._curve_rows_list('xp', xp_rows)
         if batch is None:
-            batch = max(len(xs), np.size(gain) if np.ndim(gain) > 0 else 1, np.size(offset) if np.ndim(offset) > 0 else 1)
+            batch = max(len(xs), _given_rows(gain, offset))
         curve = _engine.curve_rows_arguments(xp_rows, fp_rows, left, right, batch, n, dtype)   # the curve's rules first
         rows = len(curve[0]) - 1
-        gains, offsets = (_per_row('CurveIirDacStage', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v,
-                                   rows) for what, v in (('gain', gain), ('offset', offset)))
+        gains, offsets = _gain_offset_rows('CurveIirDacStage', gain, offset, rows)
         _engine.dac_rows_arguments(gains, offsets, n, bits, shift, 1, dtype)                    # then the converter's
-        depth = _nesting(sections_rows)
-        if depth == 2:                                             # an SOS matrix
-            sec = np.asarray(sections_rows, dtype=np.float64)
-            if sec.ndim != 2 or sec.shape[1] != 6:
-                raise ValueError('CurveIirDacStage: an SOS matrix has shape (n_sections, 6)')
-            sections_rows, depth = _engine.sos_sections(sec), 3
-        if depth not in (3, 4):
-            raise ValueError('CurveIirDacStage: sections is one [(b, a), ...] per row, one [(b, a), ...], or an SOS '
-                             'matrix')
-        if depth == 3:                                             # one cascade: every row gets it
-            sections_rows = [list(sections_rows)] * rows
-        sections_rows = list(sections_rows)
-        if len(sections_rows) != rows:
-            raise ValueError(f'CurveIirDacStage: {len(sections_rows)} cascades for {rows} rows')
+        sections_rows, _ = _cascade_rows('CurveIirDacStage', sections_rows, rows,
+                                         'one [(b, a), ...] per row, one [(b, a), ...], or an SOS matrix')
         self.plan = _engine.CurveIirDacPlan(xp_rows, fp_rows, sections_rows, gains, offsets, n, bits, shift, left, right,
                                             rows, dtype)
         p = self.plan
@@ -2034,13 +2006,7 @@ class CurveIirDacStage:
     def from_full_scale(cls, xp_rows, fp_rows, sections_rows, n: int, full_scale, **kw):
         """the stage whose gain[r] = hi / full_scale[r], so that a filtered +-full scale (volts) maps to +-hi (a scalar:
         every row).  ValueError: a full scale that is not finite or not positive."""
-        bits = int(kw.get('bits', 16))
-        if not 2 <= bits <= 16:
-            raise ValueError('bits must lie in [2, 16]')
-        fs = np.asarray(full_scale, dtype=np.float64)
-        if not np.all(np.isfinite(fs) & (fs > 0.0)):
-            raise ValueError('CurveIirDacStage: every full scale must be finite and positive')
-        return cls(xp_rows, fp_rows, sections_rows, n, (2**(bits - 1) - 1) / fs, **kw)
+        return cls(xp_rows, fp_rows, sections_rows, n, _full_scale_gain('CurveIirDacStage', full_scale, kw), **kw)
 
     def kernel_name(self) -> str:
         """'iir_rows_curve_dac<T,NSEC,ORD>'"""
@@ -2071,22 +2037,9 @@ class CurveIirDacStage:
             codes = torch.empty((self.batch, self.n), dtype=torch.int16, device=x.device)
         y0, ys = _rows.check_rows(codes, self.batch, self.n, torch.int16,
                                   'expected codes: (batch, >=n) row-contiguous int16 device tensor')
-        c0 = _rows.check_state(counts, (self.batch, 3), 'expected counts: contiguous (batch, 3) int64 device tensor',
-                               dtype=np.int64)
-        b0 = _rows.check_state(beyond, (self.batch, 3), 'expected beyond: contiguous (batch, 3) int64 device tensor',
-                               dtype=np.int64)
-        zip_, zfp = (_rows.check_state(z, (self.batch, self.state_dim),
-                                       'zi / zf must be contiguous (batch, state_dim) float64 device tensors')
-                     for z in (zi, zf))
-        xr, yr = (x0, xs, in_rows, self.n, self.dtype.itemsize), (y0, ys, self.batch, self.n, 2)
-        if not _rows.rows_disjoint(xr, yr):
-            raise ValueError('curve iir dac stage is out of place: codes overlaps x')
-        if not _rows.report_disjoint(c0, self.batch, 3, xr, yr):
-            raise ValueError('curve iir dac stage: counts overlaps x / codes')
-        if not _rows.report_disjoint(b0, self.batch, 3, xr, yr):
-            raise ValueError('curve iir dac stage: beyond overlaps x / codes')
-        if c0 is not None and b0 is not None and abs(c0 - b0) < self.batch * 24:
-            raise ValueError('curve iir dac stage: beyond overlaps counts')
+        sides = (x0, xs, in_rows, self.n, self.dtype.itemsize), (y0, ys, self.batch, self.n, 2)
+        c0, b0, zip_, zfp = _check_reports('curve iir dac stage', 'codes', 'batch', self.batch, sides, counts, beyond,
+                                           zi, zf, self.state_dim)
         ini = _initial_rows(self, self.batch, initial, x.device)
         inip = None if ini is None else ini.data_ptr()
         stream = torch.cuda.current_stream(x.device).cuda_stream
@@ -2119,31 +2072,15 @@ def curve_iir_dac_rows(sig, xp_rows, fp_rows, filters_rows, gain, offset=0.0, bi
     if len(filters_rows) != batch:
         raise ValueError(f'curve_iir_dac_rows: {len(filters_rows)} filter lists for {batch} rows')
     packed = _engine.pack_sections_rows(filters_rows)
-    ini = np.asarray(initial, dtype=np.float64)
-    if ini.ndim == 0:
-        ini = np.full(batch, float(ini))
-    if ini.shape != (batch, ):
-        raise ValueError('curve_iir_dac_rows: initial is a scalar or one value per row')
-    if n == 0:
-        codes, zero = np.zeros((batch, 0), dtype=np.int16), np.zeros((batch, 3), dtype=np.int64)
-        return (codes, zero, zero.copy()) if return_counts else codes
-    with _engine.CurveIirDacPlan(xp_rows, fp_rows, filters_rows, gains, offsets, n, bits, shift, left, right, batch,
-                                 sig2.dtype, packed=packed) as plan, \
-            _engine.DeviceBuffer(sig2.nbytes) as x, _engine.DeviceBuffer(batch * n * 2) as y, \
-            _engine.DeviceBuffer(batch * 24) as c, _engine.DeviceBuffer(batch * 24) as b, \
-            _engine.DeviceBuffer(batch * 8) as lv:
-        x.upload(sig2)
-        lv.upload(np.ascontiguousarray(ini))
-        plan.apply(x.ptr, n, y.ptr, n, c.ptr if return_counts else None, b.ptr if return_counts else None, None, None,
-                   lv.ptr if ini.any() else None)
-        _engine.sync()
-        codes = y.download((batch, n), np.int16)
-        if not return_counts:
-            return codes
-        return codes, c.download((batch, 3), np.int64), b.download((batch, 3), np.int64)
+    ini = _initial_host(initial, batch, 'curve_iir_dac_rows: initial is a scalar or one value per row')
+    return _one_shot(
+        sig2, lambda: _engine.CurveIirDacPlan(xp_rows, fp_rows, filters_rows, gains, offsets, n, bits, shift, left, right,
+                                              batch, sig2.dtype, packed=packed),
+        lambda plan, x, y, reports, levels: plan.apply(x, n, y, n, reports[0], reports[1], None, None, levels),
+        shape=(batch, n), dtype=np.int16, report_rows=batch, reports=2, return_counts=return_counts, initial=ini)
 
 
-class SampledCurveIirDac:
+class SampledCurveIirDac(_LentScratch):
     """`BatchSampler(channels, grid)` (float64 rows), `CurveStage(xp_rows, fp_rows, n, left=, right=)` in place and
     `IirDacStage(filters_rows, n, gain, offset, bits, shift)`, device-resident and bit for bit -- codes, both reports
     and zf -- with the float64 rows left out: a whole flux line programmed in its physical unit -- waveform, measured
@@ -2176,8 +2113,7 @@ class SampledCurveIirDac:
             grid = _flatten.grid_from_desc(grid)
         # argument errors before any device work: the curve's, the converter's, the cascades'
         _engine.curve_rows_arguments(xp_rows, fp_rows, left, right, rows, int(grid.n), np.float64)
-        gains, offsets = (_per_row('SampledCurveIirDac', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v,
-                                   rows) for what, v in (('gain', gain), ('offset', offset)))
+        gains, offsets = _gain_offset_rows('SampledCurveIirDac', gain, offset, rows)
         _engine.dac_rows_arguments(gains, offsets, int(grid.n), bits, shift, 1)
         if len(filters_rows) != rows:
             raise ValueError(f'SampledCurveIirDac: {len(filters_rows)} cascades for {rows} rows')
@@ -2196,20 +2132,14 @@ class SampledCurveIirDac:
         self.state_dim, self.own_orders, self.section_order = p.state_dim, packed[3], int(packed[0][0])
         self.fused, self.why_not = p.fused, p.why_not
         self._initial_cache = None
-        # the unfused path's float64 rows: taken once, here
-        self._scratch = None if self.fused else _engine.DeviceBuffer(max(self.n_channels * self.n, 1) * 8)
+        self._take_scratch()                                       # the unfused path's float64 rows: taken once, here
 
     @classmethod
     def from_full_scale(cls, channels, grid, xp_rows, fp_rows, filters_rows, full_scale, **kw):
         """the plan whose gain[r] = hi / full_scale[r], so that a filtered +-full scale (volts) maps to +-hi (a scalar:
         every row).  ValueError: a full scale that is not finite or not positive."""
-        bits = int(kw.get('bits', 16))
-        if not 2 <= bits <= 16:
-            raise ValueError('bits must lie in [2, 16]')
-        fs = np.asarray(full_scale, dtype=np.float64)
-        if not np.all(np.isfinite(fs) & (fs > 0.0)):
-            raise ValueError('SampledCurveIirDac: every full scale must be finite and positive')
-        return cls(channels, grid, xp_rows, fp_rows, filters_rows, (2**(bits - 1) - 1) / fs, **kw)
+        return cls(channels, grid, xp_rows, fp_rows, filters_rows,
+                   _full_scale_gain('SampledCurveIirDac', full_scale, kw), **kw)
 
     def row_state(self, z, r: int):
         """row r's own state (scipy layout, its sections back to back) out of a (n_channels, state_dim) host array"""
@@ -2237,20 +2167,9 @@ class SampledCurveIirDac:
         import torch
         y0, ys = _rows.check_rows(codes, self.n_channels, self.n, torch.int16,
                                   'expected codes: (n_channels, >=n) row-contiguous int16 device tensor')
-        c0 = _rows.check_state(counts, (self.n_channels, 3),
-                               'expected counts: contiguous (n_channels, 3) int64 device tensor', dtype=np.int64)
-        b0 = _rows.check_state(beyond, (self.n_channels, 3),
-                               'expected beyond: contiguous (n_channels, 3) int64 device tensor', dtype=np.int64)
-        zip_, zfp = (_rows.check_state(z, (self.n_channels, self.state_dim),
-                                       'zi / zf must be contiguous (n_channels, state_dim) float64 device tensors')
-                     for z in (zi, zf))
-        yr = (y0, ys, self.n_channels, self.n, 2)
-        if not _rows.report_disjoint(c0, self.n_channels, 3, yr):
-            raise ValueError('sampled curve iir dac: counts overlaps codes')
-        if not _rows.report_disjoint(b0, self.n_channels, 3, yr):
-            raise ValueError('sampled curve iir dac: beyond overlaps codes')
-        if c0 is not None and b0 is not None and abs(c0 - b0) < self.n_channels * 24:
-            raise ValueError('sampled curve iir dac: beyond overlaps counts')
+        c0, b0, zip_, zfp = _check_reports('sampled curve iir dac', 'codes', 'n_channels', self.n_channels,
+                                           ((y0, ys, self.n_channels, self.n, 2), ), counts, beyond,
+                                           zi, zf, self.state_dim)
         ini = _initial_rows(self, self.n_channels, initial, codes.device)
         self.launch(y0, ys, c0, b0, zip_, zfp, None if ini is None else ini.data_ptr(),
                     torch.cuda.current_stream(codes.device).cuda_stream)
@@ -2259,38 +2178,10 @@ class SampledCurveIirDac:
     def to_host(self, initial=0.0, zi=None, return_counts=False, return_beyond=False, return_zf=False):
         """NumPy codes (n_channels, n) [, counts (n_channels, 3)] [, beyond (n_channels, 3)] [, zf (n_channels,
         state_dim)]; initial: a scalar or one value per row; zi: (n_channels, state_dim)"""
-        D = max(self.state_dim, 1)
-        ini = np.broadcast_to(np.asarray(initial, dtype=np.float64), (self.n_channels, ))
-        with contextlib.ExitStack() as stack:
-            y = _dev(stack, self.n_channels * self.n * 2)
-            c = _dev(stack, self.n_channels * 24) if return_counts else None
-            b = _dev(stack, self.n_channels * 24) if return_beyond else None
-            dzi = _dev(stack, self.n_channels * D * 8) if zi is not None else None
-            dzf = _dev(stack, self.n_channels * D * 8) if return_zf else None
-            dini = _dev(stack, self.n_channels * 8) if ini.any() else None
-            if zi is not None:
-                dzi.upload(np.ascontiguousarray(np.broadcast_to(np.asarray(zi, dtype=np.float64),
-                                                                (self.n_channels, self.state_dim))))
-            if dini is not None:
-                dini.upload(np.ascontiguousarray(ini))
-            self.launch(y.ptr, None, None if c is None else c.ptr, None if b is None else b.ptr,
-                        None if dzi is None else dzi.ptr, None if dzf is None else dzf.ptr,
-                        None if dini is None else dini.ptr)
-            _engine.sync()
-            out = [y.download((self.n_channels, self.n), np.int16)]
-            if return_counts:
-                out.append(c.download((self.n_channels, 3), np.int64))
-            if return_beyond:
-                out.append(b.download((self.n_channels, 3), np.int64))
-            if return_zf:
-                out.append(dzf.download((self.n_channels, D), np.float64)[:, :self.state_dim])
-            return out[0] if len(out) == 1 else tuple(out)
-
-    def close(self):
-        self.plan.close()
-        if self._scratch is not None:
-            self._scratch.close()
-            self._scratch = None
+        return _host_trip(
+            lambda y, reports, dzi, dzf, levels: self.launch(y, None, reports[0], reports[1], dzi, dzf, levels),
+            shape=(self.n_channels, self.n), dtype=np.int16, rows=self.n_channels,
+            reports=(return_counts, return_beyond), state_dim=self.state_dim, zi=zi, return_zf=return_zf, initial=initial)
 
 
 class MarkerStage:
@@ -2327,9 +2218,8 @@ class MarkerStage:
             raise ValueError('MarkerStage: no rows')
         if batch % group:
             raise ValueError(f'MarkerStage: {batch} rows are no multiple of the group {group}')
-        leads, trails, thresholds = (
-            _per_row('MarkerStage', what, list(np.asarray(v).reshape(-1)) if np.ndim(v) > 0 else v, batch // group)
-            for what, v in (('lead', lead), ('trail', trail), ('threshold', threshold)))
+        leads, trails, thresholds = (_per_row_flat('MarkerStage', what, v, batch // group)
+                                     for what, v in (('lead', lead), ('trail', trail), ('threshold', threshold)))
         self.plan = _engine.MarkerRowsPlan(thresholds, leads, trails, n, group, dtype)
         p = self.plan
         self.n, self.batch, self.group, self.out_rows, self.dtype = p.n, p.batch, p.group, p.out_rows, p.dtype
